@@ -45,6 +45,7 @@ WORKLOADS = {
     "c3": (200_000, 30_000, 0.03, 30, 0, 0),
 }
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured float4 copy; the line carries this box's own: peak_measured)
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000   # --dump-outputs: all files together stay under 64 MB
 
 
 def alg_bytes(m, n, nnz, l, k, q, tsize=4):
@@ -111,6 +112,30 @@ def reference_binary_baseline(timeout_s=120):
         return {"available": False, "reason": "reference binary: " + repr(e)}
 
 
+def dump_outputs(dump_dir, est, out):
+    """--dump-outputs: what a caller of the timed fit_transform holds after its last step -- the projection and the fitted
+    fields -- as DIR/<name>.npy in the fitted precision.  A projection too large for what the fitted fields leave of
+    DUMP_BUDGET_BYTES is written as a fixed sample of its rows (seed 0, ascending; their indices in transform_rows.npy), so
+    the same arguments write the same files from run to run.  Returns the names written."""
+    dtype = np.float64 if out.dtype == torch.float64 else np.float32
+    arrays = {"components": est.components_(dtype), "singular_values": est.singular_values_(dtype),
+              "explained_variance": est.explained_variance_(dtype), "explained_variance_ratio": est.explained_variance_ratio(dtype),
+              "mean": est.mean_(dtype)}
+    left = DUMP_BUDGET_BYTES - 4096 - sum(a.nbytes for a in arrays.values())   # (4096: room for the .npy headers)
+    m, k = out.shape
+    row_bytes = k * out.element_size()
+    if m * row_bytes <= left:
+        arrays["transform"] = out.cpu().numpy()
+    else:
+        rows = np.sort(np.random.default_rng(0).choice(m, size=left // (row_bytes + 8), replace=False))
+        arrays["transform"] = out[torch.as_tensor(rows, device=out.device)].cpu().numpy()
+        arrays["transform_rows"] = rows.astype(np.float64)
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
 def cpu_model():
     """Model name of the host CPU the baseline ran on (SURVEY.md 8d asks for model + core count)."""
     try:
@@ -123,7 +148,7 @@ def cpu_model():
     return platform.processor() or "unknown"
 
 
-def run_lanczos(steps, warmup, local_rank, dev):
+def run_lanczos(steps, warmup, local_rank, dev, dump_dir=None):
     """configs[2]: MaskedSparsePCA fit_transform, f64, Lanczos on the mask-compacted (uncentred) operator: the record."""
     import sapca
     from sapca import synth
@@ -149,6 +174,7 @@ def run_lanczos(steps, warmup, local_rank, dev):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     assert out.shape == (m, k) and bool(torch.isfinite(out).all())
+    dumped = dump_outputs(dump_dir, est, out) if dump_dir else None
     n_used = int(mask.sum())
     nnz_used = int(torch.as_tensor(mask, device=dev)[idx.long()].sum().item())
     # per Lanczos step 2*[nnz'*(8+4) + (m+1)*8] + (m + 2n')*8 bytes
@@ -163,6 +189,8 @@ def run_lanczos(steps, warmup, local_rank, dev):
            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                         "traffic": None, "kernel": "Lanczos step (SpMV pair + re-orthogonalisation), HIP events on the library stream",
                         "algorithmic_bytes_per_launch": step_bytes, "avg_launch_ms": lz_ms / max(lsteps, 1), "launches_timed": lsteps}}
+    if dumped is not None:
+        rec["outputs_dumped"] = dumped
     del out, x, ptr, idx, val, est
     torch.cuda.empty_cache()
     return rec
@@ -170,7 +198,7 @@ def run_lanczos(steps, warmup, local_rank, dev):
 
 def bench_lanczos(args, rank, local_rank, world, dev):
     assert world == 1, "the c3 workload is a 1-GPU configuration"
-    rec = run_lanczos(args.steps, args.warmup, local_rank, dev)
+    rec = run_lanczos(args.steps, args.warmup, local_rank, dev, args.dump_outputs)
     rec.update({"n_gpus": 1, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "data": "synthetic"})
     print(json.dumps(rec))
 
@@ -304,10 +332,11 @@ def e2e_host_ms(args, m, n, density, k, p, q, dev, local_rank):
     return best, parts
 
 
-def run_randomized(workload, scaling, steps, warmup, rank, world, local_rank, dev, rdev, shared, spmm_variant):
+def run_randomized(workload, scaling, steps, warmup, rank, world, local_rank, dev, rdev, shared, spmm_variant, dump_dir=None):
     """`warmup` untimed + `steps` timed fit_transforms of one randomized-SVD workload, rows range-partitioned over the
     ranks (weak: every rank holds the workload's row count; strong: the workload's rows are split).  The timed region is
-    bracketed by a barrier + torch.cuda.synchronize() on both sides; the returned wall time is the MAX over ranks."""
+    bracketed by a barrier + torch.cuda.synchronize() on both sides; the returned wall time is the MAX over ranks.
+    `dump_dir`: rank 0 writes its last step's outputs there after the timed region (dump_outputs)."""
     import sapca
     import torch.distributed as dist
     from sapca import synth
@@ -383,6 +412,7 @@ def run_randomized(workload, scaling, steps, warmup, rank, world, local_rank, de
     else:
         nnz_total = float(nnz)
     assert out.shape == (m, k) and bool(torch.isfinite(out).all())
+    dumped = dump_outputs(dump_dir, pca, out) if (dump_dir and rank == 0) else None
     l = k + p
     sweep_bytes, _ = alg_bytes(m, n, nnz, l, k, q)                      # per rank (one launch)
     _, total_bytes = alg_bytes(m_total, n, nnz_total, l, k, q)          # whole job
@@ -392,7 +422,7 @@ def run_randomized(workload, scaling, steps, warmup, rank, world, local_rank, de
            "value": total_bytes / (dt / steps) / 1e9, "stage": stage, "transport": transport, "sweep_ms": sweep_ms,
            "avg_sweep_ms": avg_sweep_ms, "per_rank_sweep": per_rank_sweep, "per_rank_comm": per_rank_comm, "sweep_bytes": sweep_bytes,
            "achieved": sweep_bytes / (avg_sweep_ms * 1e-3) / 1e9, "sweep_kernel": int(t.sweep_kernel),
-           "slots": 0.5 * (t.sweep_slots_a + t.sweep_slots_at)}
+           "slots": 0.5 * (t.sweep_slots_a + t.sweep_slots_at), "outputs_dumped": dumped}
     del out, x, ptr, idx, val, pca
     torch.cuda.empty_cache()
     return res
@@ -430,7 +460,12 @@ def main():
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the measured copy rate, the host-path run, the C1 comparison and the secondary workloads "
                          "(c4_1gpu at one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (the projection, a fixed row sample of it when "
+                         "large, and the fitted fields; rank 0's rows at N > 1) as DIR/<name>.npy, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
@@ -471,7 +506,8 @@ def main():
         except Exception as e:   # never lose the line to an extra
             e2e = repr(e)
         torch.cuda.empty_cache()
-    r = run_randomized(args.workload, args.scaling, args.steps, args.warmup, rank, world, local_rank, dev, rdev, shared, args.spmm_variant)
+    r = run_randomized(args.workload, args.scaling, args.steps, args.warmup, rank, world, local_rank, dev, rdev, shared, args.spmm_variant,
+                       args.dump_outputs)
     # secondary workloads (every rank takes part): BASELINE configs[3] on one GPU beside the C2 headline (north_star's
     # roofline target is quoted on 1M x 30k at one GPU); the weak-scaled C2 shards beside the strong-scaled C4 headline
     extra = {}
@@ -537,6 +573,8 @@ def main():
                                              "stored_entries_per_launch": int(r["nnz"]),
                                              # the same on STORED entries only (padding slots are not work): the honest figure
                                              "frac_stored": int(r["nnz"]) * 256.0 / (avg_sweep_ms * 1e-3) / 1e9 / 150000.0}
+        if r["outputs_dumped"] is not None:
+            line["outputs_dumped"] = r["outputs_dumped"]
         line.update(extra)
         if not args.no_extras:
             peak_meas = measured_copy_gbs(local_rank)
