@@ -54,7 +54,8 @@ extern "C" {
 #define SAPCA_ABI_VERSION 4   /* 2: sapca_timings grew sweep_kernel / sweep_slots_*; sapca_comm_rccl_available
                                  3: sapca_multi_* (one handle, several GPUs), sapca_upload_values_changed
                                  4: *_csr_device_to_host_*, sapca_comm_abort / _async_error / _has_side_lane,
-                                    sapca_multi_upload_csr_* and the sapca_multi_*_resident calls        */
+                                    sapca_multi_upload_csr_* and the sapca_multi_*_resident calls
+                                 additive, ABI 4: sapca_batch_stats_csr_device_*, sapca_sum_row_n_top_csr_device_*  */
 
 typedef struct sapca_handle_s* sapca_handle;
 
@@ -316,6 +317,43 @@ sapca_status sapca_stats_csr_device_f64(sapca_handle h, uint64_t m, uint64_t n, 
                                         const int64_t* row_offsets, const int32_t* col_indices, const double* values,
                                         int32_t direction, double* sum, double* sum_squared, uint64_t* nonzero,
                                         double* min_out, double* max_out);
+
+/* BatchMatrixVariance::var_batch_row|col and BatchMatrixMean::mean_batch_row|col (csr.rs:1081-1344)
+ * on a device-resident CSR.  `codes` is a HOST array of dense batch codes in [0, n_batches):
+ *   grouped_axis 0: codes label the ROWS (codes_len == m); results per column, each n long
+ *                   (var_batch_row, mean_batch_col);
+ *   grouped_axis 1: codes label the COLUMNS (codes_len == n); results per row, each m long
+ *                   (var_batch_col, mean_batch_row).
+ * Outputs are HOST arrays of n_batches x (n or m), code-major; any may be NULL:
+ *   count[b][j] = stored entries of line j in group b (implicit zeros are not counted, stored zeros are);
+ *   var[b][j]   = sum (x - mu)^2 / (count - 1) over those entries, mu = their sum / count, 0 when count <= 1
+ *                 (the reference's two passes, csr.rs:1118-1160, 1212-1237);
+ *   mean[b][j]  = (sum of those entries) / (number of rows | columns with code b): implicit zeros count
+ *                 (csr.rs:1290-1293, 1337-1340).
+ * A code that never occurs gives 0 everywhere.  The reference accumulates in the caller's T; here every
+ * sum is accumulated in f64.  A wrong codes_len is SAPCA_ERR_ARG with the message of the reference
+ * method: var_*'s ("Batch vector length (..) doesn't match matrix row|column count (..)") when var is
+ * requested, mean_*'s ("Number of batch identifiers (..) must match number of rows|columns (..)")
+ * otherwise; so are a code outside [0, n_batches) and grouped_axis outside {0, 1}.  grouped_axis 0
+ * transposes the matrix into the buffers prepare() uses (a cached preparation is dropped).          */
+sapca_status sapca_batch_stats_csr_device_f32(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz,
+                                              const int64_t* row_offsets, const int32_t* col_indices, const float* values,
+                                              int32_t grouped_axis, const int32_t* codes, uint64_t codes_len,
+                                              uint32_t n_batches, double* mean, double* var, uint64_t* count);
+sapca_status sapca_batch_stats_csr_device_f64(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz,
+                                              const int64_t* row_offsets, const int32_t* col_indices, const double* values,
+                                              int32_t grouped_axis, const int32_t* codes, uint64_t codes_len,
+                                              uint32_t n_batches, double* mean, double* var, uint64_t* count);
+/* MatrixNTop::sum_row_n_top (csr.rs:1347-1376) for several n at once: out[i * m + r] (HOST, n_ns x m)
+ * = sum of the min(ns[i], stored entries of row r) largest STORED values of row r (negative values and
+ * stored zeros compete like any other; n = 0 gives 0), accumulated in f64 (the reference: in T).  NaN
+ * values give an unspecified result.  n_ns == 0 is SAPCA_ERR_ARG.                                     */
+sapca_status sapca_sum_row_n_top_csr_device_f32(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz,
+                                                const int64_t* row_offsets, const int32_t* col_indices, const float* values,
+                                                const uint64_t* ns, uint32_t n_ns, double* out);
+sapca_status sapca_sum_row_n_top_csr_device_f64(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz,
+                                                const int64_t* row_offsets, const int32_t* col_indices, const double* values,
+                                                const uint64_t* ns, uint32_t n_ns, double* out);
 
 /* Measurement support: the rate (GB/s, read + write counted) of a 16-byte-per-lane streaming copy of `bytes`
  * bytes on the handle's device, best of `reps` -- the HBM rate a kernel of this library can attain, reported by

@@ -466,6 +466,94 @@ sapca_status stats_device(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, 
   });
 }
 
+// BatchMatrixVariance / BatchMatrixMean (csr.rs:1081-1344) through one pass pair per code range.  grouped_axis 0: codes
+// label the rows of A (length m), results per column, computed on the rows of A^T; 1: codes label the columns (length n),
+// results per row of A.  The host counts the group sizes (the denominators of the means) and finishes mean / var.
+template <typename T>
+sapca_status batch_stats_device(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v,
+                                int32_t grouped_axis, const int32_t* codes, uint64_t codes_len, uint32_t n_batches, double* mean,
+                                double* var, uint64_t* count) {
+  return guarded(h, [&] {
+    SAPCA_CHECK(grouped_axis == 0 || grouped_axis == 1, SAPCA_ERR_ARG, "grouped_axis must be 0 (codes label rows) or 1 (columns)");
+    CsrView<T> A = device_view<T>(m, n, nnz, p, i, v);
+    const uint64_t want = grouped_axis == 0 ? m : n, len = grouped_axis == 0 ? n : m;
+    if (codes_len != want) {   // the message of the reference method this call serves (var_* when var is asked for)
+      const std::string got = std::to_string(codes_len), have = std::to_string(want);
+      if (var)
+        throw Error(SAPCA_ERR_ARG, "Batch vector length (" + got + ") doesn't match matrix " + (grouped_axis == 0 ? "row" : "column") +
+                                       " count (" + have + ")");
+      throw Error(SAPCA_ERR_ARG, "Number of batch identifiers (" + got + ") must match number of " +
+                                     (grouped_axis == 0 ? "rows" : "columns") + " (" + have + ")");
+    }
+    SAPCA_CHECK(codes != nullptr || codes_len == 0, SAPCA_ERR_ARG, "null codes");
+    std::vector<uint64_t> group(n_batches, 0);
+    for (uint64_t j = 0; j < codes_len; ++j) {
+      SAPCA_CHECK(codes[j] >= 0 && (uint32_t)codes[j] < n_batches, SAPCA_ERR_ARG,
+                  "batch code " + std::to_string(codes[j]) + " at " + std::to_string(j) + " is outside [0, n_batches)");
+      ++group[codes[j]];
+    }
+    if (n_batches == 0 || len == 0) return;
+    hipStream_t s = h->stream;
+    int32_t* d_codes = h->batch_in.as<int32_t>(std::max<uint64_t>(codes_len, 1));
+    if (codes_len) SAPCA_HIP(hipMemcpyAsync(d_codes, codes, codes_len * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    CsrView<T> R = A;
+    if (grouped_axis == 0) {
+      h->prep_key.valid = false;   // the transposition buffers are shared with prepare()
+      int64_t* at_ptr = h->at_ptr.as<int64_t>(n + 1);
+      int32_t* at_idx = h->at_idx.as<int32_t>(std::max<uint64_t>(nnz, 1));
+      T* at_val = h->at_val.as<T>(std::max<uint64_t>(nnz, 1));
+      sapca::k::transpose_csr(A, at_ptr, at_idx, at_val, h->scratch, s);
+      R.rows = (int64_t)n; R.cols = (int64_t)m; R.ptr = at_ptr; R.idx = at_idx; R.val = at_val;
+    }
+    const int per = sapca::k::batch_codes_per_launch();
+    const int nb_max = (int)std::min<uint32_t>(n_batches, (uint32_t)per);
+    double* d_sum = h->batch_out.as<double>((size_t)nb_max * len * 5 / 2 + 1);   // sum, m2 (f64) and count (u32) per slot
+    double* d_m2 = d_sum + (size_t)nb_max * len;
+    uint32_t* d_cnt = reinterpret_cast<uint32_t*>(d_m2 + (size_t)nb_max * len);
+    std::vector<double> hs, hm;
+    std::vector<uint32_t> hc;
+    for (uint32_t lo = 0; lo < n_batches; lo += (uint32_t)per) {
+      const int nb = (int)std::min<uint32_t>(n_batches - lo, (uint32_t)per);
+      const size_t cells = (size_t)nb * len;
+      sapca::k::batch_row_stats(R, d_codes, (int)lo, nb, d_sum, d_m2, d_cnt, s);
+      hs.resize(cells); hm.resize(cells); hc.resize(cells);
+      SAPCA_HIP(hipMemcpyAsync(hs.data(), d_sum, cells * sizeof(double), hipMemcpyDeviceToHost, s));
+      SAPCA_HIP(hipMemcpyAsync(hm.data(), d_m2, cells * sizeof(double), hipMemcpyDeviceToHost, s));
+      SAPCA_HIP(hipMemcpyAsync(hc.data(), d_cnt, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      SAPCA_HIP(hipStreamSynchronize(s));
+      for (int b = 0; b < nb; ++b) {
+        const uint64_t g = group[lo + b];
+        const size_t base = ((size_t)lo + b) * len;
+        for (uint64_t r = 0; r < len; ++r) {
+          const size_t c = (size_t)b * len + r;
+          if (mean) mean[base + r] = g ? hs[c] / (double)g : 0.0;                        // csr.rs:1290-1293, 1337-1340
+          if (var) var[base + r] = hc[c] > 1 ? hm[c] / (double)(hc[c] - 1) : 0.0;       // csr.rs:1151-1160
+          if (count) count[base + r] = hc[c];
+        }
+      }
+    }
+  });
+}
+
+// MatrixNTop::sum_row_n_top (csr.rs:1347-1376) for several n in one pass over the rows: out[i * m + r]
+template <typename T>
+sapca_status top_n_device(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v,
+                          const uint64_t* ns, uint32_t n_ns, double* out) {
+  return guarded(h, [&] {
+    SAPCA_CHECK(n_ns > 0 && ns != nullptr, SAPCA_ERR_ARG, "sum_row_n_top: at least one n is needed");
+    SAPCA_CHECK(out != nullptr || m == 0, SAPCA_ERR_ARG, "null output");
+    CsrView<T> A = device_view<T>(m, n, nnz, p, i, v);
+    if (m == 0) return;
+    hipStream_t s = h->stream;
+    uint64_t* d_ns = h->batch_in.as<uint64_t>(n_ns);
+    double* d_out = h->batch_out.as<double>((size_t)n_ns * m);
+    SAPCA_HIP(hipMemcpyAsync(d_ns, ns, n_ns * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    sapca::k::row_top_n(A, d_ns, (int)n_ns, d_out, s);
+    SAPCA_HIP(hipMemcpyAsync(out, d_out, (size_t)n_ns * m * sizeof(double), hipMemcpyDeviceToHost, s));
+    SAPCA_HIP(hipStreamSynchronize(s));
+  });
+}
+
 template <typename T>
 sapca_status spmm_host(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const uint64_t* ro, const uint64_t* ci,
                        const T* v, const T* mu, uint64_t l, const T* In, T* Out, bool transposed) {
@@ -754,6 +842,17 @@ sapca_status sapca_set_omega_f64(sapca_handle h, const double* omega, size_t row
                                             const int32_t* i, const T* v, int32_t direction, double* sum, double* sumsq, \
                                             uint64_t* nonzero, T* minv, T* maxv) {                                       \
     return stats_device<T>(h, m, n, nnz, p, i, v, direction, sum, sumsq, nonzero, minv, maxv);                           \
+  }                                                                                                                      \
+  sapca_status sapca_batch_stats_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, \
+                                                  const int32_t* i, const T* v, int32_t grouped_axis, const int32_t* codes, \
+                                                  uint64_t codes_len, uint32_t n_batches, double* mean, double* var,        \
+                                                  uint64_t* count) {                                                        \
+    return batch_stats_device<T>(h, m, n, nnz, p, i, v, grouped_axis, codes, codes_len, n_batches, mean, var, count);     \
+  }                                                                                                                      \
+  sapca_status sapca_sum_row_n_top_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, \
+                                                    const int32_t* i, const T* v, const uint64_t* ns, uint32_t n_ns,        \
+                                                    double* out) {                                                          \
+    return top_n_device<T>(h, m, n, nnz, p, i, v, ns, n_ns, out);                                                         \
   }                                                                                                                      \
   sapca_status sapca_spmm_csr_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const uint64_t* ro,            \
                                     const uint64_t* ci, const T* v, const T* mu, uint64_t l, const T* X, T* Y) {         \

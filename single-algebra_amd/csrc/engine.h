@@ -106,6 +106,7 @@ struct sapca_handle_s {
   sapca::DevBuf panel_x, panel_y, panel_w, panel_xs, panel_wide;   // (panel_wide: the out-of-place product of a panel wider than 128 columns)
   sapca::DevBuf small;                                           // G, R1, R2, Rinv, M, cvec, svec, info
   sapca::DevBuf stats;                                           // sum, sumsq, cnt (f64, n each)
+  sapca::DevBuf batch_in, batch_out;                             // per-batch statistics / top-n: codes or ns; results
   sapca::DevBuf mean_used_dev, o2m_dev, sel_rows_dev;
   sapca::DevBuf components_dev;                                  // k x n_used, T
   sapca::DevBuf lanczos_buf;

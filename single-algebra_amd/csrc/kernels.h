@@ -89,6 +89,17 @@ void log1p_values(T* values, int64_t nnz, hipStream_t s);
 template <typename T>
 void row_stats(const CsrView<T>& A, double* sum, double* sumsq, T* minv, T* maxv, hipStream_t s);
 
+// ---- batchstats.hip: per-batch statistics and top-n row sums (BatchMatrixVariance / BatchMatrixMean / MatrixNTop) ------
+// the most codes one batch_row_stats launch takes (its LDS budget)
+int batch_codes_per_launch();
+// Per row r of R and code b in [lo, lo + nb), over the stored entries e of row r with codes[R.idx[e]] == lo + b:
+// cnt[b * R.rows + r] = their count, sum[..] = their sum, m2[..] = sum (x - sum / count)^2 (two passes, f64).
+template <typename T>
+void batch_row_stats(const CsrView<T>& R, const int32_t* codes, int lo, int nb, double* sum, double* m2, uint32_t* cnt, hipStream_t s);
+// out[i * A.rows + r] = sum of the min(ns[i], length of row r) largest stored values of row r (f64); ns: device, n_ns
+template <typename T>
+void row_top_n(const CsrView<T>& A, const uint64_t* ns, int n_ns, double* out, hipStream_t s);
+
 // dst[0 .. bytes) = src[0 .. bytes) by a 16-byte-per-lane streaming kernel (the attainable-HBM-rate probe of sapca_measure_copy_gbs)
 void stream_copy16(const void* src, void* dst, int64_t bytes, hipStream_t s);
 

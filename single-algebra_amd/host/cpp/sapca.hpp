@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../../include/sapca.h"
@@ -65,6 +66,8 @@ template <typename T> struct ResidentAbi;
     static sapca_status normalize(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, T* v, const double* s, uint64_t sl, double t, int32_t d) { return sapca_normalize_csr_device_##SUF(h, m, n, nnz, p, i, v, s, sl, t, d); } \
     static sapca_status log1p(sapca_handle h, uint64_t nnz, T* v) { return sapca_log1p_csr_device_##SUF(h, nnz, v); } \
     static sapca_status stats(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, int32_t d, double* s, double* q, uint64_t* c, T* lo, T* hi) { return sapca_stats_csr_device_##SUF(h, m, n, nnz, p, i, v, d, s, q, c, lo, hi); } \
+    static sapca_status batch_stats(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, int32_t ax, const int32_t* c, uint64_t cl, uint32_t nb, double* mean, double* var, uint64_t* cnt) { return sapca_batch_stats_csr_device_##SUF(h, m, n, nnz, p, i, v, ax, c, cl, nb, mean, var, cnt); } \
+    static sapca_status n_top(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, const uint64_t* ns, uint32_t k, double* out) { return sapca_sum_row_n_top_csr_device_##SUF(h, m, n, nnz, p, i, v, ns, k, out); } \
   };
 SAPCA_RES(f32, float)
 SAPCA_RES(f64, double)
@@ -92,6 +95,19 @@ class ResidentCsr {
     check(ResidentAbi<T>::stats(h_, m_, n_, nnz_, ptr_, idx_, val_, (int32_t)d, nullptr, nullptr, c.data(), nullptr, nullptr));
     return c;
   }
+  // BatchMatrixVariance / BatchMatrixMean (csr.rs:1081-1344): B is any hashable label; f64 results keyed by the labels
+  // that occur.  var_batch_row / mean_batch_col: batches label the rows (one n-long vector per label); var_batch_col /
+  // mean_batch_row: batches label the columns (m-long vectors).
+  template <typename B> std::unordered_map<B, std::vector<double>> var_batch_row(const std::vector<B>& b) const { return grouped(b, 0, true); }
+  template <typename B> std::unordered_map<B, std::vector<double>> var_batch_col(const std::vector<B>& b) const { return grouped(b, 1, true); }
+  template <typename B> std::unordered_map<B, std::vector<double>> mean_batch_row(const std::vector<B>& b) const { return grouped(b, 1, false); }
+  template <typename B> std::unordered_map<B, std::vector<double>> mean_batch_col(const std::vector<B>& b) const { return grouped(b, 0, false); }
+  // MatrixNTop::sum_row_n_top (csr.rs:1347-1376), f64 accumulation
+  std::vector<double> sum_row_n_top(uint64_t n) const {
+    std::vector<double> out(m_);
+    check(ResidentAbi<T>::n_top(h_, m_, n_, nnz_, ptr_, idx_, val_, &n, 1, out.data()));
+    return out;
+  }
   const int64_t* row_offsets() const { return ptr_; }
   const int32_t* col_indices() const { return idx_; }
   T* values() const { return val_; }
@@ -99,6 +115,24 @@ class ResidentCsr {
  private:
   void check(sapca_status st) const {
     if (st != SAPCA_OK) throw Error(st, sapca_last_error(h_));
+  }
+  template <typename B>
+  std::unordered_map<B, std::vector<double>> grouped(const std::vector<B>& batches, int32_t axis, bool variance) const {
+    std::unordered_map<B, int32_t> code;
+    std::vector<const B*> label;
+    std::vector<int32_t> codes(batches.size());
+    for (size_t j = 0; j < batches.size(); ++j) {
+      auto it = code.emplace(batches[j], (int32_t)label.size());
+      if (it.second) label.push_back(&batches[j]);
+      codes[j] = it.first->second;
+    }
+    const uint64_t len = axis == 0 ? n_ : m_;
+    std::vector<double> res(label.size() * len);
+    check(ResidentAbi<T>::batch_stats(h_, m_, n_, nnz_, ptr_, idx_, val_, axis, codes.data(), codes.size(), (uint32_t)label.size(),
+                                      variance ? nullptr : res.data(), variance ? res.data() : nullptr, nullptr));
+    std::unordered_map<B, std::vector<double>> out;
+    for (size_t b = 0; b < label.size(); ++b) out.emplace(*label[b], std::vector<double>(res.begin() + b * len, res.begin() + (b + 1) * len));
+    return out;
   }
   sapca_handle h_;
   uint64_t m_, n_, nnz_;

@@ -20,11 +20,13 @@ def _p(a, ct):
 class Session:
     """A bare handle (default options) to run stage-level operators on."""
 
-    def __init__(self, seed=42, spmm_variant=0):
+    def __init__(self, seed=42, spmm_variant=0, stream=None):
         self._h = C.c_void_p()
         o = L.default_options()
         o.random_seed = seed
         o.spmm_variant = spmm_variant
+        if stream is not None:   # a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream): the handle's work goes there
+            o.stream = C.c_void_p(int(stream))
         st = L.load().sapca_create(C.byref(o), C.byref(self._h))
         if st != L.OK:
             raise L.SapcaError(st, (L.load().sapca_last_error(None) or b"").decode())
@@ -81,6 +83,22 @@ class Session:
 ROW, COLUMN = 0, 1   # Direction of the reference's Normalize / statistics traits (src/utils.rs)
 
 
+def _dense_codes(batches):
+    """(labels in order of first appearance, int32 code of every entry of `batches`); labels may be any hashable values"""
+    arr = batches if isinstance(batches, np.ndarray) else None
+    if arr is None and len(batches) and all(type(b) is int for b in batches):
+        arr = np.asarray(batches)
+    if arr is not None and arr.ndim == 1 and arr.dtype.kind in "iub":
+        uniq, first, codes = np.unique(arr, return_index=True, return_inverse=True)
+        order = np.argsort(first, kind="stable")
+        rank = np.empty_like(order)
+        rank[order] = np.arange(order.size)
+        return [uniq[j].item() for j in order], rank[codes.reshape(-1)].astype(np.int32)
+    lut = {}
+    codes = np.fromiter((lut.setdefault(b, len(lut)) for b in batches), dtype=np.int32, count=len(batches))
+    return list(lut), codes
+
+
 class ResidentCsr:
     """A CSR matrix uploaded once into buffers owned by a Session (sapca_upload_csr_*): normalize -> log1p ->
     statistics -> PCA on it without crossing PCIe again.  `as_device_csr()` gives the
@@ -135,6 +153,60 @@ class ResidentCsr:
             return np.zeros_like(sm)
         mean = sm / N
         return (sq / N - mean ** 2) * (N / (N - 1.0))
+
+    def batch_stats(self, grouped_axis, codes, n_batches, want=("mean", "var", "count")):
+        """sapca_batch_stats_csr_device_*: dense codes in [0, n_batches) label the rows (grouped_axis 0) or the columns
+        (1); returns {name: array of n_batches x (n or m)} for the names in `want` (mean, var: f64; count: u64)"""
+        suf, _ = _SUF[self.dtype]
+        m, n = self.shape
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        ln = n if int(grouped_axis) == 0 else m
+        out = {k: np.zeros((int(n_batches), ln), dtype=np.uint64 if k == "count" else np.float64) for k in want}
+        ptrs = [_p(out[k], C.c_uint64 if k == "count" else C.c_double) if k in out else None for k in ("mean", "var", "count")]
+        L.check(self._s._h, getattr(L.load(), f"sapca_batch_stats_csr_device_{suf}")(
+            *self._args(), C.c_int32(int(grouped_axis)), _p(codes, C.c_int32), C.c_uint64(codes.size), C.c_uint32(int(n_batches)), *ptrs))
+        return out
+
+    def _grouped(self, batches, grouped_axis, what, message):
+        want = self.shape[0] if grouped_axis == 0 else self.shape[1]
+        if len(batches) != want:
+            raise ValueError(message.format(len(batches), want))
+        labels, codes = _dense_codes(batches)
+        res = self.batch_stats(grouped_axis, codes, len(labels), want=(what,))[what]
+        return {b: res[c] for c, b in enumerate(labels)}
+
+    def var_batch_row(self, batches):
+        """BatchMatrixVariance::var_batch_row (csr.rs:1088-1163): batches label the rows; {label: per-column variance of the
+        stored entries in that label's rows} (count - 1 denominator, 0 for fewer than two entries)"""
+        return self._grouped(batches, 0, "var", "Batch vector length ({}) doesn't match matrix row count ({})")
+
+    def var_batch_col(self, batches):
+        """BatchMatrixVariance::var_batch_col (csr.rs:1165-1244): batches label the columns; {label: per-row variance}"""
+        return self._grouped(batches, 1, "var", "Batch vector length ({}) doesn't match matrix column count ({})")
+
+    def mean_batch_row(self, batches):
+        """BatchMatrixMean::mean_batch_row (csr.rs:1251-1296): batches label the columns; {label: per-row sum / number of
+        columns with that label}"""
+        return self._grouped(batches, 1, "mean", "Number of batch identifiers ({}) must match number of columns ({})")
+
+    def mean_batch_col(self, batches):
+        """BatchMatrixMean::mean_batch_col (csr.rs:1299-1343): batches label the rows; {label: per-column sum / number of
+        rows with that label}"""
+        return self._grouped(batches, 0, "mean", "Number of batch identifiers ({}) must match number of rows ({})")
+
+    def sum_row_n_top(self, n):
+        """MatrixNTop::sum_row_n_top (csr.rs:1347-1376): per row, the sum of the n largest stored values (all of them when
+        the row has fewer).  n an int -> m values; a sequence of ints -> len(n) x m, one pass over the rows for all."""
+        single = np.ndim(n) == 0
+        ns = np.atleast_1d(np.asarray(n))
+        if ns.size == 0 or not np.issubdtype(ns.dtype, np.integer) or (ns < 0).any():
+            raise ValueError("n must be a non-negative integer or a non-empty sequence of them")
+        ns = np.ascontiguousarray(ns, dtype=np.uint64)
+        suf, _ = _SUF[self.dtype]
+        out = np.zeros((ns.size, self.shape[0]))
+        L.check(self._s._h, getattr(L.load(), f"sapca_sum_row_n_top_csr_device_{suf}")(
+            *self._args(), _p(ns, C.c_uint64), C.c_uint32(ns.size), _p(out, C.c_double)))
+        return out[0] if single else out
 
     def values(self):
         """the current (device) values, copied to the host"""
