@@ -55,7 +55,8 @@ extern "C" {
                                  3: sapca_multi_* (one handle, several GPUs), sapca_upload_values_changed
                                  4: *_csr_device_to_host_*, sapca_comm_abort / _async_error / _has_side_lane,
                                     sapca_multi_upload_csr_* and the sapca_multi_*_resident calls
-                                 additive, ABI 4: sapca_batch_stats_csr_device_*, sapca_sum_row_n_top_csr_device_*  */
+                                 additive, ABI 4: sapca_batch_stats_csr_device_*, sapca_sum_row_n_top_csr_device_*,
+                                                  sapca_masked_stats_csr_device_*                                  */
 
 typedef struct sapca_handle_s* sapca_handle;
 
@@ -354,6 +355,32 @@ sapca_status sapca_sum_row_n_top_csr_device_f32(sapca_handle h, uint64_t m, uint
 sapca_status sapca_sum_row_n_top_csr_device_f64(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz,
                                                 const int64_t* row_offsets, const int32_t* col_indices, const double* values,
                                                 const uint64_t* ns, uint32_t n_ns, double* out);
+
+/* MatrixNonZero::nonzero_{col,row}_masked, MatrixSum::sum_{col,row}_masked, MatrixVariance::var_{col,row}_masked
+ * (csr.rs:153-252, 418-556, 815-914) and, with mask == NULL, the stored-entry variance of var_{col,row}_chunk
+ * (csr.rs:728-813) on a device-resident CSR:
+ *   direction 0 (ROW):    m results, one per row, over the stored entries whose COLUMN is kept;
+ *   direction 1 (COLUMN): n results, one per column, over the stored entries whose ROW is kept.
+ * `mask` is a HOST byte array, non-zero = kept; NULL keeps everything.  A mask_len below the masked dimension is
+ * SAPCA_ERR_ARG with the reference's message ("Mask length (..) is less than number of rows (..)" for COLUMN,
+ * ".. number of columns (..)" for ROW); a longer mask's tail is ignored (the reference's sum_col_masked /
+ * var_col_masked index past the row offsets on a true tail entry).  Outputs are HOST arrays, any may be NULL:
+ *   count = kept stored entries (stored zeros count); sum, sum_squared = their sum and sum of squares;
+ *   var   = stored-entry variance, no correction, 0 where count is 0: ROW two passes, sum (x - mean)^2 / count
+ *           (csr.rs:889-911); COLUMN sum_squared / count - mean^2 (csr.rs:852-859).
+ * The reference accumulates in the caller's T; here every sum is f64.  COLUMN sums are order-independent: the
+ * correctly rounded exact sums (the upload's accumulators, csrc/upstats.hip), bit-identical from call to call, and no
+ * transposition is made; dropped rows are not read.  A kept inf / nan propagates as in an f64 sum (those columns are
+ * then summed on a transposition, as is a matrix too wide for the accumulators, which drops a cached preparation);
+ * one in a dropped row or column changes nothing.  A direction outside {0, 1} is SAPCA_ERR_ARG.                    */
+sapca_status sapca_masked_stats_csr_device_f32(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz,
+                                               const int64_t* row_offsets, const int32_t* col_indices, const float* values,
+                                               int32_t direction, const uint8_t* mask, uint64_t mask_len,
+                                               double* sum, double* sum_squared, uint64_t* count, double* var);
+sapca_status sapca_masked_stats_csr_device_f64(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz,
+                                               const int64_t* row_offsets, const int32_t* col_indices, const double* values,
+                                               int32_t direction, const uint8_t* mask, uint64_t mask_len,
+                                               double* sum, double* sum_squared, uint64_t* count, double* var);
 
 /* Measurement support: the rate (GB/s, read + write counted) of a 16-byte-per-lane streaming copy of `bytes`
  * bytes on the handle's device, best of `reps` -- the HBM rate a kernel of this library can attain, reported by

@@ -535,6 +535,106 @@ sapca_status batch_stats_device(sapca_handle h, uint64_t m, uint64_t n, uint64_t
   });
 }
 
+// MatrixNonZero / MatrixSum / MatrixVariance *_masked (csr.rs:153-252, 418-556, 815-914) and the stored-entry variance of
+// var_*_chunk (csr.rs:728-813, mask == nullptr).  direction 0 (ROW): per row of A, `mask` over the columns (two passes in
+// the wave of a row, maskedstats.hip); 1 (COLUMN): per column, `mask` over the rows, in the exact long accumulators of
+// upstats.hip without a transposition (rows whose bit is clear are not read).  A kept inf / nan raises their flag; the
+// columns it touched then take the ROW kernel's f64 sums on A^T, so it propagates as an f64 sum does.  So does a
+// matrix too wide for the accumulators' 1 GiB.  The host finishes the variance: Σ(x − mean)² / count (ROW) or
+// sumsq / count − mean² (COLUMN), 0 where count is 0.
+template <typename T>
+sapca_status masked_stats_device(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v,
+                                 int32_t direction, const uint8_t* mask, uint64_t mask_len, double* sum, double* sumsq,
+                                 uint64_t* count, double* var) {
+  return guarded(h, [&] {
+    SAPCA_CHECK(direction == 0 || direction == 1, SAPCA_ERR_ARG, "direction must be 0 (ROW) or 1 (COLUMN)");
+    CsrView<T> A = device_view<T>(m, n, nnz, p, i, v);
+    const uint64_t masked = direction == 1 ? m : n, len = direction == 1 ? n : m;
+    if (mask != nullptr && mask_len < masked)   // the reference's message; a longer mask's tail is ignored
+      throw Error(SAPCA_ERR_ARG, "Mask length (" + std::to_string(mask_len) + ") is less than number of " +
+                                     (direction == 1 ? "rows" : "columns") + " (" + std::to_string(masked) + ")");
+    if (len == 0) return;
+    hipStream_t s = h->stream;
+    const uint64_t words = (masked + 31) / 32;
+    uint32_t* d_bits = nullptr;
+    std::vector<uint32_t> bits;   // (lives until the results are on the host: its copy is asynchronous)
+    if (mask != nullptr) {        // (no mask: no bitset, and the kernels read no mask)
+      bits.assign(std::max<uint64_t>(words, 1), 0u);
+      for (uint64_t j = 0; j < masked; ++j)
+        if (mask[j]) bits[j >> 5] |= 1u << (j & 31);
+      d_bits = h->batch_in.as<uint32_t>(bits.size());
+      SAPCA_HIP(hipMemcpyAsync(d_bits, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    }
+    std::vector<double> hs(len), hq(len), hm2;
+    std::vector<uint32_t> hc(len);
+    // the ROW kernel on R (A, or A^T for the column direction) into hs / hq / hm2 / hc
+    auto row_pass = [&](const CsrView<T>& R) {
+      double* d = h->batch_out.as<double>(3 * len + (len + 1) / 2);
+      uint32_t* dc = reinterpret_cast<uint32_t*>(d + 3 * len);
+      sapca::k::masked_row_stats(R, d_bits, d, d + len, d + 2 * len, dc, s);
+      hm2.resize(len);
+      SAPCA_HIP(hipMemcpyAsync(hs.data(), d, len * sizeof(double), hipMemcpyDeviceToHost, s));
+      SAPCA_HIP(hipMemcpyAsync(hq.data(), d + len, len * sizeof(double), hipMemcpyDeviceToHost, s));
+      SAPCA_HIP(hipMemcpyAsync(hm2.data(), d + 2 * len, len * sizeof(double), hipMemcpyDeviceToHost, s));
+      SAPCA_HIP(hipMemcpyAsync(hc.data(), dc, len * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      SAPCA_HIP(hipStreamSynchronize(s));
+    };
+    auto transposed = [&] {
+      h->prep_key.valid = false;   // the transposition buffers are shared with prepare()
+      int64_t* at_ptr = h->at_ptr.as<int64_t>(n + 1);
+      int32_t* at_idx = h->at_idx.as<int32_t>(std::max<uint64_t>(nnz, 1));
+      T* at_val = h->at_val.as<T>(std::max<uint64_t>(nnz, 1));
+      sapca::k::transpose_csr(A, at_ptr, at_idx, at_val, h->scratch, s);
+      CsrView<T> R = A;
+      R.rows = (int64_t)n; R.cols = (int64_t)m; R.ptr = at_ptr; R.idx = at_idx; R.val = at_val;
+      return R;
+    };
+    if (direction == 0) {
+      row_pass(A);
+    } else if (sapca::k::exact_colstats_bytes<T>((int64_t)n) > ((size_t)1 << 30)) {
+      row_pass(transposed());
+    } else {
+      const size_t work_bytes = (sapca::k::exact_colstats_bytes<T>((int64_t)n) + 255) / 256 * 256;
+      char* base = h->batch_out.as<char>(work_bytes + 3 * n * sizeof(double));
+      double* d_out = reinterpret_cast<double*>(base + work_bytes);
+      sapca::k::exact_colstats_reset<T>(base, (int64_t)n, s);
+      if (d_bits) sapca::k::exact_colstats_scan_rows<T>(A.ptr, A.val, (int64_t)m, d_bits, (int64_t)n, base, s);
+      else sapca::k::exact_colstats_scan_values<T>(A.val, (int64_t)nnz, (int64_t)n, base, s);
+      sapca::k::exact_colstats_add<T>(A.ptr, A.idx, A.val, 0, (int64_t)m, 0, (int64_t)nnz, (int64_t)n, base, s, d_bits);
+      int nonfinite = 0;
+      sapca::k::exact_colstats_finish<T>(base, (int64_t)n, d_out, &nonfinite, s);
+      std::vector<double> host(3 * n);
+      SAPCA_HIP(hipMemcpyAsync(host.data(), d_out, host.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+      SAPCA_HIP(hipStreamSynchronize(s));
+      for (uint64_t j = 0; j < n; ++j) {
+        hs[j] = host[j];
+        hq[j] = host[n + j];
+        hc[j] = (uint32_t)host[2 * n + j];
+      }
+      if (nonfinite) {   // the columns whose kept entries hold an inf / nan take the f64 sums of the row pass on A^T
+        const std::vector<double> es = hs, eq = hq;
+        row_pass(transposed());
+        for (uint64_t j = 0; j < n; ++j)
+          if (std::isfinite(hs[j])) {
+            hs[j] = es[j];
+            hq[j] = eq[j];
+          }
+      }
+    }
+    for (uint64_t r = 0; r < len; ++r) {
+      const double c = (double)hc[r];
+      if (sum) sum[r] = hs[r];
+      if (sumsq) sumsq[r] = hq[r];
+      if (count) count[r] = hc[r];
+      if (var) {
+        if (hc[r] == 0) var[r] = 0.0;
+        else if (direction == 0) var[r] = hm2[r] / c;                        // csr.rs:889-911
+        else var[r] = hq[r] / c - (hs[r] / c) * (hs[r] / c);               // csr.rs:852-859
+      }
+    }
+  });
+}
+
 // MatrixNTop::sum_row_n_top (csr.rs:1347-1376) for several n in one pass over the rows: out[i * m + r]
 template <typename T>
 sapca_status top_n_device(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v,
@@ -848,6 +948,12 @@ sapca_status sapca_set_omega_f64(sapca_handle h, const double* omega, size_t row
                                                   uint64_t codes_len, uint32_t n_batches, double* mean, double* var,        \
                                                   uint64_t* count) {                                                        \
     return batch_stats_device<T>(h, m, n, nnz, p, i, v, grouped_axis, codes, codes_len, n_batches, mean, var, count);     \
+  }                                                                                                                      \
+  sapca_status sapca_masked_stats_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, \
+                                                   const int32_t* i, const T* v, int32_t direction, const uint8_t* mask,    \
+                                                   uint64_t mask_len, double* sum, double* sum_squared, uint64_t* count,    \
+                                                   double* var) {                                                           \
+    return masked_stats_device<T>(h, m, n, nnz, p, i, v, direction, mask, mask_len, sum, sum_squared, count, var);        \
   }                                                                                                                      \
   sapca_status sapca_sum_row_n_top_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, \
                                                     const int32_t* i, const T* v, const uint64_t* ns, uint32_t n_ns,        \

@@ -52,13 +52,18 @@ void select_rows(const CsrView<T>& At, const int32_t* rows, int64_t n_sel, int64
 // long accumulators.  scan_values (once all values are on the device) fixes the limb window kept in LDS; add takes the
 // entries [e_lo, e_hi) of rows [r_lo, r_hi); finish writes out[0..n) = sum, out[n..2n) = sum of squares, out[2n..3n) =
 // stored-entry count, each the correctly rounded exact value, and copies the "a value was inf/nan" flag to the host
-// asynchronously.
+// asynchronously.  row_bits (device bitset over the rows, may be null): add takes only the rows whose bit is set, and reads
+// nothing of the others.
 template <typename T> size_t exact_colstats_bytes(int64_t n);
 template <typename T> void exact_colstats_reset(void* work, int64_t n, hipStream_t s);
 template <typename T> void exact_colstats_scan_values(const T* val, int64_t count, int64_t n, void* work, hipStream_t s);
+// (scan_values restricted to the stored values of the rows whose bit is set in row_bits: the window of a row-masked add)
+template <typename T>
+void exact_colstats_scan_rows(const int64_t* ptr, const T* val, int64_t rows, const uint32_t* row_bits, int64_t n, void* work,
+                              hipStream_t s);
 template <typename T>
 void exact_colstats_add(const int64_t* ptr, const int32_t* idx, const T* val, int64_t r_lo, int64_t r_hi, int64_t e_lo, int64_t e_hi,
-                        int64_t n, void* work, hipStream_t s);
+                        int64_t n, void* work, hipStream_t s, const uint32_t* row_bits = nullptr);
 template <typename T> void exact_colstats_finish(void* work, int64_t n, double* out, int* nonfinite_host, hipStream_t s);
 // out_a[where[j]] = a[where[j]], out_b[where[j]] = b[where[j]]   (the selected positions of two full-width arrays)
 void copy_selected(const double* a, const double* b, const int32_t* where, int64_t count, double* out_a, double* out_b, hipStream_t s);
@@ -99,6 +104,14 @@ void batch_row_stats(const CsrView<T>& R, const int32_t* codes, int lo, int nb, 
 // out[i * A.rows + r] = sum of the min(ns[i], length of row r) largest stored values of row r (f64); ns: device, n_ns
 template <typename T>
 void row_top_n(const CsrView<T>& A, const uint64_t* ns, int n_ns, double* out, hipStream_t s);
+
+// ---- maskedstats.hip: masked and stored-entry statistics (MatrixSum / MatrixNonZero / MatrixVariance *_masked, *_chunk) ----
+// Per row r of A, over its stored entries e whose column's bit (col_bits[c / 32] >> c % 32) & 1 is set (all of them when
+// col_bits is null): cnt[r] = their count, sum[r] / sumsq[r] = their sum / sum of squares, m2[r] = sum (x - sum / cnt)^2
+// (two passes, f64).  Any output may be null.
+template <typename T>
+void masked_row_stats(const CsrView<T>& A, const uint32_t* col_bits, double* sum, double* sumsq, double* m2, uint32_t* cnt,
+                      hipStream_t s);
 
 // dst[0 .. bytes) = src[0 .. bytes) by a 16-byte-per-lane streaming kernel (the attainable-HBM-rate probe of sapca_measure_copy_gbs)
 void stream_copy16(const void* src, void* dst, int64_t bytes, hipStream_t s);

@@ -85,12 +85,38 @@ __global__ void __launch_bounds__(256) max_exponent_kernel(const T* __restrict__
   if ((threadIdx.x & 63) == 0 && best > 0) atomicMax(emax, best);
 }
 
-// one workgroup: columns [tile * kTileCols, ..) of rows [r_lo + group * rows_per_group, ..), entries inside [e_lo, e_hi)
+// the same over the stored values of the rows whose bit is set in row_bits, one wave per row
 template <typename T>
+__global__ void __launch_bounds__(256) max_exponent_rows_kernel(const int64_t* __restrict__ ptr, const T* __restrict__ val, int64_t rows,
+                                                                const uint32_t* __restrict__ row_bits, int* __restrict__ emax) {
+  using E = Exact<T>;
+  using Bits = typename E::Bits;
+  int best = 0;
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x / 64);
+  for (int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / 64; r < rows; r += nwaves) {
+    if (!((row_bits[r >> 5] >> (r & 31)) & 1u)) continue;   // (wave-uniform)
+    const int64_t e1 = ptr[r + 1];
+    for (int64_t e = ptr[r] + lane; e < e1; e += 64) {
+      Bits b;
+      const T v = val[e];
+      __builtin_memcpy(&b, &v, sizeof(T));
+      const int ef = (int)((b >> E::kMant) & (Bits)E::kEmax);
+      if (ef != E::kEmax) best = max(best, ef);
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o));
+  if (lane == 0 && best > 0) atomicMax(emax, best);
+}
+
+// one workgroup: columns [tile * kTileCols, ..) of rows [r_lo + group * rows_per_group, ..), entries inside [e_lo, e_hi)
+// (kRowMask: only the rows r whose bit (row_bits[r / 32] >> r % 32) & 1 is set; nothing of the other rows is read)
+template <typename T, bool kRowMask>
 __global__ void __launch_bounds__(kThreads)
 colstats_tile_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx, const T* __restrict__ val, int64_t r_lo,
                      int64_t r_hi, int64_t rows_per_group, int64_t e_lo, int64_t e_hi, int64_t n, const int* __restrict__ emax,
-                     unsigned long long* __restrict__ limbs, unsigned* __restrict__ cnt, int* __restrict__ nonfinite) {
+                     unsigned long long* __restrict__ limbs, unsigned* __restrict__ cnt, int* __restrict__ nonfinite,
+                     const uint32_t* __restrict__ row_bits) {
   using E = Exact<T>;
   using Bits = typename E::Bits;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -109,6 +135,7 @@ colstats_tile_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict_
   // entries), then the segment 64 entries at a time
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int64_t r = g_lo + wave; r < g_hi; r += kThreads / 64) {
+    if (kRowMask && !((row_bits[r >> 5] >> (r & 31)) & 1u)) continue;   // (wave-uniform)
     const int64_t hi = min(ptr[r + 1], e_hi);
     int64_t a = max(ptr[r], e_lo), b = hi;
     while (a < b) {
@@ -252,23 +279,42 @@ void exact_colstats_scan_values(const T* val, int64_t count, int64_t n, void* wo
 }
 
 template <typename T>
+void exact_colstats_scan_rows(const int64_t* ptr, const T* val, int64_t rows, const uint32_t* row_bits, int64_t n, void* work,
+                              hipStream_t s) {
+  if (rows <= 0 || n <= 0) return;
+  unsigned long long* limbs;
+  unsigned* cnt;
+  int *flag, *emax;
+  split<T>(work, n, limbs, cnt, flag, emax);
+  hipLaunchKernelGGL((max_exponent_rows_kernel<T>), dim3((unsigned)std::min<int64_t>((rows + 3) / 4, 4096)), dim3(256), 0, s, ptr, val,
+                     rows, row_bits, emax);
+  SAPCA_HIP(hipGetLastError());
+}
+
+template <typename T>
 void exact_colstats_add(const int64_t* ptr, const int32_t* idx, const T* val, int64_t r_lo, int64_t r_hi, int64_t e_lo, int64_t e_hi,
-                        int64_t n, void* work, hipStream_t s) {
+                        int64_t n, void* work, hipStream_t s, const uint32_t* row_bits) {
   if (e_hi <= e_lo || r_hi <= r_lo || n <= 0) return;
   unsigned long long* limbs;
   unsigned* cnt;
   int *flag, *emax;
   split<T>(work, n, limbs, cnt, flag, emax);
-  static LdsAttrState attr;
-  ensure_dynamic_lds(reinterpret_cast<const void*>(&colstats_tile_kernel<T>), kTileLds, attr);
+  static LdsAttrState attr, attr_masked;
+  const void* kernel = row_bits ? reinterpret_cast<const void*>(&colstats_tile_kernel<T, true>)
+                                : reinterpret_cast<const void*>(&colstats_tile_kernel<T, false>);
+  ensure_dynamic_lds(kernel, kTileLds, row_bits ? attr_masked : attr);
   const int64_t tiles = (n + kTileCols - 1) / kTileCols;
   // about 1024 workgroups per chunk, at least 64 rows (four per wave) in each
   const int64_t rows = r_hi - r_lo;
   int64_t groups = std::max<int64_t>(1, std::min<int64_t>((1024 + tiles - 1) / tiles, (rows + 63) / 64));
   groups = std::min<int64_t>(groups, 65535);
   const int64_t rows_per_group = (rows + groups - 1) / groups;
-  hipLaunchKernelGGL((colstats_tile_kernel<T>), dim3((unsigned)tiles, (unsigned)groups), dim3(kThreads), kTileLds, s, ptr, idx, val, r_lo,
-                     r_hi, rows_per_group, e_lo, e_hi, n, emax, limbs, cnt, flag);
+  if (row_bits)
+    hipLaunchKernelGGL((colstats_tile_kernel<T, true>), dim3((unsigned)tiles, (unsigned)groups), dim3(kThreads), kTileLds, s, ptr, idx,
+                       val, r_lo, r_hi, rows_per_group, e_lo, e_hi, n, emax, limbs, cnt, flag, row_bits);
+  else
+    hipLaunchKernelGGL((colstats_tile_kernel<T, false>), dim3((unsigned)tiles, (unsigned)groups), dim3(kThreads), kTileLds, s, ptr, idx,
+                       val, r_lo, r_hi, rows_per_group, e_lo, e_hi, n, emax, limbs, cnt, flag, row_bits);
   SAPCA_HIP(hipGetLastError());
 }
 
@@ -289,8 +335,9 @@ void exact_colstats_finish(void* work, int64_t n, double* out, int* nonfinite_ho
   template size_t exact_colstats_bytes<T>(int64_t);                                                                      \
   template void exact_colstats_reset<T>(void*, int64_t, hipStream_t);                                                    \
   template void exact_colstats_scan_values<T>(const T*, int64_t, int64_t, void*, hipStream_t);                           \
+  template void exact_colstats_scan_rows<T>(const int64_t*, const T*, int64_t, const uint32_t*, int64_t, void*, hipStream_t); \
   template void exact_colstats_add<T>(const int64_t*, const int32_t*, const T*, int64_t, int64_t, int64_t, int64_t, int64_t, void*, \
-                                      hipStream_t);                                                                      \
+                                      hipStream_t, const uint32_t*);                                                                      \
   template void exact_colstats_finish<T>(void*, int64_t, double*, int*, hipStream_t);
 INST(float)
 INST(double)

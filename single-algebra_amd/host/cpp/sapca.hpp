@@ -67,6 +67,7 @@ template <typename T> struct ResidentAbi;
     static sapca_status log1p(sapca_handle h, uint64_t nnz, T* v) { return sapca_log1p_csr_device_##SUF(h, nnz, v); } \
     static sapca_status stats(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, int32_t d, double* s, double* q, uint64_t* c, T* lo, T* hi) { return sapca_stats_csr_device_##SUF(h, m, n, nnz, p, i, v, d, s, q, c, lo, hi); } \
     static sapca_status batch_stats(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, int32_t ax, const int32_t* c, uint64_t cl, uint32_t nb, double* mean, double* var, uint64_t* cnt) { return sapca_batch_stats_csr_device_##SUF(h, m, n, nnz, p, i, v, ax, c, cl, nb, mean, var, cnt); } \
+    static sapca_status masked_stats(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, int32_t d, const uint8_t* mk, uint64_t ml, double* s, double* q, uint64_t* c, double* var) { return sapca_masked_stats_csr_device_##SUF(h, m, n, nnz, p, i, v, d, mk, ml, s, q, c, var); } \
     static sapca_status n_top(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, const uint64_t* ns, uint32_t k, double* out) { return sapca_sum_row_n_top_csr_device_##SUF(h, m, n, nnz, p, i, v, ns, k, out); } \
   };
 SAPCA_RES(f32, float)
@@ -108,6 +109,28 @@ class ResidentCsr {
     check(ResidentAbi<T>::n_top(h_, m_, n_, nnz_, ptr_, idx_, val_, &n, 1, out.data()));
     return out;
   }
+  // *_masked (csr.rs:153-252, 418-556, 815-914): col = per column over the rows with mask[row] (mask.size() >= m),
+  // row = per row over the columns with mask[col] (mask.size() >= n); f64 sums, stored-entry variance without correction
+  std::vector<uint64_t> nonzero_col_masked(const std::vector<bool>& mask) const { return masked<uint64_t>(Direction::COLUMN, &mask, 2); }
+  std::vector<uint64_t> nonzero_row_masked(const std::vector<bool>& mask) const { return masked<uint64_t>(Direction::ROW, &mask, 2); }
+  std::vector<double> sum_col_masked(const std::vector<bool>& mask) const { return masked<double>(Direction::COLUMN, &mask, 0); }
+  std::vector<double> sum_row_masked(const std::vector<bool>& mask) const { return masked<double>(Direction::ROW, &mask, 0); }
+  std::vector<double> var_col_masked(const std::vector<bool>& mask) const { return masked<double>(Direction::COLUMN, &mask, 3); }
+  std::vector<double> var_row_masked(const std::vector<bool>& mask) const { return masked<double>(Direction::ROW, &mask, 3); }
+  // *_chunk (csr.rs:124-150, 394-416, 728-813, 939-1008): in place on the caller's vectors, as the reference does; where
+  // the reference would index out of bounds, Error(SAPCA_ERR_ARG) before anything is written
+  template <typename U> void nonzero_col_chunk(std::vector<U>& ref) const { add_into(ref, nonzero(Direction::COLUMN)); }
+  template <typename U> void nonzero_row_chunk(std::vector<U>& ref) const { add_into(ref, nonzero(Direction::ROW)); }
+  template <typename U> void sum_col_chunk(std::vector<U>& ref) const { add_into(ref, sum(Direction::COLUMN)); }
+  template <typename U> void sum_row_chunk(std::vector<U>& ref) const {
+    if (ref.size() < m_) throw Error(SAPCA_ERR_ARG, "sum_row_chunk: reference length " + std::to_string(ref.size()) + " is less than number of rows " + std::to_string(m_));
+    const std::vector<double> s = sum(Direction::ROW);
+    for (uint64_t r = 0; r < m_; ++r) ref[r] = (U)s[r];
+  }
+  template <typename U> void var_col_chunk(std::vector<U>& ref) const { var_into(ref, Direction::COLUMN, "columns"); }
+  template <typename U> void var_row_chunk(std::vector<U>& ref) const { var_into(ref, Direction::ROW, "rows"); }
+  template <typename U> void min_max_col_chunk(std::vector<U>& mins, std::vector<U>& maxs) const { min_max_into(mins, maxs, Direction::COLUMN, true); }
+  template <typename U> void min_max_row_chunk(std::vector<U>& mins, std::vector<U>& maxs) const { min_max_into(mins, maxs, Direction::ROW, false); }
   const int64_t* row_offsets() const { return ptr_; }
   const int32_t* col_indices() const { return idx_; }
   T* values() const { return val_; }
@@ -115,6 +138,48 @@ class ResidentCsr {
  private:
   void check(sapca_status st) const {
     if (st != SAPCA_OK) throw Error(st, sapca_last_error(h_));
+  }
+  // what: 0 sum, 1 sum of squares, 2 count, 3 variance
+  template <typename R>
+  std::vector<R> masked(Direction d, const std::vector<bool>* mask, int what) const {
+    const uint64_t len = d == Direction::COLUMN ? n_ : m_;
+    std::vector<uint8_t> mk;
+    if (mask) mk.assign(mask->begin(), mask->end());
+    std::vector<double> s(len), q(len), var(len);
+    std::vector<uint64_t> c(len);
+    check(ResidentAbi<T>::masked_stats(h_, m_, n_, nnz_, ptr_, idx_, val_, (int32_t)d, mask ? mk.data() : nullptr, mk.size(), s.data(),
+                                       q.data(), c.data(), var.data()));
+    const std::vector<double>& f = what == 0 ? s : what == 1 ? q : var;
+    return what == 2 ? std::vector<R>(c.begin(), c.end()) : std::vector<R>(f.begin(), f.end());
+  }
+  template <typename U, typename V>
+  static void add_into(std::vector<U>& ref, const std::vector<V>& v) {
+    for (size_t j = 0; j < ref.size() && j < v.size(); ++j) ref[j] += (U)v[j];
+  }
+  template <typename U>
+  void var_into(std::vector<U>& ref, Direction d, const char* what) const {
+    const uint64_t len = d == Direction::COLUMN ? n_ : m_;
+    if (ref.size() != len)
+      throw Error(SAPCA_ERR_ARG, "Reference slice length " + std::to_string(ref.size()) + " does not match number of " + what + " " + std::to_string(len));
+    const std::vector<double> v = masked<double>(d, nullptr, 3);
+    for (uint64_t j = 0; j < len; ++j) ref[j] = (U)v[j];
+  }
+  template <typename U>
+  void min_max_into(std::vector<U>& mins, std::vector<U>& maxs, Direction d, bool narrow) const {
+    const uint64_t len = d == Direction::COLUMN ? n_ : m_;
+    std::vector<uint64_t> c(len);
+    std::vector<T> lo(len), hi(len);
+    check(ResidentAbi<T>::stats(h_, m_, n_, nnz_, ptr_, idx_, val_, (int32_t)d, nullptr, nullptr, c.data(), lo.data(), hi.data()));
+    for (uint64_t j = 0; j < len; ++j)
+      if (c[j] && (j >= mins.size() || j >= maxs.size()))
+        throw Error(SAPCA_ERR_ARG, std::string(narrow ? "min_max_col_chunk: column " : "min_max_row_chunk: row ") + std::to_string(j) +
+                                       " has stored entries but the reference is shorter");
+    for (uint64_t j = 0; j < len; ++j) {
+      if (!c[j]) continue;
+      const U a = (U)lo[j], b = (U)hi[j];
+      if (!narrow || a < mins[j]) mins[j] = a;   // column chunk: a running min / max; row chunk: overwritten
+      if (!narrow || b > maxs[j]) maxs[j] = b;
+    }
   }
   template <typename B>
   std::unordered_map<B, std::vector<double>> grouped(const std::vector<B>& batches, int32_t axis, bool variance) const {

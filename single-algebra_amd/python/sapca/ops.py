@@ -208,6 +208,132 @@ class ResidentCsr:
             *self._args(), _p(ns, C.c_uint64), C.c_uint32(ns.size), _p(out, C.c_double)))
         return out[0] if single else out
 
+    # ---- masked and chunk statistics (MatrixNonZero / MatrixSum / MatrixVariance *_masked, *_chunk; MatrixMinMax *_chunk) ----
+    def masked_stats(self, direction, mask=None):
+        """sapca_masked_stats_csr_device_*: (sum, sum_squared, count, var) per row (ROW; `mask` over the columns) or per
+        column (COLUMN; `mask` over the rows), over the kept stored entries; mask None keeps everything.  var is the
+        stored-entry variance (no correction, 0 where count is 0).  f64 sums; count u64."""
+        suf, _ = _SUF[self.dtype]
+        m, n = self.shape
+        ln = n if int(direction) == COLUMN else m
+        out = [np.zeros(ln), np.zeros(ln), np.zeros(ln, dtype=np.uint64), np.zeros(ln)]
+        if mask is None:
+            mp, ml = None, 0
+        else:
+            mk = np.ascontiguousarray(np.asarray(mask, dtype=bool).reshape(-1), dtype=np.uint8)
+            mp, ml = _p(mk, C.c_uint8), mk.size
+        L.check(self._s._h, getattr(L.load(), f"sapca_masked_stats_csr_device_{suf}")(
+            *self._args(), C.c_int32(int(direction)), mp, C.c_uint64(ml), _p(out[0], C.c_double), _p(out[1], C.c_double),
+            _p(out[2], C.c_uint64), _p(out[3], C.c_double)))
+        return tuple(out)
+
+    def _masked(self, direction, mask, what):
+        want = self.shape[0] if int(direction) == COLUMN else self.shape[1]
+        if len(mask) < want:   # the reference's message (its Err), before any library call
+            raise ValueError(f"Mask length ({len(mask)}) is less than number of {'rows' if direction == COLUMN else 'columns'} ({want})")
+        return self.masked_stats(direction, mask)[what]
+
+    def nonzero_col_masked(self, mask):
+        """MatrixNonZero::nonzero_col_masked (csr.rs:153-186): per column, the stored entries of the rows with mask[row]"""
+        return self._masked(COLUMN, mask, 2)
+
+    def nonzero_row_masked(self, mask):
+        """MatrixNonZero::nonzero_row_masked (csr.rs:188-252): per row, the stored entries of the columns with mask[col]"""
+        return self._masked(ROW, mask, 2)
+
+    def sum_col_masked(self, mask):
+        """MatrixSum::sum_col_masked (csr.rs:418-488): per column, the sum over the rows with mask[row] (exact, correctly
+        rounded f64 sums)"""
+        return self._masked(COLUMN, mask, 0)
+
+    def sum_row_masked(self, mask):
+        """MatrixSum::sum_row_masked (csr.rs:490-556): per row, the sum over the columns with mask[col] (f64)"""
+        return self._masked(ROW, mask, 0)
+
+    def var_col_masked(self, mask):
+        """MatrixVariance::var_col_masked (csr.rs:815-862): per column, sumsq / count - mean^2 over the kept stored entries"""
+        return self._masked(COLUMN, mask, 3)
+
+    def var_row_masked(self, mask):
+        """MatrixVariance::var_row_masked (csr.rs:864-914): per row, sum (x - mean)^2 / count over the kept stored entries"""
+        return self._masked(ROW, mask, 3)
+
+    # The chunk family updates the caller's numpy array in place and returns it.  Where the reference would index out of
+    # bounds (a panic), these raise ValueError before touching it.
+    def nonzero_col_chunk(self, reference):
+        """MatrixNonZero::nonzero_col_chunk (csr.rs:124-134): reference[c] += stored entries of column c, c < len"""
+        k = min(len(reference), self.shape[1])
+        reference[:k] += self.stats(COLUMN)[2][:k].astype(reference.dtype)
+        return reference
+
+    def nonzero_row_chunk(self, reference):
+        """MatrixNonZero::nonzero_row_chunk (csr.rs:136-150): reference[r] += stored entries of row r, r < len"""
+        k = min(len(reference), self.shape[0])
+        reference[:k] += self.stats(ROW)[2][:k].astype(reference.dtype)
+        return reference
+
+    def sum_col_chunk(self, reference):
+        """MatrixSum::sum_col_chunk (csr.rs:394-405): reference[c] += sum of column c, c < len (the column's f64 sum is
+        added once; the reference adds entry by entry in T)"""
+        k = min(len(reference), self.shape[1])
+        reference[:k] += self.stats(COLUMN)[0][:k].astype(reference.dtype)
+        return reference
+
+    def sum_row_chunk(self, reference):
+        """MatrixSum::sum_row_chunk (csr.rs:407-416): reference[r] = sum of row r, overwritten; len must be >= m"""
+        m = self.shape[0]
+        if len(reference) < m:
+            raise ValueError(f"sum_row_chunk: reference length {len(reference)} is less than number of rows {m}")
+        reference[:m] = self.stats(ROW)[0]
+        return reference
+
+    def var_col_chunk(self, reference):
+        """MatrixVariance::var_col_chunk (csr.rs:728-771): reference = per-column stored-entry variance (sumsq / count -
+        mean^2); len must be n"""
+        n = self.shape[1]
+        if len(reference) != n:
+            raise ValueError(f"Reference slice length {len(reference)} does not match number of columns {n}")
+        reference[:] = self.masked_stats(COLUMN)[3]
+        return reference
+
+    def var_row_chunk(self, reference):
+        """MatrixVariance::var_row_chunk (csr.rs:773-813): reference = per-row stored-entry variance (two passes); len
+        must be m"""
+        m = self.shape[0]
+        if len(reference) != m:
+            raise ValueError(f"Reference slice length {len(reference)} does not match number of rows {m}")
+        reference[:] = self.masked_stats(ROW)[3]
+        return reference
+
+    def min_max_col_chunk(self, reference):
+        """MatrixMinMax::min_max_col_chunk (csr.rs:939-973): reference = (mins, maxs); each column's stored values narrow
+        mins[c] / maxs[c] (a nan in the arrays stays, nan values never win).  Every column with a stored entry must
+        lie inside both arrays."""
+        mins, maxs = reference
+        _, _, nz, lo, hi = self.stats(COLUMN)
+        has = np.flatnonzero(nz)
+        if has.size and has[-1] >= min(len(mins), len(maxs)):
+            raise ValueError(f"min_max_col_chunk: column {int(has[-1])} has stored entries but the reference arrays are "
+                             f"{len(mins)} / {len(maxs)} long")
+        lo, hi = lo[has], hi[has]
+        mins[has] = np.where(lo < mins[has], lo, mins[has])
+        maxs[has] = np.where(hi > maxs[has], hi, maxs[has])
+        return reference
+
+    def min_max_row_chunk(self, reference):
+        """MatrixMinMax::min_max_row_chunk (csr.rs:975-1008): reference = (mins, maxs); rows with stored entries overwrite
+        mins[r] / maxs[r] with their own min / max, the others are left alone.  Every row with a stored entry must lie
+        inside both arrays."""
+        mins, maxs = reference
+        _, _, nz, lo, hi = self.stats(ROW)
+        has = np.flatnonzero(nz)
+        if has.size and has[-1] >= min(len(mins), len(maxs)):
+            raise ValueError(f"min_max_row_chunk: row {int(has[-1])} has stored entries but the reference arrays are "
+                             f"{len(mins)} / {len(maxs)} long")
+        mins[has] = lo[has]
+        maxs[has] = hi[has]
+        return reference
+
     def values(self):
         """the current (device) values, copied to the host"""
         return self.as_device_csr().values.cpu().numpy()
