@@ -4,24 +4,32 @@
     python bench.py --gpus N --steps K --warmup W            (N > 1: starts its own N ranks through torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus N --scaling strong [--workload c4|c5]   (one matrix split over the ranks: BASELINE configs[3], [4])
+    python bench.py --full ...                               (also everything beyond the headline, below)
 
 A "step" is one fit_transform of the hot path over a device-resident CSR (inputs already in
 HBM when the timed region starts).  At N=1 the workload is BASELINE.json configs[1] (C2:
-200k x 20k f32, ~97 % sparse, randomized SVD k=50, p=10, q=4, QR normalizer); the line also
-carries every other BASELINE config on the one GPU as a sub-record: `c3` (configs[2]: masked f64
-Lanczos, 3 steps, roofline per Lanczos step), `c4_1gpu` (configs[3]'s 1M x 30k matrix: the shape
-north_star's roofline target is quoted on, 3 steps) and `c5_1gpu` (configs[4]: 2M x 50k, k=100,
-2 steps, sweep roofline + executed slots per stored entry).  For N>1 the default is BASELINE configs[3]
-STRONG-scaled: the 1M x 30k matrix split by rows over the ranks (`"scaling": "strong"`), rows
-range-partitioned, panels all-reduced over RCCL inside the library; `--scaling weak` gives
-every rank a 200k-row shard of the (N*200k) x 20k matrix instead.
+200k x 20k f32, ~97 % sparse, randomized SVD k=50, p=10, q=4, QR normalizer).  For N>1 the
+default is BASELINE configs[3] STRONG-scaled: the 1M x 30k matrix split by rows over the ranks
+(`"scaling": "strong"`), rows range-partitioned, panels all-reduced over RCCL inside the library;
+`--scaling weak` gives every rank a 200k-row shard of the (N*200k) x 20k matrix instead.
 
-One JSON line on rank 0: metric/value = whole-job algorithmic GB/s of fit_transform (SURVEY.md
-§8d formula / wall-clock), ms_per_step = fit_transform wall-clock, `roofline` for the dominant
-kernel (the sparse x dense sweep, HIP-event timed on the library's stream), `cpu_baseline` = the
-C/OpenMP restatement of the reference algorithm timed on the WHOLE workload on the box's host
-cores (rank 0, N=1 only), `cpu_baseline_reference` = the reference's own crate (baseline/rust_ref)
-where a Rust toolchain with a populated registry exists, else {"available": false, "reason": ...}.
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints one JSON line on
+rank 0: metric/value = whole-job algorithmic GB/s of fit_transform (SURVEY.md §8d formula /
+wall-clock), ms_per_step = fit_transform wall-clock, `roofline` for the dominant kernel (the sparse
+x dense sweep, HIP-event timed on the library's stream during the timed steps; `traffic` from the
+committed profiles/traffic.json).
+
+`--full` adds what takes runs of its own.  At N=1 on C2: every other BASELINE config on the one GPU
+as a sub-record -- `c3` (configs[2]: masked f64 Lanczos, 3 steps, roofline per Lanczos step),
+`c4_1gpu` (configs[3]'s 1M x 30k matrix: the shape north_star's roofline target is quoted on,
+3 steps) and `c5_1gpu` (configs[4]: 2M x 50k, k=100, 2 steps, sweep roofline + executed slots per
+stored entry); `roofline.traffic` measured in the run (two rocprofv3 --pmc child passes); the
+device's measured copy rate; `e2e_host_ms` (the host entry point); `cpu_baseline` = the C/OpenMP
+restatement of the reference algorithm timed on the WHOLE workload on the box's host cores (rank 0,
+N=1 only), `cpu_baseline_c1` (configs[0] on both sides) and `cpu_baseline_reference` = the
+reference's own crate (baseline/rust_ref) where a Rust toolchain with a populated registry exists,
+else {"available": false, "reason": ...}.  At N>1, `--weak-c2` adds the weak-scaled C2 shards.
+The --no-* options leave parts out of a --full run.
 """
 import argparse
 import json
@@ -205,7 +213,7 @@ def bench_lanczos(args, rank, local_rank, world, dev):
 
 def measure_traffic(workload, n_sweeps, timeout_s=150):
     """HBM-side bytes of one sweep, measured in THIS run: two rocprofv3 --pmc passes (FETCH_SIZE and WRITE_SIZE cannot share a
-    pass) over one step of the same workload, each a child process (`rocprofv3 ... -- python3 bench.py --steps 1 --no-extras`);
+    pass) over one step of the same workload, each a child process (`rocprofv3 ... -- python3 bench.py --steps 1`, a plain run);
     the sweep kernels' counters are summed over the step and divided by its sweeps.  Units and gfx950 corrections as
     MI355X_MICROARCH.md prescribes (KB -> bytes; FETCH_SIZE doubled: an upper estimate for this kernel's 8-byte-per-lane
     entry loads, see profiles/traffic.json).  Returns (bytes per sweep, how) or (None, why not)."""
@@ -221,7 +229,7 @@ def measure_traffic(workload, n_sweeps, timeout_s=150):
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="sapca_pmc_", dir="/tmp")
         cmd = [rp, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-               "--workload", workload, "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-extras"]
+               "--workload", workload, "--steps", "1", "--warmup", "0"]
         try:
             subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
                            timeout=timeout_s)
@@ -440,7 +448,7 @@ def sub_record(r):
                          "launches_timed": len(r["sweep_ms"])}}
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -451,21 +459,34 @@ def main():
                          "BASELINE.json configs[3]); weak: every rank holds the workload's rows (the default at one GPU, workload c2: "
                          "BASELINE.json configs[1])")
     ap.add_argument("--spmm-variant", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run what takes runs of its own: the CPU baselines, the host path, the secondary "
+                         "workloads, the rocprofv3 --pmc traffic passes and the measured copy rate (the --no-* options leave parts out)")
     ap.add_argument("--weak-c2", action="store_true",
-                    help="N > 1: after the strong-scaled C4 headline also run 3 steps of weak-scaled C2 shards (a `weak_c2` record)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="do not measure roofline.traffic with two rocprofv3 --pmc child runs (use the committed figure)")
+                    help="--full, N > 1: after the strong-scaled C4 headline also run 3 steps of weak-scaled C2 shards (a `weak_c2` record)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baselines and no probe for the reference binary")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: do not measure roofline.traffic with two rocprofv3 --pmc child runs (use the committed figure)")
     ap.add_argument("--cpu-sample-rows", type=int, default=0,
-                    help="time the CPU restatement on the first ROWS rows of the workload instead of all of it (C2 whole: about a minute)")
+                    help="--full: time the CPU restatement on the first ROWS rows of the workload instead of all of it (C2 whole: about a minute)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the measured copy rate, the host-path run, the C1 comparison and the secondary workloads "
-                         "(c4_1gpu at one GPU)")
+                    help="--full: skip the measured copy rate, the host-path run, the C1 comparison, the traffic passes and the "
+                         "secondary workloads (c3, c4_1gpu, c5_1gpu at one GPU)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps write what the last one computed (the projection, a fixed row sample of it when "
                          "large, and the fitted fields; rank 0's rows at N > 1) as DIR/<name>.npy, at most 64 MB in all")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:
+        if args.weak_c2 or args.cpu_sample_rows:
+            ap.error("--weak-c2 and --cpu-sample-rows shape parts of a --full run: add --full")
+        # a plain run is what every change's headline is measured with: nothing beyond set-up, warm-up and the timed steps
+        args.no_cpu_baseline = args.no_extras = args.no_traffic = True
+    return args
+
+
+def main():
+    args = parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)

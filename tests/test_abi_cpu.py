@@ -211,3 +211,23 @@ def test_bench_probes_for_the_reference_binary_and_says_why_not(monkeypatch):
     assert got is None and "rocprofv3" in why
     sweep, total = bench.alg_bytes(200_000, 20_000, 119_990_071, 60, 50, 4)
     assert sweep == 119_990_071 * 8 + 200_001 * 8 + 20_000 * 60 * 4 + 200_000 * 60 * 4 == 1_014_320_576   # SURVEY.md 8d formula at C2
+
+
+def test_plain_bench_run_measures_the_headline_alone():
+    """bench.py without --full runs no CPU baseline, host path, secondary workload, counter pass or copy-rate run; --full
+    runs them all unless a --no-* option leaves one out, and the options that only shape a --full run need it."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    skipped = ("no_cpu_baseline", "no_extras", "no_traffic")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and all(getattr(plain, f) for f in skipped)
+    assert (plain.steps, plain.warmup, plain.dump_outputs) == (20, 5, None)
+    full = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert full.full and not any(getattr(full, f) for f in skipped)
+    trimmed = bench.parse_args(["--full", "--no-traffic", "--cpu-sample-rows", "1000"])
+    assert trimmed.no_traffic and not trimmed.no_extras and not trimmed.no_cpu_baseline and trimmed.cpu_sample_rows == 1000
+    for only_full in (["--weak-c2"], ["--cpu-sample-rows", "1000"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(only_full)

@@ -2,7 +2,7 @@
 # usage (GPU box): bash tools/final_profiles.sh <round tag, e.g. r02>  -- the bench lines and rocprofv3 summaries kept under profiles/
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 tag=$1; out=gpurun_out/final; mkdir -p $out
-python3 bench.py > $out/${tag}_c2_bench.json 2> $out/bench.err || exit 1
+python3 bench.py --full > $out/${tag}_c2_bench.json 2> $out/bench.err || exit 1
 ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_c2 -o c2 -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-extras > $GRAFT_REPO_ROOT/$out/${tag}_c2_bench_profiled.json 2>/dev/null ) || exit 1
 cp $(find /tmp/prof_c2 -name "*kernel_stats.csv" | head -1) $out/${tag}_c2_kernel_stats.csv
 for wl in c3 c4 c5; do
