@@ -106,51 +106,44 @@ CsrView<T> upload(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const ui
   int* flag = reinterpret_cast<int*>(d64 + m + 1);
   SAPCA_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
   SAPCA_HIP(hipMemcpyAsync(d64, row_offsets, (m + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-  static const bool on_device = sapca::dbg_env("SAPCA_UPLOAD_NARROW_ON_DEVICE") != nullptr;   // the first version: ship u64, narrow on the GPU
   bool bad_host = false, stats_here = false;
   void* stats_work = nullptr;
-  if (nnz == 0 || !on_device) sapca::k::narrow_indices(d64, d64, (int64_t)m, 0, (int64_t)n, d_ptr, d_idx, flag, s);   // row offsets only
+  sapca::k::narrow_indices(d64, d64, (int64_t)m, 0, (int64_t)n, d_ptr, d_idx, flag, s);   // row offsets only
   if (nnz) {
     SAPCA_HIP(hipMemcpyAsync(d_val, values, nnz * sizeof(T), hipMemcpyHostToDevice, s));
-    if (on_device) {
-      uint64_t* d64i = h->up64i.as<uint64_t>(nnz);
-      SAPCA_HIP(hipMemcpyAsync(d64i, col_indices, nnz * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-      sapca::k::narrow_indices(d64, d64i, (int64_t)m, (int64_t)nnz, (int64_t)n, d_ptr, d_idx, flag, s);
-    } else {
-      const unsigned nthreads = std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
-      const size_t chunk = std::min<size_t>(kUpChunk, nnz);
-      for (int b = 0; b < 2; ++b) {
-        h->up_stage[b].ensure(chunk * sizeof(int32_t));
-        if (!h->up_done[b]) SAPCA_HIP(hipEventCreateWithFlags(&h->up_done[b], hipEventDisableTiming));
-      }
-      static const bool stats_off = sapca::dbg_env("SAPCA_UPLOAD_STATS_OFF") != nullptr;
-      stats_here = with_stats && !stats_off && n > 0 && sapca::k::exact_colstats_bytes<T>((int64_t)n) <= ((size_t)1 << 30);
-      if (stats_here) {
-        ensure_side_stream(h);
-        stats_work = h->up_stats.work.ensure(sapca::k::exact_colstats_bytes<T>((int64_t)n));
-        sapca::k::exact_colstats_reset<T>(stats_work, (int64_t)n, h->stream2);
-        SAPCA_HIP(hipEventRecord(h->ev_fork, s));                        // row offsets and values are on the device
-        SAPCA_HIP(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
-        sapca::k::exact_colstats_scan_values<T>(d_val, (int64_t)nnz, (int64_t)n, stats_work, h->stream2);
-      }
-      bool used[2] = {false, false};
-      int b = 0;
-      for (size_t off = 0; off < nnz; off += chunk, b ^= 1) {
-        const size_t cnt = std::min<size_t>(chunk, nnz - off);
-        if (used[b]) SAPCA_HIP(hipEventSynchronize(h->up_done[b]));   // its DMA has drained
-        int32_t* stage = static_cast<int32_t*>(h->up_stage[b].p);
-        bad_host |= narrow_chunk(col_indices + off, stage, cnt, n, nthreads);
-        SAPCA_HIP(hipMemcpyAsync(d_idx + off, stage, cnt * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        SAPCA_HIP(hipEventRecord(h->up_done[b], s));
-        used[b] = true;
-        if (stats_here) {   // this chunk's entries (the values all went first) feed the accumulators while the next chunk crosses
-          SAPCA_HIP(hipStreamWaitEvent(h->stream2, h->up_done[b], 0));
-          const uint64_t* ro_end = row_offsets + m + 1;
-          const int64_t r_lo = (int64_t)(std::upper_bound(row_offsets, ro_end, (uint64_t)off) - row_offsets) - 1;
-          const int64_t r_hi = (int64_t)(std::lower_bound(row_offsets, ro_end, (uint64_t)(off + cnt)) - row_offsets);
-          sapca::k::exact_colstats_add<T>(d_ptr, d_idx, d_val, r_lo, std::min<int64_t>(r_hi, (int64_t)m), (int64_t)off,
-                                          (int64_t)(off + cnt), (int64_t)n, stats_work, h->stream2);
-        }
+    const unsigned nthreads = std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
+    const size_t chunk = std::min<size_t>(kUpChunk, nnz);
+    for (int b = 0; b < 2; ++b) {
+      h->up_stage[b].ensure(chunk * sizeof(int32_t));
+      if (!h->up_done[b]) SAPCA_HIP(hipEventCreateWithFlags(&h->up_done[b], hipEventDisableTiming));
+    }
+    static const bool stats_off = sapca::dbg_env("SAPCA_UPLOAD_STATS_OFF") != nullptr;
+    stats_here = with_stats && !stats_off && n > 0 && sapca::k::exact_colstats_bytes<T>((int64_t)n) <= ((size_t)1 << 30);
+    if (stats_here) {
+      ensure_side_stream(h);
+      stats_work = h->up_stats.work.ensure(sapca::k::exact_colstats_bytes<T>((int64_t)n));
+      sapca::k::exact_colstats_reset<T>(stats_work, (int64_t)n, h->stream2);
+      SAPCA_HIP(hipEventRecord(h->ev_fork, s));                        // row offsets and values are on the device
+      SAPCA_HIP(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
+      sapca::k::exact_colstats_scan_values<T>(d_val, (int64_t)nnz, (int64_t)n, stats_work, h->stream2);
+    }
+    bool used[2] = {false, false};
+    int b = 0;
+    for (size_t off = 0; off < nnz; off += chunk, b ^= 1) {
+      const size_t cnt = std::min<size_t>(chunk, nnz - off);
+      if (used[b]) SAPCA_HIP(hipEventSynchronize(h->up_done[b]));   // its DMA has drained
+      int32_t* stage = static_cast<int32_t*>(h->up_stage[b].p);
+      bad_host |= narrow_chunk(col_indices + off, stage, cnt, n, nthreads);
+      SAPCA_HIP(hipMemcpyAsync(d_idx + off, stage, cnt * sizeof(int32_t), hipMemcpyHostToDevice, s));
+      SAPCA_HIP(hipEventRecord(h->up_done[b], s));
+      used[b] = true;
+      if (stats_here) {   // this chunk's entries (the values all went first) feed the accumulators while the next chunk crosses
+        SAPCA_HIP(hipStreamWaitEvent(h->stream2, h->up_done[b], 0));
+        const uint64_t* ro_end = row_offsets + m + 1;
+        const int64_t r_lo = (int64_t)(std::upper_bound(row_offsets, ro_end, (uint64_t)off) - row_offsets) - 1;
+        const int64_t r_hi = (int64_t)(std::lower_bound(row_offsets, ro_end, (uint64_t)(off + cnt)) - row_offsets);
+        sapca::k::exact_colstats_add<T>(d_ptr, d_idx, d_val, r_lo, std::min<int64_t>(r_hi, (int64_t)m), (int64_t)off,
+                                        (int64_t)(off + cnt), (int64_t)n, stats_work, h->stream2);
       }
     }
   }
@@ -683,13 +676,7 @@ sapca_status spmm_host(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, con
     if (!transposed) {
       if (mu) sapca::k::weighted_colsum(X, (int64_t)n, ld, d_mu, cvec, h->scratch, s);
       const sapca::TiledOp* top = nullptr;
-      if constexpr (sizeof(T) == 4) {
-        if (want_tiled) {
-          if (sapca::k::build_tiled(A, false, sapca::k::tiled_geometry((int)l), h->tiled_a, h->tb_a, s)) top = &h->tiled_a;   // else: row kernel
-        }
-      } else {
-        if (want_tiled && sapca::k::build_tiled(A, 64, h->tiled_a, h->tb_a, s)) top = &h->tiled_a;
-      }
+      if (want_tiled && sapca::k::build_tiled(A, 64, h->tiled_a, h->tb_a, s)) top = &h->tiled_a;   // else: row kernel
       sapca::k::spmm(A, top, X, ld, Y, ld, ld, mu ? cvec : nullptr, h->opt.spmm_variant, h->split_scratch, s);
     } else {
       int64_t* at_ptr = h->at_ptr.as<int64_t>(n + 1);
@@ -699,13 +686,7 @@ sapca_status spmm_host(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, con
       CsrView<T> At;
       At.rows = (int64_t)n; At.cols = (int64_t)m; At.nnz = (int64_t)nnz; At.ptr = at_ptr; At.idx = at_idx; At.val = at_val;
       const sapca::TiledOp* top = nullptr;
-      if constexpr (sizeof(T) == 4) {
-        if (want_tiled) {
-          if (sapca::k::build_tiled(At, false, sapca::k::tiled_geometry((int)l), h->tiled_at, h->tb_at, s)) top = &h->tiled_at;
-        }
-      } else {
-        if (want_tiled && sapca::k::build_tiled(At, 64, h->tiled_at, h->tb_at, s)) top = &h->tiled_at;
-      }
+      if (want_tiled && sapca::k::build_tiled(At, 64, h->tiled_at, h->tb_at, s)) top = &h->tiled_at;
       sapca::k::spmm(At, top, X, ld, Y, ld, ld, (const T*)nullptr, h->opt.spmm_variant, h->split_scratch, s);
       if (mu) {
         sapca::k::weighted_colsum(X, (int64_t)m, ld, (const T*)nullptr, svec, h->scratch, s);

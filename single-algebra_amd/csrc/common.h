@@ -119,14 +119,12 @@ struct PinnedBuf {
 struct TiledOp {
   bool valid = false;
   int64_t rows = 0, cols = 0, total_entries = 0;
-  int ldp = 0;              // panel leading dimension (elements) the format was built for: 64 or 128 (f32), 64 (f64)
+  int ldp = 0;              // panel leading dimension (elements) the format was built for: 64
   int elem = 4;             // bytes per value and panel element: 4 (f32) or 8 (f64)
   int tc = 0, nct = 0;      // panel rows per column tile, number of tiles
   int nrb = 0;              // row blocks (one workgroup each)
   int block_rows = 0;       // most rows a block holds (quad format: 256 f64, 512, or 1024 for the DPP-fed sweep with 16 row slots)
   int nsplit = 1, tiles_per_split = 0;
-  int slots = 2;            // lane groups per wave the entry stream was padded for
-  int fmt = 0;              // 0: two half-waves share a row; 1: "quad", one row per 16-lane group
   int tile_bytes = 0;       // LDS bytes of one panel tile (the entry staging takes the rest of the 160 KiB)
   int64_t max_chunk = 0;    // most entries of one (row block, tile): the staged-entry kernels need it to fit their LDS staging
   const int32_t* blk_row0 = nullptr;   // [nrb+1] slot positions

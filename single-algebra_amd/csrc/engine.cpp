@@ -45,7 +45,7 @@ struct SmallLayout {
 template <typename T>
 int staged_sweep_ldp(int64_t rows, int64_t cols, double entries, int64_t l, int spmm_variant) {
   if (spmm_variant == 1 || rows <= 0 || cols <= 0 || l < 1 || l > k::kMaxPanelWidth) return 0;
-  const int ldp = sizeof(T) == 4 ? k::tiled_geometry((int)l) : 64;
+  const int ldp = 64;
   const double row_bytes = (double)ldp * sizeof(T);
   const double tile_bytes = 80.0 * 1024.0, block_rows = row_bytes == 256.0 ? 512.0 : 256.0;
   const double chunks = std::ceil((double)rows / block_rows) * std::ceil((double)cols * row_bytes / tile_bytes);
@@ -140,8 +140,7 @@ void Engine<T>::prepare(H& h, const CsrView<T>& A) {
     const int64_t l = std::min<int64_t>((int64_t)(h.opt.n_components + h.opt.n_oversamples), std::min<int64_t>(m, n_kept));
     if (n_kept > 0) tiled_ldp = staged_sweep_ldp<T>(m, n_kept, (double)nnz * ((double)n_kept / (double)n), l, h.opt.spmm_variant);
   }
-  const bool from_at = dbg_env("SAPCA_TILED_FROM_A") == nullptr;   // A^T's format from the transposed CSR (default) or straight from A
-  const bool at_tile_major = tiled_ldp != 0 && from_at && dbg_env("SAPCA_AT_NATURAL") == nullptr;
+  const bool at_tile_major = tiled_ldp != 0 && dbg_env("SAPCA_AT_NATURAL") == nullptr;
   const int tiled_ldp_words = tiled_ldp * (int)sizeof(T) / 4;   // panel row in 4-byte words: what the tile arithmetic counts in
 
   // mask index maps (sparse_masked/mod.rs:264-271 and the HashMap of :462-466)
@@ -193,9 +192,8 @@ void Engine<T>::prepare(H& h, const CsrView<T>& A) {
   // come from the same kind of pass over A, on the third stream beside the iterations (a Lanczos fit does not centre:
   // nothing reads them before fit() ends).  What is left of the preparation is the mask compaction.
   // SAPCA_LANCZOS_TRANSPOSE=1 brings the transposed operator (radix sort) back.
-  const bool serial_early = dbg_env("SAPCA_PREPARE_SERIAL") != nullptr;
   bool lz_scatter = h.opt.method == SAPCA_LANCZOS && n_used > 0 && n_used <= m && m >= 4096 && nnz > 0 && k::scatter_fits(n_used) &&
-                    (!masked || !serial_early) && dbg_env("SAPCA_LANCZOS_TRANSPOSE") == nullptr;
+                    dbg_env("SAPCA_LANCZOS_TRANSPOSE") == nullptr;
   bool lz_side = false;   // its statistics run on the third stream
   if (lz_scatter && !masked) {
     // max |a| for the fixed-point scales (masked fits: the compaction gathers it on its way through the values).  Values that
@@ -217,9 +215,8 @@ void Engine<T>::prepare(H& h, const CsrView<T>& A) {
     std::thread& t;
     ~Joiner() { if (t.joinable()) t.join(); }
   } joiner{aside};
-  const bool serial = dbg_env("SAPCA_PREPARE_SERIAL") != nullptr;
-  const bool masked_aside = masked && n_used > 0 && !serial;
-  const bool try_direct = sizeof(T) == 4 && at_tile_major && !masked && !serial;   // A^T's format without a transposed CSR
+  const bool masked_aside = masked && n_used > 0;
+  const bool try_direct = sizeof(T) == 4 && at_tile_major && !masked;   // A^T's format without a transposed CSR
   // Masked fits compact first (MaskedCSRMatrix::new, sparse_masked/mod.rs:313) and transpose only what the mask keeps.  The
   // entries the compaction drops leave as (column, value) pairs: the sums of the masked-out columns (mean_ is full width,
   // sparse_masked/mod.rs:279-286) come from a stable sort of those pairs by column.  On the staged sweep (f32) the
@@ -227,26 +224,15 @@ void Engine<T>::prepare(H& h, const CsrView<T>& A) {
   const bool try_masked_direct = sizeof(T) == 4 && at_tile_major && masked_aside && n_used <= 65536 && dbg_env("SAPCA_AT_SORT") == nullptr;
   bool compaction_done = false;
   bool side_stats = false;   // the masked-out columns' sums (and the host copy of all statistics) finish on stream3, behind the fit
-  // SAPCA_MASK_SUMS_SCATTER=1: single-rank masked fits take those sums straight from A on the third stream (scatter.hip:
-  // fixed-point sums in LDS) instead of sorting the (column, value) pairs the compaction writes out for it.  Measured slower
-  // on randomized fits (C3's matrix in f32: 14.0 against 12.9 ms): the scatter kernels take a CU's whole LDS, so the sweeps
-  // cannot share the chip with them the way they do with the sort's light kernels.  Not the default.
-  const bool scatter_sums = masked && !from_upload && !lz_scatter && !h.comm.active() && dbg_env("SAPCA_MASK_STATS_INLINE") == nullptr &&
-                            dbg_env("SAPCA_MASK_SUMS_SCATTER") != nullptr;
-  auto scatter_sums_on_stream3 = [&](double* d_drop) {   // sum | sumsq of EVERY column of A (the kept ones are overwritten later)
-    unsigned long long* sc = h.lz_scalars.as<unsigned long long>(4);
-    k::absmax(A.val, nnz, sc, h.stream3);
-    k::colstats_scatter(A, sc, d_drop, d_drop + n, (double*)nullptr, h.drop_tmp, h.stream3);
-  };
   int32_t* drop_col = nullptr;
   T* drop_val = nullptr;
-  if (masked_aside && dbg_env("SAPCA_MASK_TRANSPOSE_FIRST") == nullptr) {
+  if (masked_aside) {
     Scope sc(h, C_PREPARE);
     int64_t* ca_ptr = h.ca_ptr.as<int64_t>((size_t)m + 1);
     int32_t* ca_idx = h.ca_idx.as<int32_t>((size_t)std::max<int64_t>(nnz, 1));
     T* ca_val = h.ca_val.as<T>((size_t)std::max<int64_t>(nnz, 1));
-    drop_col = (from_upload || lz_scatter || scatter_sums) ? nullptr : h.drop_col.as<int32_t>((size_t)std::max<int64_t>(nnz, 1));
-    drop_val = (from_upload || lz_scatter || scatter_sums) ? nullptr : h.drop_val.as<T>((size_t)std::max<int64_t>(nnz, 1));
+    drop_col = (from_upload || lz_scatter) ? nullptr : h.drop_col.as<int32_t>((size_t)std::max<int64_t>(nnz, 1));
+    drop_val = (from_upload || lz_scatter) ? nullptr : h.drop_val.as<T>((size_t)std::max<int64_t>(nnz, 1));
     k::compact_columns(A, d_o2m, ca_ptr, ca_idx, ca_val, &nnz_used, h.scratch, s, drop_col, drop_val,
                        lz_scatter ? h.lz_scalars.as<unsigned long long>(4) : nullptr);
     h.a_used = {m, n_used, nnz_used, ca_ptr, ca_idx, ca_val};
@@ -279,12 +265,9 @@ void Engine<T>::prepare(H& h, const CsrView<T>& A) {
         double* d_drop = h.drop_stats.as<double>((size_t)2 * n);
         SAPCA_HIP(hipEventRecord(h.ev_drop, s));
         SAPCA_HIP(hipStreamWaitEvent(h.stream3, h.ev_drop, 0));
-        if (scatter_sums)
-          scatter_sums_on_stream3(d_drop);
-        else
-          k::sums_by_column(drop_col, drop_val, nnz - nnz_used, n, h.at_ptr.as<int64_t>((size_t)n + 1),
-                            h.at_idx.as<int32_t>((size_t)std::max<int64_t>(nnz, 1)), h.at_val.as<T>((size_t)std::max<int64_t>(nnz, 1)),
-                            d_drop, d_drop + n, h.drop_tmp, h.stream3);
+        k::sums_by_column(drop_col, drop_val, nnz - nnz_used, n, h.at_ptr.as<int64_t>((size_t)n + 1),
+                          h.at_idx.as<int32_t>((size_t)std::max<int64_t>(nnz, 1)), h.at_val.as<T>((size_t)std::max<int64_t>(nnz, 1)),
+                          d_drop, d_drop + n, h.drop_tmp, h.stream3);
       }
     }
   }
@@ -297,24 +280,16 @@ void Engine<T>::prepare(H& h, const CsrView<T>& A) {
     SAPCA_HIP(hipEventRecord(h.ev_fork, s));   // A (and the index maps) are on the device
     h.tiled_a = TiledOp();
     a_built_aside = true;
-    aside = std::thread([&, n_used, tiled_ldp, compaction_done] {
+    aside = std::thread([&, tiled_ldp, compaction_done] {
       try {
         SAPCA_HIP(hipSetDevice(h.device));
         SAPCA_HIP(hipStreamWaitEvent(h.stream2, h.ev_fork, 0));
         CsrView<T> src = A;
         if (masked && compaction_done) {
           src = view(h.a_used);
-        } else if (masked) {
-          int64_t* ca_ptr = h.ca_ptr.as<int64_t>((size_t)m + 1);
-          int32_t* ca_idx = h.ca_idx.as<int32_t>((size_t)std::max<int64_t>(nnz, 1));
-          T* ca_val = h.ca_val.as<T>((size_t)std::max<int64_t>(nnz, 1));
-          k::compact_columns(A, d_o2m, ca_ptr, ca_idx, ca_val, &nnz_used, h.tb_a.tmp, h.stream2);
-          h.a_used = {m, n_used, nnz_used, ca_ptr, ca_idx, ca_val};
-          src = view(h.a_used);
         }
         if (tiled_ldp != 0) {
-          if constexpr (sizeof(T) == 4) ok_a_aside = k::build_tiled(src, false, tiled_ldp, h.tiled_a, h.tb_a, h.stream2);
-          else ok_a_aside = k::build_tiled(src, tiled_ldp, h.tiled_a, h.tb_a, h.stream2);
+          ok_a_aside = k::build_tiled(src, tiled_ldp, h.tiled_a, h.tb_a, h.stream2);
         }
         SAPCA_HIP(hipEventRecord(h.ev_join, h.stream2));
       } catch (...) {
@@ -328,10 +303,6 @@ void Engine<T>::prepare(H& h, const CsrView<T>& A) {
   bool at_direct = false;
   if constexpr (sizeof(T) == 4) {
     if (try_direct) {
-      if (dbg_env("SAPCA_PREPARE_ASIDE_FIRST") && aside.joinable()) {   // timing runs: A's format alone on the chip, then A^T's
-        aside.join();
-        SAPCA_HIP(hipStreamSynchronize(h.stream2));
-      }
       Scope sc(h, C_PREPARE);
       int64_t* at_ptr = h.at_ptr.as<int64_t>((size_t)n + 1);
       double* d_stats = h.stats.as<double>((size_t)3 * n + 1 + H::kStatsTail);
@@ -387,7 +358,7 @@ void Engine<T>::prepare(H& h, const CsrView<T>& A) {
 
   // (f64, or f32 off the bucket route: A's format is built on the side stream from this thread once the transposition is
   // queued; the side stream forks HERE, so the two run side by side on the GPU)
-  const bool a_aside_late = !a_built_aside && tiled_ldp != 0 && !masked && !serial;
+  const bool a_aside_late = !a_built_aside && tiled_ldp != 0 && !masked;
   if (a_aside_late) {
     if (!h.stream2) {
       SAPCA_HIP(hipStreamCreateWithFlags(&h.stream2, hipStreamNonBlocking));
@@ -413,8 +384,7 @@ void Engine<T>::prepare(H& h, const CsrView<T>& A) {
 
   if (a_aside_late) {
     h.tiled_a = TiledOp();
-    if constexpr (sizeof(T) == 4) ok_a_aside = k::build_tiled(A, false, tiled_ldp, h.tiled_a, h.tb_a, h.stream2);
-    else ok_a_aside = k::build_tiled(A, tiled_ldp, h.tiled_a, h.tb_a, h.stream2);
+    ok_a_aside = k::build_tiled(A, tiled_ldp, h.tiled_a, h.tb_a, h.stream2);
     SAPCA_HIP(hipEventRecord(h.ev_join, h.stream2));       // ...and the main stream waits for it at the end of prepare()
     a_built_aside = true;
   }
@@ -556,14 +526,12 @@ void Engine<T>::prepare(H& h, const CsrView<T>& A) {
   if constexpr (sizeof(T) == 4) {
     if (tiled_ldp != 0 && n_used > 0) {
       Scope sc(h, C_PREPARE);
-      if (!a_built_aside) ok_a_aside = k::build_tiled(view(h.a_used), false, tiled_ldp, h.tiled_a, h.tb_a, s);
-      if (!from_at) join_aside();   // (this route reads the compacted A)
-      bool ok_at = at_direct || masked_direct || (!from_at && k::build_tiled(view(h.a_used), true, tiled_ldp, h.tiled_at, h.tb_at, s)) ||
-                   k::build_tiled(view(h.at_used), false, tiled_ldp, h.tiled_at, h.tb_at, s, at_tile_major, at_packed, true, at_seg_ready);
+      bool ok_at = at_direct || masked_direct ||
+                   k::build_tiled(view(h.at_used), tiled_ldp, h.tiled_at, h.tb_at, s, at_tile_major, at_packed, at_seg_ready);
       if (at_packed && !ok_at) {   // someone needs the transposed CSR after all
         k::unpack_transposed(at_packed, nnz, const_cast<int32_t*>(At.idx), reinterpret_cast<float*>(const_cast<T*>(At.val)), s);
         at_packed = nullptr;
-        ok_at = k::build_tiled(view(h.at_used), false, tiled_ldp, h.tiled_at, h.tb_at, s, at_tile_major);
+        ok_at = k::build_tiled(view(h.at_used), tiled_ldp, h.tiled_at, h.tb_at, s, at_tile_major);
       }
       join_aside();
       const bool ok_a = ok_a_aside;
@@ -588,7 +556,6 @@ void Engine<T>::prepare(H& h, const CsrView<T>& A) {
   } else {
     if (tiled_ldp != 0 && n_used > 0) {
       Scope sc(h, C_PREPARE);
-      if (!a_built_aside) ok_a_aside = k::build_tiled(view(h.a_used), tiled_ldp, h.tiled_a, h.tb_a, s);
       bool ok_at = k::build_tiled(view(h.at_used), tiled_ldp, h.tiled_at, h.tb_at, s, at_tile_major);
       join_aside();
       const bool ok_a = ok_a_aside;
@@ -612,12 +579,9 @@ void Engine<T>::prepare(H& h, const CsrView<T>& A) {
     SAPCA_HIP(hipEventRecord(h.ev_kept, s));
     SAPCA_HIP(hipStreamWaitEvent(h.stream3, h.ev_kept, 0));
     if (h.opt.method == SAPCA_RANDOM) {
-      if (scatter_sums)
-        scatter_sums_on_stream3(d_drop);
-      else
-        k::sums_by_column(drop_col, drop_val, nnz - nnz_used, n, h.at_ptr.as<int64_t>((size_t)n + 1),
-                          h.at_idx.as<int32_t>((size_t)std::max<int64_t>(nnz, 1)), h.at_val.as<T>((size_t)std::max<int64_t>(nnz, 1)),
-                          d_drop, d_drop + n, h.drop_tmp, h.stream3);
+      k::sums_by_column(drop_col, drop_val, nnz - nnz_used, n, h.at_ptr.as<int64_t>((size_t)n + 1),
+                        h.at_idx.as<int32_t>((size_t)std::max<int64_t>(nnz, 1)), h.at_val.as<T>((size_t)std::max<int64_t>(nnz, 1)),
+                        d_drop, d_drop + n, h.drop_tmp, h.stream3);
     }
     k::copy_selected(d_stats, d_stats + n, d_sel, n_used, d_drop, d_drop + n, h.stream3);
     SAPCA_HIP(hipMemcpyAsync(sums, d_drop, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost, h.stream3));
@@ -1256,9 +1220,7 @@ void Engine<T>::transform(H& h, const CsrView<T>& A, T* d_out) {
         h.prep_key.valid = false;   // (tiled_a no longer belongs to the fitted matrix)
         h.tiled_at = TiledOp();
         h.tiled_a = TiledOp();
-        bool ok;
-        if constexpr (sizeof(T) == 4) ok = k::build_tiled(Au, false, ldp_t, h.tiled_a, h.tb_a, s);
-        else ok = k::build_tiled(Au, ldp_t, h.tiled_a, h.tb_a, s);
+        const bool ok = k::build_tiled(Au, ldp_t, h.tiled_a, h.tb_a, s);
         if (ok && h.tiled_a.valid) {
           top = &h.tiled_a;
           ldk = k > 128 ? (int)round_up(k, 64) : std::max(top->ldp, k <= 64 ? 64 : 128);

@@ -85,7 +85,7 @@ struct sapca_handle_s {
   int64_t vote_cut = 0;
 
   // device buffers (grow-only)
-  sapca::DevBuf in_ptr, in_idx, in_val, up64, up64i, out_tmp;    // host-entry uploads
+  sapca::DevBuf in_ptr, in_idx, in_val, up64, out_tmp;    // host-entry uploads
   sapca::PinnedBuf up_stage[2];                                   // page-locked ring of the chunked index upload
   hipEvent_t up_done[2] = {nullptr, nullptr};
   // column statistics accumulated chunk by chunk while the upload is in flight (upstats.hip); valid for exactly the

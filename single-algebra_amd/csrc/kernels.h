@@ -77,9 +77,6 @@ void row_lengths_f64(const int64_t* ptr, int64_t rows, double* out, hipStream_t 
 // out[j] = number of stored entries with column j (integer atomics; transform of a matrix that
 // was not the fitted one)
 void column_counts_f64(const int32_t* idx, int64_t nnz, int64_t n, double* out, DevBuf& scratch, hipStream_t s);
-// per-row segment table for the LDS-tiled sweep: seg[r][t] = first entry of row r with col >= t*tile_cols
-template <typename T>
-void build_tile_index(const CsrView<T>& A, int tile_cols, int n_tiles, int32_t* seg, hipStream_t s);
 
 // ---- preproc.hip (preprocessing and statistics on a device-resident CSR) ----------
 // Normalize<T> for CsrMatrix (csr.rs:1012-1066): values *= target / sums[row or column] where the sum is > 0.
@@ -147,15 +144,13 @@ void colstats_scatter(const CsrView<T>& A, const unsigned long long* amax_bits, 
                       hipStream_t s);
 
 // ---- spmm_tiled.hip ---------------------------------------------------------------------
-// Builds the tile-major format of an f32 operator for panels of leading dimension ldp (64/128).
+// Builds the tile-major format of an f32 operator for panels of leading dimension ldp (64).
 // Returns false (op.valid == false) when the operator does not fit the LDS staging; callers then
 // stay on the row kernel.
-// transposed: the operator is S^T, built straight from S (no transposed CSR needed); false when the
-// format cannot be built (the caller stays on the row kernel)
 // rows_tile_major: S's rows were produced by transpose_csr(..., tile_major_nct = tiled_tile_count(S.cols, ldp))
-bool build_tiled(const CsrView<float>& S, bool transposed, int ldp, TiledOp& op, TiledBuffers& buf, hipStream_t s,
+bool build_tiled(const CsrView<float>& S, int ldp, TiledOp& op, TiledBuffers& buf, hipStream_t s,
                  bool rows_tile_major = false, const uint64_t* packed_rows = nullptr,   // packed_rows: S.idx / S.val are not
-                 bool allow_big_tile = true,                                             // filled, read (row << 32 | value) instead
+                                                                                         // filled, read (row << 32 | value) instead
                  bool seg_ready = false);   // buf.seg already holds the per-row tile index (at_stats_index)
 // The same format with f64 values for panels of 64 f64 columns (512-byte rows: the tile geometry of the
 // 128-float panels); built from a CSR in natural row order by the direct fill.
@@ -173,8 +168,6 @@ void at_stats_index(const int64_t* ptr, const uint64_t* packed, int64_t rows, in
                     double* sum, double* sumsq, hipStream_t s);
 // number of interleaved column tiles the format uses for an operator with `cols` columns
 int tiled_tile_count(int64_t cols, int ldp);
-// tile geometry (panel columns held per LDS tile row) for a panel of l columns: 64, two column passes when l > 64
-int tiled_geometry(int l);
 void spmm_tiled(const TiledOp& op, const float* X, int ldx, float* Y, int ldy, int ncols, const float* cvec, DevBuf& scratch,
                 hipStream_t s, PanelSource<float>* keep = nullptr);
 // the DPP-fed sweep in pieces of its output rows (spmm_tiled.hip): can the operator be swept so, the pieces' row bounds, one piece

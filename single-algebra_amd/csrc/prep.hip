@@ -364,28 +364,6 @@ __global__ void copy_selected_kernel(const int64_t* __restrict__ ptr, const int3
 }
 
 
-// seg[r][t] = number of entries of row r with col < t*tile_cols (t = 0..n_tiles): one lane
-// per (row, boundary) binary search; 64 boundaries of a row share a wave.
-template <typename T>
-__global__ void tile_index_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx, int64_t rows,
-                                  int tile_cols, int n_tiles, int32_t* __restrict__ seg) {
-  const int64_t total = rows * (int64_t)(n_tiles + 1);
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < total; i += stride) {
-    const int64_t r = i / (n_tiles + 1);
-    const int t = (int)(i - r * (n_tiles + 1));
-    const int64_t e0 = ptr[r], e1 = ptr[r + 1];
-    const int64_t bound = (int64_t)t * tile_cols;
-    int64_t lo = e0, hi = e1;
-    while (lo < hi) {
-      int64_t mid = (lo + hi) >> 1;
-      if ((int64_t)idx[mid] < bound) lo = mid + 1; else hi = mid;
-    }
-    seg[i] = (int32_t)(lo - e0);
-  }
-}
-
 __global__ void ptr_diff_kernel(const int64_t* __restrict__ ptr, int64_t rows, double* __restrict__ out) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < rows) out[i] = (double)(ptr[i + 1] - ptr[i]);
@@ -768,14 +746,6 @@ void column_counts_f64(const int32_t* idx, int64_t nnz, int64_t n, double* out, 
   SAPCA_HIP(hipGetLastError());
 }
 
-template <typename T>
-void build_tile_index(const CsrView<T>& A, int tile_cols, int n_tiles, int32_t* seg, hipStream_t s) {
-  if (A.rows == 0) return;
-  hipLaunchKernelGGL((tile_index_kernel<T>), dim3(grid_for(A.rows * (int64_t)(n_tiles + 1), 256, 16384)), dim3(256), 0,
-                     s, A.ptr, A.idx, A.rows, tile_cols, n_tiles, seg);
-  SAPCA_HIP(hipGetLastError());
-}
-
 #define INSTANTIATE(T)                                                                                              \
   template void transpose_csr<T>(const CsrView<T>&, int64_t*, int32_t*, T*, DevBuf&, hipStream_t, int,              \
                                  const uint64_t**);                                                                 \
@@ -785,8 +755,7 @@ void build_tile_index(const CsrView<T>& A, int tile_cols, int n_tiles, int32_t* 
   template void sums_by_column<T>(const int32_t*, const T*, int64_t, int64_t, int64_t*, int32_t*, T*, double*, double*, DevBuf&,   \
                                   hipStream_t);                                                                     \
   template void select_rows<T>(const CsrView<T>&, const int32_t*, int64_t, int64_t*, int32_t*, T*, int64_t*,        \
-                               DevBuf&, hipStream_t);                                                               \
-  template void build_tile_index<T>(const CsrView<T>&, int, int, int32_t*, hipStream_t);
+                               DevBuf&, hipStream_t);
 INSTANTIATE(float)
 INSTANTIATE(double)
 #undef INSTANTIATE

@@ -224,24 +224,21 @@ void launch_rowgather(const CsrView<T>& A, const T* X, int ldx, T* Y, int ldy, i
   int64_t blocks = (A.rows + 3) / 4;
   if (blocks > 16384) blocks = 16384;
   if (blocks < 1) blocks = 1;
-  static const bool per_entry = dbg_env("SAPCA_ROWGATHER_PER_ENTRY") != nullptr;   // (experiments: the kernel without the DPP feed)
   if constexpr (LPR >= 16) {
-    if (!per_entry) {
-      if (shift)
-        hipLaunchKernelGGL((spmm_rowbcast_kernel<T, LPR, true>), dim3((unsigned)blocks), dim3(256), 0, s, A.ptr, A.idx, A.val,
-                           A.rows, X, ldx, Y, ldy, ncols, cvec, vec_store, shift);
-      else
-        hipLaunchKernelGGL((spmm_rowbcast_kernel<T, LPR, false>), dim3((unsigned)blocks), dim3(256), 0, s, A.ptr, A.idx, A.val,
-                           A.rows, X, ldx, Y, ldy, ncols, cvec, vec_store, shift);
-      return;
-    }
+    if (shift)
+      hipLaunchKernelGGL((spmm_rowbcast_kernel<T, LPR, true>), dim3((unsigned)blocks), dim3(256), 0, s, A.ptr, A.idx, A.val,
+                         A.rows, X, ldx, Y, ldy, ncols, cvec, vec_store, shift);
+    else
+      hipLaunchKernelGGL((spmm_rowbcast_kernel<T, LPR, false>), dim3((unsigned)blocks), dim3(256), 0, s, A.ptr, A.idx, A.val,
+                         A.rows, X, ldx, Y, ldy, ncols, cvec, vec_store, shift);
+  } else {
+    if (shift)
+      hipLaunchKernelGGL((spmm_rowgather_kernel<T, LPR, true>), dim3((unsigned)blocks), dim3(256), 0, s, A.ptr, A.idx, A.val,
+                         A.rows, X, ldx, Y, ldy, ncols, cvec, vec_store, shift);
+    else
+      hipLaunchKernelGGL((spmm_rowgather_kernel<T, LPR>), dim3((unsigned)blocks), dim3(256), 0, s, A.ptr, A.idx, A.val,
+                         A.rows, X, ldx, Y, ldy, ncols, cvec, vec_store, shift);
   }
-  if (shift)
-    hipLaunchKernelGGL((spmm_rowgather_kernel<T, LPR, true>), dim3((unsigned)blocks), dim3(256), 0, s, A.ptr, A.idx, A.val,
-                       A.rows, X, ldx, Y, ldy, ncols, cvec, vec_store, shift);
-  else
-    hipLaunchKernelGGL((spmm_rowgather_kernel<T, LPR>), dim3((unsigned)blocks), dim3(256), 0, s, A.ptr, A.idx, A.val,
-                       A.rows, X, ldx, Y, ldy, ncols, cvec, vec_store, shift);
 }
 
 }  // namespace
@@ -257,7 +254,7 @@ void spmm(const CsrView<T>& A, const TiledOp* tiled, const T* X, int ldx, T* Y, 
   if (A.rows == 0) return;
   if constexpr (sizeof(T) == 4) {
     // variant 1 forces the row kernel; otherwise the LDS-staged sweep runs whenever its format exists
-    const bool geom_ok = tiled && tiled->elem == 4 && (tiled->ldp == ldx || (tiled->fmt == 1 && tiled->ldp == 64 && ldx % 64 == 0));
+    const bool geom_ok = tiled && tiled->elem == 4 && (tiled->ldp == ldx || (tiled->ldp == 64 && ldx % 64 == 0));
     if (variant != 1 && tiled && tiled->valid && geom_ok && tiled->rows == A.rows && tiled->cols == A.cols) {
       spmm_tiled(*tiled, reinterpret_cast<const float*>(X), ldx, reinterpret_cast<float*>(Y), ldy, ncols,
                  reinterpret_cast<const float*>(cvec), scratch, s, reinterpret_cast<PanelSource<float>*>(keep));

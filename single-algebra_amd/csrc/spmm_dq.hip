@@ -321,7 +321,7 @@ bool dq_build_tables(TiledOp& op, TiledBuffers& buf, hipStream_t s) {
   op.dq = false;
   static const bool off = dbg_env("SAPCA_NO_DQ") != nullptr;
   static const bool off64 = dbg_env("SAPCA_NO_DQ_F64") != nullptr;   // f64 fits on round 1's staged-entry sweep (A/B runs)
-  if (off || !op.valid || op.fmt != 1 || op.ldp != 64 || op.tile_bytes != DQ_TILE_BYTES) return false;
+  if (off || !op.valid || op.ldp != 64 || op.tile_bytes != DQ_TILE_BYTES) return false;
   if (op.elem == 8) {
     if (off64 || op.block_rows != 64 * DQ_F64_RG) return false;
   } else if (op.elem != 4 || (op.block_rows != 512 && op.block_rows != 1024)) {

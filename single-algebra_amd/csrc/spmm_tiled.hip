@@ -1,34 +1,28 @@
-// LDS-staged sparse x dense-panel sweep (f32; f64 in the quad formulation) and the tile-major operator formats it reads.
+// LDS-staged sparse x dense-panel sweep (f32 and f64) and the tile-major "quad" operator format it reads.
 //
 // Why: per stored entry the sweep reads 8 B of A but a whole panel row (256 B at l = 60).  Served
 // from L2 that gather caps the sweep far below the HBM roofline (measured 5.8 % with
 // the row kernel of spmm.hip).  Here the panel rows of one column tile are staged in LDS once per
 // workgroup and every gather is an LDS read, while A streams from HBM exactly once, contiguously.
 //
-// Two formulations live in this file (DESIGN.md §5 has the measurements that led from one to the other):
+// The format (DESIGN.md §5 has the measurements that led to it): rows in blocks of <= 512 (one workgroup
+// of 16 waves), columns in `nct` INTERLEAVED tiles (tile t = columns == t mod nct, 80 KiB of LDS).  A wave
+// is four groups of 16 lanes and every group walks its own row with ds_read_b128; four consecutive rows (a
+// quad) advance in lockstep, so the format stores a quad's segment step by step, 4 entries per step,
+// padded with {0, 0.0f} to its longest row.  8 quads per wave, accumulators in VGPRs across all tiles,
+// no cross-lane reduction.  Builders: histogram/index + count + fill (LDS-staged for A, streaming for
+// the tile-major rows of A^T, direct scatter as the fallback), or A^T straight from A through per-chunk
+// buckets (atd_*, round 2: the default for unmasked f32 fits; no transposed CSR, no sort).  The
+// production sweep over this format is spmm_dq.hip's; the staged-entry sweep here takes the operators it
+// refuses.
 //
-//  * "quad" (default; second half of the file): rows in blocks of <= 512 (one workgroup of 16 waves),
-//    columns in `nct` INTERLEAVED tiles (tile t = columns == t mod nct, 80 KiB of LDS).  A wave is four
-//    groups of 16 lanes and every group walks its own row with ds_read_b128; four consecutive rows (a
-//    quad) advance in lockstep, so the format stores a quad's segment step by step, 4 entries per step,
-//    padded with {0, 0.0f} to its longest row.  8 quads per wave, accumulators in VGPRs across all tiles,
-//    no cross-lane reduction.  Builders: histogram/index + count + fill (LDS-staged for A, streaming for
-//    the tile-major rows of A^T, direct scatter as the fallback), or A^T straight from A: through per-chunk
-//    buckets (atd_*, round 2: the default for unmasked f32 fits; no transposed CSR, no sort) or round 1's
-//    tquad_* (short runs of A per chunk).  The production sweep over this format is spmm_dq.hip's.
+// Panels wider than 64 columns take two column passes over the same format (spmm_tiled); f64 values and
+// panels use the same format with 16-byte entries and 512-byte panel rows (spmm_quad_f64_kernel).
 //
-//  * "pair" (SAPCA_TILED_FMT=0; first half): contiguous column tiles of 96 KiB; the two half-waves of a
-//    wave take two consecutive entries of ONE row per step (ds_read_b64), accumulators duplicated in the
-//    two halves and summed at the end.  1.47 ms per C2 sweep against 0.89 ms for the quad kernel; kept
-//    for A/B runs and because its ablation switches (SAPCA_ABL) document how the numbers were obtained.
-//
-//    Panels wider than 64 columns take two column passes over the same format (spmm_tiled); f64 values and
-//    panels use the same format with 16-byte entries and 512-byte panel rows (spmm_quad_f64_kernel).
-//
-// Common to both: an entry is {u32 byte offset of its panel row inside the LDS tile, f32 value}; per
-// column tile the workgroup does  barrier; panel tile + the block's entry chunk -> LDS (both prefetched
-// into registers during the previous tile's compute); barrier; compute.  Tile ranges can be split over
-// workgroups (A^T has few rows): partial sums go to a slab that a second kernel adds in fixed order.
+// An entry is {u32 byte offset of its panel row inside the LDS tile, f32 value}; per column tile the
+// workgroup does  barrier; panel tile + the block's entry chunk -> LDS (both prefetched into registers
+// during the previous tile's compute); barrier; compute.  Tile ranges can be split over workgroups
+// (A^T has few rows): partial sums go to a slab that a second kernel adds in fixed order.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -44,109 +38,12 @@ namespace k {
 namespace {
 
 constexpr int WAVE = 64;
-constexpr int RW = 32;            // max rows per wave (register accumulators)
-#ifndef SAPCA_RW2
-#define SAPCA_RW2 32
-#endif
-#ifndef SAPCA_PADSTEPS
-#define SAPCA_PADSTEPS 1   // row segments of the two-lane-group format are padded to this many steps
-#endif
-#ifndef SAPCA_ABL
-#define SAPCA_ABL 0   // compile-time ablations of the sweep's inner loop (tools/abl_build.sh); 0 in the product
-#endif
-constexpr int RW2 = SAPCA_RW2;   // rows per wave of the default (2 lane groups, LDP 64) configuration
-constexpr int BLOCK_ROWS = 512;   // stride of the per-(block, tile) step table; max rows per block
-// lane groups ("slots") per wave: 2 half-waves (16 waves/workgroup, 512 rows) or 4 quarter-waves
-// (8 waves/workgroup, 256 rows, half the LDS instructions per entry)
-constexpr int waves_for(int slots) { return slots == 2 ? 16 : 8; }
-constexpr int TILE_BYTES = 96 * 1024;
 constexpr int LDS_TOTAL = 160 * 1024;
-constexpr int STAGE_BYTES = LDS_TOTAL - TILE_BYTES - 1024;   // entry staging capacity
-constexpr int STAGE_ENTRIES = STAGE_BYTES / 8 - WAVE;        // keep one chunk of slack for read-ahead
 
 struct Ent { uint32_t off; float val; };
 struct EntD { uint32_t off; uint32_t pad; double val; };   // the same entry for f64 values (16 bytes)
 template <typename VT> struct EntOf { typedef Ent type; };
 template <> struct EntOf<double> { typedef EntD type; };
-
-// ---------------------------------------------------------------------------------- builder
-// seg[r][t] (t = 0..nct) = number of entries of row r with col < t*TC  (prep.hip: tile_index_kernel)
-
-// one block per (row block, column tile): batch counts, wave offsets, chunk size
-template <int WAVES, int PAD>
-__global__ void __launch_bounds__(BLOCK_ROWS)
-tiled_count_kernel(const int32_t* __restrict__ seg, const int32_t* __restrict__ blk_row0, int nct,
-                   uint8_t* __restrict__ steps, uint32_t* __restrict__ wave_off, int64_t* __restrict__ chunk_size) {
-  __shared__ uint32_t scan[BLOCK_ROWS];
-  const int rb = blockIdx.x / nct, ct = blockIdx.x % nct;
-  const int row0 = blk_row0[rb], nrows = blk_row0[rb + 1] - row0;
-  const int rpw = (nrows + WAVES - 1) / WAVES;
-  const int lr = threadIdx.x;
-  uint32_t padded = 0, nb = 0;
-  if (lr < nrows) {
-    const int64_t r = row0 + lr;
-    const int len = seg[r * (nct + 1) + ct + 1] - seg[r * (nct + 1) + ct];
-    nb = (uint32_t)((len + PAD - 1) / PAD);
-    padded = nb * PAD;
-  }
-  steps[(int64_t)blockIdx.x * BLOCK_ROWS + lr] = (uint8_t)(WAVES == 16 ? nb * SAPCA_PADSTEPS : nb);
-  scan[lr] = padded;
-  __syncthreads();
-  for (int off = 1; off < BLOCK_ROWS; off <<= 1) {   // inclusive prefix (Hillis-Steele)
-    uint32_t v = lr >= off ? scan[lr - off] : 0;
-    __syncthreads();
-    scan[lr] += v;
-    __syncthreads();
-  }
-  const uint32_t excl = scan[lr] - padded;
-  if (lr < nrows && lr % rpw == 0) wave_off[(int64_t)blockIdx.x * WAVES + lr / rpw] = excl;
-  if (lr == BLOCK_ROWS - 1) chunk_size[blockIdx.x] = scan[lr];
-  if (lr < WAVES && lr * rpw >= nrows) wave_off[(int64_t)blockIdx.x * WAVES + lr] = scan[BLOCK_ROWS - 1];
-}
-
-// one single-wave workgroup per (row block, wave): it copies that wave's rows' entries into every
-// column tile's chunk (one wave per workgroup so that operators with few row blocks -- A^T -- still
-// spread over all CUs)
-template <int WAVES, int PAD>
-__global__ void __launch_bounds__(WAVE)
-tiled_fill_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx, const float* __restrict__ val,
-                  const int32_t* __restrict__ seg, const int32_t* __restrict__ blk_row0, int nct, int tc,
-                  int ldp_bytes, const int64_t* __restrict__ chunk_off, const uint32_t* __restrict__ wave_off,
-                  Ent* __restrict__ ent, uint32_t* __restrict__ run_global) {
-  extern __shared__ uint32_t run[];  // [nct] next free slot of this wave in every tile's chunk,
-                                     // relative to the block's first chunk (one LDS read per entry)
-  const int rb = blockIdx.x / WAVES;
-  const int wave = blockIdx.x % WAVES, lane = threadIdx.x;
-  const int row0 = blk_row0[rb], nrows = blk_row0[rb + 1] - row0;
-  const int rpw = (nrows + WAVES - 1) / WAVES;
-  // many column tiles (A^T of a tall matrix): the table does not fit LDS and lives in HBM/L2 instead
-  uint32_t* mybase = run_global ? run_global + (size_t)blockIdx.x * nct : run;
-  const int64_t block_base = chunk_off[(int64_t)rb * nct];
-  for (int t = lane; t < nct; t += WAVE)
-    mybase[t] = (uint32_t)(chunk_off[(int64_t)rb * nct + t] - block_base) + wave_off[((int64_t)rb * nct + t) * WAVES + wave];
-  __builtin_amdgcn_wave_barrier();
-  Ent* __restrict__ out = ent + block_base;
-  const int lr0 = wave * rpw, lr1 = min(nrows, lr0 + rpw);
-  for (int lr = lr0; lr < lr1; ++lr) {
-    const int64_t r = row0 + lr;
-    const int64_t e0 = ptr[r], e1 = ptr[r + 1];
-    const int32_t* sg = seg + r * (nct + 1);
-    for (int64_t e = e0 + lane; e < e1; e += WAVE) {
-      const int c = idx[e];
-      const int t = c / tc;
-      Ent x;
-      x.off = (uint32_t)(c - t * tc) * (uint32_t)ldp_bytes;
-      x.val = val[e];
-      out[mybase[t] + (uint32_t)((e - e0) - sg[t])] = x;
-    }
-    __builtin_amdgcn_wave_barrier();  // the wave's reads of mybase (above) precede its update (below)
-    for (int t = lane; t < nct; t += WAVE) {
-      const int len = sg[t + 1] - sg[t];
-      mybase[t] += (uint32_t)((len + PAD - 1) / PAD * PAD);
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-}
 
 inline int grid_for(int64_t work_items, int block, int cap = 8192) {
   int64_t g = (work_items + block - 1) / block;
@@ -156,60 +53,8 @@ inline int grid_for(int64_t work_items, int block, int cap = 8192) {
 }
 
 // ---------------------------------------------------------------------------------- sweep
-typedef float v2f __attribute__((ext_vector_type(2)));
-template <int VPL> struct Lane;
-template <> struct Lane<2> {
-  using V = v2f;
-  __device__ static inline V load(const char* p) { return *reinterpret_cast<const v2f*>(p); }
-};
-template <> struct Lane<4> {
-  typedef float V __attribute__((ext_vector_type(4)));
-  __device__ static inline V load(const char* p) { return *reinterpret_cast<const V*>(p); }
-};
-
-// U consecutive steps of one row: entry reads first, panel gathers next, FMAs last, so U gathers
-// per wave are in flight.
-template <int VPL, int PAD, int U>
-__device__ __forceinline__ void steps_batch(typename Lane<VPL>::V& acc, const char* stage_lane, const char* tile_lane) {
-  typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-  u2 e[U];
-#if SAPCA_ABL & 2   // ablation: no entry reads (one fixed entry held in registers, no extra VALU)
-  {
-    u2 f;
-    f.x = (unsigned)(size_t)stage_lane & 0xff00u;
-    f.y = 0x3f800000u;
-    asm volatile("" : "+v"(f));
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      e[u] = f;
-      e[u].x += u * 256;   // folds into the ds_read offset field
-    }
-  }
-#else
-#pragma unroll
-  for (int u = 0; u < U; ++u) e[u] = *reinterpret_cast<const u2*>(stage_lane + u * (PAD * 8));
-#endif
-  typename Lane<VPL>::V w[U];
-#if SAPCA_ABL & 1   // ablation: no panel gathers
-#pragma unroll
-  for (int u = 0; u < U; ++u) w[u] = typename Lane<VPL>::V(__uint_as_float(e[u].x));
-#else
-#pragma unroll
-  for (int u = 0; u < U; ++u) w[u] = Lane<VPL>::load(tile_lane + e[u].x);
-#endif
-#if SAPCA_ABL & 4   // ablation: no FMAs
-#pragma unroll
-  for (int u = 0; u < U; ++u) asm volatile("" ::"v"(w[u]), "v"(e[u].y));
-#else
-#pragma unroll
-  for (int u = 0; u < U; ++u) acc += __uint_as_float(e[u].y) * w[u];
-#endif
-}
-
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef float v4f_a4 __attribute__((ext_vector_type(4), aligned(4)));   // output rows are only element-aligned (ldo = k)
-constexpr int np_tile(int threads) { return TILE_BYTES / (threads * 16); }
-constexpr int np_stage(int threads) { return (STAGE_BYTES + threads * 16 - 1) / (threads * 16); }
 
 // loads are unconditional (addresses clamped into the valid range) so the arrays stay in VGPRs
 template <int N, int THREADS>
@@ -224,119 +69,6 @@ __device__ __forceinline__ void store_regs(const v4f (&r)[N], char* dst, int cap
   for (int i = 0; i < N; ++i) {
     const int b = (i * THREADS + (int)threadIdx.x) * 16;
     if ((i + 1) * THREADS * 16 <= capacity || b + 16 <= capacity) *reinterpret_cast<v4f*>(dst + b) = r[i];
-  }
-}
-
-#define SAPCA_PREFETCH(CT)                                                                          \
-  {                                                                                                 \
-    const int64_t cidx_ = (int64_t)rb * nct + (CT);                                                 \
-    const int64_t c_lo_ = chunk_off[cidx_];                                                         \
-    const int64_t first_ = (int64_t)(CT) * tc;                                                      \
-    load_regs<NP_TILE, THREADS>(pt, reinterpret_cast<const char*>(X + first_ * LDP),                         \
-                       (int)min<int64_t>(tc, panel_rows - first_) * LDP * 4);                       \
-    load_regs<NP_STAGE, THREADS>(ps, reinterpret_cast<const char*>(ent + c_lo_),                             \
-                        max(16, (int)(chunk_off[cidx_ + 1] - c_lo_) * 8));                          \
-  }
-
-template <int LDP, int SLOTS, bool PREFETCH>  // LDP: panel leading dimension in floats (64 or 128)
-__global__ void __launch_bounds__(waves_for(SLOTS) * WAVE)
-spmm_tiled_kernel(const int32_t* __restrict__ blk_row0, int nct, int tc, const int64_t* __restrict__ chunk_off,
-                  const uint32_t* __restrict__ wave_off, const uint8_t* __restrict__ steps,
-                  const Ent* __restrict__ ent, int64_t panel_rows, const float* __restrict__ X, int nsplit,
-                  int tiles_per_split, float* __restrict__ out, int64_t out_rows_total, int ldo, int ncols,
-                  const float* __restrict__ cvec, int mode) {
-  constexpr int WAVES = waves_for(SLOTS), THREADS = WAVES * WAVE, PAD = SLOTS;
-  constexpr int LPE = WAVE / SLOTS;   // lanes that cover one panel row
-  constexpr int VPL = LDP / LPE;      // panel values per lane
-  constexpr int RWK = (SLOTS == 2 && LDP == 128) ? RW / 2 : (SLOTS == 2 ? RW2 : RW);   // rows per wave: the accumulators must fit the VGPR budget
-  constexpr int NP_TILE = np_tile(THREADS), NP_STAGE = np_stage(THREADS);
-  using LN = Lane<VPL>;
-  using V = typename LN::V;
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  char* tile = lds;
-  char* stage = lds + TILE_BYTES;
-  const int rb = blockIdx.x / nsplit, sp = blockIdx.x % nsplit;
-  const int ct0 = sp * tiles_per_split, ct1 = min(nct, ct0 + tiles_per_split);
-  const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
-  const int half = lane / LPE, q = lane % LPE;   // half = lane group (slot)
-  const int row0 = blk_row0[rb], nrows = blk_row0[rb + 1] - row0;
-  const int rpw = (nrows + WAVES - 1) / WAVES;
-  const int my_rows = max(0, min(nrows - wave * rpw, rpw));
-  const char* tl = tile + q * (VPL * 4);
-
-  V acc[RWK];
-#pragma unroll
-  for (int i = 0; i < RWK; ++i) acc[i] = V(0.f);
-
-  v4f pt[NP_TILE], ps[NP_STAGE];
-  // per-tile bookkeeping of this wave (step counts of its rows, start of its entries), fetched one
-  // tile ahead and BEFORE the bulk prefetch: vmcnt retires in order, so a small load issued after
-  // the prefetch would make its first use wait for the whole prefetch
-  int cnt_next = 0;
-  unsigned woff_next = 0;
-#define SAPCA_BOOKKEEPING(CT)                                                                      \
-  {                                                                                                \
-    const int64_t cidx_ = (int64_t)rb * nct + (CT);                                                \
-    cnt_next = lane < my_rows ? (int)steps[cidx_ * BLOCK_ROWS + wave * rpw + lane] : 0;            \
-    woff_next = wave_off[cidx_ * WAVES + wave];                                                    \
-  }
-  if (ct0 < ct1) SAPCA_BOOKKEEPING(ct0)
-  if (PREFETCH && ct0 < ct1) SAPCA_PREFETCH(ct0)
-  for (int ct = ct0; ct < ct1; ++ct) {
-    if (!(mode & 8) || ct == ct0) {
-      __syncthreads();  // the previous tile's readers are done
-      if (!PREFETCH && (!(mode & 2) || ct == ct0)) SAPCA_PREFETCH(ct)
-      store_regs<NP_TILE, THREADS>(pt, tile, TILE_BYTES);
-      store_regs<NP_STAGE, THREADS>(ps, stage, STAGE_BYTES);
-      __syncthreads();
-    }
-    const int cnt_v = cnt_next;
-    const unsigned woff = woff_next;
-    if (ct + 1 < ct1 && !(mode & 8)) SAPCA_BOOKKEEPING(ct + 1)
-    if (PREFETCH && ct + 1 < ct1 && !(mode & 10)) SAPCA_PREFETCH(ct + 1)
-    if (mode & 1) continue;
-    if (my_rows > 0) {
-      const char* sl = stage + (size_t)woff * 8 + half * 8;
-#pragma unroll
-      for (int rr = 0; rr < RWK; ++rr) {
-        int n = __builtin_amdgcn_readlane(cnt_v, rr);
-        while (n >= 4) {
-          steps_batch<VPL, PAD, 4>(acc[rr], sl, tl);
-          sl += 4 * PAD * 8;
-          n -= 4;
-        }
-        if (n >= 2) {
-          steps_batch<VPL, PAD, 2>(acc[rr], sl, tl);
-          sl += 2 * PAD * 8;
-          n -= 2;
-        }
-        if ((SLOTS != 2 || SAPCA_PADSTEPS < 2) && n) {
-          steps_batch<VPL, PAD, 1>(acc[rr], sl, tl);
-          sl += PAD * 8;
-        }
-      }
-    }
-  }
-
-  // sum the two half-waves; half 0 writes columns VPL*q .. of every row of this wave
-  float* dst_base = out + (nsplit > 1 ? (int64_t)sp * out_rows_total * ldo : 0);
-  const int col = q * VPL;
-  float cv[VPL];
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) cv[i] = (cvec && nsplit == 1) ? cvec[col + i] : 0.f;
-#pragma unroll
-  for (int rr = 0; rr < RWK; ++rr) {
-    V a = acc[rr];
-#pragma unroll
-    for (int off = LPE; off < WAVE; off <<= 1)
-#pragma unroll
-      for (int i = 0; i < VPL; ++i) a[i] += __shfl_xor(a[i], off);
-    if (rr < my_rows && half == 0) {
-      float* y = dst_base + (int64_t)(row0 + wave * rpw + rr) * ldo + col;
-#pragma unroll
-      for (int i = 0; i < VPL; ++i)
-        if (col + i < ncols) y[i] = a[i] - cv[i];
-    }
   }
 }
 
@@ -371,11 +103,8 @@ __global__ void split_reduce_rows_kernel(const float* __restrict__ part, int nsp
   }
 }
 
-#undef SAPCA_PREFETCH
-#undef SAPCA_BOOKKEEPING
-
 // ------------------------------------------------------------------------ "quad" format and sweep
-// Second formulation of the staged sweep.  Measured on the first one (profiles/): a
+// Measured on round 1's first formulation, two half-waves per row (profiles/): a
 // SIMD retires about one instruction per 4-6 cycles whatever its kind, so the sweep time follows
 // the number of instructions per stored entry.  Here a wave is four groups of 16 lanes and every
 // group walks its OWN row (ds_read_b128: a lane holds 4 of the 64 panel columns, 8 of 128), so
@@ -389,7 +118,6 @@ __global__ void split_reduce_rows_kernel(const float* __restrict__ part, int nsp
 constexpr int QGROUPS = 4, QLANES = WAVE / QGROUPS, QWAVES = SAPCA_QWAVES, QTHREADS = QWAVES * WAVE;
 constexpr int Q_TILE_BYTES = 80 * 1024;          // default split of the 160 KiB: 80 KiB panel tile + 79 KiB entry staging
 constexpr int Q_MAX_TILES_RUNS = 16384;          // tile-major builder (bounded by the tile arithmetic's float reciprocal and the index tables' size)
-constexpr int Q_TILE_BYTES_BIG = 96 * 1024;      // for operators whose chunks leave room: fewer, longer tile steps
 constexpr int q_stage_bytes(int tile_bytes) { return LDS_TOTAL - tile_bytes - 1024; }
 constexpr int QBLOCK_ROWS = 1024;                // most rows of a quad-format block (the DPP-fed sweep with 16 row slots per lane group)
 constexpr int Q_BLOCK_QUADS = QBLOCK_ROWS / 4;   // stride of the per-chunk quad step table
@@ -915,208 +643,22 @@ quad_fill_runs_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict
   }
 }
 
-// ---- the same format for A^T, built straight from A (no transposed CSR, no global sort) ----------
-// Operator T = S^T for a source S (m x n CSR): T's rows are S's columns, T's interleaved tiles run
-// over S's rows.  The chunk (block b of T rows, tile t) receives, from every source row r = t + i*nct,
-// the contiguous run of its entries whose column lies in block b (found through segb), so one
-// workgroup per chunk reads ~|block| * density entries per source row and owns the chunk's whole
-// output region.  The rank of an entry inside its T row's segment (= the number of earlier source
-// rows of this tile holding the same column) comes from per-column bit masks over the tile's rows,
-// so the result is byte-identical to what the builder above makes from a transposed CSR.
-
-// segb[r][b] = number of entries of row r with column < bounds[b]   (b = 0..nb)
-__global__ void bound_index_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx, int64_t rows,
-                                   const int32_t* __restrict__ bounds, int nb, int32_t* __restrict__ segb) {
-  const int64_t total = rows * (int64_t)(nb + 1);
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < total; i += stride) {
-    const int64_t r = i / (nb + 1);
-    const int b = (int)(i - r * (nb + 1));
-    const int64_t e0 = ptr[r], e1 = ptr[r + 1];
-    const int bound = bounds[b];
-    int64_t lo = e0, hi = e1;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (idx[mid] < bound) lo = mid + 1; else hi = mid;
-    }
-    segb[i] = (int32_t)(lo - e0);
-  }
-}
-
-constexpr int TQ_THREADS = 1024, TQ_GROUPS = TQ_THREADS / 16;
-constexpr int TQ_NI = 5;   // source rows per 16-lane group: a tile holds at most 320 = 5 * 64 rows
-
-// the run of source row i of this tile inside the chunk's column block: [e0, e1)
-__device__ __forceinline__ void tquad_runs(int64_t (&e0)[TQ_NI], int64_t (&e1)[TQ_NI], const int64_t* __restrict__ ptr,
-                                           const int32_t* __restrict__ segb, int nb, int b, int t, int nct, int nr) {
-  const int grp = threadIdx.x / 16;
-#pragma unroll
-  for (int j = 0; j < TQ_NI; ++j) {
-    const int i = grp + j * TQ_GROUPS;
-    e0[j] = e1[j] = 0;
-    if (i < nr) {
-      const int64_t r = (int64_t)t + (int64_t)i * nct;
-      const int64_t base = ptr[r];
-      const int32_t* sb = segb + r * (nb + 1) + b;
-      e0[j] = base + sb[0];
-      e1[j] = base + sb[1];
-    }
-  }
-}
-
-// Per chunk: bit i of mask[column] <- source row i stores the column; the number of set bits below
-// bit i is the entry's rank in its T row's segment (written to rank[], aligned with the source
-// entries); the longest of a quad's four columns gives its steps.
-__global__ void __launch_bounds__(TQ_THREADS)
-tquad_count_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx, const int32_t* __restrict__ segb,
-                   int64_t src_rows, const int32_t* __restrict__ blk_row0, int nb, int nct, int maskw,
-                   uint16_t* __restrict__ rank, uint16_t* __restrict__ steps, uint32_t* __restrict__ quad_off,
-                   uint32_t* __restrict__ wave_off, int64_t* __restrict__ chunk_size) {
-  extern __shared__ uint32_t tq_lds[];
-  uint32_t* mask = tq_lds;                                   // [QBLOCK_ROWS][maskw]
-  uint32_t* pre = tq_lds + (size_t)QBLOCK_ROWS * maskw;       // [QBLOCK_ROWS][maskw]: set bits in the words before
-  __shared__ uint32_t wsum[QBLOCK_ROWS / WAVE];
-  __shared__ uint32_t qex[Q_BLOCK_QUADS];
-  // launch order: all column blocks of one tile are neighbours, so the source rows they share
-  // (and the segb lines) are fetched from HBM once and then hit in L2 / Infinity Cache
-  const int t = blockIdx.x / nb, b = blockIdx.x % nb;
-  const int64_t chunk = (int64_t)b * nct + t;
-  const int c0 = blk_row0[b], nrows = blk_row0[b + 1] - c0;
-  const int nquads = (nrows + 3) / 4;
-  const int nr = (int)((src_rows - t + nct - 1) / nct);
-  const int grp = threadIdx.x / 16, gl = threadIdx.x & 15;
-  int64_t e0[TQ_NI], e1[TQ_NI];
-  tquad_runs(e0, e1, ptr, segb, nb, b, t, nct, nr);
-  for (int i = threadIdx.x; i < QBLOCK_ROWS * maskw; i += TQ_THREADS) mask[i] = 0;
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < TQ_NI; ++j) {
-    const int i = grp + j * TQ_GROUPS;
-    for (int64_t e = e0[j] + gl; e < e1[j]; e += 16) atomicOr(&mask[(idx[e] - c0) * maskw + (i >> 5)], 1u << (i & 31));
-  }
-  __syncthreads();
-  const int lr = threadIdx.x;
-  int len = 0;
-  if (lr < nrows) {
-    for (int d = 0; d < maskw; ++d) {
-      pre[lr * maskw + d] = (uint32_t)len;
-      len += __popc(mask[lr * maskw + d]);
-    }
-  }
-  // steps of every quad, exclusive scan of the padded quad sizes (wave scans + 8 wave totals)
-  uint32_t padded = 0, incl = 0;
-  const int lane = lr & (WAVE - 1), wv = lr / WAVE;
-  if (lr < QBLOCK_ROWS) {
-    int qmax = max(len, __shfl_xor(len, 1));
-    qmax = q_steps(max(qmax, __shfl_xor(qmax, 2)));
-    padded = (lr & 3) == 0 ? (uint32_t)qmax * 4u : 0u;
-    if ((lr & 3) == 0) steps[chunk * Q_BLOCK_QUADS + lr / 4] = (uint16_t)qmax;
-    incl = padded;
-#pragma unroll
-    for (int off = 1; off < WAVE; off <<= 1) {
-      const uint32_t y = __shfl_up(incl, off);
-      if (lane >= off) incl += y;
-    }
-    if (lane == WAVE - 1) wsum[wv] = incl;
-  }
-  __syncthreads();
-  if (lr < QBLOCK_ROWS) {
-    uint32_t before = 0;
-    for (int w = 0; w < wv; ++w) before += wsum[w];
-    incl += before;
-    if ((lr & 3) == 0) {
-      quad_off[chunk * Q_BLOCK_QUADS + lr / 4] = incl - padded;
-      qex[lr / 4] = incl - padded;
-    }
-    if (lr == QBLOCK_ROWS - 1) chunk_size[chunk] = incl;
-  }
-  __syncthreads();
-  if (lr < QWAVES) wave_off[chunk * QWAVES + lr] = qex[q_first(lr, nquads)];
-  // ranks of this chunk's entries (idx is re-read: cache hits)
-#pragma unroll
-  for (int j = 0; j < TQ_NI; ++j) {
-    const int i = grp + j * TQ_GROUPS;
-    for (int64_t e = e0[j] + gl; e < e1[j]; e += 16) {
-      const int w = (idx[e] - c0) * maskw + (i >> 5);
-      rank[e] = (uint16_t)(pre[w] + __popc(mask[w] & ((1u << (i & 31)) - 1u)));
-    }
-  }
-}
-
-__global__ void __launch_bounds__(TQ_THREADS)
-tquad_fill_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx, const float* __restrict__ val,
-                  const uint16_t* __restrict__ rank, const int32_t* __restrict__ segb, int64_t src_rows,
-                  const int32_t* __restrict__ blk_row0, int nb, int nct, int ldp_bytes,
-                  const int64_t* __restrict__ chunk_off, const uint32_t* __restrict__ quad_off, Ent* __restrict__ ent) {
-  __shared__ uint32_t qoff[Q_BLOCK_QUADS];
-  const int t = blockIdx.x / nb, b = blockIdx.x % nb;
-  const int64_t chunk = (int64_t)b * nct + t;
-  const int c0 = blk_row0[b];
-  const int nr = (int)((src_rows - t + nct - 1) / nct);
-  const int grp = threadIdx.x / 16, gl = threadIdx.x & 15;
-  int64_t e0[TQ_NI], e1[TQ_NI];
-  tquad_runs(e0, e1, ptr, segb, nb, b, t, nct, nr);
-  if (threadIdx.x < Q_BLOCK_QUADS) qoff[threadIdx.x] = quad_off[chunk * Q_BLOCK_QUADS + threadIdx.x];
-  __syncthreads();
-  Ent* __restrict__ out = ent + chunk_off[chunk];
-#pragma unroll
-  for (int j = 0; j < TQ_NI; ++j) {
-    const int i = grp + j * TQ_GROUPS;
-    for (int64_t e = e0[j] + gl; e < e1[j]; e += 16) {
-      const int lr = idx[e] - c0;
-      Ent x;
-      x.off = (uint32_t)i * (uint32_t)ldp_bytes;
-      x.val = val[e];
-      out[qoff[lr >> 2] + (uint32_t)rank[e] * 4u + (uint32_t)(lr & 3)] = x;
-    }
-  }
-}
-
 // U consecutive steps of one quad: four rows advance together, one per lane group
 template <int NV, int U>
 __device__ __forceinline__ void quad_batch(v4f (&acc)[NV], const char* stage_lane, const char* tile_lane) {
   typedef unsigned int u2 __attribute__((ext_vector_type(2)));
   u2 e[U];
-#if SAPCA_ABL & 2   // ablation: no entry reads
-  {
-    u2 f;
-    f.x = (unsigned)(size_t)stage_lane & 0xff00u;
-    f.y = 0x3f800000u;
-    asm volatile("" : "+v"(f));
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      e[u] = f;
-      e[u].x += u * 512;
-    }
-  }
-#else
 #pragma unroll
   for (int u = 0; u < U; ++u) e[u] = *reinterpret_cast<const u2*>(stage_lane + u * (QGROUPS * 8));
-#endif
   v4f w[U][NV];
-#if SAPCA_ABL & 1   // ablation: no panel gathers
-#pragma unroll
-  for (int u = 0; u < U; ++u)
-#pragma unroll
-    for (int v = 0; v < NV; ++v) w[u][v] = v4f(__uint_as_float(e[u].x));
-#else
 #pragma unroll
   for (int u = 0; u < U; ++u)
 #pragma unroll
     for (int v = 0; v < NV; ++v) w[u][v] = *reinterpret_cast<const v4f*>(tile_lane + e[u].x + v * 256);
-#endif
-#if SAPCA_ABL & 4   // ablation: no FMAs
-#pragma unroll
-  for (int u = 0; u < U; ++u)
-#pragma unroll
-    for (int v = 0; v < NV; ++v) asm volatile("" ::"v"(w[u][v]), "v"(e[u].y));
-#else
 #pragma unroll
   for (int u = 0; u < U; ++u)
 #pragma unroll
     for (int v = 0; v < NV; ++v) acc[v] += __uint_as_float(e[u].y) * w[u][v];
-#endif
 }
 
 // panel rows t, t + nct, t + 2 nct, ... (clamped: slots past the last row are never referenced)
@@ -1153,8 +695,7 @@ spmm_quad_kernel(const int32_t* __restrict__ blk_row0, const uint32_t* __restric
                  const int64_t* __restrict__ chunk_off,
                  const uint32_t* __restrict__ wave_off, const uint16_t* __restrict__ steps, const Ent* __restrict__ ent,
                  int64_t panel_rows, const float* __restrict__ X, int ldx, int nsplit, int tiles_per_split,
-                 float* __restrict__ out, int64_t out_rows_total, int ldo, int ncols, const float* __restrict__ cvec,
-                 int mode) {
+                 float* __restrict__ out, int64_t out_rows_total, int ldo, int ncols, const float* __restrict__ cvec) {
   constexpr int NV = LDP / 64;            // b128 reads per panel row per lane
   constexpr int RG = q_rows_per_group(LDP);
   constexpr int STAGE_B = q_stage_bytes(TILE_B);
@@ -1184,18 +725,15 @@ spmm_quad_kernel(const int32_t* __restrict__ blk_row0, const uint32_t* __restric
   if (ct0 < ct1) SAPCA_QBOOKKEEPING(ct0)
   if (PREFETCH && ct0 < ct1) SAPCA_QPREFETCH(ct0)
   for (int ct = ct0; ct < ct1; ++ct) {
-    if (!(mode & 8) || ct == ct0) {
-      __syncthreads();  // the previous tile's readers are done
-      if (!PREFETCH) SAPCA_QPREFETCH(ct)
-      store_regs<NP_TILE, QTHREADS>(pt, tile, TILE_B);
-      store_regs<NP_STAGE, QTHREADS>(ps, stage, STAGE_B);
-      __syncthreads();
-    }
+    __syncthreads();  // the previous tile's readers are done
+    if (!PREFETCH) SAPCA_QPREFETCH(ct)
+    store_regs<NP_TILE, QTHREADS>(pt, tile, TILE_B);
+    store_regs<NP_STAGE, QTHREADS>(ps, stage, STAGE_B);
+    __syncthreads();
     const int cnt_v = cnt_next;
     const unsigned woff = woff_next;
-    if (ct + 1 < ct1 && !(mode & 8)) SAPCA_QBOOKKEEPING(ct + 1)
-    if (PREFETCH && ct + 1 < ct1 && !(mode & 10)) SAPCA_QPREFETCH(ct + 1)
-    if (mode & 1) continue;
+    if (ct + 1 < ct1) SAPCA_QBOOKKEEPING(ct + 1)
+    if (PREFETCH && ct + 1 < ct1) SAPCA_QPREFETCH(ct + 1)
     if (my_quads > 0) {
       const char* sl = stage + (size_t)woff * 8 + g * 8;
 #pragma unroll
@@ -1257,14 +795,13 @@ spmm_quad_kernel(const int32_t* __restrict__ blk_row0, const uint32_t* __restric
 #undef SAPCA_QBOOKKEEPING
 
 template <int LDP, bool PREFETCH, int TILE_B>
-void launch_quad(const TiledOp& op, const float* X, int ldx, float* out, int ldo, int ncols, const float* cvec, int mode,
-                 hipStream_t s) {
+void launch_quad(const TiledOp& op, const float* X, int ldx, float* out, int ldo, int ncols, const float* cvec, hipStream_t s) {
   static LdsAttrState attr;
   ensure_dynamic_lds(reinterpret_cast<const void*>(&spmm_quad_kernel<LDP, PREFETCH, TILE_B>), LDS_TOTAL, attr);
   hipLaunchKernelGGL((spmm_quad_kernel<LDP, PREFETCH, TILE_B>), dim3((unsigned)(op.nrb * op.nsplit)), dim3(QTHREADS), LDS_TOTAL, s,
                      op.blk_row0, op.row_perm, op.nct, op.tc, op.chunk_off, op.wave_off, reinterpret_cast<const uint16_t*>(op.steps),
                      reinterpret_cast<const Ent*>(op.ent), op.cols, X, ldx, op.nsplit, op.tiles_per_split, out, op.rows, ldo,
-                     ncols, cvec, mode);
+                     ncols, cvec);
 }
 
 // ---- the same sweep for f64 panels and values ------------------------------------------------------
@@ -1395,17 +932,6 @@ void launch_quad_f64(const TiledOp& op, const double* X, int ldx, double* out, i
                      op.blk_row0, op.row_perm, op.nct, op.chunk_off, op.wave_off, reinterpret_cast<const uint16_t*>(op.steps),
                      reinterpret_cast<const EntD*>(op.ent), op.cols, X, ldx, op.nsplit, op.tiles_per_split, out, op.rows, ldo,
                      ncols, cvec);
-}
-
-template <int LDP, int SLOTS, bool PREFETCH>
-void launch_tiled(const TiledOp& op, const float* X, float* out, int ldo, int ncols, const float* cvec, int mode,
-                  hipStream_t s) {
-  static LdsAttrState attr;
-  ensure_dynamic_lds(reinterpret_cast<const void*>(&spmm_tiled_kernel<LDP, SLOTS, PREFETCH>), LDS_TOTAL, attr);
-  hipLaunchKernelGGL((spmm_tiled_kernel<LDP, SLOTS, PREFETCH>), dim3((unsigned)(op.nrb * op.nsplit)), dim3(waves_for(SLOTS) * WAVE), LDS_TOTAL,
-                     s, op.blk_row0, op.nct, op.tc, op.chunk_off, op.wave_off, op.steps,
-                     reinterpret_cast<const Ent*>(op.ent), op.cols, X, op.nsplit, op.tiles_per_split, out, op.rows, ldo,
-                     ncols, cvec, mode);
 }
 
 
@@ -2056,76 +1582,48 @@ inline unsigned qf_grid(int64_t nquads) {
 }
 
 template <typename VT>
-bool build_tiled_t(const CsrView<VT>& S, bool transposed, int ldp_elems, TiledOp& op, TiledBuffers& buf, hipStream_t s,
-                   bool rows_tile_major, const uint64_t* packed_rows, bool allow_big_tile, bool seg_ready,
+bool build_tiled_t(const CsrView<VT>& S, int ldp_elems, TiledOp& op, TiledBuffers& buf, hipStream_t s,
+                   bool rows_tile_major, const uint64_t* packed_rows, bool seg_ready,
                    const AtDirectSrc* direct = nullptr) {
   typedef typename EntOf<VT>::type E;
   constexpr bool f32 = sizeof(VT) == 4;
   const int ldp = ldp_elems * (int)sizeof(VT) / 4;
-  SAPCA_CHECK(ldp == 64 || ldp == 128, SAPCA_ERR_ARG, "tiled sweep: panel rows must be 256 or 512 bytes");
+  SAPCA_CHECK(ldp_elems == 64, SAPCA_ERR_ARG, "tiled sweep: panels must have 64 columns");
   op = TiledOp();
-  if (!f32 && (transposed || packed_rows)) return false;
+  if (!f32 && packed_rows) return false;
   if (S.rows == 0 || S.cols == 0 || S.nnz == 0) return false;
-  // the operator is S, or S^T built straight from S (quad format only)
-  const int64_t op_rows = transposed ? S.cols : S.rows, op_cols = transposed ? S.rows : S.cols;
-  static const int fmt_env = dbg_env("SAPCA_TILED_FMT") ? atoi(dbg_env("SAPCA_TILED_FMT")) : 1;
-  const bool quad = fmt_env == 1 || !f32;   // 1: a row per 16-lane group (default); 0: two half-waves per row
-  int tile_bytes = quad ? Q_TILE_BYTES : TILE_BYTES;
-  int tc = tile_bytes / (ldp * 4);
-  if (transposed && (!quad || (tc + 63) / 64 > TQ_NI)) return false;
-  if (rows_tile_major && !quad) return false;
-  if (packed_rows && !(quad && !transposed && rows_tile_major)) return false;   // only the tile-major builders read packed rows
-  int nct = (int)((op_cols + tc - 1) / tc);
-  const int maskw = (Q_TILE_BYTES / (ldp * 4) + 31) / 32;   // only the transposed builder uses it (default split)
+  const int64_t op_rows = S.rows, op_cols = S.cols;
+  const int tile_bytes = Q_TILE_BYTES;
+  const int tc = tile_bytes / (ldp * 4);
+  if (packed_rows && !rows_tile_major) return false;   // only the tile-major builders read packed rows
+  const int nct = (int)((op_cols + tc - 1) / tc);
   // row blocks of <= 512 rows.  With enough rows the block count is a multiple of the 256 CUs (every
   // CU runs the same number of workgroups); with few rows (A^T) the tile range is split instead.
-  static const int slots_env = dbg_env("SAPCA_TILED_SLOTS") ? atoi(dbg_env("SAPCA_TILED_SLOTS")) : 2;
-  const int slots = (ldp == 64 && slots_env == 4) ? 4 : 2;
-  const int waves = quad ? QWAVES : waves_for(slots);
+  const int waves = QWAVES;
   // (the DPP-fed sweep double-buffers the default 80 KiB tile and holds 8 or 16 row slots per lane group: f32 operators
   // with 64-column tiles keep that split, and take 1024-row blocks -- half the tile refills and barriers per entry --
   // when the operator has at least 16 of them (A^T of a tall matrix: the tile range is split over workgroups instead))
-  const bool dq_candidate = f32 && quad && ldp == 64 && dbg_env("SAPCA_NO_DQ") == nullptr;
-  const int block_rows = dq_candidate ? dq_block_rows(op_rows)
-                         : quad ? QWAVES * QGROUPS * q_rows_per_group(ldp)
-                                : waves * ((slots == 2 && ldp == 128) ? RW / 2 : (slots == 2 ? RW2 : RW));
-  int stage_cap = quad ? q_stage_bytes(tile_bytes) / (int)sizeof(E) - WAVE : STAGE_ENTRIES;
+  const bool dq_candidate = f32 && ldp == 64 && dbg_env("SAPCA_NO_DQ") == nullptr;
+  const int block_rows = dq_candidate ? dq_block_rows(op_rows) : QWAVES * QGROUPS * q_rows_per_group(ldp);
+  const int stage_cap = q_stage_bytes(tile_bytes) / (int)sizeof(E) - WAVE;
   int64_t nrb = 0;
   int nsplit = 1;
   natural_partition(op_rows, nct, block_rows, nrb, nsplit);
-  // the bigger tile (fewer, longer tile steps, less quad padding) when the chunks are expected to leave room
-  // in the smaller staging area; operators fed by the tile-major transposition keep the default split
-  // (their tile count is fixed before the transposition runs)
-  // (f64 operators keep the default split too: the f64 DPP-fed sweep double-buffers the 80 KiB tile)
-  const bool dq64_candidate = !f32 && quad && dbg_env("SAPCA_NO_DQ") == nullptr && dbg_env("SAPCA_NO_DQ_F64") == nullptr;
-  if (quad && !transposed && !rows_tile_major && allow_big_tile && !dq_candidate && !dq64_candidate && dbg_env("SAPCA_TILE_DEFAULT") == nullptr) {
-    const int tcb = Q_TILE_BYTES_BIG / (ldp * 4);
-    const double est = 1.3 * (double)S.nnz / ((double)nrb * std::ceil((double)op_cols / tcb));
-    if (est <= 0.78 * (q_stage_bytes(Q_TILE_BYTES_BIG) / (int)sizeof(E) - WAVE)) {
-      tile_bytes = Q_TILE_BYTES_BIG;
-      tc = tcb;
-      nct = (int)((op_cols + tc - 1) / tc);
-      stage_cap = q_stage_bytes(tile_bytes) / (int)sizeof(E) - WAVE;
-      if (nsplit > 1) nsplit = (int)std::min<int64_t>(nct, nsplit);
-    }
-  }
-  if (quad && !transposed && (op_cols >= (1 << 24) || nct > (rows_tile_major ? Q_MAX_TILES_RUNS : 4096))) return false;   // float-reciprocal tile arithmetic, LDS tables of the builders
+  if (op_cols >= (1 << 24) || nct > (rows_tile_major ? Q_MAX_TILES_RUNS : 4096)) return false;   // float-reciprocal tile arithmetic, LDS tables of the builders
   const float inv_nct = 1.0f / (float)nct;
   int32_t* d_seg = nullptr;
-  if (direct && !(f32 && quad && !transposed && rows_tile_major && dq_candidate && tc <= 32 * ATD_MASK_WORDS && block_rows <= QBLOCK_ROWS))
+  if (direct && !(f32 && rows_tile_major && dq_candidate && tc <= 32 * ATD_MASK_WORDS && block_rows <= QBLOCK_ROWS))
     return false;
-  if (!transposed && !direct) {
+  if (!direct) {
     d_seg = buf.seg.as<int32_t>((size_t)S.rows * (nct + 1));
-    if (quad && rows_tile_major && seg_ready) {
+    if (rows_tile_major && seg_ready) {
       // at_stats_index() filled it in the statistics pass
-    } else if (quad && rows_tile_major) {
+    } else if (rows_tile_major) {
       hipLaunchKernelGGL(tile_index_mod_kernel, dim3(grid_for(S.rows * (int64_t)(nct + 1), 256, 16384)), dim3(256), 0, s,
                          S.ptr, S.idx, packed_rows, S.rows, nct, inv_nct, d_seg);
-    } else if (quad) {
+    } else {
       hipLaunchKernelGGL(tile_hist_kernel, dim3(grid_for(S.rows, 4, 8192)), dim3(256), (size_t)4 * nct * sizeof(uint32_t), s,
                          S.ptr, S.idx, S.rows, nct, inv_nct, d_seg);
-    } else {
-      if constexpr (f32) build_tile_index(S, tc, nct, d_seg, s);
     }
   }
   // Rows sorted by length, longest first (quad format built from a CSR): the four rows of a quad and the
@@ -2134,7 +1632,7 @@ bool build_tiled_t(const CsrView<VT>& S, bool transposed, int ldp_elems, TiledOp
   // detection rate).  Blocks are cut from the sorted order with about equal entry counts (at most 512 rows).
   uint32_t* d_perm = nullptr;
   std::vector<uint32_t> sorted_len;
-  bool sort_rows = quad && !transposed && dbg_env("SAPCA_NO_ROWSORT") == nullptr;
+  bool sort_rows = dbg_env("SAPCA_NO_ROWSORT") == nullptr;
   // page-locked staging of this builder: [0] slots of the natural quads, [1..2] largest chunk | total, then the block table
   int64_t* pinned = static_cast<int64_t*>(buf.host.ensure((size_t)(8 + 65536 + 2) * sizeof(int64_t)));
   bool speculate = false;
@@ -2177,7 +1675,6 @@ bool build_tiled_t(const CsrView<VT>& S, bool transposed, int ldp_elems, TiledOp
   uint8_t* d_steps = nullptr;
   uint32_t* d_wave_off = nullptr;
   uint32_t* d_quad_off = nullptr;
-  uint16_t* d_rank = nullptr;
   int64_t* d_chunk = nullptr;
   int64_t* d_raw = nullptr;   // (bucket route) stored entries per chunk, then their exclusive scan
   for (int attempt = 0;; ++attempt) {
@@ -2209,9 +1706,9 @@ bool build_tiled_t(const CsrView<VT>& S, bool transposed, int ldp_elems, TiledOp
     nchunks = nrb * nct;
     mid_row0 = blk[(size_t)(nrb / 2)];
     d_blk = buf.blk.as<int32_t>((size_t)nrb + 1);
-    d_steps = buf.steps.as<uint8_t>((size_t)nchunks * (quad ? (size_t)Q_BLOCK_QUADS * 2 : (size_t)BLOCK_ROWS));
+    d_steps = buf.steps.as<uint8_t>((size_t)nchunks * Q_BLOCK_QUADS * 2);
     d_wave_off = buf.wave_off.as<uint32_t>((size_t)nchunks * waves);
-    if (quad) d_quad_off = buf.run.as<uint32_t>((size_t)nchunks * Q_BLOCK_QUADS);
+    d_quad_off = buf.run.as<uint32_t>((size_t)nchunks * Q_BLOCK_QUADS);
     d_chunk = buf.chunk_off.as<int64_t>((size_t)nchunks + 1);
     if (blk.size() <= 2 * 65536) {   // (through the page-locked staging: the copy does not wait on a bounce buffer)
       std::memcpy(pinned + 8, blk.data(), blk.size() * sizeof(int32_t));
@@ -2219,29 +1716,13 @@ bool build_tiled_t(const CsrView<VT>& S, bool transposed, int ldp_elems, TiledOp
     } else {
       SAPCA_HIP(hipMemcpyAsync(d_blk, blk.data(), blk.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     }
-    if (transposed) {
-      d_seg = buf.seg.as<int32_t>((size_t)S.rows * (nrb + 1));
-      hipLaunchKernelGGL(bound_index_kernel, dim3(grid_for(S.rows * (nrb + 1), 256, 16384)), dim3(256), 0, s, S.ptr, S.idx,
-                         S.rows, d_blk, (int)nrb, d_seg);
-      d_rank = buf.rank.as<uint16_t>((size_t)S.nnz);
-      static LdsAttrState tq_attr;
-      ensure_dynamic_lds(reinterpret_cast<const void*>(&tquad_count_kernel), (size_t)2 * QBLOCK_ROWS * maskw * sizeof(uint32_t), tq_attr);
-      hipLaunchKernelGGL(tquad_count_kernel, dim3((unsigned)nchunks), dim3(TQ_THREADS),
-                         (size_t)2 * QBLOCK_ROWS * maskw * sizeof(uint32_t), s, S.ptr, S.idx, d_seg, S.rows, d_blk, (int)nrb, nct,
-                         maskw, d_rank, reinterpret_cast<uint16_t*>(d_steps), d_quad_off, d_wave_off, d_chunk);
-    } else if (quad && direct) {
+    if (direct) {
       d_raw = buf.rank.as<int64_t>((size_t)nchunks + 1);
       hipLaunchKernelGGL(quad_count_kernel, dim3((unsigned)(nrb * ((nct + QC_TILES - 1) / QC_TILES))), dim3(Q_BLOCK_QUADS), 0, s, d_seg, d_blk, d_perm, nct,
                          reinterpret_cast<uint16_t*>(d_steps), (uint32_t*)nullptr, d_wave_off, d_chunk, direct->cnt16, direct->n2, d_raw);
-    } else if (quad)
+    } else
       hipLaunchKernelGGL(quad_count_kernel, dim3((unsigned)(nrb * ((nct + QC_TILES - 1) / QC_TILES))), dim3(Q_BLOCK_QUADS), 0, s, d_seg, d_blk, d_perm, nct,
                          reinterpret_cast<uint16_t*>(d_steps), d_quad_off, d_wave_off, d_chunk);
-    else if (slots == 2)
-      hipLaunchKernelGGL((tiled_count_kernel<16, 2 * SAPCA_PADSTEPS>), dim3((unsigned)nchunks), dim3(BLOCK_ROWS), 0, s, d_seg, d_blk, nct,
-                         d_steps, d_wave_off, d_chunk);
-    else
-      hipLaunchKernelGGL((tiled_count_kernel<8, 4>), dim3((unsigned)nchunks), dim3(BLOCK_ROWS), 0, s, d_seg, d_blk, nct,
-                         d_steps, d_wave_off, d_chunk);
     // maximum chunk size (staging capacity check) and the exclusive scans of the chunk sizes (and, on the bucket route, of
     // the stored-entry counts) in one launch
     int64_t* d_max = buf.misc.as<int64_t>(8);
@@ -2262,12 +1743,10 @@ bool build_tiled_t(const CsrView<VT>& S, bool transposed, int ldp_elems, TiledOp
     max_chunk = host[0];
     total = host[1];
     if (dbg_env("SAPCA_DEBUG"))
-      fprintf(stderr, "sapca: build_tiled%s rows %lld cols %lld nrb %lld nct %d split %d max_chunk %lld (cap %d) total %lld\n",
-              transposed ? " (transposed source)" : "", (long long)op_rows, (long long)op_cols, (long long)nrb, nct, nsplit,
+      fprintf(stderr, "sapca: build_tiled rows %lld cols %lld nrb %lld nct %d split %d max_chunk %lld (cap %d) total %lld\n",
+              (long long)op_rows, (long long)op_cols, (long long)nrb, nct, nsplit,
               (long long)max_chunk, stage_cap, (long long)total);
     if (max_chunk <= stage_cap || dq_candidate) break;   // the DPP-fed sweep stages no entries: nothing to fit
-    if (tile_bytes == Q_TILE_BYTES_BIG)   // the estimate was too optimistic: take the default split instead of halving the row blocks
-      return build_tiled_t<VT>(S, transposed, ldp_elems, op, buf, s, rows_tile_major, packed_rows, false, seg_ready);
     if (attempt == 3 || nrb * 2 > op_rows) return false;  // does not fit: the caller stays on the row kernel
     nrb *= 2;
     if (nsplit > 1) nsplit = std::max(1, nsplit / 2);
@@ -2275,7 +1754,7 @@ bool build_tiled_t(const CsrView<VT>& S, bool transposed, int ldp_elems, TiledOp
   E* d_ent = reinterpret_cast<E*>(buf.ent.ensure((size_t)(total + ENT_SLACK) * sizeof(E)));
   bool aux_pending = false;
   op.rows = op_rows; op.cols = op_cols; op.ldp = ldp_elems; op.elem = (int)sizeof(VT); op.tc = tc; op.nct = nct; op.nrb = (int)nrb; op.block_rows = block_rows; op.max_chunk = max_chunk;
-  op.nsplit = nsplit; op.tiles_per_split = tiles_per_split; op.total_entries = total; op.slots = slots; op.fmt = quad ? 1 : 0; op.tile_bytes = tile_bytes;
+  op.nsplit = nsplit; op.tiles_per_split = tiles_per_split; op.total_entries = total; op.tile_bytes = tile_bytes;
   op.mid_row0 = mid_row0;
   op.blk_row0 = d_blk; op.row_perm = d_perm; op.chunk_off = d_chunk; op.wave_off = d_wave_off; op.steps = d_steps; op.ent = d_ent;
   if constexpr (f32) {
@@ -2298,18 +1777,16 @@ bool build_tiled_t(const CsrView<VT>& S, bool transposed, int ldp_elems, TiledOp
       return false;
     }
   }
-  if constexpr (!f32) {
-    if (quad) {   // the f64 DPP-fed sweep reads the same tables (an operator it cannot take stays on the staged-entry sweep)
-      op.valid = true;
-      (void)dq_build_tables(op, buf, s);
-      op.valid = false;
-    }
+  if constexpr (!f32) {   // the f64 DPP-fed sweep reads the same tables (an operator it cannot take stays on the staged-entry sweep)
+    op.valid = true;
+    (void)dq_build_tables(op, buf, s);
+    op.valid = false;
   }
   // quads that fit the LDS image on average: staged fill (coalesced stores, pads itself); otherwise
   // the direct fill over a zeroed buffer
   // f64 entries are 16 bytes: the LDS image holds QF_CAP_MIN of them (64 KiB), two workgroups per CU
   const int qf_cap_max = f32 ? QF_CAP_MAX : QF_CAP_MIN;
-  const bool staged_fill = quad && !transposed && !rows_tile_major && dbg_env("SAPCA_FILL_DIRECT") == nullptr &&
+  const bool staged_fill = !rows_tile_major && dbg_env("SAPCA_FILL_DIRECT") == nullptr &&
                            (double)total <= 0.93 * qf_cap_max * ((double)op_rows / 4.0) && nct <= 768;   // (a quad above the image takes the direct route inside the kernel)
   // The image is sized to the operator's average quad + 12 % (round 5; rounds 1-4: 4096 or 6144 entries): a workgroup's LDS is
   // what limits the fill's residency (its waves sit out two memory round trips each), and C2's quads of 3 100 slots fit five
@@ -2318,19 +1795,13 @@ bool build_tiled_t(const CsrView<VT>& S, bool transposed, int ldp_elems, TiledOp
   const double quad_avg = (double)total / std::max(1.0, (double)op_rows / 4.0);
   const int qf_cap_fit = (int)std::min<int64_t>(qf_cap_max, std::max<int64_t>(2048, round_up((int64_t)(1.12 * quad_avg) + 64, 256)));
   const int qf_cap = (!f32 || qf_cap_fixed) ? ((double)total <= 0.85 * QF_CAP_MIN * ((double)op_rows / 4.0) ? QF_CAP_MIN : qf_cap_max) : qf_cap_fit;
-  const bool runs_fill = quad && !transposed && rows_tile_major && nct <= Q_MAX_TILES_RUNS;
+  const bool runs_fill = rows_tile_major && nct <= Q_MAX_TILES_RUNS;
   if ((packed_rows || direct) && !runs_fill) {
     if (aux_pending) SAPCA_HIP(hipStreamWaitEvent(s, buf.aux_join, 0));
     return false;
   }
   if (staged_fill || runs_fill || direct) SAPCA_HIP(hipMemsetAsync(d_ent + total, 0, (size_t)ENT_SLACK * sizeof(E), s));
   else SAPCA_HIP(hipMemsetAsync(d_ent, 0, (size_t)(total + ENT_SLACK) * sizeof(E), s));
-  size_t lds = (size_t)nct * sizeof(uint32_t);
-  uint32_t* run_global = nullptr;
-  if (!quad && lds > 48 * 1024) {
-    run_global = buf.run.as<uint32_t>((size_t)nrb * waves * nct);
-    lds = 0;
-  }
   if constexpr (f32) {
   if (direct) {
     // bucket offsets, column -> (block, slot), the scatter of A's entries, one workgroup per chunk for the format
@@ -2368,10 +1839,7 @@ bool build_tiled_t(const CsrView<VT>& S, bool transposed, int ldp_elems, TiledOp
     if (direct->stats)
       hipLaunchKernelGGL(atd_stats_reduce_kernel, dim3((unsigned)((op_rows + 63) / 64)), dim3(1024), 0, s, d_psum, d_psq, op_rows, nct,
                          direct->stats, direct->stats + op_rows);
-  } else if (transposed)
-    hipLaunchKernelGGL(tquad_fill_kernel, dim3((unsigned)nchunks), dim3(TQ_THREADS), 0, s, S.ptr, S.idx, S.val, d_rank, d_seg,
-                       S.rows, d_blk, (int)nrb, nct, ldp * 4, d_chunk, d_quad_off, d_ent);
-  else if (runs_fill) {
+  } else if (runs_fill) {
     const int seg_lds_max = dbg_env("SAPCA_RUNS_SEG_LDS_MAX") ? atoi(dbg_env("SAPCA_RUNS_SEG_LDS_MAX")) : 1024;   // tiles; above: bounds from global memory
     if (nct <= seg_lds_max)
       hipLaunchKernelGGL(quad_fill_runs_kernel<true>, dim3((unsigned)(nrb * Q_BLOCK_QUADS)), dim3(256),
@@ -2384,17 +1852,10 @@ bool build_tiled_t(const CsrView<VT>& S, bool transposed, int ldp_elems, TiledOp
     hipLaunchKernelGGL(quad_fill_staged_kernel<float>, dim3(qf_grid((int64_t)nrb * Q_BLOCK_QUADS)), dim3(256),
                        (size_t)qf_cap * sizeof(Ent) + ((size_t)7 * nct + 1) * sizeof(uint32_t), s, S.ptr, S.idx, S.val, d_seg, d_blk,
                        d_perm, nct, qf_cap, inv_nct, ldp * 4, d_chunk, d_quad_off, d_ent, (int)(nrb * Q_BLOCK_QUADS));
-  else if (quad)
+  else
     hipLaunchKernelGGL(quad_fill_kernel<float>, dim3((unsigned)((S.rows + 3) / 4)), dim3(256), (size_t)4 * nct * sizeof(uint32_t), s,
                        S.ptr, S.idx, S.val, S.rows, d_blk, d_perm, (int)nrb, nct, inv_nct, ldp * 4, d_chunk, d_quad_off, d_ent);
-  else if (slots == 2)
-    hipLaunchKernelGGL((tiled_fill_kernel<16, 2 * SAPCA_PADSTEPS>), dim3((unsigned)(nrb * 16)), dim3(WAVE), lds, s, S.ptr, S.idx, S.val, d_seg,
-                       d_blk, nct, tc, ldp * 4, d_chunk, d_wave_off, d_ent, run_global);
-  else
-    hipLaunchKernelGGL((tiled_fill_kernel<8, 4>), dim3((unsigned)(nrb * 8)), dim3(WAVE), lds, s, S.ptr, S.idx, S.val, d_seg,
-                       d_blk, nct, tc, ldp * 4, d_chunk, d_wave_off, d_ent, run_global);
   } else {
-    (void)lds; (void)run_global; (void)d_rank;
     if (runs_fill) {
       // rows grouped by tile (the tile-major transposition): a quad's run in a tile is contiguous in its rows
       const int seg_lds_max = dbg_env("SAPCA_RUNS_SEG_LDS_MAX") ? atoi(dbg_env("SAPCA_RUNS_SEG_LDS_MAX")) : 1024;
@@ -2422,12 +1883,12 @@ bool build_tiled_t(const CsrView<VT>& S, bool transposed, int ldp_elems, TiledOp
 }
 }  // namespace
 
-bool build_tiled(const CsrView<float>& S, bool transposed, int ldp, TiledOp& op, TiledBuffers& buf, hipStream_t s,
-                 bool rows_tile_major, const uint64_t* packed_rows, bool allow_big_tile, bool seg_ready) {
-  return build_tiled_t<float>(S, transposed, ldp, op, buf, s, rows_tile_major, packed_rows, allow_big_tile, seg_ready);
+bool build_tiled(const CsrView<float>& S, int ldp, TiledOp& op, TiledBuffers& buf, hipStream_t s,
+                 bool rows_tile_major, const uint64_t* packed_rows, bool seg_ready) {
+  return build_tiled_t<float>(S, ldp, op, buf, s, rows_tile_major, packed_rows, seg_ready);
 }
 bool build_tiled(const CsrView<double>& S, int ldp, TiledOp& op, TiledBuffers& buf, hipStream_t s, bool rows_tile_major) {
-  return build_tiled_t<double>(S, false, ldp, op, buf, s, rows_tile_major, nullptr, true, false);
+  return build_tiled_t<double>(S, ldp, op, buf, s, rows_tile_major, nullptr, false);
 }
 
 bool build_tiled_at_direct(const CsrView<float>& A, int ldp, TiledOp& op, TiledBuffers& buf, int64_t* at_ptr, double* stats,
@@ -2475,7 +1936,7 @@ bool build_tiled_at_direct(const CsrView<float>& A, int ldp, TiledOp& op, TiledB
   CsrView<float> At;
   At.rows = n; At.cols = m; At.nnz = A.nnz; At.ptr = at_ptr; At.idx = nullptr; At.val = nullptr;
   AtDirectSrc src{&A, cnt16, n2, &scratch, stats, bnd, nrb_nat, &blk_nat, true};
-  return build_tiled_t<float>(At, false, ldp, op, buf, s, true, nullptr, true, false, &src);
+  return build_tiled_t<float>(At, ldp, op, buf, s, true, nullptr, false, &src);
 }
 
 void at_stats_index(const int64_t* ptr, const uint64_t* packed, int64_t rows, int64_t cols, int ldp, TiledBuffers& buf,
@@ -2496,15 +1957,13 @@ int tiled_tile_count(int64_t cols, int ldp) {
 void spmm_tiled(const TiledOp& op, const float* X, int ldx, float* Y, int ldy, int ncols, const float* cvec, DevBuf& scratch,
                 hipStream_t s, PanelSource<float>* keep) {
   SAPCA_CHECK(op.valid && op.elem == 4, SAPCA_ERR_ARG, "tiled sweep: operator not built");
-  SAPCA_CHECK(ldx == op.ldp || (op.fmt == 1 && op.ldp == 64 && ldx % 64 == 0), SAPCA_ERR_ARG,
+  SAPCA_CHECK(ldx == op.ldp || (op.ldp == 64 && ldx % 64 == 0), SAPCA_ERR_ARG,
               "tiled sweep: panel leading dimension does not match the operator's tile geometry");
-  static const int mode = dbg_env("SAPCA_TILED_MODE") ? atoi(dbg_env("SAPCA_TILED_MODE")) : 0;  // ablation switches (debug)
   // A 128-wide panel over the 64-wide tile geometry goes through in two column passes: twice the entry
   // traffic, but a tile holds twice the panel rows of the 128-wide geometry (half the tiles, less quad
   // padding, chunks that amortise their refill) -- what keeps wide panels on sparse operators (C5) staged.
   const int passes = ldx / op.ldp;
   float* part = op.nsplit > 1 ? scratch.as<float>((size_t)op.nsplit * op.rows * op.ldp) : nullptr;
-  const bool pf = !(mode & 4);
   for (int pass = 0; pass < passes; ++pass) {
     const int c0 = pass * op.ldp;
     if (c0 >= ncols && pass > 0) break;
@@ -2521,25 +1980,11 @@ void spmm_tiled(const TiledOp& op, const float* X, int ldx, float* Y, int ldy, i
     static const bool force_staged = dbg_env("SAPCA_SWEEP_STAGED") != nullptr;   // A/B: the staged-entry quad sweep
     // (blocks of more than 512 rows exist only for the DPP-fed sweep: the switches below do not apply to them)
     const bool staged_ok = op.block_rows <= 512 && op.max_chunk <= (int64_t)(q_stage_bytes(op.tile_bytes) / 8 - WAVE);
-    SAPCA_CHECK(op.fmt != 1 || staged_ok || dq_usable(op, ldx), SAPCA_ERR_ARG, "tiled sweep: this operator needs the DPP-fed sweep");
-    if (op.fmt == 1 && dq_usable(op, ldx) && (!staged_ok || (!force_staged && mode == 0))) {
+    SAPCA_CHECK(staged_ok || dq_usable(op, ldx), SAPCA_ERR_ARG, "tiled sweep: this operator needs the DPP-fed sweep");
+    if (dq_usable(op, ldx) && (!staged_ok || !force_staged)) {
       launch_dq(op, Xp, ldx, out, ldo, nc, cv, s);
-    } else if (op.fmt == 1) {
-      const bool big = op.tile_bytes == Q_TILE_BYTES_BIG;
-      if (op.ldp == 64 && pf && big) launch_quad<64, true, Q_TILE_BYTES_BIG>(op, Xp, ldx, out, ldo, nc, cv, mode, s);
-      else if (op.ldp == 64 && pf) launch_quad<64, true, Q_TILE_BYTES>(op, Xp, ldx, out, ldo, nc, cv, mode, s);
-      else if (op.ldp == 64 && big) launch_quad<64, false, Q_TILE_BYTES_BIG>(op, Xp, ldx, out, ldo, nc, cv, mode, s);
-      else if (op.ldp == 64) launch_quad<64, false, Q_TILE_BYTES>(op, Xp, ldx, out, ldo, nc, cv, mode, s);
-      else if (big) launch_quad<128, false, Q_TILE_BYTES_BIG>(op, Xp, ldx, out, ldo, nc, cv, mode, s);
-      else launch_quad<128, false, Q_TILE_BYTES>(op, Xp, ldx, out, ldo, nc, cv, mode, s);
-    } else if (op.ldp == 64 && op.slots == 4) {
-      if (pf) launch_tiled<64, 4, true>(op, Xp, out, ldo, nc, cv, mode, s);
-      else launch_tiled<64, 4, false>(op, Xp, out, ldo, nc, cv, mode, s);
-    } else if (op.ldp == 64) {
-      if (pf) launch_tiled<64, 2, true>(op, Xp, out, ldo, nc, cv, mode, s);
-      else launch_tiled<64, 2, false>(op, Xp, out, ldo, nc, cv, mode, s);
     } else {
-      launch_tiled<128, 2, false>(op, Xp, out, ldo, nc, cv, mode, s);
+      launch_quad<64, true, Q_TILE_BYTES>(op, Xp, ldx, out, ldo, nc, cv, s);
     }
     if (op.nsplit > 1) {
       const int64_t total = op.rows * (int64_t)op.ldp;
@@ -2562,7 +2007,7 @@ void spmm_tiled(const TiledOp& op, const float* X, int ldx, float* Y, int ldy, i
 // slabs are summed in fixed order.  Requires natural row order (no row_perm: a block's rows are then a contiguous range of
 // the output) and a 64-column panel.  Returns false when the operator cannot be swept this way (nothing is launched).
 bool spmm_tiled_pieces_ok(const TiledOp& op, int npieces, int ldx) {
-  return op.valid && op.elem == 4 && op.fmt == 1 && dq_usable(op, ldx) && ldx == op.ldp && op.row_perm == nullptr && npieces >= 1 && op.nrb >= npieces;
+  return op.valid && op.elem == 4 && dq_usable(op, ldx) && ldx == op.ldp && op.row_perm == nullptr && npieces >= 1 && op.nrb >= npieces;
 }
 
 // bounds[p] = first output row of piece p (bounds[npieces] = rows): one small copy from the device, synchronous
@@ -2602,7 +2047,7 @@ void spmm_tiled_piece(const TiledOp& op, int piece, int npieces, int wgs, int64_
 
 void spmm_tiled(const TiledOp& op, const double* X, int ldx, double* Y, int ldy, int ncols, const double* cvec, DevBuf& scratch,
                 hipStream_t s, PanelSource<double>* keep) {
-  SAPCA_CHECK(op.valid && op.elem == 8 && op.fmt == 1, SAPCA_ERR_ARG, "tiled sweep: no f64 operator built");
+  SAPCA_CHECK(op.valid && op.elem == 8, SAPCA_ERR_ARG, "tiled sweep: no f64 operator built");
   SAPCA_CHECK(ldx >= op.ldp && ldx % op.ldp == 0, SAPCA_ERR_ARG,
               "tiled sweep: panel leading dimension does not match the operator's tile geometry");
   double* part = op.nsplit > 1 ? scratch.as<double>((size_t)op.nsplit * op.rows * op.ldp) : nullptr;
@@ -2621,7 +2066,6 @@ void spmm_tiled(const TiledOp& op, const double* X, int ldx, double* Y, int ldy,
       nc = op.ldp;
     }
     if (op.dq) launch_dq_f64(op, Xp, ldx, out, ldo, nc, cv, s);   // the DPP-fed sweep (spmm_dq.hip)
-    else if (op.tile_bytes == Q_TILE_BYTES_BIG) launch_quad_f64<Q_TILE_BYTES_BIG>(op, Xp, ldx, out, ldo, nc, cv, s);
     else launch_quad_f64<Q_TILE_BYTES>(op, Xp, ldx, out, ldo, nc, cv, s);
     if (op.nsplit > 1) {
       const int64_t total = op.rows * (int64_t)op.ldp;
@@ -2636,11 +2080,6 @@ void spmm_tiled(const TiledOp& op, const double* X, int ldx, double* Y, int ldy,
     }
   }
   SAPCA_HIP(hipGetLastError());
-}
-
-int tiled_geometry(int l) {
-  static const bool wide = dbg_env("SAPCA_TILED_GEOM128") != nullptr;   // the 128-wide tile geometry for l > 64 (one pass)
-  return (l > 64 && wide) ? 128 : 64;
 }
 
 }  // namespace k

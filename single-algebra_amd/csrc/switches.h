@@ -11,16 +11,14 @@
 //   SAPCA_MULTI_INPROCESS=1 multi.cpp    sapca_multi_* members talk through page-locked host memory instead of RCCL
 //
 // The switches of the debug variant (name: effect), by file:
-//   engine.cpp   SAPCA_TILED_MIN_ENTRIES (floor of the staged sweep), SAPCA_TILED_FROM_A, SAPCA_AT_NATURAL, SAPCA_AT_UNPACK,
-//                SAPCA_AT_SORT, SAPCA_PREPARE_SERIAL, SAPCA_PREPARE_ASIDE_FIRST, SAPCA_LANCZOS_TRANSPOSE, SAPCA_MASK_STATS_INLINE,
-//                SAPCA_MASK_SUMS_SCATTER, SAPCA_MASK_TRANSPOSE_FIRST, SAPCA_SMALL_SVD_QR, SAPCA_Q3_ROWKERNEL
-//   spmm_tiled.hip  SAPCA_DQ_BLOCK_ROWS, SAPCA_SPLIT_WGS, SAPCA_TILED_FMT, SAPCA_TILED_SLOTS, SAPCA_TILED_MODE, SAPCA_TILED_GEOM128,
-//                SAPCA_TILE_DEFAULT, SAPCA_QF_CAP_FIXED, SAPCA_NO_ROWSORT, SAPCA_ROWSORT_ALWAYS, SAPCA_FILL_DIRECT, SAPCA_AT_BUCKETS, SAPCA_AT_SORT,
-//                SAPCA_RUNS_SEG_LDS_MAX, SAPCA_SWEEP_STAGED, SAPCA_NO_DQ, SAPCA_DEBUG
-//   spmm_dq.hip  SAPCA_NO_DQ, SAPCA_NO_DQ_F64      spmm.hip  SAPCA_ROWGATHER_PER_ENTRY      prep.hip  SAPCA_TRANSPOSE_GATHER
+//   engine.cpp   SAPCA_TILED_MIN_ENTRIES (floor of the staged sweep), SAPCA_AT_NATURAL, SAPCA_AT_UNPACK, SAPCA_AT_SORT,
+//                SAPCA_LANCZOS_TRANSPOSE, SAPCA_MASK_STATS_INLINE, SAPCA_SMALL_SVD_QR, SAPCA_Q3_ROWKERNEL
+//   spmm_tiled.hip  SAPCA_DQ_BLOCK_ROWS, SAPCA_SPLIT_WGS, SAPCA_QF_CAP_FIXED, SAPCA_NO_ROWSORT, SAPCA_ROWSORT_ALWAYS, SAPCA_FILL_DIRECT,
+//                SAPCA_AT_BUCKETS, SAPCA_AT_SORT, SAPCA_RUNS_SEG_LDS_MAX, SAPCA_SWEEP_STAGED, SAPCA_NO_DQ, SAPCA_DEBUG
+//   spmm_dq.hip  SAPCA_NO_DQ, SAPCA_NO_DQ_F64      prep.hip  SAPCA_TRANSPOSE_GATHER
 //   dense.hip    SAPCA_CHOL_GENERAL, SAPCA_EIG_DEVICE
 //   lanczos.hip  SAPCA_SPMV_NO_LDS, SAPCA_SPMV_NO_SLICE_GRID, SAPCA_SPMV_IDX32, SAPCA_LANCZOS_CHECK
-//   api.cpp      SAPCA_UPLOAD_NARROW_ON_DEVICE, SAPCA_UPLOAD_STATS_OFF
+//   api.cpp      SAPCA_UPLOAD_STATS_OFF
 //   comm.cpp     SAPCA_COMM_FORCE_RCCL (a one-rank RCCL communicator: how a one-GPU box tests the binding), SAPCA_COMM_NO_SPLIT,
 //                SAPCA_RCCL_LIBRARY (path of the tests' stand-in for librccl: tests/fake_rccl)
 #pragma once

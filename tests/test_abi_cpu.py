@@ -155,7 +155,7 @@ def test_generated_sweep_loop_is_what_its_generator_writes(tmp_path):
     assert out.read_text() == committed, "spmm_dq2_gen.h is stale: run python tools/gen_spmm_dq2.py"
 
 
-def test_release_library_reads_no_experiment_switches():
+def test_release_library_reads_no_debug_switches():
     """csrc/switches.h: the SAPCA_* route / layout switches exist only in the -DSAPCA_DEBUG_SWITCHES variant.  The release
     library does not even carry their names; what it does read is listed in switches.h (two deployment escapes)."""
     import glob
@@ -169,16 +169,29 @@ def test_release_library_reads_no_experiment_switches():
     assert names == ["SAPCA_AT_OVERLAP", "SAPCA_MULTI_INPROCESS"], names
     assert len(sites) <= 8, sites
     rel = open(L.LIB_PATH, "rb").read()
-    for name in (b"SAPCA_TILED_FMT", b"SAPCA_AT_NATURAL", b"SAPCA_TRANSPOSE_GATHER", b"SAPCA_MASK_TRANSPOSE_FIRST", b"SAPCA_COMM_FORCE_RCCL",
+    for name in (b"SAPCA_AT_SORT", b"SAPCA_AT_NATURAL", b"SAPCA_TRANSPOSE_GATHER", b"SAPCA_FILL_DIRECT", b"SAPCA_COMM_FORCE_RCCL",
                  b"SAPCA_RCCL_LIBRARY"):   # (the tests' stand-in for librccl is reachable from the debug build only)
         assert name not in rel, f"the release library carries the switch {name.decode()}"
     assert b"SAPCA_AT_OVERLAP" in rel
     if os.path.exists(L.DEBUG_LIB_PATH):
         dbg = open(L.DEBUG_LIB_PATH, "rb").read()
-        assert b"SAPCA_TILED_FMT" in dbg and b"SAPCA_COMM_FORCE_RCCL" in dbg and b"SAPCA_RCCL_LIBRARY" in dbg
+        assert b"SAPCA_AT_SORT" in dbg and b"SAPCA_COMM_FORCE_RCCL" in dbg and b"SAPCA_RCCL_LIBRARY" in dbg
         lib = L.load_debug()
         for name in L.EXPORTED_SYMBOLS:
             assert hasattr(lib, name), name
+
+
+def test_switch_list_names_every_switch_read():
+    """csrc/switches.h lists the switches of the debug variant by file: exactly the names read through dbg_env / dbg_on."""
+    import glob
+    src = os.path.join(ROOT, "single-algebra_amd", "csrc")
+    read = set()
+    for f in glob.glob(os.path.join(src, "*")):
+        if os.path.basename(f) != "switches.h":
+            read |= set(re.findall(r'\bdbg_(?:env|on)\("(SAPCA_\w+)"\)', open(f, errors="replace").read()))
+    header = open(os.path.join(src, "switches.h")).read()
+    listed = header[header.index("The switches of the debug variant"):header.index("#pragma once")]
+    assert read and read == set(re.findall(r"\bSAPCA_\w+", listed)), (sorted(read), sorted(set(re.findall(r"\bSAPCA_\w+", listed))))
 
 
 def test_stand_in_librccl_is_test_infrastructure_only():

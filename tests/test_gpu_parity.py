@@ -1361,9 +1361,8 @@ def test_every_route_to_the_transposed_format_gives_the_same_fit(debug_switches,
     ptr, idx, val = csr_np(synth.gapped_csr(m, n, 0.05, k, seed=5, dtype=torch.float32))
     om = synth.gaussian_panel(n, k + p, 3).numpy()
     out = []
-    routes = ("SAPCA_AT_SORT", "SAPCA_AT_UNPACK", "SAPCA_AT_NATURAL", "SAPCA_TILED_FROM_A", None)
-    monkeypatch.setenv("SAPCA_TILE_DEFAULT", "1")   # same LDS split on every route (a natural-order A^T could take the bigger tile)
-    monkeypatch.setenv("SAPCA_NO_ROWSORT", "1")     # and the same row order: the builder straight from A does not sort rows by length
+    routes = ("SAPCA_AT_SORT", "SAPCA_AT_UNPACK", "SAPCA_AT_NATURAL", None)
+    monkeypatch.setenv("SAPCA_NO_ROWSORT", "1")     # the same row order on every route: natural, not sorted by length
     for route in routes:
         for r in routes[:-1]:
             monkeypatch.delenv(r, raising=False)

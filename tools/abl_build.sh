@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds experiment variants of libsapca.so that differ only in spmm_tiled.hip's compile-time switches:
-#   tools/abl_build.sh NAME "-DSAPCA_ABL=1 ..."   ->  single-algebra_amd/lib/exp/libsapca_NAME.so
+#   tools/abl_build.sh NAME "-DSAPCA_QF_WGS=2048 ..."   ->  single-algebra_amd/lib/exp/libsapca_NAME.so
 # Run one with SAPCA_LIB_PATH=single-algebra_amd/lib/exp/libsapca_NAME.so python bench.py ...
 set -e
 cd "$(dirname "$0")/../single-algebra_amd"

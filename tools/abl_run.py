@@ -1,4 +1,4 @@
-"""Times the C2 sweeps with whatever library SAPCA_LIB_PATH / SAPCA_TILED_MODE select (kernel experiments).
+"""Times the C2 sweeps with whatever library SAPCA_LIB_PATH selects (kernel experiments).
 Results of ablated builds are numerically meaningless; only the per-sweep times are read."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,5 +24,5 @@ for it in range(3):
     t = pca.timings()
     if it:
         a += list(t.spmm_sweep_ms[: t.n_spmm]); at += list(t.spmmt_sweep_ms[: t.n_spmmt])
-tag = os.path.basename(os.environ.get("SAPCA_LIB_PATH", "default")) + " mode " + os.environ.get("SAPCA_TILED_MODE", "0") + " fmt " + os.environ.get("SAPCA_TILED_FMT", "1") + " " + os.environ.get("GEN", "gapped")
+tag = os.path.basename(os.environ.get("SAPCA_LIB_PATH", "default")) + " " + os.environ.get("GEN", "gapped")
 print(f"{tag:52s} A sweep {np.mean(a):.3f} ms   At sweep {np.mean(at):.3f} ms   (n={len(a)},{len(at)})")
