@@ -111,17 +111,446 @@ void collect_timings(sapca_handle_s& h, bool is_fit) {
   if (is_fit) t.comm_ms = comm_dev_ms > 0 ? comm_dev_ms : h.comm.host_ms;
 }
 
+// ------------------------------------------------------------------------------------------
+// prepare: A^T, column statistics, mask compaction (and the few helpers it shares with fit_randomized and transform()).
+// ------------------------------------------------------------------------------------------
+using H = sapca_handle_s;
+
+// A stream beside the main one and its two events, created on first use.
+void lazy_stream(hipStream_t& st, hipEvent_t& a, hipEvent_t& b) {
+  if (st) return;
+  SAPCA_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  SAPCA_HIP(hipEventCreateWithFlags(&a, hipEventDisableTiming));
+  SAPCA_HIP(hipEventCreateWithFlags(&b, hipEventDisableTiming));
+}
+hipStream_t side_stream(H& h) { lazy_stream(h.stream2, h.ev_fork, h.ev_join); return h.stream2; }    // A's format beside A^T
+hipStream_t stats_stream(H& h) { lazy_stream(h.stream3, h.ev_kept, h.ev_stats); return h.stream3; }  // statistics beside the fit
+// what is queued on `later` from here on runs behind everything queued on `earlier` so far
+void order_after(hipStream_t later, hipEvent_t ev, hipStream_t earlier) {
+  SAPCA_HIP(hipEventRecord(ev, earlier));
+  SAPCA_HIP(hipStreamWaitEvent(later, ev, 0));
+}
+// the device statistics: sum | sumsq | count (n each), then what rides behind them in a multi-rank all-reduce
+double* stats_dev(H& h, int64_t n) { return h.stats.as<double>((size_t)3 * n + 1 + H::kStatsTail); }
+// leading dimension of a k-column panel swept through a tile-major format built for ldp columns (0: none)
+// (above 128 columns every panel is a multiple of 64 wide: column passes of the sweeps, 64 / 128-column blocks of the dense kernels)
+int panel_ld(int k, int ldp) { return k > 128 ? (int)round_up(k, 64) : std::max(ldp, k <= 64 ? 64 : 128); }
+
+// The three arrays of a CSR with `rows` rows and room for `cap` entries, in grow-only buffers of the handle.
+template <typename T>
+struct CsrBuf {
+  int64_t* ptr; int32_t* idx; T* val;
+  H::RawCsr raw(int64_t rows, int64_t cols, int64_t nnz) const { return {rows, cols, nnz, ptr, idx, val}; }
+};
+template <typename T>
+CsrBuf<T> csr_buffers(DevBuf& ptr, DevBuf& idx, DevBuf& val, int64_t rows, int64_t cap) {
+  const size_t entries = (size_t)std::max<int64_t>(cap, 1);
+  return {ptr.as<int64_t>((size_t)rows + 1), idx.as<int32_t>(entries), val.as<T>(entries)};
+}
+
+// The original -> compacted column map of the handle's mask on the device.  Main stream, no wait: `o2m32` is pageable
+// memory the copy reads, so it has to outlive the stream's next synchronisation.
+int32_t* upload_o2m(H& h, std::vector<int32_t>& o2m32) {
+  const size_t n = h.orig_to_masked.size();
+  o2m32.resize(n);
+  for (size_t j = 0; j < n; ++j) o2m32[j] = (int32_t)h.orig_to_masked[j];
+  int32_t* d_o2m = h.o2m_dev.as<int32_t>(std::max<size_t>(n, 1));
+  SAPCA_HIP(hipMemcpyAsync(d_o2m, o2m32.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h.stream));
+  return d_o2m;
+}
+// MaskedCSRMatrix::new (sparse_masked/mod.rs:313): A without the masked-out columns, in ca_*.  Main stream; synchronises
+// with the host (the entry count comes back).  drop_* / amax_bits: see k::compact_columns.
+template <typename T>
+H::RawCsr compact_a(H& h, const CsrView<T>& A, const int32_t* d_o2m, int64_t n_used, int32_t* drop_col = nullptr,
+                    T* drop_val = nullptr, unsigned long long* amax_bits = nullptr) {
+  const CsrBuf<T> ca = csr_buffers<T>(h.ca_ptr, h.ca_idx, h.ca_val, A.rows, A.nnz);
+  int64_t nnz_used = 0;
+  k::compact_columns(A, d_o2m, ca.ptr, ca.idx, ca.val, &nnz_used, h.scratch, h.stream, drop_col, drop_val, amax_bits);
+  return ca.raw(A.rows, n_used, nnz_used);
+}
+
+// The route of a preparation: what prepare() knows before it enqueues its first kernel, as three choices.
+//  A^T                 | taken by                                   | what happens
+//  Nothing             | Lanczos, n_used <= m, m >= 4096, nnz > 0,  | no transposed operator: the second product of a step scatters into LDS (scatter.hip,
+//                      | k::scatter_fits (~19k columns: C3 has 18k) | fixed-point sums: reproducible); masked fits still compact A
+//  FormatFromA         | f32, staged sweep, unmasked                | A^T's tile-major format straight from A (spmm_tiled.hip, "bucket route"): no sort, no
+//                      |                                            | transposed CSR; outside its limits (more than 65536 columns, ...) refused: Transposed
+//  FormatFromCompacted | f32, staged sweep, masked, n_used <= 65536 | compaction, then the same builder on its result; refused: CompactedTransposed
+//  CompactedTransposed | every other masked fit                     | compaction, then its transposition into cat_*
+//  Transposed          | every other unmasked fit                   | transposition of A into at_* (tile-major and packed, tile-major, or natural rows)
+//  statistics from     |                                            |
+//  Upload              | a host matrix that came through upload()   | the exact sums gathered behind the DMA (not if a value was inf / nan)
+//  Scatter             | A^T Nothing                                | k::colstats_scatter: the same kind of pass over A as the products
+//  FormatBuild         | A^T FormatFromA                            | by-product of the builder + k::row_lengths_f64; Transposed where it refused
+//  KeptAndDropped      | masked                                     | the kept columns' sums (the builder's, or row sums of the compacted A^T) scattered
+//                      |                                            | over the sums of the (column, value) pairs the compaction dropped
+//  Transposed          | the rest                                   | k::at_stats_index on packed rows, else k::row_sums; k::row_lengths_f64
+//  statistics to host  |                                            |
+//  AllReduce           | more than one rank                         | all-reduce with the tail (row count, piece votes), wait, finish_statistics now
+//  MainCopy            | one rank; unmasked, or statistics Upload   | async copy on the main stream, read at the end of fit() (or SAPCA_MASK_STATS_INLINE)
+//  SideChain           | one rank, statistics KeptAndDropped        | a chain on stream3 queued at the end of prepare(); a Lanczos fit queues the dropped
+//                      |                                            | pairs' sort at once and only the rest of the chain at the end
+//  ScatterSide         | one rank, statistics Scatter               | colstats_scatter and the host copy on stream3, queued at once: a Lanczos fit does not
+//                      |                                            | centre, nothing reads them before fit() ends
+enum class AtFrom { Nothing, FormatFromA, FormatFromCompacted, CompactedTransposed, Transposed };
+enum class StatsFrom { Upload, Scatter, FormatBuild, KeptAndDropped, Transposed };
+enum class StatsTo { AllReduce, MainCopy, SideChain, ScatterSide };
+
+struct PrepPlan {
+  int64_t m = 0, n = 0, nnz = 0, n_used = 0;   // A's shape; the columns the mask keeps (no mask: n)
+  bool masked = false;
+  int tiled_ldp = 0;   // panel leading dimension of the LDS-staged sweep's formats; 0: row kernel, no formats
+  int at_nct = 0;      // > 0: transposed rows come out grouped by the interleaved tile of the A row they came from
+  AtFrom at = AtFrom::Transposed;
+  StatsFrom stats = StatsFrom::Transposed;
+  StatsTo deliver = StatsTo::MainCopy;
+};
+
+// What only a builder's return value settles; the stages fill it in.
+template <typename T>
+struct PrepOutcome {
+  int64_t nnz_used = 0;                  // entries the compaction kept
+  bool at_direct = false;                // build_tiled_at_direct took the operator (A, or the compacted matrix)
+  bool a_aside = false, ok_a = false;    // A's format: queued on the side stream; came out
+  CsrView<T> At;                         // unmasked fits: the transposed CSR (FormatFromA: its row offsets only)
+  const uint64_t* at_packed = nullptr;   // the transposition left its rows packed (row << 32 | value bits)
+  bool at_seg_ready = false;             // ... and the statistics pass left the format builder's per-row tile index
+};
+
+// The mask's index maps as the device wants them.  Pageable memory read by async copies: alive until prepare() has synchronised.
+struct MaskMaps {
+  std::vector<int32_t> o2m32, sel;
+  int32_t *d_o2m = nullptr, *d_sel = nullptr;
+};
+
+// The thread that drives A's format build.  Joined on every exit of prepare(), exceptions included: it must not run into freed state.
+struct Aside {
+  std::thread t;
+  std::exception_ptr err;
+  ~Aside() { if (t.joinable()) t.join(); }
+  void join() { if (t.joinable()) t.join(); if (err) std::rethrow_exception(err); }
+};
+
+// Enqueues nothing; waits on the host for the upload's accumulator flag where a host matrix brought its statistics along.
+template <typename T>
+PrepPlan plan_preparation(H& h, const CsrView<T>& A) {
+  PrepPlan p;
+  const int64_t m = p.m = A.rows, n = p.n = A.cols, nnz = p.nnz = A.nnz;
+  p.masked = !h.mask.empty();
+  const int64_t n_used = p.n_used = p.masked ? (int64_t)std::count_if(h.mask.begin(), h.mask.end(), [](uint8_t b) { return b != 0; }) : n;
+  // LDS-staged sweep (randomized fits; staged_sweep_ldp has the break-even): it fixes the order the transposed rows are produced in
+  if (h.opt.method == SAPCA_RANDOM && m > 0 && n > 0 && n_used > 0) {
+    const int64_t l = std::min<int64_t>((int64_t)(h.opt.n_components + h.opt.n_oversamples), std::min<int64_t>(m, n_used));
+    p.tiled_ldp = staged_sweep_ldp<T>(m, n_used, (double)nnz * ((double)n_used / (double)n), l, h.opt.spmm_variant);
+  }
+  const bool at_tile_major = p.tiled_ldp != 0 && dbg_env("SAPCA_AT_NATURAL") == nullptr;
+  p.at_nct = at_tile_major ? k::tiled_tile_count(m, p.tiled_ldp * (int)sizeof(T) / 4) : 0;   // (a panel row in 4-byte words)
+
+  bool from_upload = h.up_stats.valid && A.ptr == h.in_ptr.p && A.idx == h.in_idx.p && A.val == h.in_val.p &&
+                     h.up_stats.m == (uint64_t)m && h.up_stats.n == (uint64_t)n && h.up_stats.nnz == (uint64_t)nnz &&
+                     h.up_stats.dtype == Engine<T>::kDtype && n > 0 && !h.comm.active();   // (ranks must not differ in their collectives)
+  if (from_upload) {
+    // the last chunk's share of those statistics may still be in flight; the accumulators refuse inf/nan (the flag is
+    // final once the side stream has passed up_stats_done): the sums of the transposed matrix take over then
+    SAPCA_HIP(hipEventSynchronize(h.up_stats_done));
+    if (*static_cast<const int*>(h.up_stats.flag.p) != 0) h.up_stats.valid = from_upload = false;
+  }
+  // (SAPCA_LANCZOS_TRANSPOSE=1 brings the transposed operator of a Lanczos fit, a radix sort, back)
+  const bool lz_scatter = h.opt.method == SAPCA_LANCZOS && n_used > 0 && n_used <= m && m >= 4096 && nnz > 0 &&
+                          k::scatter_fits(n_used) && dbg_env("SAPCA_LANCZOS_TRANSPOSE") == nullptr;
+  const bool bucket_route = sizeof(T) == 4 && at_tile_major;
+  if (lz_scatter) p.at = AtFrom::Nothing;
+  else if (!p.masked) p.at = bucket_route ? AtFrom::FormatFromA : AtFrom::Transposed;
+  else p.at = bucket_route && n_used <= 65536 && dbg_env("SAPCA_AT_SORT") == nullptr ? AtFrom::FormatFromCompacted : AtFrom::CompactedTransposed;
+
+  p.stats = from_upload ? StatsFrom::Upload : lz_scatter ? StatsFrom::Scatter : p.masked ? StatsFrom::KeptAndDropped
+            : p.at == AtFrom::FormatFromA ? StatsFrom::FormatBuild : StatsFrom::Transposed;
+  if (h.comm.active()) p.deliver = StatsTo::AllReduce;
+  else if (p.stats == StatsFrom::Scatter) p.deliver = StatsTo::ScatterSide;
+  else if (p.stats == StatsFrom::KeptAndDropped && dbg_env("SAPCA_MASK_STATS_INLINE") == nullptr) p.deliver = StatsTo::SideChain;
+  return p;
+}
+
+// Mask index maps (sparse_masked/mod.rs:264-271, the HashMap of :462-466): host, then two copies on the main stream.  No wait.
+void mask_maps(H& h, const PrepPlan& p, MaskMaps& maps) {
+  h.cols_to_use.clear();
+  h.orig_to_masked.clear();
+  h.has_mask_maps = p.masked;
+  if (!p.masked) return;
+  h.orig_to_masked.assign((size_t)p.n, -1);
+  for (int64_t j = 0; j < p.n; ++j)
+    if (h.mask[(size_t)j]) {
+      h.orig_to_masked[(size_t)j] = (int64_t)h.cols_to_use.size();
+      h.cols_to_use.push_back((uint64_t)j);
+    }
+  // (sapca_get_mask_index_maps answers from here on; every rank of a sharded fit fails here, before its first collective)
+  if (p.n_used == 0) throw Error(SAPCA_ERR_SVD, "SVD computation failed: the mask selects no feature");
+  maps.sel.assign(h.cols_to_use.begin(), h.cols_to_use.end());
+  maps.d_o2m = upload_o2m(h, maps.o2m32);
+  maps.d_sel = h.sel_rows_dev.as<int32_t>((size_t)p.n_used);
+  SAPCA_HIP(hipMemcpyAsync(maps.d_sel, maps.sel.data(), (size_t)p.n_used * sizeof(int32_t), hipMemcpyHostToDevice, h.stream));
+}
+
+// The sums of the masked-out columns (sum | sumsq of every column, zero where one is kept: mean_ is full width, sparse_masked/
+// mod.rs:279-286) from the pairs the compaction dropped, sorted by column in at_*: to dst | dst + n.  stream3 only.
+template <typename T>
+void drop_sums(H& h, const PrepPlan& p, int64_t nnz_used, double* dst) {
+  const CsrBuf<T> work = csr_buffers<T>(h.at_ptr, h.at_idx, h.at_val, p.n, p.nnz);
+  k::sums_by_column(h.drop_col.ptr<int32_t>(), h.drop_val.ptr<T>(), p.nnz - nnz_used, p.n, work.ptr, work.idx, work.val, dst,
+                    dst + p.n, h.drop_tmp, h.stream3);
+}
+
+// Masked fits compact first and transpose only what the mask keeps.  Main stream, synchronises with the host (the count);
+// the dropped pairs' sums on stream3, beside the transposition / the bucket route of the kept part and A's format build.
+template <typename T>
+void compact_and_drop_sums(H& h, const CsrView<T>& A, const PrepPlan& p, const MaskMaps& maps, PrepOutcome<T>& out) {
+  hipStream_t s = h.stream;
+  Scope sc(h, C_PREPARE);
+  const bool pairs = p.stats == StatsFrom::KeptAndDropped;
+  const size_t cap = (size_t)std::max<int64_t>(p.nnz, 1);
+  // (Lanczos scatter: the compaction gathers max |a| for the fixed-point scales on its way through the values)
+  h.a_used = compact_a(h, A, maps.d_o2m, p.n_used, pairs ? h.drop_col.as<int32_t>(cap) : nullptr, pairs ? h.drop_val.as<T>(cap) : nullptr,
+                       p.at == AtFrom::Nothing ? h.lz_scalars.as<unsigned long long>(4) : nullptr);
+  out.nnz_used = h.a_used.nnz;
+  if (!pairs) return;
+  hipStream_t s3 = stats_stream(h);
+  if (!h.ev_drop) SAPCA_HIP(hipEventCreateWithFlags(&h.ev_drop, hipEventDisableTiming));
+  double* d_stats = stats_dev(h, p.n);
+  SAPCA_HIP(hipMemsetAsync(d_stats + 2 * p.n, 0, (size_t)p.n * sizeof(double), s));
+  if (p.deliver != StatsTo::SideChain) {
+    // into the statistics themselves: the main stream waits for ev_drop before it puts the kept columns' sums on top
+    order_after(s3, h.ev_drop, s);   // (the compaction synchronised: this only orders the side stream after it)
+    drop_sums<T>(h, p, out.nnz_used, d_stats);
+    SAPCA_HIP(hipEventRecord(h.ev_drop, s3));
+  } else if (h.opt.method != SAPCA_RANDOM) {
+    // SideChain keeps them in their own arrays and never waits for them on the main stream.  Randomized fits: queued at the
+    // end of prepare(), behind the format builds -- they are the ones the first sweep waits for and the sort shares HBM
+    // badly with them, while the sweeps leave most of the HBM rate unused.  Lanczos fits (HBM-bound steps, no formats):
+    // now, beside the transposition.
+    double* d_drop = h.drop_stats.as<double>((size_t)2 * p.n);
+    order_after(s3, h.ev_drop, s);
+    drop_sums<T>(h, p, out.nnz_used, d_drop);
+  }
+}
+
+// A's format runs beside the main stream.  build_tiled synchronises with the host (entry counts come back), so where the main
+// thread has such work of its own ahead a helper thread drives it: ev_fork on the main stream, the thread enqueues on stream2.
+template <typename T>
+void start_a_format_aside(H& h, const CsrView<T>& A, const PrepPlan& p, PrepOutcome<T>& out, Aside& aside) {
+  side_stream(h);
+  SAPCA_HIP(hipEventRecord(h.ev_fork, h.stream));   // A (and the index maps) are on the device
+  h.tiled_a = TiledOp();                            // (while the thread that writes it does not exist yet)
+  out.a_aside = true;
+  const CsrView<T> src = p.masked ? Engine<T>::view(h.a_used) : A;
+  aside.t = std::thread([&h, &p, &out, &aside, src] {
+    try {
+      SAPCA_HIP(hipSetDevice(h.device));
+      SAPCA_HIP(hipStreamWaitEvent(h.stream2, h.ev_fork, 0));
+      if (p.tiled_ldp != 0) out.ok_a = k::build_tiled(src, p.tiled_ldp, h.tiled_a, h.tb_a, h.stream2);
+      SAPCA_HIP(hipEventRecord(h.ev_join, h.stream2));
+    } catch (...) {
+      aside.err = std::current_exception();
+    }
+  });
+}
+
+// The kept columns' sums (compact numbering) over the dropped pairs' (the per-column counts are only read by the unmasked
+// projection).  Main stream; waits for stream3's ev_drop unless the side chain merges the two at the end of prepare().
+void scatter_kept_sums(H& h, const PrepPlan& p, const double* d_part, const int32_t* d_sel) {
+  double* d_stats = stats_dev(h, p.n);
+  if (p.deliver != StatsTo::SideChain) SAPCA_HIP(hipStreamWaitEvent(h.stream, h.ev_drop, 0));   // (the dropped pairs' sums)
+  k::scatter_pairs(d_part, d_part + p.n_used, d_sel, p.n_used, d_stats, d_stats + p.n, h.stream);
+}
+
+// FormatFromA / FormatFromCompacted: the column sums of the operator it reads come out of the same pass.  Main stream, synchronises with the host.
+template <typename T>
+void at_format_direct(H& h, const CsrView<T>& A, const PrepPlan& p, const MaskMaps& maps, PrepOutcome<T>& out) {
+  if constexpr (sizeof(T) == 4) {
+    if (p.masked && out.nnz_used <= 0) return;
+    Scope sc(h, C_PREPARE);
+    const CsrView<T> src = p.masked ? Engine<T>::view(h.a_used) : A;
+    int64_t* t_ptr = (p.masked ? h.cat_ptr : h.at_ptr).template as<int64_t>((size_t)src.cols + 1);
+    // A's sums are the statistics; the compacted matrix's are the kept columns' (sums | sums of squares, compact numbering)
+    double* d_sums = p.masked ? h.scratch2.as<double>((size_t)2 * p.n_used + 2) : stats_dev(h, p.n);
+    h.tiled_at = TiledOp();
+    out.at_direct = k::build_tiled_at_direct(src, p.tiled_ldp, h.tiled_at, h.tb_at, t_ptr,
+                                             p.stats == StatsFrom::Upload ? nullptr : d_sums, h.scratch, h.stream);
+    if (!out.at_direct) return;
+    if (!p.masked) out.At = CsrView<T>{p.n, p.m, p.nnz, t_ptr, nullptr, nullptr};
+    else h.at_used = {p.n_used, p.m, out.nnz_used, t_ptr, nullptr, nullptr};
+    if (p.stats == StatsFrom::KeptAndDropped) scatter_kept_sums(h, p, d_sums, maps.d_sel);
+  }
+}
+
+// The transposed CSR: of the compacted matrix into cat_* (the kept columns' sums: its row sums), of A into at_*.  Main stream, no wait.
+template <typename T>
+void at_transpose(H& h, const CsrView<T>& A, const PrepPlan& p, const MaskMaps& maps, PrepOutcome<T>& out) {
+  Scope sc(h, C_PREPARE);
+  // p.at_nct: rows of A^T grouped by the interleaved tile of the A row they came from -- its format fill streams
+  if (p.masked) {
+    const CsrBuf<T> cat = csr_buffers<T>(h.cat_ptr, h.cat_idx, h.cat_val, p.n_used, p.nnz);
+    k::transpose_csr(Engine<T>::view(h.a_used), cat.ptr, cat.idx, cat.val, h.scratch, h.stream, p.at_nct, nullptr);
+    h.at_used = cat.raw(p.n_used, p.m, out.nnz_used);
+    if (p.stats != StatsFrom::KeptAndDropped) return;
+    double* d_part = h.scratch2.as<double>((size_t)2 * p.n_used + 2);
+    k::row_sums(Engine<T>::view(h.at_used), d_part, d_part + p.n_used, h.stream);
+    scatter_kept_sums(h, p, d_part, maps.d_sel);
+  } else {
+    const CsrBuf<T> at = csr_buffers<T>(h.at_ptr, h.at_idx, h.at_val, p.n, p.nnz);
+    // the statistics and the format builder read the sort's packed rows directly and the unpack pass into (at_idx, at_val)
+    // is skipped (done lazily in build_formats if the row kernel has to take over)
+    k::transpose_csr(A, at.ptr, at.idx, at.val, h.scratch, h.stream, p.at_nct,
+                     (p.at_nct != 0 && dbg_env("SAPCA_AT_UNPACK") == nullptr) ? &out.at_packed : nullptr);
+    out.At = CsrView<T>{p.n, p.m, p.nnz, at.ptr, at.idx, at.val};
+  }
+}
+
+// R1/R2 (csr.rs:259-312, 558-608) as row sums of A^T, plus the per-column stored-entry count, and their way to the host.
+// Main stream (ScatterSide: stream3); AllReduce: the collective, then a wait for the main stream and finish_statistics.
+template <typename T>
+void column_statistics(H& h, const CsrView<T>& A, const PrepPlan& p, PrepOutcome<T>& out) {
+  hipStream_t s = h.stream;
+  const int64_t m = p.m, n = p.n;
+  double* sums = static_cast<double*>(h.stats_host.ensure(((size_t)2 * n + 1) * sizeof(double)));
+  {
+    Scope sc(h, C_STATS);
+    double* d_stats = stats_dev(h, n);
+    switch (p.stats == StatsFrom::FormatBuild && !out.at_direct ? StatsFrom::Transposed : p.stats) {
+      case StatsFrom::Upload:
+        SAPCA_HIP(hipMemcpyAsync(d_stats, h.up_stats.out.p, (size_t)3 * n * sizeof(double), hipMemcpyDeviceToDevice, s));
+        break;
+      case StatsFrom::Scatter: {   // every column of A, masked-out ones included, straight from A
+        const bool side = p.deliver == StatsTo::ScatterSide;   // on stream3, with the copy to the host behind it: fit() waits for ev_stats at its end
+        hipStream_t st = side ? stats_stream(h) : s;
+        if (side) order_after(st, h.ev_kept, s);   // (A and max |a| are in place on the main stream)
+        k::colstats_scatter(A, h.lz_scalars.ptr<unsigned long long>(), d_stats, d_stats + n, d_stats + 2 * n, side ? h.drop_tmp : h.scratch, st);
+        if (side) {
+          SAPCA_HIP(hipMemcpyAsync(sums, d_stats, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost, st));
+          SAPCA_HIP(hipEventRecord(h.ev_stats, st));
+        }
+        break;
+      }
+      case StatsFrom::FormatBuild:
+        k::row_lengths_f64(out.At.ptr, n, d_stats + 2 * n, s);   // (the sums came out of the format build)
+        break;
+      case StatsFrom::KeptAndDropped: break;   // (sums in place; the per-column counts are only read by the unmasked projection)
+      case StatsFrom::Transposed:
+        if constexpr (sizeof(T) == 4) {
+          // packed tile-major rows: the statistics pass also leaves the A^T builder's per-row tile index behind
+          if (out.at_packed) {
+            k::at_stats_index(out.At.ptr, out.at_packed, n, m, p.tiled_ldp, h.tb_at, d_stats, d_stats + n, s);
+            out.at_seg_ready = true;
+          }
+        }
+        if (!out.at_seg_ready) k::row_sums(out.At, d_stats, d_stats + n, s);
+        k::row_lengths_f64(out.At.ptr, n, d_stats + 2 * n, s);
+        break;
+    }
+    // one rank: the count is m -- no 8-byte copies in either direction in front of the first sweep (each a ~15 us hole)
+    sums[(size_t)2 * n] = (double)m;
+    // SideChain: the main stream holds the kept columns' sums (all the sweeps' centring reads); stream3 puts them over the dropped
+    // columns' arrays and copies the lot to the host (queue_side_statistics) -- the main stream never waits for the dropped pairs' sort
+    h.stats_on_side = p.deliver == StatsTo::SideChain || p.deliver == StatsTo::ScatterSide;
+    if (p.deliver == StatsTo::MainCopy) {
+      SAPCA_HIP(hipMemcpyAsync(sums, d_stats, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost, s));
+    } else if (p.deliver == StatsTo::AllReduce) {
+      // the global row count rides along in the statistics' all-reduce, and so does this rank's vote on where the two-piece A^T sweep cuts
+      // the panel (fit_randomized) when its A^T format exists by now (the bucket route builds it first): tail = {rows, ranks that voted, votes}
+      double* tail = h.stats_tail;   // (a member: the copy may still be reading it when this function has returned)
+      const uint32_t nr = h.comm.nranks;
+      const bool ride = Engine<T>::vote_rides(h);
+      const size_t ntail = 1 + (ride ? (size_t)nr + 1 : 0);
+      std::fill(tail, tail + ntail, 0.0);
+      tail[0] = (double)m;
+      if (ride && h.tiled_at.valid) {
+        tail[1] = 1.0;
+        tail[2 + h.comm.rank] = (double)Engine<T>::piece_vote(h, h.tiled_at.ldp);
+      }
+      SAPCA_HIP(hipMemcpyAsync(d_stats + 3 * n, tail, ntail * sizeof(double), hipMemcpyHostToDevice, s));
+      { Scope cs(h, C_COMM); h.comm.allreduce(d_stats, (uint64_t)3 * n + ntail, 1, s); }
+      SAPCA_HIP(hipMemcpyAsync(sums, d_stats, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost, s));
+      SAPCA_HIP(hipMemcpyAsync(tail, d_stats + 3 * n, ntail * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+  }
+  h.stats_cols = n;
+  h.vote_ready = false;
+  if (p.deliver == StatsTo::AllReduce) {   // the global row count is the sum over the ranks: needed on the host now
+    SAPCA_HIP(hipStreamSynchronize(s));
+    sums[(size_t)2 * n] = h.stats_tail[0];
+    if (Engine<T>::vote_rides(h) && (uint32_t)std::llround(h.stats_tail[1]) == h.comm.nranks) {
+      h.vote_cut = (int64_t)*std::min_element(h.stats_tail + 2, h.stats_tail + 2 + h.comm.nranks);
+      h.vote_ready = true;
+    }
+    h.m_global = (uint64_t)std::llround(sums[(size_t)2 * n]);
+    h.stats_pending = false;
+    Engine<T>::finish_statistics(h);
+  } else {   // one rank: the sums reach the host by the time fit() ends (the sweeps centre with means computed on the device)
+    h.m_global = (uint64_t)m;
+    h.stats_pending = true;
+  }
+}
+
+// Tile-major companions for the LDS-staged sweep: A^T's on the main stream (build_tiled synchronises with the host), then
+// the helper thread that built A's is joined.  Both or neither: a fit sweeps through the formats or through the CSRs.
+template <typename T>
+void build_formats(H& h, const PrepPlan& p, PrepOutcome<T>& out, Aside& aside) {
+  hipStream_t s = h.stream;
+  if (!out.a_aside) h.tiled_a = TiledOp();
+  if (!out.at_direct) h.tiled_at = TiledOp();
+  if (p.tiled_ldp == 0) return;
+  Scope sc(h, C_PREPARE);
+  const CsrView<T> at = Engine<T>::view(h.at_used);
+  bool ok_at = out.at_direct;
+  if constexpr (sizeof(T) == 4) {
+    if (!ok_at) ok_at = k::build_tiled(at, p.tiled_ldp, h.tiled_at, h.tb_at, s, p.at_nct != 0, out.at_packed, out.at_seg_ready);
+    if (out.at_packed && !ok_at) {   // someone needs the transposed CSR after all
+      k::unpack_transposed(out.at_packed, p.nnz, const_cast<int32_t*>(out.At.idx), const_cast<float*>(out.At.val), s);
+      out.at_packed = nullptr;
+      ok_at = k::build_tiled(at, p.tiled_ldp, h.tiled_at, h.tb_at, s, p.at_nct != 0);
+    }
+  } else {
+    ok_at = k::build_tiled(at, p.tiled_ldp, h.tiled_at, h.tb_at, s, p.at_nct != 0);
+  }
+  aside.join();
+  const bool ok_a = out.ok_a;
+  ok_at = ok_at && ok_a;
+  if (h.opt.verbose)
+    fprintf(stderr, "sapca: tile-major formats%s: A %s (nrb %d, nct %d, split %d, %lld entries), A^T %s (nrb %d, nct %d, split %d, %lld entries)\n",
+            sizeof(T) == 8 ? " (f64)" : "", ok_a ? "ok" : "no", h.tiled_a.nrb, h.tiled_a.nct, h.tiled_a.nsplit,
+            (long long)h.tiled_a.total_entries, ok_at ? "ok" : "no", h.tiled_at.nrb, h.tiled_at.nct, h.tiled_at.nsplit,
+            (long long)h.tiled_at.total_entries);
+  if (ok_a && ok_at) return;
+  h.tiled_a = TiledOp();
+  h.tiled_at = TiledOp();
+  if (out.at_direct) {   // the row kernel reads a transposed CSR, which the bucket route never made
+    const CsrView<T> src = Engine<T>::view(h.a_used);   // (the compacted matrix on the masked route)
+    const CsrBuf<T> t = p.masked ? csr_buffers<T>(h.cat_ptr, h.cat_idx, h.cat_val, src.cols, p.nnz)
+                                 : csr_buffers<T>(h.at_ptr, h.at_idx, h.at_val, src.cols, p.nnz);
+    k::transpose_csr(src, t.ptr, t.idx, t.val, h.scratch, s, 0, nullptr);
+    h.at_used = t.raw(src.cols, src.rows, src.nnz);
+  }
+}
+
+// SideChain: everything the first sweep needs is queued; now the masked-out columns' sums (randomized fits), the kept columns'
+// over them, the copy of all statistics to the host (read at the end of fit()).  stream3, behind the main stream; no wait.
+template <typename T>
+void queue_side_statistics(H& h, const PrepPlan& p, const PrepOutcome<T>& out, const MaskMaps& maps) {
+  const int64_t n = p.n;
+  double* d_stats = stats_dev(h, n);
+  double* d_drop = h.drop_stats.as<double>((size_t)2 * n);
+  order_after(h.stream3, h.ev_kept, h.stream);
+  if (h.opt.method == SAPCA_RANDOM) drop_sums<T>(h, p, out.nnz_used, d_drop);
+  k::copy_selected(d_stats, d_stats + n, maps.d_sel, p.n_used, d_drop, d_drop + n, h.stream3);
+  SAPCA_HIP(hipMemcpyAsync(h.stats_host.p, d_drop, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost, h.stream3));
+  SAPCA_HIP(hipEventRecord(h.ev_stats, h.stream3));
+}
+
 }  // namespace
 
-// ------------------------------------------------------------------------------------------
-// prepare: A^T, column statistics, mask compaction.
-// ------------------------------------------------------------------------------------------
 template <typename T>
 void Engine<T>::prepare(H& h, const CsrView<T>& A) {
   hipStream_t s = h.stream;
-  const int64_t m = A.rows, n = A.cols, nnz = A.nnz;
-  const bool masked = !h.mask.empty();
-  if (masked && (int64_t)h.mask.size() != n)  // sparse_masked/mod.rs:258-262
+  if (!h.mask.empty() && (int64_t)h.mask.size() != A.cols)  // sparse_masked/mod.rs:258-262
     throw Error(SAPCA_ERR_MASK_LEN, "The mask vector length and the number of features (columns) have to be the same!");
   h.prep_key.valid = false;
   // A masked fit that failed after its prepare() (n_components check, SVD failure, no Lanczos convergence) leaves its
@@ -132,464 +561,49 @@ void Engine<T>::prepare(H& h, const CsrView<T>& A) {
   h.stats_on_side = false;
   h.lz_scatter = false;
 
-  // LDS-staged sweep (randomized fits): decided here because it fixes the order in which the transposed rows are produced
-  // (staged_sweep_ldp above has the break-even).
-  int tiled_ldp = 0;
-  if (h.opt.method == SAPCA_RANDOM && m > 0 && n > 0) {
-    const int64_t n_kept = masked ? (int64_t)std::count_if(h.mask.begin(), h.mask.end(), [](uint8_t b) { return b != 0; }) : n;
-    const int64_t l = std::min<int64_t>((int64_t)(h.opt.n_components + h.opt.n_oversamples), std::min<int64_t>(m, n_kept));
-    if (n_kept > 0) tiled_ldp = staged_sweep_ldp<T>(m, n_kept, (double)nnz * ((double)n_kept / (double)n), l, h.opt.spmm_variant);
-  }
-  const bool at_tile_major = tiled_ldp != 0 && dbg_env("SAPCA_AT_NATURAL") == nullptr;
-  const int tiled_ldp_words = tiled_ldp * (int)sizeof(T) / 4;   // panel row in 4-byte words: what the tile arithmetic counts in
-
-  // mask index maps (sparse_masked/mod.rs:264-271 and the HashMap of :462-466)
-  h.cols_to_use.clear();
-  h.orig_to_masked.clear();
-  h.has_mask_maps = masked;
-  std::vector<int32_t> o2m32, sel;   // (alive until the copies below have been synchronised)
-  int32_t *d_o2m = nullptr, *d_sel = nullptr;
-  if (masked) {
-    h.orig_to_masked.assign((size_t)n, -1);
-    for (int64_t j = 0; j < n; ++j)
-      if (h.mask[(size_t)j]) {
-        h.orig_to_masked[(size_t)j] = (int64_t)h.cols_to_use.size();
-        h.cols_to_use.push_back((uint64_t)j);
-      }
-  }
-  const int64_t n_used = masked ? (int64_t)h.cols_to_use.size() : n;
-  if (masked) {
-    o2m32.resize((size_t)n);
-    sel.resize((size_t)std::max<int64_t>(n_used, 1));
-    for (int64_t j = 0; j < n; ++j) o2m32[(size_t)j] = (int32_t)h.orig_to_masked[(size_t)j];
-    for (int64_t j = 0; j < n_used; ++j) sel[(size_t)j] = (int32_t)h.cols_to_use[(size_t)j];
-    d_o2m = h.o2m_dev.as<int32_t>((size_t)std::max<int64_t>(n, 1));
-    d_sel = h.sel_rows_dev.as<int32_t>((size_t)std::max<int64_t>(n_used, 1));
-    SAPCA_HIP(hipMemcpyAsync(d_o2m, o2m32.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    SAPCA_HIP(hipMemcpyAsync(d_sel, sel.data(), (size_t)n_used * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  }
-
-  CsrView<T> At;
-  const uint64_t* at_packed = nullptr;
-  bool at_seg_ready = false;
-  // a host matrix that came through upload() brought its statistics along (gathered behind the DMA, exact sums)
-  bool from_upload = h.up_stats.valid && A.ptr == h.in_ptr.p && A.idx == h.in_idx.p && A.val == h.in_val.p &&
-                     h.up_stats.m == (uint64_t)m && h.up_stats.n == (uint64_t)n && h.up_stats.nnz == (uint64_t)nnz &&
-                     h.up_stats.dtype == kDtype && n > 0 && !h.comm.active();   // (ranks must not differ in their collectives)
-
-  if (from_upload) {
-    // the last chunk's share of those statistics may still be in flight; the accumulators refuse inf/nan (the flag is
-    // final once the side stream has passed up_stats_done): the sums of the transposed matrix take over then
-    SAPCA_HIP(hipEventSynchronize(h.up_stats_done));
-    if (*static_cast<const int*>(h.up_stats.flag.p) != 0) {
-      h.up_stats.valid = false;
-      from_upload = false;
-    }
-  }
-
-  // Lanczos fits whose transposed side fits a workgroup's LDS (at most ~19k kept columns: C3 keeps 18k) never build A^T: the
-  // second product of a step scatters into LDS (scatter.hip, fixed-point sums: reproducible) and the column statistics
-  // come from the same kind of pass over A, on the third stream beside the iterations (a Lanczos fit does not centre:
-  // nothing reads them before fit() ends).  What is left of the preparation is the mask compaction.
-  // SAPCA_LANCZOS_TRANSPOSE=1 brings the transposed operator (radix sort) back.
-  bool lz_scatter = h.opt.method == SAPCA_LANCZOS && n_used > 0 && n_used <= m && m >= 4096 && nnz > 0 && k::scatter_fits(n_used) &&
-                    dbg_env("SAPCA_LANCZOS_TRANSPOSE") == nullptr;
-  bool lz_side = false;   // its statistics run on the third stream
-  if (lz_scatter && !masked) {
-    // max |a| for the fixed-point scales (masked fits: the compaction gathers it on its way through the values).  Values that
-    // are not finite turn the scale, and with it every product and sum, into nan: the fit then fails to converge, as it does
-    // on the floating-point route.
-    k::absmax(A.val, nnz, h.lz_scalars.as<unsigned long long>(4), s);
+  const PrepPlan p = plan_preparation(h, A);
+  const bool lz_scatter = p.at == AtFrom::Nothing;
+  PrepOutcome<T> out;
+  MaskMaps maps;
+  Aside aside;   // (declared last: joined before anything above dies)
+  mask_maps(h, p, maps);
+  if (lz_scatter && !p.masked) {
+    // max |a| for the fixed-point scales (masked fits: the compaction gathers it).  Values that are not finite turn the scale, and
+    // with it every product and sum, into nan: the fit then fails to converge, as it does on the floating-point route.
+    k::absmax(A.val, p.nnz, h.lz_scalars.as<unsigned long long>(4), s);
   }
   h.lz_scatter = lz_scatter;
-
-  // A's side of the preparation runs beside the main stream.  Its pieces synchronise with the host (entry counts come
-  // back), so where the main thread has its own synchronising work a helper thread drives them on the side stream:
-  //  * masked fits: the column compaction (MaskedCSRMatrix::new, sparse_masked/mod.rs:313), then the compacted matrix's format;
-  //  * unmasked f32 fits on the staged sweep: A's format, while this thread builds A^T's straight from A (below).
-  bool a_built_aside = false, ok_a_aside = false;
-  std::thread aside;
-  std::exception_ptr aside_err;
-  int64_t nnz_used = 0;
-  struct Joiner {   // (an exception on the main path must not leave the helper running into freed state)
-    std::thread& t;
-    ~Joiner() { if (t.joinable()) t.join(); }
-  } joiner{aside};
-  const bool masked_aside = masked && n_used > 0;
-  const bool try_direct = sizeof(T) == 4 && at_tile_major && !masked;   // A^T's format without a transposed CSR
-  // Masked fits compact first (MaskedCSRMatrix::new, sparse_masked/mod.rs:313) and transpose only what the mask keeps.  The
-  // entries the compaction drops leave as (column, value) pairs: the sums of the masked-out columns (mean_ is full width,
-  // sparse_masked/mod.rs:279-286) come from a stable sort of those pairs by column.  On the staged sweep (f32) the
-  // compacted matrix then takes the bucket route to A^T's format; otherwise it is transposed into a CSR.
-  const bool try_masked_direct = sizeof(T) == 4 && at_tile_major && masked_aside && n_used <= 65536 && dbg_env("SAPCA_AT_SORT") == nullptr;
-  bool compaction_done = false;
-  bool side_stats = false;   // the masked-out columns' sums (and the host copy of all statistics) finish on stream3, behind the fit
-  int32_t* drop_col = nullptr;
-  T* drop_val = nullptr;
-  if (masked_aside) {
-    Scope sc(h, C_PREPARE);
-    int64_t* ca_ptr = h.ca_ptr.as<int64_t>((size_t)m + 1);
-    int32_t* ca_idx = h.ca_idx.as<int32_t>((size_t)std::max<int64_t>(nnz, 1));
-    T* ca_val = h.ca_val.as<T>((size_t)std::max<int64_t>(nnz, 1));
-    drop_col = (from_upload || lz_scatter) ? nullptr : h.drop_col.as<int32_t>((size_t)std::max<int64_t>(nnz, 1));
-    drop_val = (from_upload || lz_scatter) ? nullptr : h.drop_val.as<T>((size_t)std::max<int64_t>(nnz, 1));
-    k::compact_columns(A, d_o2m, ca_ptr, ca_idx, ca_val, &nnz_used, h.scratch, s, drop_col, drop_val,
-                       lz_scatter ? h.lz_scalars.as<unsigned long long>(4) : nullptr);
-    h.a_used = {m, n_used, nnz_used, ca_ptr, ca_idx, ca_val};
-    compaction_done = true;
-    if (!from_upload && !lz_scatter) {
-      // the masked-out columns' sums on their own stream, beside the transposition / the bucket route of the kept part and
-      // A's format build (sum | sumsq of every column, zero where a column is kept).  Single-rank fits (`side_stats`) keep
-      // them in their own arrays and never wait for them on the main stream: see the statistics below.
-      if (!h.stream3) {
-        SAPCA_HIP(hipStreamCreateWithFlags(&h.stream3, hipStreamNonBlocking));
-        SAPCA_HIP(hipEventCreateWithFlags(&h.ev_kept, hipEventDisableTiming));
-        SAPCA_HIP(hipEventCreateWithFlags(&h.ev_stats, hipEventDisableTiming));
-      }
-      if (!h.ev_drop) SAPCA_HIP(hipEventCreateWithFlags(&h.ev_drop, hipEventDisableTiming));
-      side_stats = !h.comm.active() && dbg_env("SAPCA_MASK_STATS_INLINE") == nullptr;
-      double* d_stats = h.stats.as<double>((size_t)3 * n + 1 + H::kStatsTail);
-      SAPCA_HIP(hipMemsetAsync(d_stats + 2 * n, 0, (size_t)n * sizeof(double), s));
-      if (!side_stats) {
-        SAPCA_HIP(hipEventRecord(h.ev_drop, s));   // (the compaction synchronised: this only orders the side stream after it)
-        SAPCA_HIP(hipStreamWaitEvent(h.stream3, h.ev_drop, 0));
-        k::sums_by_column(drop_col, drop_val, nnz - nnz_used, n, h.at_ptr.as<int64_t>((size_t)n + 1),
-                          h.at_idx.as<int32_t>((size_t)std::max<int64_t>(nnz, 1)), h.at_val.as<T>((size_t)std::max<int64_t>(nnz, 1)),
-                          d_stats, d_stats + n, h.drop_tmp, h.stream3);
-        SAPCA_HIP(hipEventRecord(h.ev_drop, h.stream3));
-      }
-      // side_stats, randomized fits: queued at the end of prepare(), behind the format builds -- they are the ones the first
-      // sweep waits for and the sort shares HBM badly with them, while the sweeps leave most of the HBM rate unused.
-      // Lanczos fits (HBM-bound steps, no formats): now, beside the transposition.
-      if (side_stats && h.opt.method != SAPCA_RANDOM) {
-        double* d_drop = h.drop_stats.as<double>((size_t)2 * n);
-        SAPCA_HIP(hipEventRecord(h.ev_drop, s));
-        SAPCA_HIP(hipStreamWaitEvent(h.stream3, h.ev_drop, 0));
-        k::sums_by_column(drop_col, drop_val, nnz - nnz_used, n, h.at_ptr.as<int64_t>((size_t)n + 1),
-                          h.at_idx.as<int32_t>((size_t)std::max<int64_t>(nnz, 1)), h.at_val.as<T>((size_t)std::max<int64_t>(nnz, 1)),
-                          d_drop, d_drop + n, h.drop_tmp, h.stream3);
-      }
-    }
-  }
-  if (masked_aside || try_direct) {
-    if (!h.stream2) {
-      SAPCA_HIP(hipStreamCreateWithFlags(&h.stream2, hipStreamNonBlocking));
-      SAPCA_HIP(hipEventCreateWithFlags(&h.ev_fork, hipEventDisableTiming));
-      SAPCA_HIP(hipEventCreateWithFlags(&h.ev_join, hipEventDisableTiming));
-    }
-    SAPCA_HIP(hipEventRecord(h.ev_fork, s));   // A (and the index maps) are on the device
-    h.tiled_a = TiledOp();
-    a_built_aside = true;
-    aside = std::thread([&, tiled_ldp, compaction_done] {
-      try {
-        SAPCA_HIP(hipSetDevice(h.device));
-        SAPCA_HIP(hipStreamWaitEvent(h.stream2, h.ev_fork, 0));
-        CsrView<T> src = A;
-        if (masked && compaction_done) {
-          src = view(h.a_used);
-        }
-        if (tiled_ldp != 0) {
-          ok_a_aside = k::build_tiled(src, tiled_ldp, h.tiled_a, h.tb_a, h.stream2);
-        }
-        SAPCA_HIP(hipEventRecord(h.ev_join, h.stream2));
-      } catch (...) {
-        aside_err = std::current_exception();
-      }
-    });
-  }
-
-  // A^T's tile-major format straight from A (spmm_tiled.hip, "bucket route"): no transposed CSR, no sort; the column
-  // statistics come out of the same pass.  Outside its limits (more than 65536 columns, ...) the transposition takes over.
-  bool at_direct = false;
-  if constexpr (sizeof(T) == 4) {
-    if (try_direct) {
-      Scope sc(h, C_PREPARE);
-      int64_t* at_ptr = h.at_ptr.as<int64_t>((size_t)n + 1);
-      double* d_stats = h.stats.as<double>((size_t)3 * n + 1 + H::kStatsTail);
-      h.tiled_at = TiledOp();
-      at_direct = k::build_tiled_at_direct(A, tiled_ldp, h.tiled_at, h.tb_at, at_ptr, from_upload ? nullptr : d_stats, h.scratch, s);
-      if (at_direct) { At.rows = n; At.cols = m; At.nnz = nnz; At.ptr = at_ptr; At.idx = nullptr; At.val = nullptr; }
-    }
-  }
-
-  bool masked_direct = false;
-  if constexpr (sizeof(T) == 4) {
-    if (compaction_done && try_masked_direct && nnz_used > 0) {
-      Scope sc(h, C_PREPARE);
-      double* d_stats = h.stats.as<double>((size_t)3 * n + 1 + H::kStatsTail);
-      int64_t* cat_ptr = h.cat_ptr.as<int64_t>((size_t)n_used + 1);
-      double* d_part = h.scratch2.as<double>((size_t)2 * n_used + 2);   // sums | sums of squares of the kept columns, compact numbering
-      h.tiled_at = TiledOp();
-      masked_direct = k::build_tiled_at_direct(view(h.a_used), tiled_ldp, h.tiled_at, h.tb_at, cat_ptr, from_upload ? nullptr : d_part, h.scratch, s);
-      if (masked_direct) {
-        h.at_used = {n_used, m, nnz_used, cat_ptr, nullptr, nullptr};
-        if (!from_upload) {
-          // sums of every column from the pairs the compaction dropped (zero where a column is kept), then the kept
-          // columns' sums from the bucket route on top; the per-column counts are only read by the unmasked projection
-          if (!side_stats) SAPCA_HIP(hipStreamWaitEvent(s, h.ev_drop, 0));   // (the dropped pairs' sums, from the side stream)
-          k::scatter_pairs(d_part, d_part + n_used, d_sel, n_used, d_stats, d_stats + n, s);
-        }
-        At.rows = n; At.cols = m; At.nnz = nnz; At.ptr = nullptr; At.idx = nullptr; At.val = nullptr;
-      }
-    }
-  }
-
-  // masked, off the bucket route: the compacted matrix transposed into a CSR (tile-major rows where the staged sweep's format
-  // is built from them), the kept columns' sums as its row sums, the masked-out columns' from the dropped pairs
-  bool masked_compact = false;
-  if (compaction_done && !masked_direct && !lz_scatter) {
-    Scope sc(h, C_PREPARE);
-    double* d_stats = h.stats.as<double>((size_t)3 * n + 1 + H::kStatsTail);
-    int64_t* cat_ptr = h.cat_ptr.as<int64_t>((size_t)n_used + 1);
-    int32_t* cat_idx = h.cat_idx.as<int32_t>((size_t)std::max<int64_t>(nnz, 1));
-    T* cat_val = h.cat_val.as<T>((size_t)std::max<int64_t>(nnz, 1));
-    k::transpose_csr(view(h.a_used), cat_ptr, cat_idx, cat_val, h.scratch, s, at_tile_major ? k::tiled_tile_count(m, tiled_ldp_words) : 0,
-                     nullptr);
-    h.at_used = {n_used, m, nnz_used, cat_ptr, cat_idx, cat_val};
-    if (!from_upload) {
-      double* d_part = h.scratch2.as<double>((size_t)2 * n_used + 2);
-      k::row_sums(view(h.at_used), d_part, d_part + n_used, s);
-      if (!side_stats) SAPCA_HIP(hipStreamWaitEvent(s, h.ev_drop, 0));   // (the dropped pairs' sums, from the side stream)
-      k::scatter_pairs(d_part, d_part + n_used, d_sel, n_used, d_stats, d_stats + n, s);
-    }
-    At.rows = n; At.cols = m; At.nnz = nnz; At.ptr = nullptr; At.idx = nullptr; At.val = nullptr;
-    masked_compact = true;
-  }
-
-  // (f64, or f32 off the bucket route: A's format is built on the side stream from this thread once the transposition is
-  // queued; the side stream forks HERE, so the two run side by side on the GPU)
-  const bool a_aside_late = !a_built_aside && tiled_ldp != 0 && !masked;
-  if (a_aside_late) {
-    if (!h.stream2) {
-      SAPCA_HIP(hipStreamCreateWithFlags(&h.stream2, hipStreamNonBlocking));
-      SAPCA_HIP(hipEventCreateWithFlags(&h.ev_fork, hipEventDisableTiming));
-      SAPCA_HIP(hipEventCreateWithFlags(&h.ev_join, hipEventDisableTiming));
-    }
-    SAPCA_HIP(hipEventRecord(h.ev_fork, s));               // A is ready on the main stream at this point
-    SAPCA_HIP(hipStreamWaitEvent(h.stream2, h.ev_fork, 0));
-  }
-
-  if (!at_direct && !masked_direct && !masked_compact && !lz_scatter) {
-    Scope sc(h, C_PREPARE);
-    int64_t* at_ptr = h.at_ptr.as<int64_t>((size_t)n + 1);
-    int32_t* at_idx = h.at_idx.as<int32_t>((size_t)std::max<int64_t>(nnz, 1));
-    T* at_val = h.at_val.as<T>((size_t)std::max<int64_t>(nnz, 1));
-    // rows of A^T grouped by the interleaved tile of the A row they came from: its format fill streams
-    // unmasked: the statistics and the format builder read the sort's packed rows directly and the
-    // unpack pass into (at_idx, at_val) is skipped (done lazily below if the row kernel has to take over)
-    k::transpose_csr(A, at_ptr, at_idx, at_val, h.scratch, s, at_tile_major ? k::tiled_tile_count(m, tiled_ldp_words) : 0,
-                     (at_tile_major && !masked && dbg_env("SAPCA_AT_UNPACK") == nullptr) ? &at_packed : nullptr);
-    At.rows = n; At.cols = m; At.nnz = nnz; At.ptr = at_ptr; At.idx = at_idx; At.val = at_val;
-  }
-
+  if (p.masked) compact_and_drop_sums(h, A, p, maps, out);
+  if (p.masked || p.at == AtFrom::FormatFromA) start_a_format_aside(h, A, p, out, aside);
+  if (p.at == AtFrom::FormatFromA || p.at == AtFrom::FormatFromCompacted) at_format_direct(h, A, p, maps, out);
+  // (unmasked f64, or f32 off the bucket route: A's format is built on the side stream from this thread once the
+  // transposition is queued; the side stream forks HERE, so the two run side by side on the GPU)
+  const bool a_aside_late = p.tiled_ldp != 0 && !out.a_aside;
+  if (a_aside_late) order_after(side_stream(h), h.ev_fork, s);   // A is ready on the main stream at this point
+  if (!lz_scatter && !out.at_direct) at_transpose(h, A, p, maps, out);
   if (a_aside_late) {
     h.tiled_a = TiledOp();
-    ok_a_aside = k::build_tiled(A, tiled_ldp, h.tiled_a, h.tb_a, h.stream2);
-    SAPCA_HIP(hipEventRecord(h.ev_join, h.stream2));       // ...and the main stream waits for it at the end of prepare()
-    a_built_aside = true;
+    out.ok_a = k::build_tiled(A, p.tiled_ldp, h.tiled_a, h.tb_a, h.stream2);
+    SAPCA_HIP(hipEventRecord(h.ev_join, h.stream2));   // ...and the main stream waits for it at the end of prepare()
+    out.a_aside = true;
   }
 
-  // R1/R2 (csr.rs:259-312, 558-608) as row sums of A^T, plus the per-column stored-entry count.
-  double* sums = static_cast<double*>(h.stats_host.ensure(((size_t)2 * n + 1) * sizeof(double)));
-  auto column_statistics = [&](bool uploaded) {
-    Scope sc(h, C_STATS);
-    double* d_stats = h.stats.as<double>((size_t)3 * n + 1 + H::kStatsTail);
-    if (uploaded) {
-      SAPCA_HIP(hipMemcpyAsync(d_stats, h.up_stats.out.p, (size_t)3 * n * sizeof(double), hipMemcpyDeviceToDevice, s));
-    } else if (lz_scatter) {
-      // every column of A (masked-out ones included: mean_ is full width, sparse_masked/mod.rs:279-286) straight from A
-      const unsigned long long* sc = h.lz_scalars.ptr<unsigned long long>();
-      if (!h.comm.active()) {
-        // one rank: on the third stream, with the copy to the host behind it; fit() waits for ev_stats at its end
-        if (!h.stream3) {
-          SAPCA_HIP(hipStreamCreateWithFlags(&h.stream3, hipStreamNonBlocking));
-          SAPCA_HIP(hipEventCreateWithFlags(&h.ev_kept, hipEventDisableTiming));
-          SAPCA_HIP(hipEventCreateWithFlags(&h.ev_stats, hipEventDisableTiming));
-        }
-        SAPCA_HIP(hipEventRecord(h.ev_kept, s));   // (A and max |a| are in place on the main stream)
-        SAPCA_HIP(hipStreamWaitEvent(h.stream3, h.ev_kept, 0));
-        k::colstats_scatter(A, sc, d_stats, d_stats + n, d_stats + 2 * n, h.drop_tmp, h.stream3);
-        SAPCA_HIP(hipMemcpyAsync(sums, d_stats, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost, h.stream3));
-        SAPCA_HIP(hipEventRecord(h.ev_stats, h.stream3));
-        sums[(size_t)2 * n] = (double)m;
-        h.stats_on_side = true;
-        lz_side = true;
-        return;
-      }
-      k::colstats_scatter(A, sc, d_stats, d_stats + n, d_stats + 2 * n, h.scratch, s);
-    } else if (at_direct) {
-      k::row_lengths_f64(At.ptr, n, d_stats + 2 * n, s);   // (the sums came out of the format build)
-    } else if (masked_direct || masked_compact) {
-      // (sums in place; the per-column counts are only read by the unmasked projection)
-    } else {
-      if constexpr (sizeof(T) == 4) {
-        // packed tile-major rows: the statistics pass also leaves the A^T builder's per-row tile index behind
-        if (at_packed) {
-          k::at_stats_index(At.ptr, at_packed, n, m, tiled_ldp, h.tb_at, d_stats, d_stats + n, s);
-          at_seg_ready = true;
-        }
-      }
-      if (!at_seg_ready) k::row_sums(At, d_stats, d_stats + n, s);
-      k::row_lengths_f64(At.ptr, n, d_stats + 2 * n, s);
-    }
-    h.stats_on_side = false;
-    if (side_stats && !uploaded && (masked_direct || masked_compact)) {
-      // single rank, masked: the main stream holds the kept columns' sums (all the sweeps' centring reads); stream3 puts
-      // them over the dropped columns' arrays once both are there and copies the lot to the host -- the main stream
-      // never waits for the sort of the dropped pairs
-      sums[(size_t)2 * n] = (double)m;
-      h.stats_on_side = true;   // (the chain itself is queued at the end of prepare())
-      return;
-    }
-    if (h.comm.active()) {
-      // the global row count rides along in the statistics' all-reduce
-      // ... and so does this rank's vote on where the two-piece A^T sweep cuts the panel (fit_randomized), when its A^T format
-      // exists by now (the bucket / gather route builds it in front of the statistics): tail = {rows, ranks that voted, votes}
-      double* tail = h.stats_tail;   // (a member: the copy may still be reading it when this function has returned)
-      const uint32_t nr = h.comm.nranks;
-      const bool ride = vote_rides(h);
-      const size_t ntail = 1 + (ride ? (size_t)nr + 1 : 0);
-      std::fill(tail, tail + ntail, 0.0);
-      tail[0] = (double)m;
-      if (ride && h.tiled_at.valid) {
-        tail[1] = 1.0;
-        tail[2 + h.comm.rank] = (double)piece_vote(h, h.tiled_at.ldp);
-      }
-      SAPCA_HIP(hipMemcpyAsync(d_stats + 3 * n, tail, ntail * sizeof(double), hipMemcpyHostToDevice, s));
-      { Scope cs(h, C_COMM); h.comm.allreduce(d_stats, (uint64_t)3 * n + ntail, 1, s); }
-      SAPCA_HIP(hipMemcpyAsync(sums, d_stats, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost, s));
-      SAPCA_HIP(hipMemcpyAsync(tail, d_stats + 3 * n, ntail * sizeof(double), hipMemcpyDeviceToHost, s));
-    } else {
-      // one rank: the count is m -- no 8-byte copies in either direction in front of the first sweep (each a ~15 us hole)
-      sums[(size_t)2 * n] = (double)m;
-      SAPCA_HIP(hipMemcpyAsync(sums, d_stats, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-  };
-  column_statistics(from_upload);
-  h.stats_cols = n;
-  h.vote_ready = false;
-  if (h.comm.active()) {   // the global row count is the sum over the ranks: needed on the host now
-    SAPCA_HIP(hipStreamSynchronize(s));
-    sums[(size_t)2 * n] = h.stats_tail[0];
-    if (vote_rides(h) && (uint32_t)std::llround(h.stats_tail[1]) == h.comm.nranks) {
-      h.vote_cut = (int64_t)*std::min_element(h.stats_tail + 2, h.stats_tail + 2 + h.comm.nranks);
-      h.vote_ready = true;
-    }
-    h.m_global = (uint64_t)std::llround(sums[(size_t)2 * n]);
-    h.stats_pending = false;
-    finish_statistics(h);
-  } else {
-    // one rank: the count is m; the sums reach the host by the time fit() ends (the sweeps centre with means computed on
-    // the device), so nothing waits here
-    h.m_global = (uint64_t)m;
-    h.stats_pending = true;
+  column_statistics(h, A, p, out);
+  // operator seen by the SVD engines (masked fits: the compacted pair, set above; Lanczos scatter: at_used is only a shape)
+  if (!p.masked) {
+    h.a_used = {p.m, p.n, p.nnz, A.ptr, A.idx, A.val};
+    h.at_used = {p.n, p.m, p.nnz, out.At.ptr, out.At.idx, out.At.val};
+  } else if (lz_scatter) {
+    h.at_used = {p.n_used, p.m, out.nnz_used, nullptr, nullptr, nullptr};
   }
 
-  // operator seen by the SVD engines: MaskedCSRMatrix::new (sparse_masked/mod.rs:313)
-  int64_t nnz_used_t = 0;
-  if (lz_scatter) {
-    // no transposed operator: a_used is A or its compaction (set above), at_used only carries the shape
-    if (!masked) { h.a_used = {m, n, nnz, A.ptr, A.idx, A.val}; nnz_used = nnz; }
-    SAPCA_CHECK(!masked || compaction_done, SAPCA_ERR_HIP, "internal: Lanczos scatter route without its compaction");
-    h.at_used = {n_used, m, nnz_used, nullptr, nullptr, nullptr};
-    nnz_used_t = nnz_used;
-  } else if (masked_direct || masked_compact) {
-    nnz_used_t = nnz_used;   // (a_used and at_used were set above)
-  } else if (masked) {
-    Scope sc(h, C_PREPARE);
-    if (!masked_aside && !compaction_done) {
-      int64_t* ca_ptr = h.ca_ptr.as<int64_t>((size_t)m + 1);
-      int32_t* ca_idx = h.ca_idx.as<int32_t>((size_t)std::max<int64_t>(nnz, 1));
-      T* ca_val = h.ca_val.as<T>((size_t)std::max<int64_t>(nnz, 1));
-      k::compact_columns(A, d_o2m, ca_ptr, ca_idx, ca_val, &nnz_used, h.scratch, s);
-      h.a_used = {m, n_used, nnz_used, ca_ptr, ca_idx, ca_val};
-    }
-    int64_t* cat_ptr = h.cat_ptr.as<int64_t>((size_t)n_used + 1);
-    int32_t* cat_idx = h.cat_idx.as<int32_t>((size_t)std::max<int64_t>(nnz, 1));
-    T* cat_val = h.cat_val.as<T>((size_t)std::max<int64_t>(nnz, 1));
-    k::select_rows(At, d_sel, n_used, cat_ptr, cat_idx, cat_val, &nnz_used_t, h.scratch, s);
-    h.at_used = {n_used, m, nnz_used_t, cat_ptr, cat_idx, cat_val};
-  } else {
-    h.a_used = {m, n, nnz, A.ptr, A.idx, A.val};
-    h.at_used = {n, m, nnz, At.ptr, At.idx, At.val};
-  }
-  // (the helper thread is joined below, after A^T's format has been enqueued on the main stream)
-  auto join_aside = [&] {
-    if (aside.joinable()) aside.join();
-    if (aside_err) std::rethrow_exception(aside_err);
-    if (masked) SAPCA_CHECK(nnz_used == nnz_used_t, SAPCA_ERR_HIP, "internal: mask compaction of A and A^T disagree");
-  };
-
-  // tile-major companions for the LDS-staged sweep
-  if (!a_built_aside) h.tiled_a = TiledOp();
-  if (!at_direct && !masked_direct) h.tiled_at = TiledOp();
-  if constexpr (sizeof(T) == 4) {
-    if (tiled_ldp != 0 && n_used > 0) {
-      Scope sc(h, C_PREPARE);
-      bool ok_at = at_direct || masked_direct ||
-                   k::build_tiled(view(h.at_used), tiled_ldp, h.tiled_at, h.tb_at, s, at_tile_major, at_packed, at_seg_ready);
-      if (at_packed && !ok_at) {   // someone needs the transposed CSR after all
-        k::unpack_transposed(at_packed, nnz, const_cast<int32_t*>(At.idx), reinterpret_cast<float*>(const_cast<T*>(At.val)), s);
-        at_packed = nullptr;
-        ok_at = k::build_tiled(view(h.at_used), tiled_ldp, h.tiled_at, h.tb_at, s, at_tile_major);
-      }
-      join_aside();
-      const bool ok_a = ok_a_aside;
-      ok_at = ok_at && ok_a;
-      if (h.opt.verbose)
-        fprintf(stderr, "sapca: tile-major formats: A %s (nrb %d, nct %d, split %d, %lld entries), A^T %s (nrb %d, nct %d, split %d, %lld entries)\n",
-                ok_a ? "ok" : "no", h.tiled_a.nrb, h.tiled_a.nct, h.tiled_a.nsplit, (long long)h.tiled_a.total_entries,
-                ok_at ? "ok" : "no", h.tiled_at.nrb, h.tiled_at.nct, h.tiled_at.nsplit, (long long)h.tiled_at.total_entries);
-      if (!ok_a || !ok_at) {
-        h.tiled_a = TiledOp();
-        h.tiled_at = TiledOp();
-        if (at_direct || masked_direct) {   // the row kernel reads a transposed CSR, which the bucket route never made
-          const CsrView<T> src = view(h.a_used);   // (the compacted matrix on the masked route)
-          int64_t* t_ptr = masked_direct ? h.cat_ptr.as<int64_t>((size_t)n_used + 1) : h.at_ptr.as<int64_t>((size_t)n + 1);
-          int32_t* t_idx = (masked_direct ? h.cat_idx : h.at_idx).template as<int32_t>((size_t)std::max<int64_t>(nnz, 1));
-          T* t_val = (masked_direct ? h.cat_val : h.at_val).template as<T>((size_t)std::max<int64_t>(nnz, 1));
-          k::transpose_csr(src, t_ptr, t_idx, t_val, h.scratch, s, 0, nullptr);
-          h.at_used = {src.cols, src.rows, src.nnz, t_ptr, t_idx, t_val};
-        }
-      }
-    }
-  } else {
-    if (tiled_ldp != 0 && n_used > 0) {
-      Scope sc(h, C_PREPARE);
-      bool ok_at = k::build_tiled(view(h.at_used), tiled_ldp, h.tiled_at, h.tb_at, s, at_tile_major);
-      join_aside();
-      const bool ok_a = ok_a_aside;
-      ok_at = ok_at && ok_a;
-      if (h.opt.verbose)
-        fprintf(stderr, "sapca: tile-major formats (f64): A %s (nrb %d, nct %d, split %d, %lld entries), A^T %s (nrb %d, nct %d, split %d, %lld entries)\n",
-                ok_a ? "ok" : "no", h.tiled_a.nrb, h.tiled_a.nct, h.tiled_a.nsplit, (long long)h.tiled_a.total_entries,
-                ok_at ? "ok" : "no", h.tiled_at.nrb, h.tiled_at.nct, h.tiled_at.nsplit, (long long)h.tiled_at.total_entries);
-      if (!ok_a || !ok_at) { h.tiled_a = TiledOp(); h.tiled_at = TiledOp(); }
-    }
-  }
-
-  join_aside();   // (fits without tile-major formats)
-  if (a_built_aside) SAPCA_HIP(hipStreamWaitEvent(s, h.ev_join, 0));
-
-  if (h.stats_on_side && !lz_side) {
-    // everything the first sweep needs is queued: now the masked-out columns' sums, the kept columns' sums over them, the
-    // copy of all statistics to the host (read at the end of fit())
-    double* d_stats = h.stats.ptr<double>();
-    double* d_drop = h.drop_stats.as<double>((size_t)2 * n);
-    SAPCA_HIP(hipEventRecord(h.ev_kept, s));
-    SAPCA_HIP(hipStreamWaitEvent(h.stream3, h.ev_kept, 0));
-    if (h.opt.method == SAPCA_RANDOM) {
-      k::sums_by_column(drop_col, drop_val, nnz - nnz_used, n, h.at_ptr.as<int64_t>((size_t)n + 1),
-                        h.at_idx.as<int32_t>((size_t)std::max<int64_t>(nnz, 1)), h.at_val.as<T>((size_t)std::max<int64_t>(nnz, 1)),
-                        d_drop, d_drop + n, h.drop_tmp, h.stream3);
-    }
-    k::copy_selected(d_stats, d_stats + n, d_sel, n_used, d_drop, d_drop + n, h.stream3);
-    SAPCA_HIP(hipMemcpyAsync(sums, d_drop, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost, h.stream3));
-    SAPCA_HIP(hipEventRecord(h.ev_stats, h.stream3));
-  }
+  build_formats(h, p, out, aside);
+  aside.join();   // (fits without tile-major formats)
+  if (out.a_aside) SAPCA_HIP(hipStreamWaitEvent(s, h.ev_join, 0));
+  if (p.deliver == StatsTo::SideChain) queue_side_statistics(h, p, out, maps);
 
   h.prep_key.ptr = A.ptr; h.prep_key.idx = A.idx; h.prep_key.val = A.val;
-  h.prep_key.m = (uint64_t)m; h.prep_key.n = (uint64_t)n; h.prep_key.nnz = (uint64_t)nnz;
+  h.prep_key.m = (uint64_t)p.m; h.prep_key.n = (uint64_t)p.n; h.prep_key.nnz = (uint64_t)p.nnz;
   h.prep_key.mask_version = h.mask_version; h.prep_key.dtype = kDtype; h.prep_key.valid = true;
 }
 
@@ -703,9 +717,7 @@ void Engine<T>::fit_randomized(H& h) {
   // not depend on anything a rank decides locally (its own entry count against the staged-sweep floor, whether its
   // format build succeeded): row-sharded fits always use the staged sweep's panel geometry, whichever kernel a rank
   // picks for its shard (the row kernel takes any multiple of 16).
-  // (above 128 columns every panel is a multiple of 64 wide: column passes of the sweeps, 64 / 128-column blocks of the dense kernels)
-  const int ld = l > 128 ? (int)round_up(l, 64)
-                         : (tiled || h.comm.active()) ? std::max(tiled ? h.tiled_a.ldp : 0, l <= 64 ? 64 : 128) : (int)round_up(l, 16);
+  const int ld = (l > 128 || tiled || h.comm.active()) ? panel_ld(l, tiled ? h.tiled_a.ldp : 0) : (int)round_up(l, 16);
   const int q = (int)h.opt.n_power_iterations;
   const int norm = h.opt.normalizer;
   const bool center = h.opt.center != 0;
@@ -789,11 +801,7 @@ void Engine<T>::fit_randomized(H& h) {
     if (overlap) {
       hipDeviceProp_t pr;
       if (hipGetDeviceProperties(&pr, h.device) == hipSuccess) piece_wgs = std::max(16, pr.multiProcessorCount - 16);
-      if (!h.stream_comm) {
-        SAPCA_HIP(hipStreamCreateWithFlags(&h.stream_comm, hipStreamNonBlocking));
-        SAPCA_HIP(hipEventCreateWithFlags(&h.ev_piece, hipEventDisableTiming));
-        SAPCA_HIP(hipEventCreateWithFlags(&h.ev_comm, hipEventDisableTiming));
-      }
+      lazy_stream(h.stream_comm, h.ev_piece, h.ev_comm);
     }
   }
   // one collective carries the l column sums of this rank's Y too: they live in the row behind the panel then
@@ -1039,9 +1047,8 @@ void Engine<T>::fit(H& h, const CsrView<T>& A, bool defer_finish) {
   h.timings.lanczos_steps = 0;
   SAPCA_CHECK(h.opt.n_components > 0, SAPCA_ERR_ARG, "n_components must be positive");
   SAPCA_CHECK(A.rows > 0 && A.cols > 0, SAPCA_ERR_ARG, "empty matrix");
-  prepare(h, A);
+  prepare(h, A);   // (throws where the mask selects no feature)
   const int64_t n_used = h.a_used.cols;
-  if (n_used == 0) throw Error(SAPCA_ERR_SVD, "SVD computation failed: the mask selects no feature");
   if ((int64_t)h.opt.n_components > std::min<int64_t>((int64_t)h.m_global, n_used))
     throw Error(SAPCA_ERR_SVD, std::string(h.opt.method == SAPCA_RANDOM ? "Randomized SVD" : "SVD") +
                                    " computation failed: n_components exceeds the matrix dimensions");
@@ -1184,7 +1191,7 @@ void Engine<T>::transform(H& h, const CsrView<T>& A, T* d_out) {
     // (operators with few row blocks -- a shard of a strong-scaled fit -- split their tile range over workgroups: the sweep sums
     //  the slabs itself; only the masked Q3 projection insists on an unsplit operator and checks that on its own)
     const TiledOp* top = (prepared && h.tiled_a.valid && k <= k::kMaxPanelWidth) ? &h.tiled_a : nullptr;
-    if (top) ldk = k > 128 ? (int)round_up(k, 64) : std::max(top->ldp, k <= 64 ? 64 : 128);
+    if (top) ldk = panel_ld(k, top->ldp);
     CsrView<T> Au;
     double* d_cnt = nullptr;
     if (prepared) {
@@ -1192,21 +1199,13 @@ void Engine<T>::transform(H& h, const CsrView<T>& A, T* d_out) {
       d_cnt = h.stats.ptr<double>() + 2 * n;
     } else if (masked) {
       h.prep_key.valid = false;  // the compaction buffers are about to be reused
-      std::vector<int32_t> o2m32((size_t)n);
-      for (int64_t j = 0; j < n; ++j) o2m32[(size_t)j] = (int32_t)h.orig_to_masked[(size_t)j];
-      int32_t* d_o2m = h.o2m_dev.as<int32_t>((size_t)n);
-      SAPCA_HIP(hipMemcpyAsync(d_o2m, o2m32.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-      int64_t* ca_ptr = h.ca_ptr.as<int64_t>((size_t)m + 1);
-      int32_t* ca_idx = h.ca_idx.as<int32_t>((size_t)std::max<int64_t>(A.nnz, 1));
-      T* ca_val = h.ca_val.as<T>((size_t)std::max<int64_t>(A.nnz, 1));
-      int64_t nnz_used = 0;
-      k::compact_columns(A, d_o2m, ca_ptr, ca_idx, ca_val, &nnz_used, h.scratch, s);
-      Au.rows = m; Au.cols = n_used; Au.nnz = nnz_used; Au.ptr = ca_ptr; Au.idx = ca_idx; Au.val = ca_val;
+      std::vector<int32_t> o2m32;   // (the compaction synchronises before it goes out of scope)
+      Au = view(compact_a(h, A, upload_o2m(h, o2m32), n_used));
     } else {
       Au = A;
       if (ref_sem) {
         h.prep_key.valid = false;
-        d_cnt = h.stats.as<double>((size_t)3 * n + 1 + H::kStatsTail) + 2 * n;
+        d_cnt = stats_dev(h, n) + 2 * n;
         k::column_counts_f64(A.idx, A.nnz, n, d_cnt, h.scratch, s);
         if (h.comm.active()) h.comm.allreduce(d_cnt, (uint64_t)n, 1, s);
       }
@@ -1223,7 +1222,7 @@ void Engine<T>::transform(H& h, const CsrView<T>& A, T* d_out) {
         const bool ok = k::build_tiled(Au, ldp_t, h.tiled_a, h.tb_a, s);
         if (ok && h.tiled_a.valid) {
           top = &h.tiled_a;
-          ldk = k > 128 ? (int)round_up(k, 64) : std::max(top->ldp, k <= 64 ? 64 : 128);
+          ldk = panel_ld(k, top->ldp);
         } else {
           h.tiled_a = TiledOp();
         }

@@ -44,10 +44,6 @@ void compact_columns(const CsrView<T>& A, const int32_t* o2m, int64_t* new_ptr, 
 template <typename T>
 void sums_by_column(const int32_t* cols, const T* vals, int64_t count, int64_t n, int64_t* seg, int32_t* keys_out, T* vals_out,
                     double* sum, double* sumsq, DevBuf& scratch, hipStream_t s);
-// Row selection of A^T: rows listed in `rows` (ascending), column indices untouched.
-template <typename T>
-void select_rows(const CsrView<T>& At, const int32_t* rows, int64_t n_sel, int64_t* new_ptr, int32_t* new_idx,
-                 T* new_val, int64_t* new_nnz_host, DevBuf& scratch, hipStream_t s);
 // Exact, order-independent column statistics of a CSR whose entries land chunk by chunk (upstats.hip).  `work` holds the
 // long accumulators.  scan_values (once all values are on the device) fixes the limb window kept in LDS; add takes the
 // entries [e_lo, e_hi) of rows [r_lo, r_hi); finish writes out[0..n) = sum, out[n..2n) = sum of squares, out[2n..3n) =

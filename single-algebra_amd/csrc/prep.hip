@@ -4,7 +4,7 @@
 // Reference semantics restated here:
 //   row_sums on A^T            == <CsrMatrix as MatrixSum>::sum_col / sum_col_squared
 //                                 (src/sparse/csr.rs:259-312, 558-608), f64 accumulation
-//   compact_columns/select_rows == MaskedCSRMatrix::new (call site
+//   compact_columns            == MaskedCSRMatrix::new (call site
 //                                 src/dimred/pca/sparse_masked/mod.rs:313): kept columns
 //                                 renumbered 0..n' in ascending order
 #include <cstdlib>
@@ -334,36 +334,6 @@ __global__ void write_kept_kernel(const int64_t* __restrict__ ptr, const int32_t
   }
 }
 
-__global__ void selected_lengths_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ rows,
-                                        int64_t n_sel, int64_t* __restrict__ len) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_sel) {
-    const int32_t r = rows[i];
-    len[i] = ptr[r + 1] - ptr[r];
-  } else if (i == n_sel) {
-    len[i] = 0;
-  }
-}
-
-template <typename T>
-__global__ void copy_selected_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx,
-                                     const T* __restrict__ val, const int32_t* __restrict__ rows, int64_t n_sel,
-                                     const int64_t* __restrict__ new_ptr, int32_t* __restrict__ new_idx,
-                                     T* __restrict__ new_val) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
-  const int64_t nwaves = (int64_t)gridDim.x * blockDim.x / WAVE;
-  for (int64_t i = wave; i < n_sel; i += nwaves) {
-    const int32_t r = rows[i];
-    const int64_t src = ptr[r], len = ptr[r + 1] - src, dst = new_ptr[i];
-    for (int64_t t = lane; t < len; t += WAVE) {
-      new_idx[dst + t] = idx[src + t];
-      new_val[dst + t] = val[src + t];
-    }
-  }
-}
-
-
 __global__ void ptr_diff_kernel(const int64_t* __restrict__ ptr, int64_t rows, double* __restrict__ out) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < rows) out[i] = (double)(ptr[i + 1] - ptr[i]);
@@ -655,22 +625,6 @@ void sums_by_column(const int32_t* cols, const T* vals, int64_t count, int64_t n
   SAPCA_HIP(hipGetLastError());
 }
 
-template <typename T>
-void select_rows(const CsrView<T>& At, const int32_t* rows, int64_t n_sel, int64_t* new_ptr, int32_t* new_idx,
-                 T* new_val, int64_t* new_nnz_host, DevBuf& scratch, hipStream_t s) {
-  hipLaunchKernelGGL(selected_lengths_kernel, dim3(grid_for(n_sel + 1, 256, 1 << 30)), dim3(256), 0, s, At.ptr, rows,
-                     n_sel, new_ptr);
-  exclusive_scan_i64(new_ptr, n_sel + 1, scratch, 0, s);
-  if (n_sel > 0)
-    hipLaunchKernelGGL((copy_selected_kernel<T>), dim3(grid_for(n_sel * WAVE, 256, 4096)), dim3(256), 0, s, At.ptr,
-                       At.idx, At.val, rows, n_sel, new_ptr, new_idx, new_val);
-  SAPCA_HIP(hipGetLastError());
-  SAPCA_HIP(hipMemcpyAsync(new_nnz_host, new_ptr + n_sel, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  SAPCA_HIP(hipStreamSynchronize(s));
-}
-
-
-
 namespace {
 template <typename T>
 __global__ void mean_from_sums_kernel(const double* __restrict__ sum, double count, const int32_t* __restrict__ sel, int64_t n_used,
@@ -753,9 +707,7 @@ void column_counts_f64(const int32_t* idx, int64_t nnz, int64_t n, double* out, 
   template void compact_columns<T>(const CsrView<T>&, const int32_t*, int64_t*, int32_t*, T*, int64_t*, DevBuf&,    \
                                    hipStream_t, int32_t*, T*, unsigned long long*);                                 \
   template void sums_by_column<T>(const int32_t*, const T*, int64_t, int64_t, int64_t*, int32_t*, T*, double*, double*, DevBuf&,   \
-                                  hipStream_t);                                                                     \
-  template void select_rows<T>(const CsrView<T>&, const int32_t*, int64_t, int64_t*, int32_t*, T*, int64_t*,        \
-                               DevBuf&, hipStream_t);
+                                  hipStream_t);
 INSTANTIATE(float)
 INSTANTIATE(double)
 #undef INSTANTIATE

@@ -3,6 +3,7 @@ golden vectors and the CPU oracle on the same seeded inputs.
 
 Bars: bit-exact for the mask index maps; f64 within 1e-10-ish of the golden
 vectors; f32 within 1e-4 relative / 1e-4 rad subspace angle (the north-star tolerance)."""
+import ctypes
 import os
 import numpy as np
 import pytest
@@ -592,9 +593,21 @@ def test_error_behaviour():
         big.fit(A)
     assert e.value.status == L.ERR_SVD
     none = sapca.MaskedSparsePCABuilder.new().n_components(2).mask(np.zeros(20, bool)).svd_method(SVDMethod.Random(3, 1)).build()
-    with pytest.raises(L.SapcaError) as e:
+    with pytest.raises(L.SapcaError, match="the mask selects no feature") as e:
         none.fit(A)
     assert e.value.status == L.ERR_SVD
+    cols, o2m = none.mask_index_maps()                     # the index maps of the refused mask still answer
+    assert cols.size == 0 and np.array_equal(o2m, np.full(20, -1))
+    # the refusal leaves the handle usable: the same handle fits once a mask that keeps something is set
+    good = np.arange(20) % 2 == 0
+    g8 = good.astype(np.uint8)
+    L.check(none._h, L.load().sapca_set_mask(none._h, g8.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.c_size_t(g8.size)))
+    none._mask = good
+    t = none.fit_transform(A)
+    assert t.shape == (50, 2) and np.isfinite(t).all()
+    fresh = sapca.MaskedSparsePCABuilder.new().n_components(2).mask(good).svd_method(SVDMethod.Random(3, 1)).build()
+    np.testing.assert_array_equal(t, fresh.fit_transform(A))
+    np.testing.assert_array_equal(none.mask_index_maps()[0], np.flatnonzero(good))
 
 
 def test_malformed_host_csr_is_refused(session):
