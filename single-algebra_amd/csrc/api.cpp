@@ -668,10 +668,9 @@ sapca_status spmm_host(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, con
       d_mu = h->mean_used_dev.as<T>(n);
       SAPCA_HIP(hipMemcpyAsync(d_mu, mu, n * sizeof(T), hipMemcpyHostToDevice, s));
     }
-    const size_t W = (size_t)std::max(ld, 128);   // (the layout of engine.cpp's SmallLayout)
-    double* small = h->small.as<double>(6 * W * W + 64 + 4 * W);
-    T* cvec = reinterpret_cast<T*>(small + 6 * W * W + 64);
-    T* svec = cvec + W;
+    const sapca::SmallLayout lay(h->small, ld);
+    T* cvec = lay.c<T>();
+    T* svec = lay.s<T>();
     SAPCA_HIP(hipStreamSynchronize(s));
     if (!transposed) {
       if (mu) sapca::k::weighted_colsum(X, (int64_t)n, ld, d_mu, cvec, h->scratch, s);
@@ -709,7 +708,7 @@ sapca_status normalize_host(sapca_handle h, int32_t normalizer, uint64_t rows, u
     T* P = h->panel_y.as<T>(rows * ld);
     SAPCA_HIP(hipMemcpyAsync(stage, panel, rows * l * sizeof(T), hipMemcpyHostToDevice, s));
     sapca::k::add_padding(stage, (int64_t)rows, (int)l, P, ld, s);
-    Engine<T>::normalize(*h, P, (int64_t)rows, (int)l, ld, normalizer, false, nullptr, nullptr);
+    Engine<T>::normalize(*h, P, (int64_t)rows, (int)l, ld, normalizer, false, {});
     sapca::k::strip_padding(P, (int64_t)rows, ld, (int)l, stage, s);
     download_out(h, stage, panel, (size_t)(rows * l));
   });
@@ -813,7 +812,7 @@ void sapca_destroy(sapca_handle h) {
     (void)hipStreamSynchronize(h->stream3);
     (void)hipStreamDestroy(h->stream3);
   }
-  if (h->ev_small) (void)hipEventDestroy(h->ev_small);
+  if (h->held_small.ev) (void)hipEventDestroy(h->held_small.ev);
   if (h->ev_kept) (void)hipEventDestroy(h->ev_kept);
   if (h->ev_stats) (void)hipEventDestroy(h->ev_stats);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);

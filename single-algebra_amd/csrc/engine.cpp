@@ -24,18 +24,6 @@ namespace sapca {
 
 namespace {
 
-// The handle's small f64 buffer: six ld x ld matrices (Gram, R^-1, scratch R, R1, R2, the small factor M), an int, and the
-// centring vectors c | s of the sweeps (T, W entries each) -- laid out for panels of W = max(ld, 128) columns.
-struct SmallLayout {
-  size_t W;
-  explicit SmallLayout(int ld) : W((size_t)std::max(ld, 128)) {}
-  size_t doubles() const { return 6 * W * W + 64 + 4 * W; }
-  size_t info_at() const { return 6 * W * W; }
-  size_t cvec_at() const { return 6 * W * W + 64; }
-  size_t wsum_at() const { return 6 * W * W + 64 + 2 * W; }   // W doubles behind c | s: the column sums a Gram pass gathers
-};
-
-
 // Does the LDS-staged sweep pay on an operator of `rows` x `cols` with `entries` stored entries and panels of l columns?  It
 // refills an 80 KiB panel tile per (row block, column tile) chunk and only beats the row-gather kernel when a chunk carries
 // enough entries to amortise that fill (measured: 64 tile bytes per entry or less -> clearly faster; 164 -> no gain, 4x the
@@ -79,7 +67,7 @@ void collect_timings(sapca_handle_s& h, bool is_fit) {
     t.lanczos_steps = keep_steps;
   } else {
     t.transform_ms = 0;
-    for (int ev : h.small_in_transform) t.transform_ms -= h.timer.ms(ev);   // the held-back small SVD counts as small_svd_ms only
+    for (int ev : h.held_small.in_transform) t.transform_ms -= h.timer.ms(ev);   // the held-back small SVD counts as small_svd_ms only
   }
   double comm_dev_ms = 0;
   for (auto& sp : h.spans) {
@@ -146,6 +134,16 @@ template <typename T>
 CsrBuf<T> csr_buffers(DevBuf& ptr, DevBuf& idx, DevBuf& val, int64_t rows, int64_t cap) {
   const size_t entries = (size_t)std::max<int64_t>(cap, 1);
   return {ptr.as<int64_t>((size_t)rows + 1), idx.as<int32_t>(entries), val.as<T>(entries)};
+}
+
+// The key of the preparation the handle would hold of A under its present mask.
+template <typename T>
+H::PrepKey prep_key_of(const H& h, const CsrView<T>& A) {
+  H::PrepKey key;
+  key.ptr = A.ptr; key.idx = A.idx; key.val = A.val;
+  key.m = (uint64_t)A.rows; key.n = (uint64_t)A.cols; key.nnz = (uint64_t)A.nnz;
+  key.mask_version = h.mask_version; key.dtype = Engine<T>::kDtype; key.valid = true;
+  return key;
 }
 
 // The original -> compacted column map of the handle's mask on the device.  Main stream, no wait: `o2m32` is pageable
@@ -602,9 +600,7 @@ void Engine<T>::prepare(H& h, const CsrView<T>& A) {
   if (out.a_aside) SAPCA_HIP(hipStreamWaitEvent(s, h.ev_join, 0));
   if (p.deliver == StatsTo::SideChain) queue_side_statistics(h, p, out, maps);
 
-  h.prep_key.ptr = A.ptr; h.prep_key.idx = A.idx; h.prep_key.val = A.val;
-  h.prep_key.m = (uint64_t)p.m; h.prep_key.n = (uint64_t)p.n; h.prep_key.nnz = (uint64_t)p.nnz;
-  h.prep_key.mask_version = h.mask_version; h.prep_key.dtype = kDtype; h.prep_key.valid = true;
+  h.prep_key = prep_key_of(h, A);
 }
 
 // R3: mean and total variance (sparse/mod.rs:106-131; masked :273-311, over cols_to_use only) from the column sums on the host
@@ -642,45 +638,36 @@ void Engine<T>::finish_statistics(H& h) {
 // R10: PowerIterationNormalizer on a rows x ld panel (CholeskyQR, f64 Gram on MFMA).
 // ------------------------------------------------------------------------------------------
 template <typename T>
-void Engine<T>::normalize(H& h, T* P, int64_t rows, int l, int ld, int normalizer, bool sharded, double* R1, double* R2,
-                          int passes_hint, const k::PanelSource<T>* src, const T* w, T* vec_out) {
-  // src (nullable): the panel is still as its producer left it (slabs of a split sweep, the centring term not yet
-  // subtracted): the first Gram applies that on its way through.  vec_out (nullable): receives sum_r w[r] Q[r][:] of the
-  // normalised panel Q = P R^-1 (w null: ones) -- the centring vector of the sweep that reads Q next -- computed as
-  // R^-T (P^T w) from sums gathered in the Gram's read pass, not from another pass over Q.
+void Engine<T>::normalize(H& h, T* P, int64_t rows, int l, int ld, int normalizer, bool sharded, const NormalizeExtras<T>& x) {
+  // x.src: the panel is still as its producer left it (slabs of a split sweep, the centring term not yet subtracted): the
+  // first Gram applies that on its way through.  x.vec_out: sum_r w[r] Q[r][:] of the normalised panel Q = P R^-1 -- the
+  // centring vector of the sweep that reads Q next -- computed as R^-T (P^T w) from sums gathered in the Gram's read pass,
+  // not from another pass over Q.
   hipStream_t s = h.stream;
   if (normalizer == SAPCA_NORM_NONE) {
-    if (src) k::materialize(P, rows, ld, *src, s);
-    if (vec_out) k::weighted_colsum(P, rows, ld, w, vec_out, h.scratch2, s);
+    if (x.src) k::materialize(P, rows, ld, *x.src, s);
+    if (x.vec_out) k::weighted_colsum(P, rows, ld, x.w, x.vec_out, h.scratch2, s);
     return;
   }
   Scope sc(h, C_ORTHO);
-  const SmallLayout lay(ld);
-  double* base = h.small.as<double>(lay.doubles());
-  double* G = base;
-  double* Rinv = base + (size_t)ld * ld;
-  double* Rtmp = base + (size_t)2 * ld * ld;
-  int* info = reinterpret_cast<int*>(base + lay.info_at());
-  double* wsum = vec_out ? base + lay.wsum_at() : nullptr;
+  const SmallLayout lay(h.small, ld);
+  double *G = lay.gram(), *wsum = x.vec_out ? lay.wsum() : nullptr;
   // QR -> CholeskyQR2 (orthonormal to working precision); LU -> one pass: a well-conditioned
   // basis of the same span, which is all the reference's LU normaliser provides.  Between power
   // iterations only the span matters (the next sweep re-mixes the basis), so the intermediate QR
-  // normalisations run the single pass too (`passes_hint` = 1); the final range basis Q and the
+  // normalisations run the single pass too (`passes` = 1); the final range basis Q and the
   // factorisation of B^T always get both passes.
-  const int passes = passes_hint > 0 ? passes_hint : (normalizer == SAPCA_NORM_QR ? 2 : 1);
+  const int passes = x.passes > 0 ? x.passes : (normalizer == SAPCA_NORM_QR ? 2 : 1);
   for (int pass = 0; pass < passes; ++pass) {
-    k::gram(P, rows, ld, G, h.scratch2, s, pass == 0 ? src : nullptr, w, wsum);
+    k::gram(P, rows, ld, G, h.scratch2, s, pass == 0 ? x.src : nullptr, x.w, wsum);
     if (sharded && h.comm.active()) { Scope cs(h, C_COMM); h.comm.allreduce(G, (uint64_t)ld * ld, 1, s); }
-    double* Rout = pass == 0 ? (R1 ? R1 : Rtmp) : (R2 ? R2 : Rtmp);
-    k::chol_inv(G, l, ld, Rout, Rinv, info, s, wsum, sizeof(T) == 4 ? reinterpret_cast<float*>(vec_out) : nullptr,
-                sizeof(T) == 8 ? reinterpret_cast<double*>(vec_out) : nullptr);
-    if (ld <= 128) {
-      k::panel_gemm(P, rows, ld, Rinv, ld, P, s, true);   // (R^-1 is upper triangular: its zero blocks are skipped)
-    } else {   // wide panels: block by block into a second panel, then back (R^-1 is upper triangular)
-      T* Q = h.panel_wide.as<T>((size_t)std::max<int64_t>(rows, 1) * ld);
-      k::panel_gemm(P, rows, ld, Rinv, ld, Q, s, true);
-      SAPCA_HIP(hipMemcpyAsync(P, Q, (size_t)rows * ld * sizeof(T), hipMemcpyDeviceToDevice, s));
-    }
+    double* Rout = pass == 0 ? x.R1 : x.R2;
+    k::chol_inv(G, l, ld, Rout ? Rout : lay.r_scratch(), lay.r_inv(), lay.info(), s, wsum,
+                sizeof(T) == 4 ? reinterpret_cast<float*>(x.vec_out) : nullptr, sizeof(T) == 8 ? reinterpret_cast<double*>(x.vec_out) : nullptr);
+    // (R^-1 is upper triangular: its zero blocks are skipped; wide panels: block by block into a second panel, then back)
+    T* Q = ld <= 128 ? P : h.panel_wide.as<T>((size_t)std::max<int64_t>(rows, 1) * ld);
+    k::panel_gemm(P, rows, ld, lay.r_inv(), ld, Q, s, true);
+    if (Q != P) SAPCA_HIP(hipMemcpyAsync(P, Q, (size_t)rows * ld * sizeof(T), hipMemcpyDeviceToDevice, s));
   }
 }
 
@@ -703,221 +690,293 @@ int64_t Engine<T>::piece_vote(H& h, int ld) {
 // ------------------------------------------------------------------------------------------
 // R7-R11, R13: randomized SVD of the (implicitly centred) prepared operator.
 // ------------------------------------------------------------------------------------------
+namespace {
+
+// The route of a randomized fit: what fit_randomized() knows before it enqueues its first kernel -- all but the piece plan of
+// the A^T sweep, which is agreed where its collective has always been queued (agree_on_at_pieces, behind the load of Omega).
+//  panel ld          | taken by                                  | why
+//  round_up(l, 16)   | one rank, l <= 128, row kernel            | the row kernel takes any multiple of 16
+//  panel_ld(l, ldp)  | staged sweep, l > 128, or several ranks   | the tile geometry (64 / 128, above that multiples of 64).  ld enters the element
+//                    |                                           | counts of the all-reduces, so with several ranks it must not depend on what a rank
+//                    |                                           | decides locally (its entry count against the staged-sweep floor, whether its format
+//                    |                                           | build succeeded): sharded fits always take this geometry, whichever kernel sweeps
+//  A^T sweep         |                                           |
+//  OnePiece          | one rank, f64, spmm_variant 1, or a vote  | one sweep, then one all-reduce of the panel (and the l column sums of Y behind it)
+//                    | of 0 from any rank                        |
+//  TwoPieces         | f32, several ranks, every rank voted > 0  | rows [0, cut) are all-reduced on stream_comm behind the first piece while the second
+//                    |                                           | runs.  A rank votes > 0 (piece_vote) where the side stream has a lane of its own and
+//                    |                                           | the path has run with several ranks: the callback / in-process transports.  Under
+//                    |                                           | RCCL (the duplicate communicator made at init: two streams never issue on one
+//                    |                                           | communicator) it is opt-in, SAPCA_AT_OVERLAP=1, until it has run on more than one
+//                    |                                           | GPU; SAPCA_AT_OVERLAP=0 switches it off everywhere.  Whether a rank takes part is ITS
+//                    |                                           | decision, so every rank votes and nobody waits in a collective a peer never joins.
+//                    |                                           | The pieces are whole row blocks of a rank's operator and ranks cut their blocks
+//                    |                                           | differently (the block count follows the shard's tile count): they agree on the
+//                    |                                           | smallest first piece, so that every rank's collectives have the same sizes
+//  small SVD         |                                           |
+//  GramHost          | f32                                       | R11 through the l x l Gram of B^T: G = B B^T = Uh S^2 Uh^T (f64, MFMA + the host
+//                    |                                           | eigensolver), vt = (B^T Uh S^-1)^T.  The Gram squares the condition number, so
+//                    |                                           | sigma_i is good to eps_f64 (sigma_1/sigma_i)^2 relative: 1e-8 even for a 1e4 decay,
+//                    |                                           | below what the f32 panels carry.  Saves two CholeskyQR passes over the n x l panel
+//                    |                                           | and 0.4 ms of host time per fit against QrJacobi
+//  GramHostHeldBack  | f32 fit_transform, unmasked, several      | the same, but fit() returns in front of the eigensolver and transform() runs it once
+//                    | ranks or m * lw^2 <= 400e3 * 64^2         | the projection sweep is queued.  Where that pays: the rotation is one more m x l by
+//                    | (lw = 64 for l_req <= 64, else 128)       | l x k panel product (0.2 ms per million rows at l <= 64, four times that at 128
+//                    |                                           | columns) against a host stall of 0.25 ms (l = 60) to 1 ms (l = 110) -- C2 and the
+//                    |                                           | shards of a strong-scaled fit gain 0.2 ms of a 9.5 ms step, a million rows on one GPU
+//                    |                                           | would lose as much (measured, round 4).  Decided in fit() from what every rank sees
+//                    |                                           | alike (m_global is not known there: a shard is about 1 / nranks of it)
+//  GramDevice        | f32 under SAPCA_EIG_DEVICE=1              | opt-in experiment, slower (k::sym_eig_device_ok): one workgroup solves the
+//                    |                                           | eigenproblem and writes M itself -- no wait for the host anywhere in the small SVD
+//  QrJacobi          | f64                                       | R11 through a QR of B^T: B^T = Qz Rz, Rz = Ur S Vr^T  =>  vt = (Qz Ur)^T
+enum class AtSweep { OnePiece, TwoPieces };
+enum class SmallSvd { GramHost, GramHostHeldBack, GramDevice, QrJacobi };
+
+struct AtPieces {
+  AtSweep sweep = AtSweep::OnePiece;
+  int64_t cut = 0, r1 = 0;   // rows [0, cut) are all-reduced behind the first piece; this rank's second piece starts at r1 >= cut
+  int wgs = 240;             // workgroups of a piece
+};
+struct RandomizedPlan {
+  int64_t m = 0, n_used = 0;
+  int l = 0, ld = 0, k = 0, ldk = 0, q = 0;
+  int norm = 0, variant = 0;
+  bool center = false, tiled = false;
+  SmallSvd small = SmallSvd::GramHost;
+  AtPieces at;
+};
+
+// The panels of a fit and what its sweeps hand one another.
 template <typename T>
-void Engine<T>::fit_randomized(H& h) {
-  hipStream_t s = h.stream;
-  const CsrView<T> A = view(h.a_used), At = view(h.at_used);
-  const int64_t m = A.rows, n_used = A.cols;
-  const int k = (int)h.opt.n_components;
+struct FitPanels {
+  T *X, *Y;                 // (n_used + 1) x ld (B^T; + one row: the column sums ride along in the all-reduce), m x ld
+  SmallLayout lay;
+  const T* mu;              // column means (null: no centring)
+  T *cvec, *sv;             // c = X^T mu of sweep_a; the column sums 1^T Y of the A^T sweep
+  bool cvec_current = false;   // the normaliser of X delivered c
+  k::PanelSource<T> src;    // what the next pass over X still has to apply
+};
+
+// Enqueues nothing.
+template <typename T>
+RandomizedPlan plan_randomized(H& h) {
+  RandomizedPlan p;
+  p.m = h.a_used.rows; p.n_used = h.a_used.cols;
+  p.k = (int)h.opt.n_components; p.ldk = (int)round_up(p.k, 16);
   const int64_t l_req = (int64_t)h.opt.n_components + (int64_t)h.opt.n_oversamples;
-  const int l = (int)std::min<int64_t>(l_req, std::min<int64_t>((int64_t)h.m_global, n_used));
-  SAPCA_CHECK(l <= k::kMaxPanelWidth, SAPCA_ERR_ARG, "n_components + n_oversamples above 1024 is not supported");
-  const bool tiled = h.tiled_a.valid && h.tiled_at.valid;
-  // The panel leading dimension enters the element counts of the all-reduces below, so with more than one rank it must
-  // not depend on anything a rank decides locally (its own entry count against the staged-sweep floor, whether its
-  // format build succeeded): row-sharded fits always use the staged sweep's panel geometry, whichever kernel a rank
-  // picks for its shard (the row kernel takes any multiple of 16).
-  const int ld = (l > 128 || tiled || h.comm.active()) ? panel_ld(l, tiled ? h.tiled_a.ldp : 0) : (int)round_up(l, 16);
-  const int q = (int)h.opt.n_power_iterations;
-  const int norm = h.opt.normalizer;
-  const bool center = h.opt.center != 0;
-  const int variant = h.opt.spmm_variant;
+  p.l = (int)std::min<int64_t>(l_req, std::min<int64_t>((int64_t)h.m_global, p.n_used));
+  SAPCA_CHECK(p.l <= k::kMaxPanelWidth, SAPCA_ERR_ARG, "n_components + n_oversamples above 1024 is not supported");
+  p.tiled = h.tiled_a.valid && h.tiled_at.valid;
+  p.ld = (p.l > 128 || p.tiled || h.comm.active()) ? panel_ld(p.l, p.tiled ? h.tiled_a.ldp : 0) : (int)round_up(p.l, 16);
+  p.q = (int)h.opt.n_power_iterations; p.norm = h.opt.normalizer;
+  p.center = h.opt.center != 0; p.variant = h.opt.spmm_variant;
+  p.small = sizeof(T) == 8 ? SmallSvd::QrJacobi : k::sym_eig_device_ok(p.l) ? SmallSvd::GramDevice
+            : h.held_small.defer ? SmallSvd::GramHostHeldBack : SmallSvd::GramHost;
+  return p;
+}
 
-  T* X = h.panel_x.as<T>(((size_t)std::max<int64_t>(n_used, 1) + 1) * ld);   // + one row: the column sums ride along in the all-reduce
-  T* Y = h.panel_y.as<T>((size_t)std::max<int64_t>(m, 1) * ld);
-  const SmallLayout lay(ld);
-  double* small = h.small.as<double>(lay.doubles());
-  double* R1 = small + (size_t)3 * ld * ld;
-  double* R2 = small + (size_t)4 * ld * ld;
-  double* Mdev = small + (size_t)5 * ld * ld;
-  int* info = reinterpret_cast<int*>(small + lay.info_at());
-  T* cvec = reinterpret_cast<T*>(small + lay.cvec_at());
-  T* svec = cvec + lay.W;
-  const T* mu = center ? h.mean_used_dev.ptr<T>() : nullptr;
-  SAPCA_HIP(hipMemsetAsync(info, 0, sizeof(int), s));
-
-  // Omega: injected (parity tests) or generated from the seed
-  if (!h.omega.empty()) {
-    SAPCA_CHECK((int64_t)h.omega_rows == n_used && (int64_t)h.omega_cols >= l, SAPCA_ERR_ARG,
-                "injected Omega must be (features seen by the SVD) x (n_components + n_oversamples)");
-    std::vector<T> tmp((size_t)n_used * l);
-    for (int64_t r = 0; r < n_used; ++r)
-      for (int j = 0; j < l; ++j) tmp[(size_t)r * l + j] = (T)h.omega[(size_t)r * h.omega_cols + j];
-    T* stage = h.scratch2.as<T>(tmp.size());
-    SAPCA_HIP(hipMemcpyAsync(stage, tmp.data(), tmp.size() * sizeof(T), hipMemcpyHostToDevice, s));
-    k::add_padding(stage, n_used, l, X, ld, s);
-    SAPCA_HIP(hipStreamSynchronize(s));  // tmp goes out of scope
-  } else {
-    k::gaussian_panel(X, n_used, l, ld, h.opt.random_seed, s);
-  }
-
-  // Centring vectors.  c = X^T mu (sweep_A) and the column sums 1^T Y (sweep_At) belong to a panel that has just been
-  // normalised: normalize() delivers them from sums gathered in its Gram pass (vec_out), so no kernel re-reads the
-  // normalised panel for them; only the very first c (of Omega) is summed here.
-  bool cvec_ready = false;
-  auto sweep_A = [&]() {  // Y = Ac X   (R8)
-    if (center && !cvec_ready) k::weighted_colsum(X, n_used, ld, mu, cvec, h.scratch2, s);
-    cvec_ready = false;
-    Scope sc(h, C_SPMM);
-    k::spmm(A, &h.tiled_a, X, ld, Y, ld, ld, center ? cvec : nullptr, variant, h.split_scratch, s);
-  };
-  std::vector<int64_t> piece_rows;
-  bool overlap = false;
-  int64_t cut = 0;   // rows [0, cut) of the panel are all-reduced behind the first piece, the rest behind the second
-  int piece_wgs = 240;
+// The piece plan of the A^T sweep.  The votes came with the column statistics when every rank had its A^T format by then (no
+// extra collective, no host round trip here); otherwise one small all-reduce on the main stream and a wait for it.
+template <typename T>
+AtPieces agree_on_at_pieces(H& h, const RandomizedPlan& p) {
+  AtPieces at;
   h.at_sweep_pieces = 1u;
-  if constexpr (sizeof(T) == 4) {
-    // On by default wherever the side stream has a lane of its own and the path has run with several ranks: the callback /
-    // in-process transports.  Under RCCL (the duplicate communicator made at init: two streams never issue on one
-    // communicator) it is opt-in, SAPCA_AT_OVERLAP=1, until it has run on more than one GPU; SAPCA_AT_OVERLAP=0 switches it
-    // off everywhere.  Whether a rank takes part is ITS decision, so every rank of a multi-rank fit votes (0 = one piece)
-    // and nobody waits in a collective a peer never joins.
-    if (h.comm.active() && variant != 1) {
-      // The pieces are whole row blocks of this rank's operator, and ranks cut their blocks differently (the block count
-      // follows the shard's own tile count): the ranks agree on one row count -- the smallest first piece, 0 if any rank
-      // cannot or will not sweep in pieces -- so that every rank's collectives have the same sizes.  The votes came with the
-      // column statistics when every rank had its A^T format by then (no extra collective, no host round trip here);
-      // otherwise one small all-reduce.
-      // (only A^T's format matters for the pieces -- the vote may have been cast before A's own format was known to be built)
-      const bool mine = h.tiled_at.valid && k::spmm_tiled_pieces_ok(h.tiled_at, 2, ld);
-      if (h.vote_ready) {
-        cut = h.vote_cut;
-        SAPCA_CHECK(cut == 0 || mine, SAPCA_ERR_COMM, "internal: the ranks agreed on a two-piece A^T sweep this rank cannot run");
-      } else {
-        const uint32_t nr = h.comm.nranks;
-        std::vector<double> votes((size_t)nr, 0.0);
-        votes[h.comm.rank] = mine ? (double)piece_vote(h, ld) : 0.0;
-        double* d_votes = h.votes.as<double>(nr);
-        SAPCA_HIP(hipMemcpyAsync(d_votes, votes.data(), nr * sizeof(double), hipMemcpyHostToDevice, s));
-        h.comm.allreduce(d_votes, nr, 1, s);
-        SAPCA_HIP(hipMemcpyAsync(votes.data(), d_votes, nr * sizeof(double), hipMemcpyDeviceToHost, s));
-        SAPCA_HIP(hipStreamSynchronize(s));
-        cut = (int64_t)*std::min_element(votes.begin(), votes.end());
-      }
-      overlap = mine && cut > 0 && cut < n_used;
-      if (overlap) k::spmm_tiled_piece_bounds(h.tiled_at, 2, piece_rows, s);
-    }
-    h.at_sweep_pieces = overlap ? 2u : 1u;
-    if (overlap) {
-      hipDeviceProp_t pr;
-      if (hipGetDeviceProperties(&pr, h.device) == hipSuccess) piece_wgs = std::max(16, pr.multiProcessorCount - 16);
-      lazy_stream(h.stream_comm, h.ev_piece, h.ev_comm);
-    }
+  if (sizeof(T) != 4 || !h.comm.active() || p.variant == 1) return at;
+  hipStream_t s = h.stream;
+  // (only A^T's format matters for the pieces -- the vote may have been cast before A's own format was known to be built)
+  const bool mine = h.tiled_at.valid && k::spmm_tiled_pieces_ok(h.tiled_at, 2, p.ld);
+  if (h.vote_ready) {
+    at.cut = h.vote_cut;
+    SAPCA_CHECK(at.cut == 0 || mine, SAPCA_ERR_COMM, "internal: the ranks agreed on a two-piece A^T sweep this rank cannot run");
+  } else {
+    const uint32_t nr = h.comm.nranks;
+    std::vector<double> votes((size_t)nr, 0.0);
+    votes[h.comm.rank] = mine ? (double)Engine<T>::piece_vote(h, p.ld) : 0.0;
+    double* d_votes = h.votes.as<double>(nr);
+    SAPCA_HIP(hipMemcpyAsync(d_votes, votes.data(), nr * sizeof(double), hipMemcpyHostToDevice, s));
+    h.comm.allreduce(d_votes, nr, 1, s);
+    SAPCA_HIP(hipMemcpyAsync(votes.data(), d_votes, nr * sizeof(double), hipMemcpyDeviceToHost, s));
+    SAPCA_HIP(hipStreamSynchronize(s));
+    at.cut = (int64_t)*std::min_element(votes.begin(), votes.end());
   }
-  // one collective carries the l column sums of this rank's Y too: they live in the row behind the panel then
-  T* const sv = h.comm.active() ? X + (size_t)n_used * ld : svec;
-  // X = Ac^T Y   (R9); partial products are summed over ranks.  The panel is left as the sweep produced it: `src` says what
-  // the next pass over X -- the Gram of its normalisation, or of the small SVD -- still has to apply (slabs of a sweep
-  // whose tile range was split over workgroups, the centring term mu (1^T Y)^T).  sv_ready: the normaliser of Y delivered 1^T Y.
-  auto sweep_At = [&](bool sv_ready, k::PanelSource<T>& src) {
-    src = k::PanelSource<T>();
-    if constexpr (sizeof(T) == 4) {
-      if (overlap) {
-        const int wgs = piece_wgs;
-        const int64_t r1 = piece_rows[1];
-        {
-          Scope sc(h, C_SPMMT);
-          k::spmm_tiled_piece(h.tiled_at, 0, 2, wgs, 0, r1, Y, ld, X, ld, ld, h.split_scratch, s);
-          SAPCA_HIP(hipEventRecord(h.ev_piece, s));
-          k::spmm_tiled_piece(h.tiled_at, 1, 2, wgs, r1, n_used - r1, Y, ld, X, ld, ld, h.split_scratch2, s);
-        }
-        if (center && !sv_ready) k::weighted_colsum(Y, m, ld, (const T*)nullptr, sv, h.scratch2, s);
-        {
-          Scope cs(h, C_COMM);   // (device time from the first piece's collective being possible to the last one's end)
-          SAPCA_HIP(hipStreamWaitEvent(h.stream_comm, h.ev_piece, 0));
-          h.comm.allreduce(X, (uint64_t)cut * ld, kDtype, h.stream_comm, 1);   // (cut <= r1: rows this rank has finished)
-          SAPCA_HIP(hipEventRecord(h.ev_comm, h.stream_comm));
-          h.comm.allreduce(X + (size_t)cut * ld, (uint64_t)(n_used - cut) * ld + (center ? (uint64_t)ld : 0), kDtype, s);
-          SAPCA_HIP(hipStreamWaitEvent(s, h.ev_comm, 0));
-        }
-        src.parts = X; src.nsplit = 1;
-        if (center) { src.mu = mu; src.sv = sv; }
-        return;
-      }
-    }
-    {
-      Scope sc(h, C_SPMMT);
-      // (one rank: the slabs may stay unsummed; several: the collective needs the sum)
-      k::spmm(At, &h.tiled_at, Y, ld, X, ld, ld, (const T*)nullptr, variant, h.split_scratch, s, h.comm.active() ? nullptr : &src);
-    }
-    if (!src.parts) { src.parts = X; src.nsplit = 1; }
-    if (center && !sv_ready) k::weighted_colsum(Y, m, ld, (const T*)nullptr, sv, h.scratch2, s);
-    if (h.comm.active()) { Scope cs(h, C_COMM); h.comm.allreduce(X, (uint64_t)n_used * ld + (center ? (uint64_t)ld : 0), kDtype, s); }
-    if (center) { src.mu = mu; src.sv = sv; }
-  };
+  if (!mine || at.cut <= 0 || at.cut >= p.n_used) return at;
+  std::vector<int64_t> piece_rows;
+  k::spmm_tiled_piece_bounds(h.tiled_at, 2, piece_rows, s);
+  at.sweep = AtSweep::TwoPieces;
+  at.r1 = piece_rows[1];
+  h.at_sweep_pieces = 2u;
+  hipDeviceProp_t pr;
+  if (hipGetDeviceProperties(&pr, h.device) == hipSuccess) at.wgs = std::max(16, pr.multiProcessorCount - 16);   // (the collective keeps the rest)
+  lazy_stream(h.stream_comm, h.ev_piece, h.ev_comm);
+  return at;
+}
 
-  k::PanelSource<T> src;
-  for (int it = 0; it < q; ++it) {
-    sweep_A();
-    normalize(h, Y, m, l, ld, norm, true, nullptr, nullptr, 1, nullptr, nullptr, center ? sv : nullptr);
-    sweep_At(true, src);
-    normalize(h, X, n_used, l, ld, norm, false, nullptr, nullptr, 1, &src, mu, center ? cvec : nullptr);
-    cvec_ready = center;
-  }
-  sweep_A();
-  normalize(h, Y, m, l, ld, SAPCA_NORM_QR, true, nullptr, nullptr, 0, nullptr, nullptr, center ? sv : nullptr);  // Q = qr(Y): always orthonormal
-  sweep_At(true, src);                                              // X = B^T = Ac^T Q  (n_used x l), completed by the Gram below
-
-  // R11 (f32): SVD of B through the l x l Gram of B^T: G = B B^T = Uh S^2 Uh^T (f64, MFMA + a host
-  // eigensolver), vt = (B^T Uh S^-1)^T.  The Gram squares the condition number, so sigma_i is good to
-  // eps_f64 (sigma_1/sigma_i)^2 relative: 1e-8 even for a 1e4 decay, below what the f32 panels carry; the
-  // f64 instantiation keeps the QR + Jacobi route below.  Saves two CholeskyQR passes over the n x l
-  // panel and 0.4 ms of host time per fit.
-  int info_host = 0;
-  const bool gram_route = sizeof(T) == 4 && dbg_env("SAPCA_SMALL_SVD_QR") == nullptr;
-  if (gram_route) {
-    Scope sc(h, C_SMALL);
-    double* G = small;
-    k::gram(X, n_used, ld, G, h.scratch2, s, &src);
-    const int ldk = (int)round_up(k, 16);
-    if (k::sym_eig_device_ok(l)) {
-      // (opt-in experiment, SAPCA_EIG_DEVICE=1: slower than the host path below -- see sym_eig_device_ok)
-      // the eigenproblem stays on the device (one workgroup, parallel Jacobi: dense.hip) and writes the factor M itself:
-      // no wait for the host anywhere in the small SVD.  The singular values (and the solver's status) cross in page-locked
-      // memory behind everything else; finish_fit() reads them after the fit's last wait.
-      double* d_sigma = small + (size_t)ld * ld;                  // (the normaliser's R^-1 slot: free here)
-      int* d_status = reinterpret_cast<int*>(d_sigma + ld);
-      k::sym_eig_device(G, l, ld, k, ldk, Mdev, d_sigma, d_status, s);
-      double* host = static_cast<double*>(h.small_host.ensure(((size_t)l + 4) * sizeof(double)));
-      int* host_i = reinterpret_cast<int*>(host + l);
-      SAPCA_HIP(hipMemcpyAsync(host, d_sigma, (size_t)l * sizeof(double), hipMemcpyDeviceToHost, s));
-      SAPCA_HIP(hipMemcpyAsync(host_i, d_status, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-      SAPCA_HIP(hipMemcpyAsync(host_i + 2, info, sizeof(int), hipMemcpyDeviceToHost, s));
-      T* VtT = h.panel_w.as<T>((size_t)std::max<int64_t>(n_used, 1) * ldk);
-      k::panel_gemm(X, n_used, ld, Mdev, ldk, VtT, s);
-      T* comps = h.components_dev.as<T>((size_t)k * std::max<int64_t>(n_used, 1));
-      k::flip_transpose(VtT, n_used, ldk, k, comps, h.scratch2, s);  // R13
-      h.sing_pending = l;
-      return;
-    }
-    // page-locked staging owned by the handle: G comes back and M goes out without the runtime's bounce buffers, and M
-    // outlives this call -- nothing here waits for the device after the eigensolver
-    double* g = static_cast<double*>(h.small_host.ensure(((size_t)ld * ld + (size_t)ld * ldk + 2) * sizeof(double)));
-    int* info_pinned = reinterpret_cast<int*>(g + (size_t)ld * ld + (size_t)ld * ldk);
-    SAPCA_HIP(hipMemcpyAsync(g, G, (size_t)ld * ld * sizeof(double), hipMemcpyDeviceToHost, s));
-    SAPCA_HIP(hipMemcpyAsync(info_pinned, info, sizeof(int), hipMemcpyDeviceToHost, s));
-    h.small_l = l;
-    h.small_ld = ld;
-    if (h.defer_small) {
-      // fit_transform: the host eigensolver runs while the GPU sweeps the projection with the un-rotated panel (transform():
-      // T = [Ac diag(cnt) B^T] M), instead of in front of an idle GPU
-      if (!h.ev_small) SAPCA_HIP(hipEventCreateWithFlags(&h.ev_small, hipEventDisableTiming));
-      SAPCA_HIP(hipEventRecord(h.ev_small, s));
-      h.small_pending = true;
-      return;
-    }
-    finish_small_svd(h, nullptr);
+// Omega into X: injected (parity tests; waits for the stream) or generated from the seed.
+template <typename T>
+void load_omega(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
+  hipStream_t s = h.stream;
+  if (h.omega.empty()) {
+    k::gaussian_panel(f.X, p.n_used, p.l, p.ld, h.opt.random_seed, s);
     return;
   }
+  SAPCA_CHECK((int64_t)h.omega_rows == p.n_used && (int64_t)h.omega_cols >= p.l, SAPCA_ERR_ARG,
+              "injected Omega must be (features seen by the SVD) x (n_components + n_oversamples)");
+  std::vector<T> tmp((size_t)p.n_used * p.l);
+  for (int64_t r = 0; r < p.n_used; ++r)
+    for (int j = 0; j < p.l; ++j) tmp[(size_t)r * p.l + j] = (T)h.omega[(size_t)r * h.omega_cols + j];
+  T* stage = h.scratch2.as<T>(tmp.size());
+  SAPCA_HIP(hipMemcpyAsync(stage, tmp.data(), tmp.size() * sizeof(T), hipMemcpyHostToDevice, s));
+  k::add_padding(stage, p.n_used, p.l, f.X, p.ld, s);
+  SAPCA_HIP(hipStreamSynchronize(s));  // tmp goes out of scope
+}
 
-  // R11 (f64): SVD of B through a QR of B^T: B^T = Qz Rz, Rz = Ur S Vr^T  =>  vt = (Qz Ur)^T.
+// Y = Ac X   (R8).  The centring vectors -- c = X^T mu here, the column sums 1^T Y of the A^T sweep -- belong to a panel that
+// has just been normalised: normalize() delivers them from sums gathered in its Gram pass (vec_out), so no kernel re-reads
+// the normalised panel for them; only the very first c (of Omega) is summed here.
+template <typename T>
+void sweep_a(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
+  hipStream_t s = h.stream;
+  if (p.center && !f.cvec_current) k::weighted_colsum(f.X, p.n_used, p.ld, f.mu, f.cvec, h.scratch2, s);
+  f.cvec_current = false;
+  Scope sc(h, C_SPMM);
+  k::spmm(Engine<T>::view(h.a_used), &h.tiled_a, f.X, p.ld, f.Y, p.ld, p.ld, p.center ? f.cvec : nullptr, p.variant, h.split_scratch, s);
+}
+
+// X = Ac^T Y   (R9); partial products are summed over ranks.  The panel is left as the sweep produced it: f.src says what the
+// next pass over X -- the Gram of its normalisation, or of the small SVD -- still has to apply (slabs of a sweep whose tile
+// range was split over workgroups, the centring term mu (1^T Y)^T; the normaliser of Y delivered 1^T Y into f.sv).
+template <typename T>
+void sweep_at_one_piece(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
+  hipStream_t s = h.stream;
+  f.src = k::PanelSource<T>();
+  {
+    Scope sc(h, C_SPMMT);
+    // (one rank: the slabs may stay unsummed; several: the collective needs the sum)
+    k::spmm(Engine<T>::view(h.at_used), &h.tiled_at, f.Y, p.ld, f.X, p.ld, p.ld, (const T*)nullptr, p.variant, h.split_scratch, s,
+            h.comm.active() ? nullptr : &f.src);
+  }
+  if (!f.src.parts) { f.src.parts = f.X; f.src.nsplit = 1; }
+  if (h.comm.active()) {
+    Scope cs(h, C_COMM);
+    h.comm.allreduce(f.X, (uint64_t)p.n_used * p.ld + (p.center ? (uint64_t)p.ld : 0), Engine<T>::kDtype, s);
+  }
+  if (p.center) { f.src.mu = f.mu; f.src.sv = f.sv; }
+}
+
+// ... in two pieces (f32, several ranks): the first piece's rows are all-reduced on stream_comm while the second piece runs.
+template <typename T>
+void sweep_at_two_pieces(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
+  if constexpr (sizeof(T) == 4) {
+    hipStream_t s = h.stream;
+    const int64_t cut = p.at.cut, r1 = p.at.r1;
+    f.src = k::PanelSource<T>();
+    {
+      Scope sc(h, C_SPMMT);
+      k::spmm_tiled_piece(h.tiled_at, 0, 2, p.at.wgs, 0, r1, f.Y, p.ld, f.X, p.ld, p.ld, h.split_scratch, s);
+      SAPCA_HIP(hipEventRecord(h.ev_piece, s));
+      k::spmm_tiled_piece(h.tiled_at, 1, 2, p.at.wgs, r1, p.n_used - r1, f.Y, p.ld, f.X, p.ld, p.ld, h.split_scratch2, s);
+    }
+    Scope cs(h, C_COMM);   // (device time from the first piece's collective being possible to the last one's end)
+    SAPCA_HIP(hipStreamWaitEvent(h.stream_comm, h.ev_piece, 0));
+    h.comm.allreduce(f.X, (uint64_t)cut * p.ld, Engine<T>::kDtype, h.stream_comm, 1);   // (cut <= r1: rows this rank has finished)
+    SAPCA_HIP(hipEventRecord(h.ev_comm, h.stream_comm));
+    h.comm.allreduce(f.X + (size_t)cut * p.ld, (uint64_t)(p.n_used - cut) * p.ld + (p.center ? (uint64_t)p.ld : 0), Engine<T>::kDtype, s);
+    SAPCA_HIP(hipStreamWaitEvent(s, h.ev_comm, 0));
+    f.src.parts = f.X; f.src.nsplit = 1;
+    if (p.center) { f.src.mu = f.mu; f.src.sv = f.sv; }
+  }
+}
+
+template <typename T>
+void sweep_at(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
+  p.at.sweep == AtSweep::TwoPieces ? sweep_at_two_pieces(h, p, f) : sweep_at_one_piece(h, p, f);
+}
+
+// R8-R10: q power iterations, then Q = qr(Ac X) and X = B^T = Ac^T Q (n_used x l), completed by the small SVD's first pass.
+template <typename T>
+void power_iterations(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
+  using Extras = NormalizeExtras<T>;
+  T* const sv_out = p.center ? f.sv : nullptr;
+  for (int it = 0; it < p.q; ++it) {
+    sweep_a(h, p, f);
+    Engine<T>::normalize(h, f.Y, p.m, p.l, p.ld, p.norm, true, Extras{.passes = 1, .vec_out = sv_out});
+    sweep_at(h, p, f);
+    Engine<T>::normalize(h, f.X, p.n_used, p.l, p.ld, p.norm, false,
+                         Extras{.passes = 1, .src = &f.src, .w = f.mu, .vec_out = p.center ? f.cvec : nullptr});
+    f.cvec_current = p.center;
+  }
+  sweep_a(h, p, f);
+  Engine<T>::normalize(h, f.Y, p.m, p.l, p.ld, SAPCA_NORM_QR, true, Extras{.vec_out = sv_out});   // Q = qr(Y): always orthonormal
+  sweep_at(h, p, f);
+}
+
+// vt = (B^T M)^T with the sign convention of svd_flip (R13): the components, from the un-rotated panel X = B^T (panel_x,
+// n_used x ld) and the small factor M (ld x ldk) of whichever small SVD produced it.  sign_out: the device address of the k flip signs.
+template <typename T>
+void rotate_into_components(H& h, int ld, const double* Mdev, const double** sign_out = nullptr) {
+  const int k = (int)h.opt.n_components, ldk = (int)round_up(k, 16);
+  const int64_t n_used = h.a_used.cols;
+  T* VtT = h.panel_w.as<T>((size_t)std::max<int64_t>(n_used, 1) * ldk);
+  k::panel_gemm(h.panel_x.ptr<T>(), n_used, ld, Mdev, ldk, VtT, h.stream);
+  T* comps = h.components_dev.as<T>((size_t)k * std::max<int64_t>(n_used, 1));
+  k::flip_transpose(VtT, n_used, ldk, k, comps, h.scratch2, h.stream, sign_out);
+}
+
+// GramDevice: the eigenproblem stays on the device (one workgroup, parallel Jacobi: dense.hip).  The singular values (and the
+// solver's status) cross in page-locked memory behind everything else; finish_fit() reads them after the fit's last wait.
+template <typename T>
+void small_svd_gram_device(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
+  hipStream_t s = h.stream;
+  Scope sc(h, C_SMALL);
+  k::gram(f.X, p.n_used, p.ld, f.lay.gram(), h.scratch2, s, &f.src);
+  double* d_sigma = f.lay.r_inv();   // (the normaliser's R^-1 slot: free here)
+  int* d_status = reinterpret_cast<int*>(d_sigma + p.ld);
+  k::sym_eig_device(f.lay.gram(), p.l, p.ld, p.k, p.ldk, f.lay.m(), d_sigma, d_status, s);
+  double* host = static_cast<double*>(h.small_host.ensure(((size_t)p.l + 4) * sizeof(double)));
+  int* host_i = reinterpret_cast<int*>(host + p.l);
+  SAPCA_HIP(hipMemcpyAsync(host, d_sigma, (size_t)p.l * sizeof(double), hipMemcpyDeviceToHost, s));
+  SAPCA_HIP(hipMemcpyAsync(host_i, d_status, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+  SAPCA_HIP(hipMemcpyAsync(host_i + 2, f.lay.info(), sizeof(int), hipMemcpyDeviceToHost, s));
+  rotate_into_components<T>(h, p.ld, f.lay.m());
+  h.held_tail.sing_l = p.l;
+}
+
+// GramHost / GramHostHeldBack: the Gram to the host in page-locked staging owned by the handle -- G comes back and M goes
+// out without the runtime's bounce buffers, and M outlives this call: nothing waits for the device after the eigensolver.
+template <typename T>
+void small_svd_gram_host(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
+  hipStream_t s = h.stream;
+  Scope sc(h, C_SMALL);
+  k::gram(f.X, p.n_used, p.ld, f.lay.gram(), h.scratch2, s, &f.src);
+  const size_t g_len = (size_t)p.ld * p.ld, m_len = (size_t)p.ld * p.ldk;
+  double* g = static_cast<double*>(h.small_host.ensure((g_len + m_len + 2) * sizeof(double)));
+  int* info_pinned = reinterpret_cast<int*>(g + g_len + m_len);
+  SAPCA_HIP(hipMemcpyAsync(g, f.lay.gram(), g_len * sizeof(double), hipMemcpyDeviceToHost, s));
+  SAPCA_HIP(hipMemcpyAsync(info_pinned, f.lay.info(), sizeof(int), hipMemcpyDeviceToHost, s));
+  h.held_small.l = p.l;
+  h.held_small.ld = p.ld;
+  if (p.small == SmallSvd::GramHostHeldBack) {
+    if (!h.held_small.ev) SAPCA_HIP(hipEventCreateWithFlags(&h.held_small.ev, hipEventDisableTiming));
+    SAPCA_HIP(hipEventRecord(h.held_small.ev, s));
+    h.held_small.pending = true;
+    return;
+  }
+  Engine<T>::finish_small_svd(h, nullptr);
+}
+
+// QrJacobi: two CholeskyQR passes over X, the product of their factors to the host, Jacobi there.  Waits for the stream twice.
+template <typename T>
+void small_svd_qr_jacobi(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
+  hipStream_t s = h.stream;
+  const int l = p.l, ld = p.ld;
+  int info_host = 0;
   std::vector<double> r1((size_t)ld * ld), r2((size_t)ld * ld);
   {
     Scope sc(h, C_SMALL);
-    normalize(h, X, n_used, l, ld, SAPCA_NORM_QR, false, R1, R2, 0, &src);
-    SAPCA_HIP(hipMemcpyAsync(r1.data(), R1, r1.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    SAPCA_HIP(hipMemcpyAsync(r2.data(), R2, r2.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    SAPCA_HIP(hipMemcpyAsync(&info_host, info, sizeof(int), hipMemcpyDeviceToHost, s));
+    Engine<T>::normalize(h, f.X, p.n_used, l, ld, SAPCA_NORM_QR, false, NormalizeExtras<T>{.R1 = f.lay.r1(), .R2 = f.lay.r2(), .src = &f.src});
+    SAPCA_HIP(hipMemcpyAsync(r1.data(), f.lay.r1(), r1.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    SAPCA_HIP(hipMemcpyAsync(r2.data(), f.lay.r2(), r2.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    SAPCA_HIP(hipMemcpyAsync(&info_host, f.lay.info(), sizeof(int), hipMemcpyDeviceToHost, s));
     SAPCA_HIP(hipStreamSynchronize(s));
     std::vector<double> Rz((size_t)l * l, 0.0), Ur, sv;
     for (int i = 0; i < l; ++i)
@@ -933,43 +992,57 @@ void Engine<T>::fit_randomized(H& h) {
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tj0).count());
     for (int i = 0; i < l; ++i)
       SAPCA_CHECK(std::isfinite(sv[i]), SAPCA_ERR_SVD, "Randomized SVD computation failed: non-finite singular value");
-    const int ldk = (int)round_up(k, 16);
-    std::vector<double> M((size_t)ld * ldk, 0.0);
+    std::vector<double> M((size_t)ld * p.ldk, 0.0);
     for (int i = 0; i < l; ++i)
-      for (int j = 0; j < k; ++j) M[(size_t)i * ldk + j] = Ur[(size_t)i * l + j];
-    SAPCA_HIP(hipMemcpyAsync(Mdev, M.data(), M.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    T* VtT = h.panel_w.as<T>((size_t)std::max<int64_t>(n_used, 1) * ldk);
-    k::panel_gemm(X, n_used, ld, Mdev, ldk, VtT, s);
-    T* comps = h.components_dev.as<T>((size_t)k * std::max<int64_t>(n_used, 1));
-    k::flip_transpose(VtT, n_used, ldk, k, comps, h.scratch2, s);  // R13
-    SAPCA_HIP(hipStreamSynchronize(s));                            // M goes out of scope
-    h.sing.assign(sv.begin(), sv.begin() + k);
+      for (int j = 0; j < p.k; ++j) M[(size_t)i * p.ldk + j] = Ur[(size_t)i * l + j];
+    SAPCA_HIP(hipMemcpyAsync(f.lay.m(), M.data(), M.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    rotate_into_components<T>(h, ld, f.lay.m());
+    SAPCA_HIP(hipStreamSynchronize(s));   // M goes out of scope
+    h.sing.assign(sv.begin(), sv.begin() + p.k);
   }
   h.chol_regularised = info_host;
 }
 
-// R11 (f32), host half: eigen-decomposition of the l x l Gram staged in small_host by fit_randomized, the factor
-// M = Uh S^-1 back to the device, vt = (B^T M)^T, svd_flip (R13).  Called at the end of fit_randomized, or -- fit_transform,
-// `small_pending` -- from transform() once the projection sweep is queued.  sign_out: the device address of the k flip signs.
+}  // namespace
+
+template <typename T>
+void Engine<T>::fit_randomized(H& h) {
+  RandomizedPlan p = plan_randomized<T>(h);
+  T* X = h.panel_x.as<T>(((size_t)std::max<int64_t>(p.n_used, 1) + 1) * p.ld);
+  T* Y = h.panel_y.as<T>((size_t)std::max<int64_t>(p.m, 1) * p.ld);
+  const SmallLayout lay(h.small, p.ld);
+  // one collective carries the l column sums of this rank's Y too: they live in the row behind the panel then
+  T* sv = h.comm.active() ? X + (size_t)p.n_used * p.ld : lay.s<T>();
+  FitPanels<T> f{X, Y, lay, p.center ? h.mean_used_dev.ptr<T>() : nullptr, lay.c<T>(), sv};
+  SAPCA_HIP(hipMemsetAsync(lay.info(), 0, sizeof(int), h.stream));
+  load_omega(h, p, f);
+  p.at = agree_on_at_pieces<T>(h, p);   // (several ranks: a collective and a host wait, at this point of the stream)
+  power_iterations(h, p, f);
+  switch (p.small) {
+    case SmallSvd::GramDevice: small_svd_gram_device(h, p, f); break;
+    case SmallSvd::QrJacobi: small_svd_qr_jacobi(h, p, f); break;
+    default: small_svd_gram_host(h, p, f); break;
+  }
+}
+
+// R11 (f32), host half: eigen-decomposition of the l x l Gram staged in small_host by small_svd_gram_host, the factor
+// M = Uh S^-1 back to the device, then the components.  Called at the end of the fit, or -- fit_transform,
+// `held_small.pending` -- from transform() once the projection sweep is queued.  sign_out: see rotate_into_components.
 template <typename T>
 void Engine<T>::finish_small_svd(H& h, const double** sign_out) {
   hipStream_t s = h.stream;
-  const bool deferred = h.small_pending;
-  h.small_pending = false;
-  const int l = h.small_l, ld = h.small_ld, k = (int)h.opt.n_components;
-  const int64_t n_used = h.a_used.cols;
+  const bool deferred = h.held_small.pending;
+  h.held_small.pending = false;
+  const int l = h.held_small.l, ld = h.held_small.ld, k = (int)h.opt.n_components;
   const int ldk = (int)round_up(k, 16);
-  const SmallLayout lay(ld);
-  double* small = h.small.as<double>(lay.doubles());
-  double* Mdev = small + (size_t)5 * ld * ld;
-  T* X = h.panel_x.ptr<T>();
+  const SmallLayout lay(h.small, ld);
   try {
-    std::unique_ptr<Scope> sc(deferred ? new Scope(h, C_SMALL) : nullptr);   // (not deferred: inside fit_randomized's own span)
-    if (sc && sc->ev >= 0) h.small_in_transform.push_back(sc->ev);             // (it lies inside the projection's span: taken out of transform_ms)
+    std::unique_ptr<Scope> sc(deferred ? new Scope(h, C_SMALL) : nullptr);   // (not deferred: inside the fit's own span)
+    if (sc && sc->ev >= 0) h.held_small.in_transform.push_back(sc->ev);       // (it lies inside the projection's span: taken out of transform_ms)
     double* g = static_cast<double*>(h.small_host.p);
     double* M = g + (size_t)ld * ld;
     const int* info_pinned = reinterpret_cast<const int*>(M + (size_t)ld * ldk);
-    if (deferred) SAPCA_HIP(hipEventSynchronize(h.ev_small));
+    if (deferred) SAPCA_HIP(hipEventSynchronize(h.held_small.ev));
     else SAPCA_HIP(hipStreamSynchronize(s));
     const int info_host = *info_pinned;
     std::vector<double> Gl((size_t)l * l), w, Vt;
@@ -992,17 +1065,14 @@ void Engine<T>::finish_small_svd(H& h, const double** sign_out) {
       const double inv = 1.0 / sv[j];
       for (int i = 0; i < l; ++i) M[(size_t)i * ldk + j] = Vt[(size_t)j * l + i] * inv;
     }
-    SAPCA_HIP(hipMemcpyAsync(Mdev, M, (size_t)ld * ldk * sizeof(double), hipMemcpyHostToDevice, s));
-    T* VtT = h.panel_w.as<T>((size_t)std::max<int64_t>(n_used, 1) * ldk);
-    k::panel_gemm(X, n_used, ld, Mdev, ldk, VtT, s);
-    T* comps = h.components_dev.as<T>((size_t)k * std::max<int64_t>(n_used, 1));
-    k::flip_transpose(VtT, n_used, ldk, k, comps, h.scratch2, s, sign_out);  // R13
+    SAPCA_HIP(hipMemcpyAsync(lay.m(), M, (size_t)ld * ldk * sizeof(double), hipMemcpyHostToDevice, s));
+    rotate_into_components<T>(h, ld, lay.m(), sign_out);
     h.sing.assign(sv.begin(), sv.begin() + k);
     h.chol_regularised = info_host;
   } catch (...) {
     if (deferred) {   // the fit had been reported as done: take that back
       h.fitted = false;
-      h.finish_pending = false;
+      h.held_tail.pending = false;
     }
     throw;
   }
@@ -1023,23 +1093,15 @@ void Engine<T>::fit_lanczos(H& h) {
 template <typename T>
 void Engine<T>::fit(H& h, const CsrView<T>& A, bool defer_finish) {
   hipStream_t s = h.stream;
-  h.finish_pending = false;
-  h.sing_pending = 0;
-  h.small_pending = false;
-  // fit_transform of an unmasked f32 randomized fit: the small SVD's host half is held back until transform() has queued
-  // the projection sweep (masked fits finish first, see below)
-  // ... where that pays: the rotation is one more m x l by l x k panel product (0.2 ms per million rows at l <= 64, four
-  // times that at 128 columns) against a host stall of 0.25 ms (l = 60) to 1 ms (l = 110) -- C2 and the shards of a
-  // strong-scaled fit gain 0.2 ms of a 9.5 ms step, a million rows on one GPU would lose as much (measured, round 4).
+  h.held_tail.reset();
+  h.held_small.reset();
   {
+    // GramHostHeldBack (RandomizedPlan's route table has the break-even)
     const double lw = (double)(h.opt.n_components + h.opt.n_oversamples) <= 64 ? 64.0 : 128.0;
-    // (decided from what every rank of a sharded fit sees alike -- the ranks' shards of one projection take one route;
-    // m_global is not known yet, the shard is about 1 / nranks of it)
-    h.defer_small = defer_finish && h.mask.empty() && h.opt.method == SAPCA_RANDOM && sizeof(T) == 4 &&
-                    (h.comm.active() || (double)A.rows * lw * lw <= 400e3 * 64.0 * 64.0);
+    h.held_small.defer = defer_finish && h.mask.empty() && h.opt.method == SAPCA_RANDOM && sizeof(T) == 4 &&
+                         (h.comm.active() || (double)A.rows * lw * lw <= 400e3 * 64.0 * 64.0);
   }
   h.spans.clear();
-  h.small_in_transform.clear();
   h.comm.host_ms = 0;
   h.timer.begin_collect(s, h.opt.collect_timings != 0);
   const int total_ev = h.timer.start();
@@ -1085,25 +1147,42 @@ void Engine<T>::fit(H& h, const CsrView<T>& A, bool defer_finish) {
   h.dtype = kDtype;
   h.fitted = true;
   h.timer.stop(total_ev);
-  h.fit_total_ev = total_ev;
-  h.finish_pending = true;
+  h.held_tail.total_ev = total_ev;
+  h.held_tail.pending = true;
   // fit_transform: the host-side tail (statistics, timings: two waits for the device) runs once the projection is queued --
   // the model the projection reads is all on the device by now
   // (masked fits finish first: their projection asks the finished statistics whether its two sweeps would cancel, Q3)
   if (!defer_finish || !h.mask.empty()) finish_fit(h);
 }
 
+namespace {
+
+// What swept, for sapca_timings: ALGORITHMIC bytes of one sparse x dense sweep, the kernel, the pieces, the formats' slots.
+template <typename T>
+void describe_sweeps(H& h) {
+  const int64_t n_used = (int64_t)h.n_used;
+  const double l = (double)std::min<uint64_t>(h.opt.n_components + h.opt.n_oversamples, std::min<uint64_t>(h.m_global, (uint64_t)n_used));
+  h.timings.bytes_per_sweep = (double)h.a_used.nnz * (sizeof(T) + 4) + ((double)h.a_used.rows + 1) * 8 +
+                              (double)n_used * l * sizeof(T) + (double)h.a_used.rows * l * sizeof(T);
+  const bool tiled = h.opt.method == SAPCA_RANDOM && h.tiled_a.valid && h.tiled_at.valid;
+  h.timings.sweep_kernel = !tiled ? 0u : (k::dq_usable(h.tiled_a, 64) && k::dq_usable(h.tiled_at, 64) && h.opt.spmm_variant != 1 ? 2u : 1u);
+  h.timings.at_sweep_pieces = h.opt.method == SAPCA_RANDOM ? h.at_sweep_pieces : 0u;
+  h.timings.sweep_slots_a = tiled ? (uint64_t)h.tiled_a.total_entries : 0;
+  h.timings.sweep_slots_at = tiled ? (uint64_t)h.tiled_at.total_entries : 0;
+}
+
+}  // namespace
+
 template <typename T>
 void Engine<T>::finish_fit(H& h) {
-  if (!h.finish_pending) return;
-  if (h.small_pending) finish_small_svd(h, nullptr);   // (a projection that failed before it reached the held-back half)
-  h.finish_pending = false;
+  if (!h.held_tail.pending) return;
+  if (h.held_small.pending) finish_small_svd(h, nullptr);   // (a projection that failed before it reached the held-back half)
+  h.held_tail.pending = false;
   hipStream_t s = h.stream;
-  const int total_ev = h.fit_total_ev;
-  const int64_t n_used = (int64_t)h.n_used;
-  if (h.sing_pending) {   // the device eigensolver's singular values and status (fit_randomized)
-    const int l = h.sing_pending;
-    h.sing_pending = 0;
+  const int total_ev = h.held_tail.total_ev;
+  if (h.held_tail.sing_l) {   // the device eigensolver's singular values and status (small_svd_gram_device)
+    const int l = h.held_tail.sing_l;
+    h.held_tail.sing_l = 0;
     SAPCA_HIP(hipStreamSynchronize(s));
     const double* host = static_cast<const double*>(h.small_host.p);
     const int* host_i = reinterpret_cast<const int*>(host + l);
@@ -1141,23 +1220,133 @@ void Engine<T>::finish_fit(H& h) {
   SAPCA_HIP(hipStreamSynchronize(s));
   collect_timings(h, true);
   if (total_ev >= 0) h.timings.fit_total_ms = h.timer.ms(total_ev);
-  {
-    // ALGORITHMIC bytes of one sparse x dense sweep
-    const double l = (double)std::min<uint64_t>(h.opt.n_components + h.opt.n_oversamples,
-                                                std::min<uint64_t>(h.m_global, (uint64_t)n_used));
-    h.timings.bytes_per_sweep = (double)h.a_used.nnz * (sizeof(T) + 4) + ((double)h.a_used.rows + 1) * 8 +
-                                (double)n_used * l * sizeof(T) + (double)h.a_used.rows * l * sizeof(T);
-    const bool tiled = h.opt.method == SAPCA_RANDOM && h.tiled_a.valid && h.tiled_at.valid;
-    h.timings.sweep_kernel = !tiled ? 0u : (k::dq_usable(h.tiled_a, 64) && k::dq_usable(h.tiled_at, 64) && h.opt.spmm_variant != 1 ? 2u : 1u);
-    h.timings.at_sweep_pieces = h.opt.method == SAPCA_RANDOM ? h.at_sweep_pieces : 0u;
-    h.timings.sweep_slots_a = tiled ? (uint64_t)h.tiled_a.total_entries : 0;
-    h.timings.sweep_slots_at = tiled ? (uint64_t)h.tiled_at.total_entries : 0;
-  }
+  describe_sweeps<T>(h);
 }
 
 // ------------------------------------------------------------------------------------------
 // transform
 // ------------------------------------------------------------------------------------------
+namespace {
+
+// The operator a projection sweeps and what the handle holds of it.
+template <typename T>
+struct Projection {
+  CsrView<T> Au;                 // the matrix without the masked-out columns
+  const TiledOp* top = nullptr;  // its tile-major format (null: row kernel)
+  int ldk = 0;                   // leading dimension of the k-column panel swept through it
+  double* d_cnt = nullptr;       // stored entries per column (Q2's weights); null where nothing reads them
+  bool prepared = false;         // A is the matrix the handle's preparation was made from
+};
+
+// The only place in transform() that invalidates the preparation's key or rebuilds tiled_a.  Main stream; a masked matrix
+// other than the prepared one synchronises with the host (its compaction).
+template <typename T>
+Projection<T> select_projection_operator(H& h, const CsrView<T>& A) {
+  hipStream_t s = h.stream;
+  const int k = (int)h.k;
+  const bool masked = !h.mask.empty(), ref_sem = h.opt.transform_semantics == SAPCA_TRANSFORM_REFERENCE;
+  Projection<T> pr;
+  pr.ldk = (int)round_up(k, 16);
+  pr.prepared = h.prep_key == prep_key_of(h, A);
+  if (pr.prepared) {
+    // the fitted matrix's tile-major format serves the projection sweep too (one row block per workgroup)
+    // (operators with few row blocks -- a shard of a strong-scaled fit -- split their tile range over workgroups: the sweep sums
+    //  the slabs itself; only the masked Q3 projection insists on an unsplit operator and checks that on its own)
+    if (h.tiled_a.valid && k <= k::kMaxPanelWidth) pr.top = &h.tiled_a;
+    pr.Au = Engine<T>::view(h.a_used);
+    pr.d_cnt = h.stats.ptr<double>() + 2 * A.cols;
+  } else if (masked) {
+    h.prep_key.valid = false;  // the compaction buffers are about to be reused
+    std::vector<int32_t> o2m32;   // (the compaction synchronises before it goes out of scope)
+    pr.Au = Engine<T>::view(compact_a(h, A, upload_o2m(h, o2m32), (int64_t)h.n_used));
+  } else {
+    pr.Au = A;
+    if (ref_sem) {
+      h.prep_key.valid = false;
+      pr.d_cnt = stats_dev(h, A.cols) + 2 * A.cols;
+      k::column_counts_f64(A.idx, A.nnz, A.cols, pr.d_cnt, h.scratch, s);
+      if (h.comm.active()) h.comm.allreduce(pr.d_cnt, (uint64_t)A.cols, 1, s);
+    }
+  }
+  // A matrix the handle holds no preparation of (a separate transform of new rows, or of caller-owned arrays): above the
+  // staged sweep's break-even its tile-major format is built for this one sweep -- 0.9 ms + a 0.55 ms sweep at C2's size
+  // against 5 ms through the row kernel.  (The masked Q3 projection checks on its own whether it can use it.)
+  if (!pr.prepared && k <= k::kMaxPanelWidth && pr.Au.nnz > 0) {
+    const int ldp_t = staged_sweep_ldp<T>(pr.Au.rows, pr.Au.cols, (double)pr.Au.nnz, k, h.opt.spmm_variant);
+    if (ldp_t != 0) {
+      h.prep_key.valid = false;   // (tiled_a no longer belongs to the fitted matrix)
+      h.tiled_at = TiledOp();
+      h.tiled_a = TiledOp();
+      if (k::build_tiled(pr.Au, ldp_t, h.tiled_a, h.tb_a, s) && h.tiled_a.valid) pr.top = &h.tiled_a;
+      else h.tiled_a = TiledOp();
+    }
+  }
+  if (pr.top) pr.ldk = panel_ld(k, pr.top->ldp);
+  return pr;
+}
+
+// fit_transform, f32 randomized: the fit stopped in front of the host eigensolver.  The projection is linear in the
+// components: with vt^T = B^T M (M = Uh S^-1 diag(sign), l x k) the reference's t = Ac diag(cnt) vt^T (Q2; cnt = 1 for the
+// centred semantics) is [Ac diag(cnt) B^T] M -- the sweep runs on the un-rotated n x l panel while the host solves the
+// l x l eigenproblem, and one m x l by l x k panel product rotates its result.  (B^T = panel_x; Q = panel_y is free.)
+template <typename T>
+void project_unrotated(H& h, const Projection<T>& pr, T* d_out) {
+  hipStream_t s = h.stream;
+  const int ld = h.held_small.ld, k = (int)h.k;
+  const int64_t m = pr.Au.rows, n_used = (int64_t)h.n_used;
+  const bool center = h.opt.center != 0, ref_sem = h.opt.transform_semantics == SAPCA_TRANSFORM_REFERENCE;
+  const SmallLayout lay(h.small, ld);
+  T* cvec = lay.c<T>();
+  T* Xs = h.panel_xs.as<T>((size_t)n_used * ld);
+  T* Tp = h.panel_y.as<T>((size_t)m * ld);
+  k::scale_rows(h.panel_x.ptr<T>(), n_used, ld, ref_sem ? pr.d_cnt : nullptr, Xs, s);
+  if (center) k::weighted_colsum(Xs, n_used, ld, h.mean_used_dev.ptr<T>(), cvec, h.scratch2, s);
+  k::spmm(pr.Au, h.tiled_a.valid ? &h.tiled_a : nullptr, Xs, ld, Tp, ld, ld, center ? cvec : nullptr, h.opt.spmm_variant, h.split_scratch, s);
+  const double* sign = nullptr;
+  Engine<T>::finish_small_svd(h, &sign);   // (waits for the Gram's copy only; the sweep above is running)
+  const int ldm = (int)round_up(k, 16);
+  k::scale_columns(lay.m(), ld, ldm, k, sign, s);
+  k::panel_gemm(Tp, m, ld, lay.m(), ldm, d_out, s, false, k, k);
+}
+
+// The projection with the fitted components (a separate transform, masked fits, f64, Lanczos, large m), in one of three semantics:
+//  Q2 (sparse/mod.rs:268-282), unmasked:            t_ik = sum_j cnt_j (x_ij - [center] mu_j) V_kj
+//  Q3 (sparse_masked/mod.rs:488-529), masked:       the mean is subtracted at stored, kept entries only
+//  centred (opt-in, SAPCA_TRANSFORM_CENTERED):      the mathematically centred projection (A - 1 mu^T) V^T
+template <typename T>
+void project_with_components(H& h, const Projection<T>& pr, T* d_out) {
+  hipStream_t s = h.stream;
+  const int k = (int)h.k, ldk = pr.ldk, variant = h.opt.spmm_variant;
+  const int64_t m = pr.Au.rows, n_used = (int64_t)h.n_used;
+  const bool center = h.opt.center != 0, masked = !h.mask.empty(), ref_sem = h.opt.transform_semantics == SAPCA_TRANSFORM_REFERENCE;
+  const T* mu = h.mean_used_dev.ptr<T>();
+  T* cvec = SmallLayout(h.small, ldk).c<T>();
+  T* W = h.panel_w.as<T>((size_t)n_used * ldk);
+  k::scaled_transpose(h.components_dev.ptr<T>(), n_used, k, ref_sem && !masked ? pr.d_cnt : nullptr, W, ldk, s);
+  if (!(ref_sem && masked)) {   // Q2, centred: one sweep, centred through c = W^T mu
+    if (center) k::weighted_colsum(W, n_used, ldk, mu, cvec, h.scratch2, s);
+    k::spmm(pr.Au, pr.top, W, ldk, d_out, k, k, center ? cvec : nullptr, variant, h.split_scratch, s);
+    return;
+  }
+  // Q3.  TwoSweeps: A'W - P diag(mu) W through the fitted matrix's tile-major format (spmm_dq.hip) -- only for the fitted
+  // matrix: `q3_cancels` was decided from ITS column statistics.  ShiftedRows: the row kernel subtracts mu_j entry by entry,
+  // like the reference; it also takes over where the two sweeps refuse the operator.  Plain: nothing to subtract.
+  enum class Q3 { TwoSweeps, ShiftedRows, Plain };
+  const bool dq = sizeof(T) == 4 && pr.top && pr.prepared && variant != 1 && !h.q3_cancels && dbg_env("SAPCA_Q3_ROWKERNEL") == nullptr;
+  Q3 route = !center ? Q3::Plain : dq ? Q3::TwoSweeps : Q3::ShiftedRows;
+  if constexpr (sizeof(T) == 4) {
+    if (route == Q3::TwoSweeps) {
+      float* W2 = h.scratch2.as<float>((size_t)n_used * ldk);
+      float* tmp = h.panel_y.as<float>((size_t)m * std::max(k, 1));
+      if (!k::q3_projection_dq(pr.Au, *pr.top, W, ldk, mu, W2, tmp, d_out, k, s)) route = Q3::ShiftedRows;
+    }
+  }
+  if (route == Q3::ShiftedRows) k::spmm_rows_shifted(pr.Au, W, ldk, d_out, k, k, mu, s);
+  if (route == Q3::Plain) k::spmm(pr.Au, pr.top, W, ldk, d_out, k, k, (const T*)nullptr, variant, h.split_scratch, s);
+}
+
+}  // namespace
+
 template <typename T>
 void Engine<T>::transform(H& h, const CsrView<T>& A, T* d_out) {
   hipStream_t s = h.stream;
@@ -1172,128 +1361,18 @@ void Engine<T>::transform(H& h, const CsrView<T>& A, T* d_out) {
   h.spans.erase(std::remove_if(h.spans.begin(), h.spans.end(), [](const std::pair<int, int>& p) { return p.first == C_TRANSFORM; }),
                 h.spans.end());
   if (h.spans.empty()) h.timer.begin_collect(s, h.opt.collect_timings != 0);
-  const int64_t m = A.rows, n = A.cols, n_used = (int64_t)h.n_used;
-  const int k = (int)h.k;
-  int ldk = (int)round_up(k, 16);
-  const bool center = h.opt.center != 0;
-  const bool ref_sem = h.opt.transform_semantics == SAPCA_TRANSFORM_REFERENCE;
-  if (m == 0) {   // (a rank with an empty shard still completes a fit whose tail was held back)
+  if (A.rows == 0) {   // (a rank with an empty shard still completes a fit whose tail was held back)
     finish_fit(h);
     return;
   }
   {
     Scope sc(h, C_TRANSFORM);
-    H::PrepKey key;
-    key.ptr = A.ptr; key.idx = A.idx; key.val = A.val; key.m = (uint64_t)m; key.n = (uint64_t)n;
-    key.nnz = (uint64_t)A.nnz; key.mask_version = h.mask_version; key.dtype = kDtype; key.valid = true;
-    const bool prepared = h.prep_key == key;
-    // the fitted matrix's tile-major format serves the projection sweep too (one row block per workgroup)
-    // (operators with few row blocks -- a shard of a strong-scaled fit -- split their tile range over workgroups: the sweep sums
-    //  the slabs itself; only the masked Q3 projection insists on an unsplit operator and checks that on its own)
-    const TiledOp* top = (prepared && h.tiled_a.valid && k <= k::kMaxPanelWidth) ? &h.tiled_a : nullptr;
-    if (top) ldk = panel_ld(k, top->ldp);
-    CsrView<T> Au;
-    double* d_cnt = nullptr;
-    if (prepared) {
-      Au = view(h.a_used);
-      d_cnt = h.stats.ptr<double>() + 2 * n;
-    } else if (masked) {
-      h.prep_key.valid = false;  // the compaction buffers are about to be reused
-      std::vector<int32_t> o2m32;   // (the compaction synchronises before it goes out of scope)
-      Au = view(compact_a(h, A, upload_o2m(h, o2m32), n_used));
+    const Projection<T> pr = select_projection_operator(h, A);
+    if (h.held_small.pending && pr.prepared && !masked) {
+      project_unrotated(h, pr, d_out);
     } else {
-      Au = A;
-      if (ref_sem) {
-        h.prep_key.valid = false;
-        d_cnt = stats_dev(h, n) + 2 * n;
-        k::column_counts_f64(A.idx, A.nnz, n, d_cnt, h.scratch, s);
-        if (h.comm.active()) h.comm.allreduce(d_cnt, (uint64_t)n, 1, s);
-      }
-    }
-    // A matrix the handle holds no preparation of (a separate transform of new rows, or of caller-owned arrays): above the
-    // staged sweep's break-even its tile-major format is built for this one sweep -- 0.9 ms + a 0.55 ms sweep at C2's size
-    // against 5 ms through the row kernel.  (The masked Q3 projection checks on its own whether it can use it.)
-    if (!top && !prepared && k <= k::kMaxPanelWidth && Au.nnz > 0) {
-      const int ldp_t = staged_sweep_ldp<T>(Au.rows, Au.cols, (double)Au.nnz, k, h.opt.spmm_variant);
-      if (ldp_t != 0) {
-        h.prep_key.valid = false;   // (tiled_a no longer belongs to the fitted matrix)
-        h.tiled_at = TiledOp();
-        h.tiled_a = TiledOp();
-        const bool ok = k::build_tiled(Au, ldp_t, h.tiled_a, h.tb_a, s);
-        if (ok && h.tiled_a.valid) {
-          top = &h.tiled_a;
-          ldk = panel_ld(k, top->ldp);
-        } else {
-          h.tiled_a = TiledOp();
-        }
-      }
-    }
-    const T* mu = h.mean_used_dev.ptr<T>();
-    // fit_transform, f32 randomized: the fit stopped in front of the host eigensolver.  The projection is linear in the
-    // components: with vt^T = B^T M (M = Uh S^-1 diag(sign), l x k) the reference's t = Ac diag(cnt) vt^T (Q2; cnt = 1 for the
-    // centred semantics) is [Ac diag(cnt) B^T] M -- the sweep runs on the un-rotated n x l panel while the host solves the
-    // l x l eigenproblem, and one m x l by l x k panel product rotates its result.  (B^T = panel_x; Q = panel_y is free.)
-    auto project_unrotated = [&] {
-      const int ld = h.small_ld;
-      const SmallLayout lay(ld);
-      double* small = h.small.as<double>(lay.doubles());
-      T* cvec = reinterpret_cast<T*>(small + lay.cvec_at());
-      double* Mdev = small + (size_t)5 * ld * ld;
-      const T* X = h.panel_x.ptr<T>();
-      T* Xs = h.panel_xs.as<T>((size_t)n_used * ld);
-      T* Tp = h.panel_y.as<T>((size_t)m * ld);
-      const TiledOp* topl = h.tiled_a.valid ? &h.tiled_a : nullptr;
-      k::scale_rows(X, n_used, ld, ref_sem ? d_cnt : nullptr, Xs, s);
-      if (center) k::weighted_colsum(Xs, n_used, ld, mu, cvec, h.scratch2, s);
-      k::spmm(Au, topl, Xs, ld, Tp, ld, ld, center ? cvec : nullptr, h.opt.spmm_variant, h.split_scratch, s);
-      const double* sign = nullptr;
-      finish_small_svd(h, &sign);   // (waits for the Gram's copy only; the sweep above is running)
-      const int ldm = (int)round_up(k, 16);
-      k::scale_columns(Mdev, ld, ldm, k, sign, s);
-      k::panel_gemm(Tp, m, ld, Mdev, ldm, d_out, s, false, k, k);
-    };
-    // the projection with the fitted components (a separate transform, masked fits, f64, Lanczos, large m)
-    auto project_with_components = [&] {
-      const SmallLayout lay(ldk);
-      double* small = h.small.as<double>(lay.doubles());
-      T* cvec = reinterpret_cast<T*>(small + lay.cvec_at());
-      const T* comps = h.components_dev.ptr<T>();
-      T* W = h.panel_w.as<T>((size_t)n_used * ldk);
-      if (ref_sem && !masked) {
-        // Q2 (sparse/mod.rs:268-282): t_ik = sum_j cnt_j (x_ij - [center] mu_j) V_kj
-        k::scaled_transpose(comps, n_used, k, d_cnt, W, ldk, s);
-        if (center) k::weighted_colsum(W, n_used, ldk, mu, cvec, h.scratch2, s);
-        k::spmm(Au, top, W, ldk, d_out, k, k, center ? cvec : nullptr, h.opt.spmm_variant, h.split_scratch, s);
-      } else if (ref_sem && masked) {
-        // Q3 (sparse_masked/mod.rs:488-529): mean subtracted at stored, kept entries only
-        k::scaled_transpose(comps, n_used, k, (const double*)nullptr, W, ldk, s);
-        bool done = false;
-        if constexpr (sizeof(T) == 4) {
-          // the fitted matrix's tile-major format: A'W - P diag(mu) W as two sweeps (spmm_dq.hip)
-          // (only for the fitted matrix: `q3_cancels` was decided from ITS column statistics; another matrix takes the row
-          // kernel, which subtracts entry by entry like the reference)
-          if (center && top && prepared && h.opt.spmm_variant != 1 && !h.q3_cancels && dbg_env("SAPCA_Q3_ROWKERNEL") == nullptr) {
-            float* W2 = h.scratch2.as<float>((size_t)n_used * ldk);
-            float* tmp = h.panel_y.as<float>((size_t)m * std::max(k, 1));
-            done = k::q3_projection_dq(Au, *top, W, ldk, mu, W2, tmp, d_out, k, s);
-          }
-        }
-        if (!done) {
-          if (center) k::spmm_rows_shifted(Au, W, ldk, d_out, k, k, mu, s);   // (the row kernel subtracts mu_j entry by entry)
-          else k::spmm(Au, top, W, ldk, d_out, k, k, (const T*)nullptr, h.opt.spmm_variant, h.split_scratch, s);
-        }
-      } else {
-        // opt-in: the mathematically centred projection (A - 1 mu^T) V^T
-        k::scaled_transpose(comps, n_used, k, (const double*)nullptr, W, ldk, s);
-        if (center) k::weighted_colsum(W, n_used, ldk, mu, cvec, h.scratch2, s);
-        k::spmm(Au, top, W, ldk, d_out, k, k, center ? cvec : nullptr, h.opt.spmm_variant, h.split_scratch, s);
-      }
-    };
-    if (h.small_pending && prepared && !masked) {
-      project_unrotated();
-    } else {
-      if (h.small_pending) finish_small_svd(h, nullptr);   // (a held-back small SVD whose projection cannot take the un-rotated route)
-      project_with_components();
+      if (h.held_small.pending) finish_small_svd(h, nullptr);   // (a held-back small SVD whose projection cannot take the un-rotated route)
+      project_with_components(h, pr, d_out);
     }
   }
   SAPCA_HIP(hipStreamSynchronize(s));

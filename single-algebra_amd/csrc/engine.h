@@ -1,5 +1,6 @@
 // The handle behind the C ABI and the typed engine that drives the kernels.
 #pragma once
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -66,14 +67,21 @@ struct sapca_handle_s {
   // of fit() instead of stalling the stream between the preparation and the first sweep
   sapca::PinnedBuf stats_host;
   sapca::PinnedBuf small_host;    // the l x l Gram on its way to the host eigensolver, its factor on the way back
-  int fit_total_ev = -1;
-  bool finish_pending = false;    // fit() returned with its host-side tail still to run (fit_transform)
+  struct HeldTail {   // fit_transform: fit() returned with its host-side tail (statistics, timings) still to run
+    bool pending = false;
+    int total_ev = -1;
+    int sing_l = 0;   // l: the singular values of the device eigensolver are still on their way (read in finish_fit)
+    void reset() { pending = false; sing_l = 0; }
+  } held_tail;
   // fit_transform (unmasked f32 randomized fits): fit() returns in front of the host eigensolver of the l x l Gram and
   // transform() runs it once the projection sweep is queued (engine.cpp, finish_small_svd)
-  bool defer_small = false, small_pending = false;
-  int small_l = 0, small_ld = 0;
-  hipEvent_t ev_small = nullptr;
-  int sing_pending = 0;           // l: the singular values of the device eigensolver are still on their way (read in finish_fit)
+  struct HeldSmall {
+    bool defer = false, pending = false;
+    int l = 0, ld = 0;
+    hipEvent_t ev = nullptr;          // the Gram's copy to the host has landed
+    std::vector<int> in_transform;    // events of a held-back small SVD that ran inside the projection's span
+    void reset() { defer = pending = false; in_transform.clear(); }
+  } held_small;
   sapca::PinnedBuf lanczos_host;  // alpha | beta of the Lanczos tridiagonal, read back at each convergence check
   bool stats_pending = false;
   int64_t stats_cols = 0;
@@ -104,7 +112,7 @@ struct sapca_handle_s {
   sapca::DevBuf drop_col, drop_val;                                // the entries the compaction dropped, as (column, value) pairs
   sapca::DevBuf scratch, scratch2;
   sapca::DevBuf panel_x, panel_y, panel_w, panel_xs, panel_wide;   // (panel_wide: the out-of-place product of a panel wider than 128 columns)
-  sapca::DevBuf small;                                           // G, R1, R2, Rinv, M, cvec, svec, info
+  sapca::DevBuf small;                                           // (laid out by sapca::SmallLayout)
   sapca::DevBuf stats;                                           // sum, sumsq, cnt (f64, n each)
   sapca::DevBuf batch_in, batch_out;                             // per-batch statistics / top-n: codes or ns; results
   sapca::DevBuf mean_used_dev, o2m_dev, sel_rows_dev;
@@ -117,12 +125,47 @@ struct sapca_handle_s {
 
   sapca::EventTimer timer;
   std::vector<std::pair<int, int>> spans;  // (category, event index) of the last fit/transform
-  std::vector<int> small_in_transform;      // events of a held-back small SVD that ran inside the projection's span
   sapca_timings timings{};
   sapca::Comm comm;
 };
 
 namespace sapca {
+
+// The handle's small f64 buffer as a view bound to its base address: six ld x ld matrices (slot stride ld * ld), then -- at
+// offsets laid out for panels of W = max(ld, 128) columns -- an int, the centring vectors c | s of the sweeps (T, W entries
+// each) and W doubles of column sums a Gram pass gathers.  `behind`: doubles wanted behind the layout (Lanczos' Ritz matrix).
+// A function acquires the buffer ONCE, by constructing the view.  DevBuf::ensure frees and reallocates when asked for more
+// than it holds, so a slot's contents outlive the next acquisition only because that one asks for the same ld: info and c
+// across every normalize() of a randomized fit; the Gram across the host eigensolver and M from finish_small_svd() to the
+// rotation of the un-rotated projection (both acquire with held_small.ld, the fit's ld).
+struct SmallLayout {
+  size_t ld, W;
+  double* base;
+  SmallLayout(DevBuf& buf, int ld_, size_t behind = 0)
+      : ld((size_t)ld_), W((size_t)std::max(ld_, 128)), base(buf.as<double>(6 * W * W + 64 + 4 * W + behind)) {}
+  double* slot(size_t i) const { return base + i * ld * ld; }
+  double* gram() const { return slot(0); }
+  double* r_inv() const { return slot(1); }
+  double* r_scratch() const { return slot(2); }
+  double* r1() const { return slot(3); }
+  double* r2() const { return slot(4); }
+  double* m() const { return slot(5); }   // the small factor M (ld x ldk)
+  int* info() const { return reinterpret_cast<int*>(base + 6 * W * W); }
+  template <typename T> T* c() const { return reinterpret_cast<T*>(base + 6 * W * W + 64); }
+  template <typename T> T* s() const { return c<T>() + W; }
+  double* wsum() const { return base + 6 * W * W + 64 + 2 * W; }
+  double* behind() const { return base + 6 * W * W + 64 + 4 * W; }
+};
+
+// What a normalisation takes beyond its panel.
+template <typename T>
+struct NormalizeExtras {
+  double *R1 = nullptr, *R2 = nullptr;       // ld x ld f64 device: receive the upper factor of the first / second CholeskyQR pass
+  int passes = 0;                            // 0: what the normaliser implies (QR two, LU one)
+  const k::PanelSource<T>* src = nullptr;    // the panel is still as its producer left it: the first Gram applies the rest
+  const T* w = nullptr;                      // weights of vec_out (null: ones)
+  T* vec_out = nullptr;                      // receives sum_r w[r] Q[r][:] of the normalised panel
+};
 
 template <typename T>
 struct Engine {
@@ -138,10 +181,8 @@ struct Engine {
   static void fit_lanczos(H& h);
   static bool vote_rides(const H& h);          // the cut of the two-piece A^T sweep is agreed inside the statistics' all-reduce
   static int64_t piece_vote(H& h, int ld);     // this rank's vote: the first output row of its second piece, 0 = one piece
-  // normaliser on a rows x ld panel; R_out (ld x ld f64 device, may be null) receives the
-  // accumulated upper factor of the last CholeskyQR2.
-  static void normalize(H& h, T* P, int64_t rows, int l, int ld, int normalizer, bool sharded, double* R1, double* R2,
-                        int passes_hint = 0, const k::PanelSource<T>* src = nullptr, const T* w = nullptr, T* vec_out = nullptr);
+  // normaliser on a rows x ld panel
+  static void normalize(H& h, T* P, int64_t rows, int l, int ld, int normalizer, bool sharded, const NormalizeExtras<T>& x);
   static CsrView<T> view(const H::RawCsr& r) {
     CsrView<T> v;
     v.rows = r.rows; v.cols = r.cols; v.nnz = r.nnz;

@@ -635,8 +635,7 @@ void lanczos_fit(sapca_handle_s& h) {
     for (int64_t j = 0; j < steps; ++j) Sk[(size_t)j * k + i] = S[(size_t)j * steps + c];
   }
   const int ldk = (int)round_up(k, 16);
-  double* Sdev = h.small.as<double>((size_t)6 * 128 * 128 + 64 + 4 * 128 + (size_t)steps * k);
-  Sdev += (size_t)6 * 128 * 128 + 64 + 4 * 128;
+  double* Sdev = SmallLayout(h.small, 128, (size_t)steps * k).behind();
   SAPCA_HIP(hipMemcpyAsync(Sdev, Sk.data(), Sk.size() * sizeof(double), hipMemcpyHostToDevice, s));
   T* VtT = h.panel_w.as<T>((size_t)std::max<int64_t>(n_used, 1) * ldk);
   k::fill_zero(VtT, n_used * ldk, s);

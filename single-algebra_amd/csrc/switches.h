@@ -12,7 +12,7 @@
 //
 // The switches of the debug variant (name: effect), by file:
 //   engine.cpp   SAPCA_TILED_MIN_ENTRIES (floor of the staged sweep), SAPCA_AT_NATURAL, SAPCA_AT_UNPACK, SAPCA_AT_SORT,
-//                SAPCA_LANCZOS_TRANSPOSE, SAPCA_MASK_STATS_INLINE, SAPCA_SMALL_SVD_QR, SAPCA_Q3_ROWKERNEL
+//                SAPCA_LANCZOS_TRANSPOSE, SAPCA_MASK_STATS_INLINE, SAPCA_Q3_ROWKERNEL
 //   spmm_tiled.hip  SAPCA_DQ_BLOCK_ROWS, SAPCA_SPLIT_WGS, SAPCA_QF_CAP_FIXED, SAPCA_NO_ROWSORT, SAPCA_ROWSORT_ALWAYS, SAPCA_FILL_DIRECT,
 //                SAPCA_AT_BUCKETS, SAPCA_AT_SORT, SAPCA_RUNS_SEG_LDS_MAX, SAPCA_SWEEP_STAGED, SAPCA_NO_DQ, SAPCA_DEBUG
 //   spmm_dq.hip  SAPCA_NO_DQ, SAPCA_NO_DQ_F64      prep.hip  SAPCA_TRANSPOSE_GATHER
