@@ -56,7 +56,9 @@ extern "C" {
                                  4: *_csr_device_to_host_*, sapca_comm_abort / _async_error / _has_side_lane,
                                     sapca_multi_upload_csr_* and the sapca_multi_*_resident calls
                                  additive, ABI 4: sapca_batch_stats_csr_device_*, sapca_sum_row_n_top_csr_device_*,
-                                                  sapca_masked_stats_csr_device_*                                  */
+                                                  sapca_masked_stats_csr_device_*
+                                 additive, ABI 4: sapca_options.reserved0 became lanczos_center (same size and offsets;
+                                                  0, the value every caller passed, is the behaviour of before)        */
 
 typedef struct sapca_handle_s* sapca_handle;
 
@@ -80,7 +82,8 @@ typedef enum sapca_method { SAPCA_LANCZOS = 0, SAPCA_RANDOM = 1 } sapca_method;
 /* PowerIterationNormalizer (re-export)          src/dimred/pca/mod.rs:41                      */
 typedef enum sapca_normalizer { SAPCA_NORM_QR = 0, SAPCA_NORM_LU = 1, SAPCA_NORM_NONE = 2 } sapca_normalizer;
 /* transform semantics: REFERENCE reproduces quirks Q2/Q3; CENTERED is the
- * mathematically centred projection (A - 1 mu^T) V^T, offered as an opt-in superset.          */
+ * mathematically centred projection (A - 1 mu^T) V^T, offered as an opt-in superset; its counterpart on the fit side
+ * is sapca_options.lanczos_center (the Lanczos SVD of the centred operator).  Both together: the textbook PCA.      */
 typedef enum sapca_transform_semantics { SAPCA_TRANSFORM_REFERENCE = 0, SAPCA_TRANSFORM_CENTERED = 1 } sapca_transform_semantics;
 
 /* Builder fields.  SparsePCABuilder sparse/mod.rs:375-484 (defaults :392-401);
@@ -95,7 +98,10 @@ typedef struct sapca_options {
   uint8_t center;                /* .center(bool), default 1                                    */
   uint8_t verbose;               /* .verbose(bool), default 0                                   */
   uint8_t collect_timings;       /* record per-stage HIP-event timings (sapca_get_timings)      */
-  uint8_t reserved0;
+  uint8_t lanczos_center;        /* opt-in, default 0: with center = 1 and SAPCA_LANCZOS the SVD runs on the centred
+                                    operator A - 1 mu^T (a real PCA) instead of the raw matrix (the reference's quirk Q1);
+                                    mean_, the total variance and transform are what they are without it.  No effect
+                                    with center = 0 or SAPCA_RANDOM (which centres anyway)                            */
   int32_t method;                /* sapca_method, default SAPCA_LANCZOS                         */
   uint64_t n_oversamples;        /* SVDMethod::Random.n_oversamples (n_components + this: at most 1024; above 128 block-wise, untuned) */
   uint64_t n_power_iterations;   /* SVDMethod::Random.n_power_iterations                        */

@@ -743,6 +743,7 @@ void sapca_options_default(sapca_options* o) {
   o->tolerance = 1e-6;        // :396
   o->center = 1;              // :398
   o->verbose = 0;             // :399
+  o->lanczos_center = 0;      // (no reference counterpart: the reference's Lanczos fit runs on the raw matrix, quirk Q1)
   o->method = SAPCA_LANCZOS;  // pca/mod.rs:64-68
   o->n_oversamples = 10;
   o->n_power_iterations = 4;

@@ -188,8 +188,10 @@ H::RawCsr compact_a(H& h, const CsrView<T>& A, const int32_t* d_o2m, int64_t n_u
 //  MainCopy            | one rank; unmasked, or statistics Upload   | async copy on the main stream, read at the end of fit() (or SAPCA_MASK_STATS_INLINE)
 //  SideChain           | one rank, statistics KeptAndDropped        | a chain on stream3 queued at the end of prepare(); a Lanczos fit queues the dropped
 //                      |                                            | pairs' sort at once and only the rest of the chain at the end
-//  ScatterSide         | one rank, statistics Scatter               | colstats_scatter and the host copy on stream3, queued at once: a Lanczos fit does not
-//                      |                                            | centre, nothing reads them before fit() ends
+//  ScatterSide         | one rank, statistics Scatter               | colstats_scatter and the host copy on stream3, queued at once: an uncentred Lanczos
+//                      |                                            | fit reads them when fit() ends.  A centred one (sapca_options.lanczos_center) needs the
+//                      |                                            | means before its first step: fit() makes the main stream wait for ev_stats in front of
+//                      |                                            | the iterations and gives the overlap up
 enum class AtFrom { Nothing, FormatFromA, FormatFromCompacted, CompactedTransposed, Transposed };
 enum class StatsFrom { Upload, Scatter, FormatBuild, KeptAndDropped, Transposed };
 enum class StatsTo { AllReduce, MainCopy, SideChain, ScatterSide };
@@ -1079,12 +1081,12 @@ void Engine<T>::finish_small_svd(H& h, const double** sign_out) {
 }
 
 // ------------------------------------------------------------------------------------------
-// R12: Lanczos on the raw operator (no centring: quirk Q1).
+// R12: Lanczos on the raw operator (no centring: quirk Q1); centred: on A - 1 mu^T, mu in h.lz_mu (opt-in, lanczos.hip).
 // ------------------------------------------------------------------------------------------
 template <typename T>
-void Engine<T>::fit_lanczos(H& h) {
+void Engine<T>::fit_lanczos(H& h, bool centred) {
   Scope sc(h, C_LANCZOS);
-  lanczos_fit<T>(h);
+  lanczos_fit<T>(h, centred);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1129,12 +1131,21 @@ void Engine<T>::fit(H& h, const CsrView<T>& A, bool defer_finish) {
     device_means();
     fit_randomized(h);
   } else {
-    // the Lanczos branch never centres (Q1): only transform reads the means.  On the scatter route the column sums arrive
-    // from the third stream, beside the iterations: the main stream meets them here, behind the last step
+    // the Lanczos branch does not centre (Q1) unless asked to: only transform reads the means.  On the scatter route the
+    // column sums arrive from the third stream, beside the iterations: the main stream meets them here, behind the last step
+    // -- or, for a centred fit (lanczos_center, opt-in), in front of the first one: its operator is A - 1 mu^T.  That mu is
+    // f64 straight from the f64 column sums (all n-sized Lanczos data is f64; the T-rounded means of the sweeps would leave
+    // an operator that is not symmetric to working precision where the mean term dwarfs sigma_k)
+    const bool centred = h.opt.lanczos_center != 0 && h.opt.center != 0;
     const bool sums_on_side = h.lz_scatter && h.stats_on_side;
-    if (!sums_on_side) device_means();
-    fit_lanczos(h);
-    if (sums_on_side) {
+    const bool means_first = !sums_on_side || centred;
+    if (sums_on_side && centred) SAPCA_HIP(hipStreamWaitEvent(s, h.ev_stats, 0));
+    if (means_first) device_means();
+    if (centred)
+      k::mean_from_sums(h.stats.ptr<double>(), (double)h.m_global, h.has_mask_maps ? h.sel_rows_dev.ptr<int32_t>() : nullptr, n_used,
+                        h.lz_mu.as<double>((size_t)n_used), s);
+    fit_lanczos(h, centred);
+    if (!means_first) {
       SAPCA_HIP(hipStreamWaitEvent(s, h.ev_stats, 0));
       device_means();
     }

@@ -118,6 +118,7 @@ struct sapca_handle_s {
   sapca::DevBuf mean_used_dev, o2m_dev, sel_rows_dev;
   sapca::DevBuf components_dev;                                  // k x n_used, T
   sapca::DevBuf lanczos_buf;
+  sapca::DevBuf lz_mu;                                           // f64 column means of the operator's columns (centred Lanczos fits)
   sapca::DevBuf idx16_a, idx16_b;                                 // 2-byte index copies of the two operators of a Lanczos step
   sapca::TiledBuffers tb_a, tb_at;                               // tile-major formats for the LDS-staged sweep
   sapca::TiledOp tiled_a, tiled_at;
@@ -178,7 +179,7 @@ struct Engine {
   static void finish_fit(H& h);          // host-side tail of fit(): statistics, timings (after the last wait for the device)
   static void transform(H& h, const CsrView<T>& A, T* d_out);
   static void fit_randomized(H& h);
-  static void fit_lanczos(H& h);
+  static void fit_lanczos(H& h, bool centred);
   static bool vote_rides(const H& h);          // the cut of the two-piece A^T sweep is agreed inside the statistics' all-reduce
   static int64_t piece_vote(H& h, int ld);     // this rank's vote: the first output row of its second piece, 0 = one piece
   // normaliser on a rows x ld panel

@@ -1,4 +1,4 @@
-// R12: Lanczos SVD of the prepared operator (raw values, NO centring: quirk Q1) --
+// R12: Lanczos SVD of the prepared operator (raw values, NO centring: quirk Q1; opt-in: the centred operator, below) --
 // single_svdlib::lanczos::svd_las2 call sites
 //   /root/reference/src/dimred/pca/sparse/mod.rs:134-144          (iterations = max(m, n))
 //   /root/reference/src/dimred/pca/sparse_masked/mod.rs:316-331   (iterations = max(2 max(m, n'), 100))
@@ -13,10 +13,24 @@
 // to working precision and needs no eta/oldeta bookkeeping.  All n-sized data stays on the GPU
 // in f64; at a convergence check (every step while T is small, see check_due) the host downloads
 // alpha/beta (2j doubles) and runs QL on the j x j tridiagonal with the bottom eigenvector row only.
+//
+// sapca_options.lanczos_center (opt-in, no reference counterpart): the same iteration on A_c = A - 1 mu^T, mu the f64 column
+// means over the global row count.  Nothing n- or m-sized is added to a step:
+//   tall side (A_c^T A_c):  y = A v - (mu^T v) 1,  out = A^T y.   1^T y = 1^T A v - m mu^T v = 0 (1^T A = m mu^T), so
+//                           A_c^T y = A^T y - mu (1^T y) = A^T y: the second product needs no correction, on the scatter
+//                           route, the transposed-operator route and with rows sharded alike (mu and v are replicated, the
+//                           shift is the same number on every rank, the all-reduce is the one of today)
+//   wide side (A_c A_c^T):  t = A^T v - mu (1^T v),  out = A t - (mu^T t) 1  with  mu^T t = g^T v,  g = A_c mu (once per fit)
+// The scalars (mu^T v; 1^T v and g^T v) come out of the kernels that produce v: the pass that leaves w (norm2_kernel for the
+// start vector, gemv_n_sub_norm_kernel in a step) adds per-block partial sums of d . w beside those of ||w||^2, and
+// scale_kernel, which reduces the latter in a fixed order to beta, reduces the former the same way and writes (d . w) / beta
+// next to it.  Every SpMV variant takes such a scalar by device pointer and subtracts it (times an optional per-row factor)
+// where it writes y; a null pointer is the uncentred code.
 #include <algorithm>
 #include <cmath>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "lanczos.h"
 #include "small_svd.h"
@@ -31,10 +45,12 @@ constexpr int WAVE = 64;
 template <typename T>
 __global__ void __launch_bounds__(256)
 spmv_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx, const T* __restrict__ val, int64_t rows,
-            const double* __restrict__ x, double* __restrict__ y) {
+            const double* __restrict__ x, double* __restrict__ y, const double* __restrict__ shift,
+            const double* __restrict__ rowscale) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
   const int64_t nwaves = (int64_t)gridDim.x * blockDim.x / WAVE;
+  const double sh = shift ? *shift : 0.0;   // y[r] -= sh * rowscale[r]  (null rowscale: ones; null shift: nothing)
   for (int64_t r = wave; r < rows; r += nwaves) {
     const int64_t e0 = ptr[r], e1 = ptr[r + 1];
     // four independent (value, index, gather) chains per lane: the loop is bound by memory latency, not bytes
@@ -54,6 +70,7 @@ spmv_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx, co
     a0 = (a0 + a1) + (a2 + a3);
 #pragma unroll
     for (int off = WAVE / 2; off > 0; off >>= 1) a0 += __shfl_xor(a0, off);
+    if (shift) a0 -= sh * (rowscale ? rowscale[r] : 1.0);
     if (lane == 0) y[r] = a0;
   }
 }
@@ -65,8 +82,10 @@ spmv_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx, co
 template <typename T, typename I>
 __global__ void __launch_bounds__(1024)
 spmv_ldsx_kernel(const int64_t* __restrict__ ptr, const I* __restrict__ idx, const T* __restrict__ val, int64_t rows,
-                 int64_t cols, const double* __restrict__ x, double* __restrict__ y, unsigned long long* __restrict__ ymax_bits) {
+                 int64_t cols, const double* __restrict__ x, double* __restrict__ y, unsigned long long* __restrict__ ymax_bits,
+                 const double* __restrict__ shift, const double* __restrict__ rowscale) {
   extern __shared__ double xs[];
+  const double sh = shift ? *shift : 0.0;
   bool ybad = false;
   double ymax = 0.0;   // (lane 0 of every wave: the largest |y| it wrote, for the fixed-point scale of the scatter product that follows)
   for (int64_t i = threadIdx.x; i < cols; i += blockDim.x) xs[i] = x[i];
@@ -92,6 +111,7 @@ spmv_ldsx_kernel(const int64_t* __restrict__ ptr, const I* __restrict__ idx, con
     a0 = (a0 + a1) + (a2 + a3);
 #pragma unroll
     for (int off = WAVE / 2; off > 0; off >>= 1) a0 += __shfl_xor(a0, off);
+    if (shift) a0 -= sh * (rowscale ? rowscale[r] : 1.0);   // (before max |y|: the fixed-point scale follows the centred values)
     if (lane == 0) y[r] = a0;
     ybad |= !(fabs(a0) <= 1.7976931348623157e308);   // (a non-finite y must reach the fixed-point scale: fmax would drop a nan)
     ymax = fmax(ymax, fabs(a0));
@@ -108,9 +128,11 @@ constexpr int SLICE_WAVES = 16, SLICE_MAX_RPW = 8;
 template <typename T>
 __global__ void __launch_bounds__(SLICE_WAVES * WAVE)
 spmv_sliced_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx, const T* __restrict__ val, int64_t rows,
-                   int64_t cols, int slice, int nslices, int rpw, const double* __restrict__ x, double* __restrict__ y) {
+                   int64_t cols, int slice, int nslices, int rpw, const double* __restrict__ x, double* __restrict__ y,
+                   const double* __restrict__ shift, const double* __restrict__ rowscale) {
   extern __shared__ double xs[];
   const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+  const double sh = shift ? *shift : 0.0;
   const int64_t r0 = ((int64_t)blockIdx.x * SLICE_WAVES + wave) * rpw;
   // lane (j, t): first entry of row r0 + j whose column is >= t * slice   (t = 0..nslices; rpw * (nslices+1) <= 64)
   int64_t bnd = 0;
@@ -160,7 +182,7 @@ spmv_sliced_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ 
     double a = acc[j];
 #pragma unroll
     for (int off = WAVE / 2; off > 0; off >>= 1) a += __shfl_xor(a, off);
-    if (lane == 0 && j < rpw && r0 + j < rows) y[r0 + j] = a;
+    if (lane == 0 && j < rpw && r0 + j < rows) y[r0 + j] = shift ? a - sh * (rowscale ? rowscale[r0 + j] : 1.0) : a;
   }
 }
 
@@ -233,11 +255,13 @@ spmv_slice_grid_kernel(const int64_t* __restrict__ ptr, const int32_t* __restric
   }
 }
 
-__global__ void slice_sum_kernel(const double* __restrict__ part, int64_t rows, int nslices, double* __restrict__ y) {
+__global__ void slice_sum_kernel(const double* __restrict__ part, int64_t rows, int nslices, double* __restrict__ y,
+                                 const double* __restrict__ shift, const double* __restrict__ rowscale) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= rows) return;
   double s = 0;
   for (int t = 0; t < nslices; ++t) s += part[(int64_t)t * rows + r];
+  if (shift) s -= *shift * (rowscale ? rowscale[r] : 1.0);
   y[r] = s;
 }
 
@@ -283,48 +307,73 @@ gemv_n_sub_kernel(const double* __restrict__ V, int64_t len, int nvec, const dou
   w[r] -= s;
 }
 
+// The partial sums a pass over w leaves for scale_kernel: partial[b] = this block's share of ||w||^2 and, for a centred fit,
+// partial[(1 + i) * kPartStride + b] = its share of d_i . w, i < NDOTS (d0 null: ones).  NDOTS = 0 is the uncentred code.
+constexpr int kPartStride = 1024;   // (at most 1024 blocks write partial sums)
+template <int NDOTS>
+__device__ inline void block_partials(double acc, double q0, double q1, double* __restrict__ partial) {
+  __shared__ double red[3][4];
+#pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    acc += __shfl_xor(acc, off);
+    if constexpr (NDOTS >= 1) q0 += __shfl_xor(q0, off);
+    if constexpr (NDOTS >= 2) q1 += __shfl_xor(q1, off);
+  }
+  if ((threadIdx.x & (WAVE - 1)) == 0) {
+    red[0][threadIdx.x / WAVE] = acc;
+    if constexpr (NDOTS >= 1) red[1][threadIdx.x / WAVE] = q0;
+    if constexpr (NDOTS >= 2) red[2][threadIdx.x / WAVE] = q1;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+    if constexpr (NDOTS >= 1) partial[kPartStride + blockIdx.x] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    if constexpr (NDOTS >= 2) partial[2 * kPartStride + blockIdx.x] = red[2][0] + red[2][1] + red[2][2] + red[2][3];
+  }
+}
+
 // The second Gram-Schmidt pass fused with what follows it: w -= V^T h2, the partial sums of ||w||^2 of this block's
 // elements (for scale_kernel), and alpha[j] = h1[j] + h2[j] (the diagonal of T is the projection on v_j itself).
+template <int NDOTS>
 __global__ void __launch_bounds__(256)
 gemv_n_sub_norm_kernel(const double* __restrict__ V, int64_t len, int nvec, const double* __restrict__ h1,
                        const double* __restrict__ h2, double* __restrict__ w, double* __restrict__ partial, int j,
-                       double* __restrict__ alpha) {
-  __shared__ double red[4];
-  double acc = 0;
+                       double* __restrict__ alpha, const double* __restrict__ d0, const double* __restrict__ d1) {
+  double acc = 0, q0 = 0, q1 = 0;
   for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < len; r += (int64_t)gridDim.x * blockDim.x) {
     double s = 0;
     for (int i = 0; i < nvec; ++i) s = fma(h2[i], V[(int64_t)i * len + r], s);
     const double x = w[r] - s;
     w[r] = x;
     acc = fma(x, x, acc);
+    if constexpr (NDOTS >= 1) q0 = d0 ? fma(d0[r], x, q0) : q0 + x;
+    if constexpr (NDOTS >= 2) q1 = fma(d1[r], x, q1);
   }
-#pragma unroll
-  for (int off = WAVE / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-  if ((threadIdx.x & (WAVE - 1)) == 0) red[threadIdx.x / WAVE] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-    if (blockIdx.x == 0) alpha[j] = h1[j] + h2[j];
-  }
+  block_partials<NDOTS>(acc, q0, q1, partial);
+  if (threadIdx.x == 0 && blockIdx.x == 0) alpha[j] = h1[j] + h2[j];
 }
 
 // beta = ||w||; out[j] = beta; vnext = w / beta  (single block computes the norm, then all scale)
+template <int NDOTS>
 __global__ void __launch_bounds__(256)
-norm2_kernel(const double* __restrict__ w, int64_t len, double* __restrict__ partial) {
-  __shared__ double red[4];
-  double s = 0;
-  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < len; r += (int64_t)gridDim.x * blockDim.x)
-    s = fma(w[r], w[r], s);
-#pragma unroll
-  for (int off = WAVE / 2; off > 0; off >>= 1) s += __shfl_xor(s, off);
-  if ((threadIdx.x & (WAVE - 1)) == 0) red[threadIdx.x / WAVE] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+norm2_kernel(const double* __restrict__ w, int64_t len, double* __restrict__ partial, const double* __restrict__ d0,
+             const double* __restrict__ d1) {
+  double s = 0, q0 = 0, q1 = 0;
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < len; r += (int64_t)gridDim.x * blockDim.x) {
+    const double x = w[r];
+    s = fma(x, x, s);
+    if constexpr (NDOTS >= 1) q0 = d0 ? fma(d0[r], x, q0) : q0 + x;
+    if constexpr (NDOTS >= 2) q1 = fma(d1[r], x, q1);
+  }
+  block_partials<NDOTS>(s, q0, q1, partial);
 }
 
+// dots_out[i] = d_i . vnext = (d_i . w) / beta from the same kind of partial sums: the centring scalars of the step that
+// multiplies vnext, written by the kernel that writes vnext (no pass of their own, no launch of their own)
+template <int NDOTS>
 __global__ void __launch_bounds__(256)
 scale_kernel(const double* __restrict__ w, int64_t len, const double* __restrict__ partial, int nparts,
-             double* __restrict__ beta_out, double* __restrict__ vnext) {
+             double* __restrict__ beta_out, double* __restrict__ vnext, double* __restrict__ dots_out) {
   // the partial sums of ||w||^2 (norm2_kernel or the fused second Gram-Schmidt pass), reduced in a fixed order by every wave
   const int lane = threadIdx.x & (WAVE - 1);
   double s = 0;
@@ -334,8 +383,33 @@ scale_kernel(const double* __restrict__ w, int64_t len, const double* __restrict
   const double beta = sqrt(s);
   if (blockIdx.x == 0 && threadIdx.x == 0) *beta_out = beta;
   const double inv = beta > 0 ? 1.0 / beta : 0.0;
+  if constexpr (NDOTS >= 1) {
+    if (blockIdx.x == 0 && threadIdx.x < WAVE) {   // (one wave, the same fixed order)
+#pragma unroll
+      for (int d = 0; d < NDOTS; ++d) {
+        double q = 0;
+        for (int i = lane; i < nparts; i += WAVE) q += partial[(1 + d) * kPartStride + i];
+#pragma unroll
+        for (int off = WAVE / 2; off > 0; off >>= 1) q += __shfl_xor(q, off);
+        if (lane == 0) dots_out[d] = q * inv;
+      }
+    }
+  }
   for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < len; r += (int64_t)gridDim.x * blockDim.x)
     vnext[r] = w[r] * inv;
+}
+
+// out[0] = sum_r a[r] b[r]  (b null: ones), one block, fixed order: the few scalars a centred fit needs once (||mu||^2, 1^T u_i)
+__global__ void __launch_bounds__(256)
+dot_kernel(const double* __restrict__ a, const double* __restrict__ b, int64_t len, double* __restrict__ out) {
+  __shared__ double red[4];
+  double s = 0;
+  for (int64_t r = threadIdx.x; r < len; r += blockDim.x) s = b ? fma(a[r], b[r], s) : s + a[r];
+#pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  if ((threadIdx.x & (WAVE - 1)) == 0) red[threadIdx.x / WAVE] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) out[0] = red[0] + red[1] + red[2] + red[3];
 }
 
 // out[r][i] = sum_j V[j][r] S[j][i]   (Ritz vectors; out row-major len x ldo as T)
@@ -419,7 +493,9 @@ const uint16_t* spmv_narrow_indices(const CsrView<T>& A, bool has_scratch, DevBu
 
 template <typename T>
 void spmv_launch(const CsrView<T>& A, const double* x, double* y, hipStream_t s, DevBuf* scratch = nullptr,
-                 const uint16_t* idx16 = nullptr, unsigned long long* ymax_bits = nullptr, bool* ymax_done = nullptr) {
+                 const uint16_t* idx16 = nullptr, unsigned long long* ymax_bits = nullptr, bool* ymax_done = nullptr,
+                 const double* shift = nullptr, const double* rowscale = nullptr) {
+  // shift (device scalar, null: none): y[r] -= *shift * rowscale[r] (null rowscale: ones) where the product writes y
   if (ymax_done) *ymax_done = false;   // (only the kernel with x in LDS gathers max |y| on the way)
   if (A.rows == 0) return;
   const size_t xbytes = (size_t)A.cols * sizeof(double);
@@ -428,10 +504,10 @@ void spmv_launch(const CsrView<T>& A, const double* x, double* y, hipStream_t s,
     static LdsAttrState attr, attr16;   // one per instantiation of this function template
     if (idx16) {
       ensure_dynamic_lds(reinterpret_cast<const void*>(&spmv_ldsx_kernel<T, uint16_t>), 150 * 1024, attr16);
-      hipLaunchKernelGGL((spmv_ldsx_kernel<T, uint16_t>), dim3(256), dim3(1024), xbytes, s, A.ptr, idx16, A.val, A.rows, A.cols, x, y, ymax_bits);
+      hipLaunchKernelGGL((spmv_ldsx_kernel<T, uint16_t>), dim3(256), dim3(1024), xbytes, s, A.ptr, idx16, A.val, A.rows, A.cols, x, y, ymax_bits, shift, rowscale);
     } else {
       ensure_dynamic_lds(reinterpret_cast<const void*>(&spmv_ldsx_kernel<T, int32_t>), 150 * 1024, attr);
-      hipLaunchKernelGGL((spmv_ldsx_kernel<T, int32_t>), dim3(256), dim3(1024), xbytes, s, A.ptr, A.idx, A.val, A.rows, A.cols, x, y, ymax_bits);
+      hipLaunchKernelGGL((spmv_ldsx_kernel<T, int32_t>), dim3(256), dim3(1024), xbytes, s, A.ptr, A.idx, A.val, A.rows, A.cols, x, y, ymax_bits, shift, rowscale);
     }
     if (ymax_done) *ymax_done = ymax_bits != nullptr;
     return;
@@ -459,7 +535,7 @@ void spmv_launch(const CsrView<T>& A, const double* x, double* y, hipStream_t s,
                            (size_t)slice * sizeof(double), s, A.ptr, A.idx, (const uint16_t*)nullptr, A.val, A.rows, A.cols, slice,
                            nslices, rows_per_group, x, part);
       }
-      hipLaunchKernelGGL(slice_sum_kernel, dim3(grid1(A.rows)), dim3(256), 0, s, part, A.rows, nslices, y);
+      hipLaunchKernelGGL(slice_sum_kernel, dim3(grid1(A.rows)), dim3(256), 0, s, part, A.rows, nslices, y, shift, rowscale);
       return;
     }
     // one round of workgroups (256 CUs x 16 waves) when the wave's run-limit table fits its 64 lanes
@@ -471,12 +547,12 @@ void spmv_launch(const CsrView<T>& A, const double* x, double* y, hipStream_t s,
       const int rows_per_block = SLICE_WAVES * rpw;
       hipLaunchKernelGGL((spmv_sliced_kernel<T>), dim3((unsigned)((A.rows + rows_per_block - 1) / rows_per_block)),
                          dim3(SLICE_WAVES * WAVE), (size_t)slice * sizeof(double), s, A.ptr, A.idx, A.val, A.rows, A.cols, slice,
-                         nslices, rpw, x, y);
+                         nslices, rpw, x, y, shift, rowscale);
       return;
     }
   }
   hipLaunchKernelGGL((spmv_kernel<T>), dim3(grid1(A.rows * WAVE, 256, 8192)), dim3(256), 0, s, A.ptr, A.idx, A.val,
-                     A.rows, x, y);
+                     A.rows, x, y, shift, rowscale);
 }
 
 }  // namespace
@@ -492,7 +568,7 @@ template void spmv<double>(const CsrView<double>&, const double*, double*, hipSt
 }  // namespace k
 
 template <typename T>
-void lanczos_fit(sapca_handle_s& h) {
+void lanczos_fit(sapca_handle_s& h, bool centred) {
   hipStream_t s = h.stream;
   const CsrView<T> A = Engine<T>::view(h.a_used), At = Engine<T>::view(h.at_used);
   const int64_t m = A.rows, n_used = A.cols;
@@ -514,8 +590,10 @@ void lanczos_fit(sapca_handle_s& h) {
   const double kappa = 10e-6;  // sparse/mod.rs:141
 
   // device workspace: basis V [(jmax+1) x len], w [len], tmp [other], h1/h2 [jmax+1], alpha/beta [jmax+1], partials
+  // (||w||^2, then two centring dots), four scalars, g [m] (centred fits on the wide side)
   const size_t nV = (size_t)(jmax + 1) * len;
-  double* base = h.lanczos_buf.as<double>(nV + len + other + 4 * (size_t)(jmax + 2) + 1024);
+  double* base = h.lanczos_buf.as<double>(nV + len + other + 4 * (size_t)(jmax + 2) + 3 * kPartStride + 4 +
+                                          (centred && !right_side ? (size_t)m : 0));
   double* V = base;
   double* w = V + nV;
   double* tmp = w + len;
@@ -524,12 +602,33 @@ void lanczos_fit(sapca_handle_s& h) {
   double* alpha = h2 + (jmax + 2);
   double* beta = alpha + (jmax + 2);
   double* partial = beta + (jmax + 2);
+  double* dots = partial + 3 * kPartStride;   // the centring scalars of the step ahead (scale_kernel); dots[2]: once-per-fit scalars
+  double* g = dots + 4;
   const int nparts = 256;
+  // centred fits (header comment): the f64 column means of the operator's columns, and what the kernels that produce a
+  // basis vector v dot it with -- tall: mu (the shift mu^T v); wide: ones and g = A_c mu (the shifts 1^T v and mu^T t)
+  const double* mu = centred ? h.lz_mu.ptr<double>() : nullptr;
+  const double *d0 = nullptr, *d1 = nullptr;
+  if (centred && right_side) d0 = mu;
+  if (centred && !right_side) {
+    hipLaunchKernelGGL(dot_kernel, dim3(1), dim3(256), 0, s, mu, mu, n_used, dots + 2);
+    spmv_launch(A, mu, g, s, nullptr, nullptr, nullptr, nullptr, dots + 2);   // g = A mu - ||mu||^2 1
+    d1 = g;
+  }
 
   // start vector from the seed (las2 takes random_seed: u32), normalised
   k::gaussian_panel(w, len, 1, 1, h.opt.random_seed, s);
-  hipLaunchKernelGGL(norm2_kernel, dim3(nparts), dim3(256), 0, s, w, len, partial);
-  hipLaunchKernelGGL(scale_kernel, dim3(grid1(len, 256, 1024)), dim3(256), 0, s, w, len, partial, nparts, beta + jmax + 1, V);
+  // (the kernels that leave and normalise w are compiled per number of centring dots: 0 is the uncentred code)
+  auto with_ndots = [&](auto&& launch) {
+    if (!centred) launch(std::integral_constant<int, 0>{});
+    else if (right_side) launch(std::integral_constant<int, 1>{});
+    else launch(std::integral_constant<int, 2>{});
+  };
+  with_ndots([&](auto nd) {
+    constexpr int ND = decltype(nd)::value;
+    hipLaunchKernelGGL(norm2_kernel<ND>, dim3(nparts), dim3(256), 0, s, w, len, partial, d0, d1);
+    hipLaunchKernelGGL(scale_kernel<ND>, dim3(grid1(len, 256, 1024)), dim3(256), 0, s, w, len, partial, nparts, beta + jmax + 1, V, dots);
+  });
 
   // No transposed operator (prepare() took the scatter route: the transposed side fits LDS): the second product of a step
   // scatters A's rows into per-workgroup fixed-point copies of the output (scatter.hip) -- same bytes read as a gather
@@ -543,22 +642,23 @@ void lanczos_fit(sapca_handle_s& h) {
   // 2-byte index copies for the two products of a step (one pass over the indices each, paid back in a few steps)
   const uint16_t* first16 = spmv_narrow_indices(right_side ? A : At, false, h.idx16_a, s);
   const uint16_t* second16 = scatter ? nullptr : spmv_narrow_indices(right_side ? At : A, true, h.idx16_b, s);
-  auto apply_B = [&](const double* v, double* out) {  // out = A^T A v  (or A A^T v)
+  const double* shift = centred ? dots : nullptr;   // (of the v a step multiplies: written by the scale_kernel that wrote v)
+  auto apply_B = [&](const double* v, double* out) {  // out = A^T A v  (or A A^T v); centred: A_c for A
     if (scatter) {
       unsigned long long* ymax = sc + 1 + (product & 1), *next = sc + 1 + ((product + 1) & 1);
       ++product;
       bool have_max = false;
-      spmv_launch(A, v, tmp, s, nullptr, first16, ymax, &have_max);
+      spmv_launch(A, v, tmp, s, nullptr, first16, ymax, &have_max, shift);
       if (!have_max) k::vecmax(tmp, other, ymax, s);
       k::spmvt_scatter(A, first16, tmp, sc, ymax, next, out, h.scratch2, s);   // (the same 2-byte indices: one copy serves both products)
       if (h.comm.active()) h.comm.allreduce(out, (uint64_t)len, 1, s);
     } else if (right_side) {
-      spmv_launch(A, v, tmp, s, nullptr, first16);
-      spmv_launch(At, tmp, out, s, &h.scratch2, second16);
+      spmv_launch(A, v, tmp, s, nullptr, first16, nullptr, nullptr, shift);
+      spmv_launch(At, tmp, out, s, &h.scratch2, second16);   // (centred: A^T y is A_c^T y, 1^T y = 0)
       if (h.comm.active()) h.comm.allreduce(out, (uint64_t)len, 1, s);
     } else {
-      spmv_launch(At, v, tmp, s, nullptr, first16);
-      spmv_launch(A, tmp, out, s, &h.scratch2, second16);
+      spmv_launch(At, v, tmp, s, nullptr, first16, nullptr, nullptr, shift, mu);                            // t = A^T v - mu (1^T v)
+      spmv_launch(A, tmp, out, s, &h.scratch2, second16, nullptr, nullptr, centred ? dots + 1 : nullptr);   // A t - (g^T v) 1
     }
   };
 
@@ -584,9 +684,12 @@ void lanczos_fit(sapca_handle_s& h) {
     hipLaunchKernelGGL(gemv_n_sub_kernel, dim3(grid1(len)), dim3(256), 0, s, V, len, nvec, h1, w);
     hipLaunchKernelGGL(gemv_t_kernel, dim3(nvec), dim3(GEMV_T_THREADS), 0, s, V, len, nvec, w, h2, 0);
     const int nb2 = (int)std::min<int64_t>((len + 255) / 256, 1024);   // (one partial sum of ||w||^2 per block: at most the 1024 slots)
-    hipLaunchKernelGGL(gemv_n_sub_norm_kernel, dim3(nb2), dim3(256), 0, s, V, len, nvec, h1, h2, w, partial, (int)j, alpha);
-    hipLaunchKernelGGL(scale_kernel, dim3(grid1(len, 256, 1024)), dim3(256), 0, s, w, len, partial, nb2, beta + j,
-                       V + (size_t)(j + 1) * len);
+    double* vnext = V + (size_t)(j + 1) * len;
+    with_ndots([&](auto nd) {
+      constexpr int ND = decltype(nd)::value;
+      hipLaunchKernelGGL(gemv_n_sub_norm_kernel<ND>, dim3(nb2), dim3(256), 0, s, V, len, nvec, h1, h2, w, partial, (int)j, alpha, d0, d1);
+      hipLaunchKernelGGL(scale_kernel<ND>, dim3(grid1(len, 256, 1024)), dim3(256), 0, s, w, len, partial, nb2, beta + j, vnext, dots);
+    });
     steps = j + 1;
     const bool last = steps == jmax;
     if (steps >= k && (check_due(steps) || last)) {
@@ -642,12 +745,13 @@ void lanczos_fit(sapca_handle_s& h) {
   if (right_side) {
     hipLaunchKernelGGL((combine_kernel<T>), dim3(grid1(len), k), dim3(256), 0, s, V, len, (int)steps, Sdev, k, ldk, VtT);
   } else {
-    // left vectors U from the Krylov basis, then v_i = A^T u_i / sigma_i
+    // left vectors U from the Krylov basis, then v_i = A^T u_i / sigma_i  (centred: (A^T u_i - mu (1^T u_i)) / sigma_i)
     T* Ut = h.panel_y.as<T>((size_t)std::max<int64_t>(m, 1) * ldk);
     hipLaunchKernelGGL((combine_kernel<T>), dim3(grid1(len), k), dim3(256), 0, s, V, len, (int)steps, Sdev, k, ldk, Ut);
     for (int i = 0; i < k; ++i) {
       hipLaunchKernelGGL((load_column_kernel<T>), dim3(grid1(m)), dim3(256), 0, s, Ut, m, i, ldk, w);
-      spmv_launch(At, w, tmp, s);
+      if (centred) hipLaunchKernelGGL(dot_kernel, dim3(1), dim3(256), 0, s, w, (const double*)nullptr, m, dots + 2);
+      spmv_launch(At, w, tmp, s, nullptr, nullptr, nullptr, nullptr, centred ? dots + 2 : nullptr, mu);
       hipLaunchKernelGGL(column_scale_f64_kernel, dim3(grid1(n_used)), dim3(256), 0, s, tmp, n_used,
                          h.sing[i] > 0 ? 1.0 / h.sing[i] : 0.0);
       hipLaunchKernelGGL((store_column_kernel<T>), dim3(grid1(n_used)), dim3(256), 0, s, tmp, n_used, i, ldk, VtT);
@@ -659,7 +763,7 @@ void lanczos_fit(sapca_handle_s& h) {
   SAPCA_HIP(hipStreamSynchronize(s));
 }
 
-template void lanczos_fit<float>(sapca_handle_s&);
-template void lanczos_fit<double>(sapca_handle_s&);
+template void lanczos_fit<float>(sapca_handle_s&, bool);
+template void lanczos_fit<double>(sapca_handle_s&, bool);
 
 }  // namespace sapca

@@ -209,13 +209,14 @@ class ResidentCsr {
 template <typename T>
 class SparsePCA {
  public:
+  // lanczos_center: no reference counterpart (sapca_options.lanczos_center: the Lanczos SVD of the centred operator, opt-in)
   SparsePCA(size_t n_components, T alpha, T tolerance, uint32_t seed, bool center, bool verbose, SVDMethod m,
-            const std::vector<bool>* mask = nullptr)
+            const std::vector<bool>* mask = nullptr, bool lanczos_center = false)
       : k_(n_components), mask_len_(mask ? mask->size() : 0), masked_(mask != nullptr) {
     sapca_options o;
     sapca_options_default(&o);
     o.n_components = n_components; o.alpha = alpha; o.tolerance = tolerance; o.random_seed = seed;
-    o.center = center; o.verbose = verbose;
+    o.center = center; o.verbose = verbose; o.lanczos_center = lanczos_center;
     o.method = m.random ? SAPCA_RANDOM : SAPCA_LANCZOS;
     o.n_oversamples = m.n_oversamples; o.n_power_iterations = m.n_power_iterations; o.normalizer = (int32_t)m.normalizer;
     sapca_status st = sapca_create(&o, &h_);
@@ -282,11 +283,13 @@ class BuilderT {
   BuilderT& center(bool c) { center_ = c; return *this; }
   BuilderT& verbose(bool v) { verbose_ = v; return *this; }
   BuilderT& svd_method(SVDMethod m) { method_ = m; return *this; }
+  BuilderT& lanczos_center(bool on = true) { lanczos_center_ = on; return *this; }   // (extension: sapca_options.lanczos_center)
   BuilderT& mask(std::vector<bool> m) { static_assert(Masked, "mask() belongs to MaskedSparsePCABuilder"); mask_ = std::move(m); return *this; }
-  SparsePCA<T>* build() const { return new SparsePCA<T>(k_, alpha_, tol_, seed_, center_, verbose_, method_, Masked ? &mask_ : nullptr); }
+  SparsePCA<T>* build() const { return new SparsePCA<T>(k_, alpha_, tol_, seed_, center_, verbose_, method_, Masked ? &mask_ : nullptr, lanczos_center_); }
 
  private:
   size_t k_ = 50; T alpha_ = 1; T tol_ = (T)1e-6; uint32_t seed_ = 42; bool center_ = true, verbose_ = false;   // :392-401
+  bool lanczos_center_ = false;
   SVDMethod method_{};
   std::vector<bool> mask_;
 };

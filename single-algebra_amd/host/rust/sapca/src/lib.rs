@@ -131,12 +131,13 @@ fn check(h: ffi::sapca_handle, status: i32) -> Result<()> {
 }
 
 fn create(n_components: usize, alpha: f64, tolerance: f64, seed: u32, center: bool, verbose: bool,
-          method: SVDMethod, mask: Option<&[bool]>, devices: &[i32]) -> Result<Handle> {
+          method: SVDMethod, mask: Option<&[bool]>, devices: &[i32], lanczos_center: bool) -> Result<Handle> {
     let mut o: ffi::sapca_options = unsafe { std::mem::zeroed() };
     unsafe { ffi::sapca_options_default(&mut o) };
     o.n_components = n_components as u64;
     o.alpha = alpha; o.tolerance = tolerance; o.random_seed = seed;
     o.center = center as u8; o.verbose = verbose as u8;
+    o.lanczos_center = lanczos_center as u8;
     match method {
         SVDMethod::Lanczos => o.method = ffi::SAPCA_LANCZOS,
         SVDMethod::Random { n_oversamples, n_power_iterations, normalizer } => {
@@ -181,12 +182,12 @@ fn create(n_components: usize, alpha: f64, tolerance: f64, seed: u32, center: bo
 #[derive(Clone)]
 struct Config {
     n_components: usize, alpha: f64, tolerance: f64, random_seed: u32, center: bool, verbose: bool,
-    svdmethod: SVDMethod, mask: Option<Vec<bool>>, devices: Vec<i32>,
+    svdmethod: SVDMethod, mask: Option<Vec<bool>>, devices: Vec<i32>, lanczos_center: bool,
 }
 impl Config {
     fn create(&self) -> Result<Handle> {
         create(self.n_components, self.alpha, self.tolerance, self.random_seed, self.center, self.verbose, self.svdmethod,
-               self.mask.as_deref(), &self.devices)
+               self.mask.as_deref(), &self.devices, self.lanczos_center)
     }
 }
 
@@ -198,7 +199,8 @@ impl<T: SapcaFloat> SparsePCA<T> {
     pub fn new(n_components: usize, alpha: T, tollerance: Option<T>, random_seed: Option<u32>, center: bool, verbose: bool,
                svdmethod: SVDMethod) -> Self {
         Self::from_config(Config { n_components, alpha: alpha.to_f64(), tolerance: tollerance.map(|t| t.to_f64()).unwrap_or(1e-6),
-                                   random_seed: random_seed.unwrap_or(42), center, verbose, svdmethod, mask: None, devices: Vec::new() })
+                                   random_seed: random_seed.unwrap_or(42), center, verbose, svdmethod, mask: None, devices: Vec::new(),
+                                   lanczos_center: false })
     }
     fn from_config(cfg: Config) -> Self { Self { cfg, h: None, _t: PhantomData } }
     /// the handle, created on the first fit (a creation failure -- no GPU, no memory -- surfaces in that call's Result)
@@ -312,12 +314,12 @@ impl<T: SapcaFloat> SparsePCA<T> {
 /// SparsePCABuilder<T> (sparse/mod.rs:375-484; defaults :392-401)
 pub struct SparsePCABuilder<T: SapcaFloat> {
     n_components: usize, alpha: f64, tolerance: f64, random_seed: Option<u32>, center: bool, verbose: bool,
-    svdmethod: SVDMethod, devices: Vec<i32>, _t: PhantomData<T>,
+    svdmethod: SVDMethod, devices: Vec<i32>, lanczos_center: bool, _t: PhantomData<T>,
 }
 impl<T: SapcaFloat> Default for SparsePCABuilder<T> {
     fn default() -> Self {
         Self { n_components: 50, alpha: 1.0, tolerance: 1e-6, random_seed: Some(42), center: true, verbose: false,
-               svdmethod: SVDMethod::default(), devices: Vec::new(), _t: PhantomData }
+               svdmethod: SVDMethod::default(), devices: Vec::new(), lanczos_center: false, _t: PhantomData }
     }
 }
 impl<T: SapcaFloat> SparsePCABuilder<T> {
@@ -333,10 +335,13 @@ impl<T: SapcaFloat> SparsePCABuilder<T> {
     /// the rows of every matrix passed to fit / transform / fit_transform are range-partitioned over them inside the
     /// library (include/sapca.h, sapca_multi_*), the call itself unchanged.
     pub fn devices(mut self, d: Vec<i32>) -> Self { self.devices = d; self }
+    /// Extension (not in the reference, default off): with `center(true)` and `SVDMethod::Lanczos` the SVD runs on the centred
+    /// operator A - 1 mu^T, a real PCA, instead of the raw matrix (include/sapca.h, sapca_options.lanczos_center).
+    pub fn lanczos_center(mut self, on: bool) -> Self { self.lanczos_center = on; self }
     fn config(&self, mask: Option<Vec<bool>>) -> Config {
         Config { n_components: self.n_components, alpha: self.alpha, tolerance: self.tolerance,
                  random_seed: self.random_seed.unwrap_or(42), center: self.center, verbose: self.verbose,
-                 svdmethod: self.svdmethod, mask, devices: self.devices.clone() }
+                 svdmethod: self.svdmethod, mask, devices: self.devices.clone(), lanczos_center: self.lanczos_center }
     }
     /// sparse/mod.rs:470-483: infallible, records the parameters (the handle is created by the first fit)
     pub fn build(self) -> SparsePCA<T> { SparsePCA::from_config(self.config(None)) }
@@ -353,7 +358,7 @@ impl<T: SapcaFloat> MaskedSparsePCA<T> {
         let mask_len = mask.len();
         let cfg = Config { n_components, alpha: alpha.to_f64(), tolerance: tollerance.map(|t| t.to_f64()).unwrap_or(1e-6),
                            random_seed: random_seed.unwrap_or(42), center, verbose, svdmethod: svd_method, mask: Some(mask),
-                           devices: Vec::new() };
+                           devices: Vec::new(), lanczos_center: false };
         Self { inner: SparsePCA::from_config(cfg), mask_len }
     }
     fn check_mask(&self, x: &CsrMatrix<T>) -> Result<()> {
@@ -397,6 +402,7 @@ impl<T: SapcaFloat> MaskedSparsePCABuilder<T> {
     pub fn svd_method(mut self, m: SVDMethod) -> Self { self.base = self.base.svd_method(m); self }
     pub fn mask(mut self, mask: Vec<bool>) -> Self { self.mask = mask; self }
     pub fn devices(mut self, d: Vec<i32>) -> Self { self.base = self.base.devices(d); self }
+    pub fn lanczos_center(mut self, on: bool) -> Self { self.base = self.base.lanczos_center(on); self }
     /// sparse_masked/mod.rs:146-160: infallible
     pub fn build(self) -> MaskedSparsePCA<T> {
         let mask_len = self.mask.len();

@@ -21,7 +21,7 @@ class Options(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("random_seed", C.c_uint32), ("n_components", C.c_uint64),
         ("alpha", C.c_double), ("tolerance", C.c_double),
-        ("center", C.c_uint8), ("verbose", C.c_uint8), ("collect_timings", C.c_uint8), ("reserved0", C.c_uint8),
+        ("center", C.c_uint8), ("verbose", C.c_uint8), ("collect_timings", C.c_uint8), ("lanczos_center", C.c_uint8),
         ("method", C.c_int32), ("n_oversamples", C.c_uint64), ("n_power_iterations", C.c_uint64),
         ("normalizer", C.c_int32), ("transform_semantics", C.c_int32), ("device_id", C.c_int32),
         ("spmm_variant", C.c_int32), ("stream", C.c_void_p),

@@ -86,7 +86,7 @@ class _Estimator:
     """State and marshalling shared by SparsePCA and MaskedSparsePCA."""
 
     def __init__(self, n_components, alpha, tolerance, random_seed, center, verbose, svdmethod, mask=None,
-                 device=None, transform_semantics=L.TRANSFORM_REFERENCE, spmm_variant=0, collect_timings=False):
+                 device=None, transform_semantics=L.TRANSFORM_REFERENCE, spmm_variant=0, collect_timings=False, lanczos_center=False):
         self.n_components = int(n_components)
         self.alpha = float(alpha)
         self.tolerance = float(tolerance)
@@ -103,6 +103,8 @@ class _Estimator:
         o.random_seed = self.random_seed & 0xFFFFFFFF
         o.center, o.verbose = int(self.center), int(self.verbose)
         o.collect_timings = int(bool(collect_timings))
+        self.lanczos_center = bool(lanczos_center)
+        o.lanczos_center = int(self.lanczos_center)
         o.method = L.RANDOM if svdmethod.kind == "Random" else L.LANCZOS
         o.n_oversamples = svdmethod.n_oversamples
         o.n_power_iterations = svdmethod.n_power_iterations
@@ -385,6 +387,12 @@ class _BuilderBase:
 
     def transform_semantics(self, sem):
         self._ext["transform_semantics"] = int(sem)
+        return self
+
+    def lanczos_center(self, on=True):
+        """SVDMethod.Lanczos with center(True): factor the centred operator A - 1 mu^T (a real PCA) instead of the raw
+        matrix (the reference's behaviour, the default).  No effect with center(False) or SVDMethod.Random."""
+        self._ext["lanczos_center"] = bool(on)
         return self
 
     def spmm_variant(self, v):
