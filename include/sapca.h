@@ -58,7 +58,8 @@ extern "C" {
                                  additive, ABI 4: sapca_batch_stats_csr_device_*, sapca_sum_row_n_top_csr_device_*,
                                                   sapca_masked_stats_csr_device_*
                                  additive, ABI 4: sapca_options.reserved0 became lanczos_center (same size and offsets;
-                                                  0, the value every caller passed, is the behaviour of before)        */
+                                                  0, the value every caller passed, is the behaviour of before)
+                                 additive, ABI 4: sapca_select_rows_csr_device_*                                       */
 
 typedef struct sapca_handle_s* sapca_handle;
 
@@ -387,6 +388,32 @@ sapca_status sapca_masked_stats_csr_device_f64(sapca_handle h, uint64_t m, uint6
                                                const int64_t* row_offsets, const int32_t* col_indices, const double* values,
                                                int32_t direction, const uint8_t* mask, uint64_t mask_len,
                                                double* sum, double* sum_squared, uint64_t* count, double* var);
+
+/* Rows of a device-resident CSR as a CSR of their own (the reference slices on the host: CsrMatrix has no row selection;
+ * its consumers filter cells, fit on reference cells, fit per cluster or batch, subsample and bootstrap).  Output row i is
+ * source row rows[i]: its entries in stored order, column indices unchanged, values copied bit for bit (NaN payloads, -0.0
+ * and stored zeros survive).  `rows` is a HOST array; it may be in any order and may repeat (a mask is the ascending
+ * special case), so the output is n_rows x n and *nnz_out may exceed nnz.  n_rows == 0 is valid: a one-element offset
+ * array {0} and *nnz_out = 0.
+ * SAPCA_ERR_ARG, checked on the host before anything is enqueued (the handle stays usable): rows[i] >= m ("select_rows: row
+ * index R at position I is out of range (m = M)"); rows == NULL with n_rows > 0; a null output pointer; a source that is
+ * the handle's own selection buffers.
+ * The outputs (device int64 offsets [n_rows + 1], int32 column indices, values) live in buffers owned by the handle, distinct
+ * from those of sapca_upload_csr_*: the full matrix stays resident beside its subset.  They are valid until the next
+ * sapca_select_rows_csr_device_* on this handle or its destruction, complete when the call returns, and writable
+ * (sapca_normalize_csr_device_* / sapca_log1p_csr_device_* may run on them); every *_csr_device_* entry point takes them.
+ * The source matrix, and the column statistics gathered during its upload, are untouched: a later fit of the uploaded
+ * arrays still finds them.  A cached preparation is dropped only if it was made of the previous selection.
+ * On a handle that belongs to a communicator the call is local to the rank: it selects from that rank's shard (rows index
+ * the shard) and issues no collective.                                                                              */
+sapca_status sapca_select_rows_csr_device_f32(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz,
+                                              const int64_t* row_offsets, const int32_t* col_indices, const float* values,
+                                              const uint64_t* rows, uint64_t n_rows, uint64_t* nnz_out,
+                                              const int64_t** d_row_offsets, const int32_t** d_col_indices, float** d_values);
+sapca_status sapca_select_rows_csr_device_f64(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz,
+                                              const int64_t* row_offsets, const int32_t* col_indices, const double* values,
+                                              const uint64_t* rows, uint64_t n_rows, uint64_t* nnz_out,
+                                              const int64_t** d_row_offsets, const int32_t** d_col_indices, double** d_values);
 
 /* Measurement support: the rate (GB/s, read + write counted) of a 16-byte-per-lane streaming copy of `bytes`
  * bytes on the handle's device, best of `reps` -- the HBM rate a kernel of this library can attain, reported by

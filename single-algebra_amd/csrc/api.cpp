@@ -628,6 +628,54 @@ sapca_status masked_stats_device(sapca_handle h, uint64_t m, uint64_t n, uint64_
   });
 }
 
+// Rows `rows[0 .. n_rows)` of a device CSR (any order, repeats allowed) as a CSR in the handle's selection buffers: the
+// offsets through a scan (one synchronisation: the total sizes the output), then a fill balanced over output entries
+// (select.hip).  Everything that can be refused is refused before anything is enqueued or a buffer is touched.
+template <typename T>
+sapca_status select_rows_device(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v,
+                                const uint64_t* rows, uint64_t n_rows, uint64_t* nnz_out, const int64_t** d_ptr,
+                                const int32_t** d_idx, T** d_val) {
+  return guarded(h, [&] {
+    SAPCA_CHECK(nnz_out && d_ptr && d_idx && d_val, SAPCA_ERR_ARG, "select_rows: null output pointer");
+    SAPCA_CHECK(rows != nullptr || n_rows == 0, SAPCA_ERR_ARG, "select_rows: rows is NULL with n_rows > 0");
+    CsrView<T> A = device_view<T>(m, n, nnz, p, i, v);
+    SAPCA_CHECK(n_rows < (1ull << 31), SAPCA_ERR_ARG, "more than 2^31-1 rows or columns is not supported");
+    auto inside = [](const void* q, const sapca::DevBuf& b) {
+      const char* c = static_cast<const char*>(q);
+      return b.p != nullptr && c >= static_cast<const char*>(b.p) && c < static_cast<const char*>(b.p) + b.cap;
+    };
+    SAPCA_CHECK(!inside(p, h->sub_ptr) && !inside(i, h->sub_idx) && !inside(v, h->sub_val), SAPCA_ERR_ARG,
+                "select_rows: the source is this handle's own selection, which the call overwrites (select from the uploaded matrix)");
+    for (uint64_t j = 0; j < n_rows; ++j)
+      if (rows[j] >= m)
+        throw Error(SAPCA_ERR_ARG, "select_rows: row index " + std::to_string(rows[j]) + " at position " + std::to_string(j) +
+                                       " is out of range (m = " + std::to_string(m) + ")");
+    hipStream_t s = h->stream;
+    // a preparation cached for the previous selection describes arrays that are about to change; any other stays
+    if (h->prep_key.valid && (inside(h->prep_key.ptr, h->sub_ptr) || inside(h->prep_key.idx, h->sub_idx) || inside(h->prep_key.val, h->sub_val)))
+      h->prep_key.valid = false;
+    int64_t* o_ptr = h->sub_ptr.as<int64_t>(n_rows + 1);
+    int64_t total = 0;
+    const uint64_t* d_rows = nullptr;
+    if (n_rows == 0) {
+      SAPCA_HIP(hipMemsetAsync(o_ptr, 0, sizeof(int64_t), s));
+    } else {
+      uint64_t* dr = h->sub_rows.as<uint64_t>(n_rows);
+      SAPCA_HIP(hipMemcpyAsync(dr, rows, n_rows * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+      d_rows = dr;
+      sapca::k::select_rows_offsets(A.ptr, d_rows, (int64_t)n_rows, o_ptr, &total, h->sub_scan, s);
+    }
+    int32_t* o_idx = h->sub_idx.as<int32_t>(std::max<int64_t>(total, 1));
+    T* o_val = h->sub_val.as<T>(std::max<int64_t>(total, 1));
+    sapca::k::select_rows_fill(A, d_rows, (int64_t)n_rows, o_ptr, total, o_idx, o_val, s);
+    SAPCA_HIP(hipStreamSynchronize(s));   // the arrays are complete when the call returns, whatever stream reads them next
+    *nnz_out = (uint64_t)total;
+    *d_ptr = o_ptr;
+    *d_idx = o_idx;
+    *d_val = o_val;
+  });
+}
+
 // MatrixNTop::sum_row_n_top (csr.rs:1347-1376) for several n in one pass over the rows: out[i * m + r]
 template <typename T>
 sapca_status top_n_device(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v,
@@ -935,6 +983,11 @@ sapca_status sapca_set_omega_f64(sapca_handle h, const double* omega, size_t row
                                                    uint64_t mask_len, double* sum, double* sum_squared, uint64_t* count,    \
                                                    double* var) {                                                           \
     return masked_stats_device<T>(h, m, n, nnz, p, i, v, direction, mask, mask_len, sum, sum_squared, count, var);        \
+  }                                                                                                                      \
+  sapca_status sapca_select_rows_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p,  \
+                                                  const int32_t* i, const T* v, const uint64_t* rows, uint64_t n_rows,     \
+                                                  uint64_t* nnz_out, const int64_t** dp, const int32_t** di, T** dv) {     \
+    return select_rows_device<T>(h, m, n, nnz, p, i, v, rows, n_rows, nnz_out, dp, di, dv);                               \
   }                                                                                                                      \
   sapca_status sapca_sum_row_n_top_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, \
                                                     const int32_t* i, const T* v, const uint64_t* ns, uint32_t n_ns,        \

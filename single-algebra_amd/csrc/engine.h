@@ -106,6 +106,9 @@ struct sapca_handle_s {
     bool valid = false;
   } up_stats;
   hipEvent_t up_stats_done = nullptr;
+  // the row selection of sapca_select_rows_csr_device_*: a CSR of its own beside the upload's, the row list on the device and the
+  // scan's work space (nothing else lives in these, so a selection disturbs no cached preparation but one made OF it)
+  sapca::DevBuf sub_ptr, sub_idx, sub_val, sub_rows, sub_scan;
   sapca::DevBuf at_ptr, at_idx, at_val;                          // A^T
   sapca::DevBuf ca_ptr, ca_idx, ca_val, cat_ptr, cat_idx, cat_val;  // mask-compacted A, A^T
   sapca::DevBuf drop_stats, drop_tmp;                              // their sums (sum | sumsq, full width) and the sort's work space

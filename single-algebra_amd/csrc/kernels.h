@@ -106,6 +106,19 @@ template <typename T>
 void masked_row_stats(const CsrView<T>& A, const uint32_t* col_bits, double* sum, double* sumsq, double* m2, uint32_t* cnt,
                       hipStream_t s);
 
+// ---- select.hip: rows of a CSR, in any order and with repeats, as a new CSR (sapca_select_rows_csr_device_*) ----------
+// data[0 .. count) <- its exclusive prefix sums, in place (prep.hip); work space from `scratch` at scratch_offset
+void exclusive_scan_i64(int64_t* data, int64_t count, DevBuf& scratch, size_t scratch_offset, hipStream_t s);
+// out_ptr[0 .. n_rows] = the offsets of the selection (row i = source row rows[i]; rows: device, every entry below the source's
+// row count); *total_host = out_ptr[n_rows], on the host when the call returns (one synchronisation, like compact_columns)
+void select_rows_offsets(const int64_t* ptr, const uint64_t* rows, int64_t n_rows, int64_t* out_ptr, int64_t* total_host,
+                         DevBuf& scratch, hipStream_t s);
+// out_idx / out_val[out_ptr[i] ..) = the entries of row rows[i] of A in stored order, values bit for bit; out_idx and out_val
+// are 16-byte aligned and do not overlap A.  A workgroup per span of output positions (kSelectSpan), no atomics.
+template <typename T>
+void select_rows_fill(const CsrView<T>& A, const uint64_t* rows, int64_t n_rows, const int64_t* out_ptr, int64_t total,
+                      int32_t* out_idx, T* out_val, hipStream_t s);
+
 // dst[0 .. bytes) = src[0 .. bytes) by a 16-byte-per-lane streaming kernel (the attainable-HBM-rate probe of sapca_measure_copy_gbs)
 void stream_copy16(const void* src, void* dst, int64_t bytes, hipStream_t s);
 

@@ -386,7 +386,9 @@ inline int grid_for(int64_t work_items, int block, int cap = 8192) {
   return (int)g;
 }
 
-inline void exclusive_scan_i64(int64_t* data, int64_t count, DevBuf& scratch, size_t scratch_offset, hipStream_t s) {
+}  // namespace
+
+void exclusive_scan_i64(int64_t* data, int64_t count, DevBuf& scratch, size_t scratch_offset, hipStream_t s) {
   size_t bytes = 0;
   SAPCA_HIP(rocprim::exclusive_scan(nullptr, bytes, data, data, (int64_t)0, (size_t)count,
                                     rocprim::plus<int64_t>(), s));
@@ -394,8 +396,6 @@ inline void exclusive_scan_i64(int64_t* data, int64_t count, DevBuf& scratch, si
   SAPCA_HIP(rocprim::exclusive_scan(base + scratch_offset, bytes, data, data, (int64_t)0, (size_t)count,
                                     rocprim::plus<int64_t>(), s));
 }
-
-}  // namespace
 
 void narrow_indices(const uint64_t* ptr64, const uint64_t* idx64, int64_t m, int64_t nnz, int64_t n, int64_t* ptr,
                     int32_t* idx, int* flag, hipStream_t s) {

@@ -69,6 +69,7 @@ template <typename T> struct ResidentAbi;
     static sapca_status batch_stats(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, int32_t ax, const int32_t* c, uint64_t cl, uint32_t nb, double* mean, double* var, uint64_t* cnt) { return sapca_batch_stats_csr_device_##SUF(h, m, n, nnz, p, i, v, ax, c, cl, nb, mean, var, cnt); } \
     static sapca_status masked_stats(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, int32_t d, const uint8_t* mk, uint64_t ml, double* s, double* q, uint64_t* c, double* var) { return sapca_masked_stats_csr_device_##SUF(h, m, n, nnz, p, i, v, d, mk, ml, s, q, c, var); } \
     static sapca_status n_top(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, const uint64_t* ns, uint32_t k, double* out) { return sapca_sum_row_n_top_csr_device_##SUF(h, m, n, nnz, p, i, v, ns, k, out); } \
+    static sapca_status select_rows(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, const uint64_t* rows, uint64_t nr, uint64_t* nnz_out, const int64_t** op, const int32_t** oi, T** ov) { return sapca_select_rows_csr_device_##SUF(h, m, n, nnz, p, i, v, rows, nr, nnz_out, op, oi, ov); } \
   };
 SAPCA_RES(f32, float)
 SAPCA_RES(f64, double)
@@ -131,11 +132,24 @@ class ResidentCsr {
   template <typename U> void var_row_chunk(std::vector<U>& ref) const { var_into(ref, Direction::ROW, "rows"); }
   template <typename U> void min_max_col_chunk(std::vector<U>& mins, std::vector<U>& maxs) const { min_max_into(mins, maxs, Direction::COLUMN, true); }
   template <typename U> void min_max_row_chunk(std::vector<U>& mins, std::vector<U>& maxs) const { min_max_into(mins, maxs, Direction::ROW, false); }
+  // Rows `rows` of this matrix (any order, repeats allowed) as a resident matrix of their own in the same handle, without
+  // crossing PCIe (sapca_select_rows_csr_device_*): cell filtering, a fit on reference cells, per-cluster fits, bootstraps.
+  // This matrix stays as it is; the result is valid until the next select_rows on the handle and cannot itself be the
+  // source of one.
+  ResidentCsr select_rows(const std::vector<uint64_t>& rows) const {
+    ResidentCsr out(h_, (uint64_t)rows.size(), n_);
+    check(ResidentAbi<T>::select_rows(h_, m_, n_, nnz_, ptr_, idx_, val_, rows.data(), rows.size(), &out.nnz_, &out.ptr_, &out.idx_, &out.val_));
+    return out;
+  }
+  uint64_t nrows() const { return m_; }
+  uint64_t ncols() const { return n_; }
+  uint64_t nnz() const { return nnz_; }
   const int64_t* row_offsets() const { return ptr_; }
   const int32_t* col_indices() const { return idx_; }
   T* values() const { return val_; }
 
  private:
+  ResidentCsr(sapca_handle h, uint64_t m, uint64_t n) : h_(h), m_(m), n_(n), nnz_(0) {}   // (filled in by select_rows)
   void check(sapca_status st) const {
     if (st != SAPCA_OK) throw Error(st, sapca_last_error(h_));
   }

@@ -54,6 +54,7 @@ _TYPED = [
     "sapca_normalize_panel", "sapca_generate_omega",
     "sapca_upload_csr", "sapca_normalize_csr_device", "sapca_log1p_csr_device", "sapca_stats_csr_device",
     "sapca_batch_stats_csr_device", "sapca_sum_row_n_top_csr_device", "sapca_masked_stats_csr_device",
+    "sapca_select_rows_csr_device",
     "sapca_multi_fit_csr", "sapca_multi_transform_csr", "sapca_multi_fit_transform_csr",
     "sapca_multi_upload_csr", "sapca_multi_transform_resident", "sapca_multi_fit_transform_resident",
 ]

@@ -99,6 +99,28 @@ def _dense_codes(batches):
     return list(lut), codes
 
 
+def _row_list(rows, m):
+    """The row list of ResidentCsr.select_rows as the uint64 array the C ABI takes: a boolean array of length exactly m
+    becomes its ascending true positions; an integer sequence passes through in its own order, repeats included.  Pure
+    host code (numpy only): a mask of another length, a negative index, a sequence that is neither or has more than one
+    dimension raise ValueError.  An index >= m is left to the library, which names it (SAPCA_ERR_ARG)."""
+    a = np.asarray(rows)
+    if a.ndim != 1:
+        raise ValueError(f"rows must be one-dimensional, got shape {a.shape}")
+    if a.dtype == np.bool_:
+        if a.size != int(m):
+            raise ValueError(f"Row mask length ({a.size}) does not match number of rows ({int(m)})")
+        return np.flatnonzero(a).astype(np.uint64)
+    if a.size == 0:
+        return np.zeros(0, dtype=np.uint64)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"rows must be a boolean mask or integer indices, got dtype {a.dtype}")
+    if a.dtype.kind == "i" and (a < 0).any():
+        j = int(np.flatnonzero(a < 0)[0])
+        raise ValueError(f"negative row index {int(a[j])} at position {j}")
+    return np.ascontiguousarray(a, dtype=np.uint64)
+
+
 class ResidentCsr:
     """A CSR matrix uploaded once into buffers owned by a Session (sapca_upload_csr_*): normalize -> log1p ->
     statistics -> PCA on it without crossing PCIe again.  `as_device_csr()` gives the
@@ -333,6 +355,21 @@ class ResidentCsr:
         mins[has] = lo[has]
         maxs[has] = hi[has]
         return reference
+
+    def select_rows(self, rows):
+        """sapca_select_rows_csr_device_*: the rows `rows` of this matrix -- a boolean mask of length m, or integer indices
+        in any order, repeats allowed -- as a ResidentCsr of shape (len(rows), n) in the same Session, without crossing
+        PCIe.  This matrix stays resident and unchanged beside it; every method here works on the result (normalize and
+        log1p included: its values are its own).  It lives in the Session's selection buffers: valid until the next
+        select_rows on the Session, and not itself a source of one."""
+        suf, _ = _SUF[self.dtype]
+        r = _row_list(rows, self.shape[0])
+        nnz_out = C.c_uint64()
+        dp, di, dv = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        L.check(self._s._h, getattr(L.load(), f"sapca_select_rows_csr_device_{suf}")(
+            *self._args(), _p(r, C.c_uint64) if r.size else None, C.c_uint64(r.size), C.byref(nnz_out), C.byref(dp), C.byref(di),
+            C.byref(dv)))
+        return ResidentCsr(self._s, (r.size, self.shape[1]), nnz_out.value, self.dtype, dp.value or 0, di.value or 0, dv.value or 0)
 
     def values(self):
         """the current (device) values, copied to the host"""
