@@ -23,7 +23,9 @@
  *     relied upon, not checked (unsorted rows give wrong numbers, not stray accesses).
  *   - "device" entry points take HBM-resident CSR (int64 row offsets, int32 column
  *     indices) and device output buffers; they are what bench.py times.  Device
- *     arrays are trusted (no validation pass).
+ *     arrays are trusted (no validation pass).  Arrays that did not come from
+ *     sapca_upload_csr_* go through sapca_check_csr_device_* (are they safe and
+ *     canonical?) or sapca_canonicalize_csr_device_* (make them so) first.
  *   - inputs are borrowed for the duration of a call; outputs are written into
  *     caller-allocated buffers.
  *   - a handle is not thread-safe; distinct handles may be used concurrently.
@@ -59,7 +61,8 @@ extern "C" {
                                                   sapca_masked_stats_csr_device_*
                                  additive, ABI 4: sapca_options.reserved0 became lanczos_center (same size and offsets;
                                                   0, the value every caller passed, is the behaviour of before)
-                                 additive, ABI 4: sapca_select_rows_csr_device_*                                       */
+                                 additive, ABI 4: sapca_select_rows_csr_device_*
+                                 additive, ABI 4: sapca_check_csr_device_*, sapca_canonicalize_csr_device_*           */
 
 typedef struct sapca_handle_s* sapca_handle;
 
@@ -414,6 +417,77 @@ sapca_status sapca_select_rows_csr_device_f64(sapca_handle h, uint64_t m, uint64
                                               const int64_t* row_offsets, const int32_t* col_indices, const double* values,
                                               const uint64_t* rows, uint64_t n_rows, uint64_t* nnz_out,
                                               const int64_t** d_row_offsets, const int32_t** d_col_indices, double** d_values);
+
+/* ---- the gate in front of the device entry points: check and canonicalise a device-resident CSR ----
+ * Every kernel relies on offsets that start at 0, end at nnz and never decrease, on columns < n, and on rows whose
+ * columns ascend without repeats.  Arrays that came through sapca_upload_csr_* have all of it; anything else (a
+ * transposed, multiplied or fancy-indexed scipy result, an .h5ad another tool wrote, a CSR built from COO, a caller's
+ * own kernel) is checked here, on the GPU, where it already is.  "Canonical" is (flags & 15) == 0.                  */
+#define SAPCA_CSR_BAD_OFFSETS   1u   /* ptr[0] != 0, ptr[m] != nnz, or ptr[r+1] < ptr[r]            */
+#define SAPCA_CSR_COL_RANGE     2u   /* a column index < 0 or >= n                                  */
+#define SAPCA_CSR_UNSORTED      4u   /* a row with an entry whose column is below its predecessor's */
+#define SAPCA_CSR_DUPLICATES    8u   /* an entry whose column equals its predecessor's in the row   */
+#define SAPCA_CSR_NONFINITE    16u   /* an inf / nan value (allowed by the fits; reported)          */
+
+typedef struct sapca_csr_report {
+  uint32_t struct_size;          /* = sizeof(sapca_csr_report), set by the caller (growth guard)    */
+  uint32_t flags;
+  uint64_t first_bad_offset_row, cols_out_of_range, first_out_of_range_row;
+  uint64_t unsorted_rows, first_unsorted_row;
+  uint64_t duplicate_entries, first_duplicate_row;
+  uint64_t nonfinite_values, first_nonfinite_row;
+  uint64_t stored_zeros;
+} sapca_csr_report;
+
+/* Read-only check.  Finding a defect is not an error: the call returns SAPCA_OK and fills *report; SAPCA_ERR_ARG is for
+ * a null report or a report->struct_size other than sizeof(sapca_csr_report).  Counts are exact, independent of the
+ * launch geometry and the same from call to call; a first_*_row whose count is zero is UINT64_MAX.
+ * Two stages.  The offsets are checked by a kernel that reads row_offsets[0 .. m] only, and its verdict reaches the host
+ * before anything else runs: with broken offsets the report carries SAPCA_CSR_BAD_OFFSETS and first_bad_offset_row (the
+ * first r with ptr[r+1] < ptr[r]; 0 for ptr[0] != 0; m for ptr[m] != nnz) and says nothing about the entries, which are
+ * not read.  With sound offsets one pass reads each of the three arrays once, inside [0, nnz).
+ * Columns are compared as unsigned numbers (a negative index is out of range and larger than any valid one), and only
+ * with the predecessor in the SAME row.  unsorted_rows counts rows, the other counts entries.  duplicate_entries counts
+ * duplicates that are adjacent in stored order: that is every duplicate when the row is sorted; an unsorted row can
+ * hide duplicates that are not adjacent, and the exact number is what sapca_canonicalize_csr_device_* reports.
+ * stored_zeros counts values equal to zero (either sign).  On a handle that belongs to a communicator the call is
+ * local to the rank and issues no collective.                                                                        */
+sapca_status sapca_check_csr_device_f32(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz,
+                                        const int64_t* row_offsets, const int32_t* col_indices, const float* values,
+                                        sapca_csr_report* report);
+sapca_status sapca_check_csr_device_f64(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz,
+                                        const int64_t* row_offsets, const int32_t* col_indices, const double* values,
+                                        sapca_csr_report* report);
+
+/* The canonical form: output row r holds the entries of input row r in ascending column order, and entries of equal
+ * column are merged into one whose value is their sum in T, added left to right in the input's stored order (the sort
+ * is stable: scipy's sum_duplicates, nalgebra's COO -> CSR conversion).  An entry that is not merged keeps its value bit
+ * for bit: NaN payloads, -0.0 and stored zeros survive; stored zeros are not dropped, and neither is a merged sum that
+ * comes to zero.  The result is deterministic.  Rows have fewer than 2^32 entries.
+ * Already canonical input: nothing is copied or allocated for it; *d_row_offsets == row_offsets, *d_col_indices ==
+ * col_indices, *d_values == values and *nnz_out == nnz, at the cost of the check's one pass.
+ * SAPCA_ERR_ARG, with nothing written and the handle usable: broken offsets ("canonicalize: the row offsets are broken at
+ * row R ...") or a column out of range ("canonicalize: K column indices are out of range (n = N), the first in row R
+ * ...") cannot be repaired; a null output pointer; a source inside this handle's own canonical buffers; a report with
+ * the wrong struct_size.
+ * Otherwise the outputs (device int64 offsets [m + 1], int32 column indices, values) live in a third set of buffers owned
+ * by the handle, distinct from those of sapca_upload_csr_* and sapca_select_rows_csr_device_*: the source -- the upload,
+ * the selection or the caller's own arrays -- stays resident and untouched beside them.  They are valid until the next
+ * sapca_canonicalize_csr_device_* on this handle or its destruction, complete when the call returns, and writable; every
+ * *_csr_device_* entry point takes them.  A cached preparation is dropped only if it was made of the previous canonical
+ * result; the statistics gathered at upload stay valid for the uploaded arrays.
+ * report (may be NULL; struct_size set by the caller) describes the INPUT: the flags and counts of the check, except
+ * that duplicate_entries is exact here, nnz - *nnz_out (first_duplicate_row stays the check's: the first row with an
+ * adjacent duplicate).  On a handle that belongs to a communicator the call is local to the rank (it acts on the shard)
+ * and issues no collective.                                                                                          */
+sapca_status sapca_canonicalize_csr_device_f32(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz,
+                                               const int64_t* row_offsets, const int32_t* col_indices, const float* values,
+                                               uint64_t* nnz_out, const int64_t** d_row_offsets, const int32_t** d_col_indices,
+                                               float** d_values, sapca_csr_report* report);
+sapca_status sapca_canonicalize_csr_device_f64(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz,
+                                               const int64_t* row_offsets, const int32_t* col_indices, const double* values,
+                                               uint64_t* nnz_out, const int64_t** d_row_offsets, const int32_t** d_col_indices,
+                                               double** d_values, sapca_csr_report* report);
 
 /* Measurement support: the rate (GB/s, read + write counted) of a 16-byte-per-lane streaming copy of `bytes`
  * bytes on the handle's device, best of `reps` -- the HBM rate a kernel of this library can attain, reported by

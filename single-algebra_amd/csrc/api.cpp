@@ -676,6 +676,160 @@ sapca_status select_rows_device(sapca_handle h, uint64_t m, uint64_t n, uint64_t
   });
 }
 
+// ---- the gate in front of the device entry points (canon.hip) ----------------------------------------------------------
+bool inside_buf(const void* q, const sapca::DevBuf& b) {
+  const char* c = static_cast<const char*>(q);
+  return b.p != nullptr && c >= static_cast<const char*>(b.p) && c < static_cast<const char*>(b.p) + b.cap;
+}
+
+// The check of a device CSR: the offsets first (one synchronisation: nothing reads an entry before they are known to be
+// sound), then one pass over the entries; with_lists: the rows that need sorting are listed behind it for canonicalize.
+// ctr_host receives the counter block; the per-row words stay in h->canon_rows.
+template <typename T>
+void run_check(sapca_handle h, const CsrView<T>& A, sapca_csr_report* rep, unsigned long long* ctr_host, bool with_lists) {
+  namespace K = sapca::k;
+  hipStream_t s = h->stream;
+  const int64_t m = A.rows;
+  unsigned long long* ctr = h->canon_ctr.as<unsigned long long>(K::kCtrSlots);
+  // per row: defect bits, and for canonicalize behind them distinct columns | three lists (uint32 each)
+  uint32_t* rows = h->canon_rows.as<uint32_t>((size_t)std::max<int64_t>(with_lists ? 5 * m : m, 1));
+  unsigned long long* long_off = with_lists ? h->canon_long.as<unsigned long long>((size_t)std::max<int64_t>(m, 1)) : nullptr;
+  K::canon_check_offsets(A.ptr, m, A.nnz, ctr, s);
+  SAPCA_HIP(hipMemcpyAsync(ctr_host, ctr, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  SAPCA_HIP(hipStreamSynchronize(s));
+  const uint64_t none = UINT64_MAX;
+  sapca_csr_report r{};
+  r.struct_size = (uint32_t)sizeof(sapca_csr_report);
+  r.first_bad_offset_row = ctr_host[K::kCtrFirstBadOffset];
+  r.first_out_of_range_row = r.first_unsorted_row = r.first_duplicate_row = r.first_nonfinite_row = none;
+  if (r.first_bad_offset_row != none) {
+    r.flags = SAPCA_CSR_BAD_OFFSETS;
+  } else {
+    K::canon_check_entries(A, rows, ctr, s);
+    if (with_lists) K::canon_list_rows(A.ptr, rows, m, rows + 2 * m, long_off, ctr, s);
+    SAPCA_HIP(hipMemcpyAsync(ctr_host, ctr, K::kCtrSlots * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    SAPCA_HIP(hipStreamSynchronize(s));
+    r.cols_out_of_range = ctr_host[K::kCtrColsOutOfRange];
+    r.first_out_of_range_row = ctr_host[K::kCtrFirstOutOfRange];
+    r.unsorted_rows = ctr_host[K::kCtrUnsortedRows];
+    r.first_unsorted_row = ctr_host[K::kCtrFirstUnsorted];
+    r.duplicate_entries = ctr_host[K::kCtrDuplicates];
+    r.first_duplicate_row = ctr_host[K::kCtrFirstDuplicate];
+    r.nonfinite_values = ctr_host[K::kCtrNonfinite];
+    r.first_nonfinite_row = ctr_host[K::kCtrFirstNonfinite];
+    r.stored_zeros = ctr_host[K::kCtrStoredZeros];
+    r.flags = (r.cols_out_of_range ? SAPCA_CSR_COL_RANGE : 0u) | (r.unsorted_rows ? SAPCA_CSR_UNSORTED : 0u) |
+              (r.duplicate_entries ? SAPCA_CSR_DUPLICATES : 0u) | (r.nonfinite_values ? SAPCA_CSR_NONFINITE : 0u);
+  }
+  *rep = r;
+}
+
+void check_report_arg(const sapca_csr_report* report, const char* who) {
+  SAPCA_CHECK(report->struct_size == sizeof(sapca_csr_report), SAPCA_ERR_ARG,
+              std::string(who) + ": report->struct_size is " + std::to_string(report->struct_size) + ", this library's sapca_csr_report has " +
+                  std::to_string(sizeof(sapca_csr_report)) + " bytes");
+}
+
+template <typename T>
+sapca_status check_device(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v,
+                          sapca_csr_report* report) {
+  return guarded(h, [&] {
+    SAPCA_CHECK(report != nullptr, SAPCA_ERR_ARG, "check_csr: null report");
+    check_report_arg(report, "check_csr");
+    CsrView<T> A = device_view<T>(m, n, nnz, p, i, v);
+    unsigned long long ctr_host[sapca::k::kCtrSlots] = {};
+    sapca_csr_report r;
+    run_check(h, A, &r, ctr_host, false);
+    *report = r;
+  });
+}
+
+// dst <- src, `bytes` of device memory on the stream: the 16-byte streaming copy where both ends allow it, the tail (and an
+// unaligned source) through the runtime's copy
+void device_copy(const void* src, void* dst, size_t bytes, hipStream_t s) {
+  if (bytes == 0) return;
+  size_t body = 0;
+  if ((reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+    body = bytes & ~(size_t)15;
+    sapca::k::stream_copy16(src, dst, (int64_t)body, s);
+  }
+  if (body < bytes)
+    SAPCA_HIP(hipMemcpyAsync(static_cast<char*>(dst) + body, static_cast<const char*>(src) + body, bytes - body, hipMemcpyDeviceToDevice, s));
+}
+
+// Rows sorted by column, equal columns summed (canon.hip).  Everything that can be refused is refused before a canonical
+// buffer is touched; a canonical input is handed back as it is.
+template <typename T>
+sapca_status canonicalize_device(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v,
+                                 uint64_t* nnz_out, const int64_t** d_ptr, const int32_t** d_idx, T** d_val, sapca_csr_report* report) {
+  return guarded(h, [&] {
+    namespace K = sapca::k;
+    SAPCA_CHECK(nnz_out && d_ptr && d_idx && d_val, SAPCA_ERR_ARG, "canonicalize: null output pointer");
+    if (report) check_report_arg(report, "canonicalize");
+    CsrView<T> A = device_view<T>(m, n, nnz, p, i, v);
+    auto own = [&](const void* q) {
+      return inside_buf(q, h->canon_ptr) || inside_buf(q, h->canon_idx) || inside_buf(q, h->canon_val) || inside_buf(q, h->canon_idx2) ||
+             inside_buf(q, h->canon_val2);
+    };
+    SAPCA_CHECK(!own(p) && !own(i) && !own(v), SAPCA_ERR_ARG,
+                "canonicalize: the source is this handle's own canonical result, which the call overwrites (it is canonical already)");
+    unsigned long long ctr_host[K::kCtrSlots] = {};
+    sapca_csr_report r;
+    run_check(h, A, &r, ctr_host, true);
+    if (r.flags & SAPCA_CSR_BAD_OFFSETS)
+      throw Error(SAPCA_ERR_ARG, "canonicalize: the row offsets are broken at row " + std::to_string(r.first_bad_offset_row) +
+                                     " (ptr[0] != 0, a decreasing offset, or ptr[m] != nnz): this cannot be repaired");
+    if (r.flags & SAPCA_CSR_COL_RANGE)
+      throw Error(SAPCA_ERR_ARG, "canonicalize: " + std::to_string(r.cols_out_of_range) + " column indices are out of range (n = " +
+                                     std::to_string(n) + "), the first in row " + std::to_string(r.first_out_of_range_row) +
+                                     ": this cannot be repaired");
+    if ((r.flags & (SAPCA_CSR_UNSORTED | SAPCA_CSR_DUPLICATES)) == 0) {   // the common case: the check's one pass is all it costs
+      *nnz_out = nnz;
+      *d_ptr = p;
+      *d_idx = i;
+      *d_val = const_cast<T*>(v);
+      if (report) *report = r;
+      return;
+    }
+    hipStream_t s = h->stream;
+    // a preparation cached for the previous canonical result describes arrays that are about to change; any other stays
+    if (h->prep_key.valid && (own(h->prep_key.ptr) || own(h->prep_key.idx) || own(h->prep_key.val))) h->prep_key.valid = false;
+    const int64_t rows = A.rows;
+    int64_t* o_ptr = h->canon_ptr.as<int64_t>(m + 1);
+    int32_t* o_idx = h->canon_idx.as<int32_t>(nnz);
+    T* o_val = h->canon_val.as<T>(nnz);
+    device_copy(A.idx, o_idx, nnz * sizeof(int32_t), s);
+    device_copy(A.val, o_val, nnz * sizeof(T), s);
+    uint32_t* row_bits = h->canon_rows.ptr<uint32_t>();
+    const int64_t counts[3] = {(int64_t)ctr_host[K::kCtrListWave], (int64_t)ctr_host[K::kCtrListLds], (int64_t)ctr_host[K::kCtrListLong]};
+    unsigned long long* keys = counts[2] ? h->canon_keys.as<unsigned long long>(ctr_host[K::kCtrLongEntries]) : nullptr;
+    unsigned long long* ctr = h->canon_ctr.ptr<unsigned long long>();
+    K::canon_sort_rows(A, row_bits + 2 * rows, h->canon_long.ptr<unsigned long long>(), counts, keys, o_idx, o_val, row_bits + rows, ctr, s);
+    unsigned long long merged = 0;
+    SAPCA_HIP(hipMemcpyAsync(&merged, ctr + K::kCtrMerged, sizeof(merged), hipMemcpyDeviceToHost, s));
+    SAPCA_HIP(hipStreamSynchronize(s));
+    if (merged == 0) {   // the rows did not move: the offsets are the input's
+      device_copy(A.ptr, o_ptr, (m + 1) * sizeof(int64_t), s);
+    } else {
+      K::canon_new_lengths(A.ptr, row_bits, row_bits + rows, rows, o_ptr, s);
+      K::exclusive_scan_i64(o_ptr, rows + 1, h->canon_scan, 0, s);
+      int32_t* f_idx = h->canon_idx2.as<int32_t>(nnz - merged + 1);
+      T* f_val = h->canon_val2.as<T>(nnz - merged + 1);
+      K::canon_merge_fill(A.ptr, o_idx, o_val, rows, o_ptr, f_idx, f_val, s);
+      o_idx = f_idx;
+      o_val = f_val;
+    }
+    SAPCA_HIP(hipStreamSynchronize(s));   // the arrays are complete when the call returns, whatever stream reads them next
+    r.duplicate_entries = merged;         // exact here: adjacent or not, every entry that merged
+    if (merged) r.flags |= SAPCA_CSR_DUPLICATES;
+    *nnz_out = nnz - merged;
+    *d_ptr = o_ptr;
+    *d_idx = o_idx;
+    *d_val = o_val;
+    if (report) *report = r;
+  });
+}
+
 // MatrixNTop::sum_row_n_top (csr.rs:1347-1376) for several n in one pass over the rows: out[i * m + r]
 template <typename T>
 sapca_status top_n_device(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v,
@@ -988,6 +1142,15 @@ sapca_status sapca_set_omega_f64(sapca_handle h, const double* omega, size_t row
                                                   const int32_t* i, const T* v, const uint64_t* rows, uint64_t n_rows,     \
                                                   uint64_t* nnz_out, const int64_t** dp, const int32_t** di, T** dv) {     \
     return select_rows_device<T>(h, m, n, nnz, p, i, v, rows, n_rows, nnz_out, dp, di, dv);                               \
+  }                                                                                                                      \
+  sapca_status sapca_check_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p,        \
+                                            const int32_t* i, const T* v, sapca_csr_report* report) {                      \
+    return check_device<T>(h, m, n, nnz, p, i, v, report);                                                                \
+  }                                                                                                                      \
+  sapca_status sapca_canonicalize_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, \
+                                                   const int32_t* i, const T* v, uint64_t* nnz_out, const int64_t** dp,    \
+                                                   const int32_t** di, T** dv, sapca_csr_report* report) {                 \
+    return canonicalize_device<T>(h, m, n, nnz, p, i, v, nnz_out, dp, di, dv, report);                                    \
   }                                                                                                                      \
   sapca_status sapca_sum_row_n_top_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, \
                                                     const int32_t* i, const T* v, const uint64_t* ns, uint32_t n_ns,        \

@@ -109,6 +109,10 @@ struct sapca_handle_s {
   // the row selection of sapca_select_rows_csr_device_*: a CSR of its own beside the upload's, the row list on the device and the
   // scan's work space (nothing else lives in these, so a selection disturbs no cached preparation but one made OF it)
   sapca::DevBuf sub_ptr, sub_idx, sub_val, sub_rows, sub_scan;
+  // the canonical form of sapca_canonicalize_csr_device_*: a third CSR beside the upload's and the selection's (canon_idx2 /
+  // canon_val2 hold it when duplicates merged: the fill's output), and the work space of the check and the sort: the counter
+  // block, per row {defect bits, distinct columns, three row lists} and the long rows' key offsets, their keys, the scan's
+  sapca::DevBuf canon_ptr, canon_idx, canon_val, canon_idx2, canon_val2, canon_ctr, canon_rows, canon_long, canon_keys, canon_scan;
   sapca::DevBuf at_ptr, at_idx, at_val;                          // A^T
   sapca::DevBuf ca_ptr, ca_idx, ca_val, cat_ptr, cat_idx, cat_val;  // mask-compacted A, A^T
   sapca::DevBuf drop_stats, drop_tmp;                              // their sums (sum | sumsq, full width) and the sort's work space

@@ -119,6 +119,43 @@ template <typename T>
 void select_rows_fill(const CsrView<T>& A, const uint64_t* rows, int64_t n_rows, const int64_t* out_ptr, int64_t total,
                       int32_t* out_idx, T* out_val, hipStream_t s);
 
+// ---- canon.hip: check and canonicalise a device CSR (sapca_check_csr_device_*, sapca_canonicalize_csr_device_*) ----------
+// slots of the 64-bit counter block `ctr` (device, kCtrSlots words): first rows (start at all bits set), then counts
+enum CanonCtr {
+  kCtrFirstBadOffset = 0, kCtrFirstOutOfRange, kCtrFirstUnsorted, kCtrFirstDuplicate, kCtrFirstNonfinite, kCtrFirstCount,
+  kCtrColsOutOfRange = kCtrFirstCount, kCtrUnsortedRows, kCtrDuplicates, kCtrNonfinite, kCtrStoredZeros,
+  kCtrListWave, kCtrListLds, kCtrListLong,   // rows listed per length class (canon_list_rows)
+  kCtrLongEntries,                           // entries of the rows of the last class: the key work space they need
+  kCtrMerged,                                // entries that merged into a predecessor of equal column (canon_sort_rows)
+  kCtrSlots = 16
+};
+// resets ctr and checks ptr[0] == 0, ptr[r + 1] >= ptr[r], ptr[m] == nnz: ctr[kCtrFirstBadOffset] = the first r that fails
+// (m for the last test).  Reads ptr[0 .. m] and nothing else.
+void canon_check_offsets(const int64_t* ptr, int64_t m, int64_t nnz, unsigned long long* ctr, hipStream_t s);
+// one pass over the entries of A (offsets sound): the counters above, and row_bits[r] (A.rows words, cleared here) |= 1 where
+// row r has an entry whose column is below its predecessor's, |= 2 where one equals its predecessor's
+template <typename T>
+void canon_check_entries(const CsrView<T>& A, uint32_t* row_bits, unsigned long long* ctr, hipStream_t s);
+// rows with row_bits != 0 -> lists[c * m ..) for length class c (0: <= 64 entries, 1: <= canon_lds_cap(), 2: longer),
+// counted in ctr[kCtrListWave + c]; long_off[j] = where the j-th row of class 2 keeps its keys (ctr[kCtrLongEntries] in all)
+void canon_list_rows(const int64_t* ptr, const uint32_t* row_bits, int64_t m, uint32_t* lists, unsigned long long* long_off,
+                     unsigned long long* ctr, hipStream_t s);
+int64_t canon_lds_cap();
+// the listed rows of A, sorted by (column, stored position), into out_idx / out_val at A's offsets (values gathered from A,
+// which the outputs must not overlap); distinct[r] = the row's distinct columns; ctr[kCtrMerged] += length - distinct
+template <typename T>
+void canon_sort_rows(const CsrView<T>& A, const uint32_t* lists, const unsigned long long* long_off, const int64_t counts[3],
+                     unsigned long long* key_space, int32_t* out_idx, T* out_val, uint32_t* distinct, unsigned long long* ctr,
+                     hipStream_t s);
+// new_ptr[r] = row_bits[r] ? distinct[r] : ptr[r + 1] - ptr[r], new_ptr[m] = 0 (exclusive_scan_i64 makes offsets of them)
+void canon_new_lengths(const int64_t* ptr, const uint32_t* row_bits, const uint32_t* distinct, int64_t m, int64_t* new_ptr,
+                       hipStream_t s);
+// (idx, val) at offsets ptr, every row sorted -> (out_idx, out_val) at new_ptr: a run of equal columns becomes one entry, its
+// value the run's sum added left to right in T; an entry that does not merge keeps its bit pattern
+template <typename T>
+void canon_merge_fill(const int64_t* ptr, const int32_t* idx, const T* val, int64_t m, const int64_t* new_ptr, int32_t* out_idx,
+                      T* out_val, hipStream_t s);
+
 // dst[0 .. bytes) = src[0 .. bytes) by a 16-byte-per-lane streaming kernel (the attainable-HBM-rate probe of sapca_measure_copy_gbs)
 void stream_copy16(const void* src, void* dst, int64_t bytes, hipStream_t s);
 

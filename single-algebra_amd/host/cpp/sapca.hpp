@@ -59,6 +59,10 @@ enum class Direction : int32_t { ROW = 0, COLUMN = 1 };
 // A CsrMatrix uploaded once into buffers owned by a handle: Normalize / Log1P / MatrixSum / MatrixNonZero /
 // MatrixMinMax (src/sparse/csr.rs:23-134, 259-392, 558-630, 917-1078) run on the resident copy and the device
 // entry points of the estimators take the same arrays (src/lib.rs:28-33: normalize -> log1p -> PCA).
+// sapca_csr_report: what the check found in a device CSR; canonical: safe offsets and columns, rows ascending without repeats
+using CsrReport = sapca_csr_report;
+inline bool is_canonical(const CsrReport& r) { return (r.flags & 15u) == 0; }
+
 template <typename T> struct ResidentAbi;
 #define SAPCA_RES(SUF, T)                                                                                          \
   template <> struct ResidentAbi<T> {                                                                              \
@@ -69,6 +73,8 @@ template <typename T> struct ResidentAbi;
     static sapca_status batch_stats(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, int32_t ax, const int32_t* c, uint64_t cl, uint32_t nb, double* mean, double* var, uint64_t* cnt) { return sapca_batch_stats_csr_device_##SUF(h, m, n, nnz, p, i, v, ax, c, cl, nb, mean, var, cnt); } \
     static sapca_status masked_stats(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, int32_t d, const uint8_t* mk, uint64_t ml, double* s, double* q, uint64_t* c, double* var) { return sapca_masked_stats_csr_device_##SUF(h, m, n, nnz, p, i, v, d, mk, ml, s, q, c, var); } \
     static sapca_status n_top(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, const uint64_t* ns, uint32_t k, double* out) { return sapca_sum_row_n_top_csr_device_##SUF(h, m, n, nnz, p, i, v, ns, k, out); } \
+    static sapca_status check(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, sapca_csr_report* rep) { return sapca_check_csr_device_##SUF(h, m, n, nnz, p, i, v, rep); } \
+    static sapca_status canonicalize(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, uint64_t* nnz_out, const int64_t** op, const int32_t** oi, T** ov, sapca_csr_report* rep) { return sapca_canonicalize_csr_device_##SUF(h, m, n, nnz, p, i, v, nnz_out, op, oi, ov, rep); } \
     static sapca_status select_rows(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, const uint64_t* rows, uint64_t nr, uint64_t* nnz_out, const int64_t** op, const int32_t** oi, T** ov) { return sapca_select_rows_csr_device_##SUF(h, m, n, nnz, p, i, v, rows, nr, nnz_out, op, oi, ov); } \
   };
 SAPCA_RES(f32, float)
@@ -139,6 +145,22 @@ class ResidentCsr {
   ResidentCsr select_rows(const std::vector<uint64_t>& rows) const {
     ResidentCsr out(h_, (uint64_t)rows.size(), n_);
     check(ResidentAbi<T>::select_rows(h_, m_, n_, nnz_, ptr_, idx_, val_, rows.data(), rows.size(), &out.nnz_, &out.ptr_, &out.idx_, &out.val_));
+    return out;
+  }
+  // What the arrays are (sapca_check_csr_device_*): safe offsets and columns, rows ascending without repeats.  Read-only.
+  CsrReport check_csr() const {
+    CsrReport rep{};
+    rep.struct_size = (uint32_t)sizeof(rep);
+    check(ResidentAbi<T>::check(h_, m_, n_, nnz_, ptr_, idx_, val_, &rep));
+    return rep;
+  }
+  // The same matrix with every row sorted by column and equal columns summed left to right (sapca_canonicalize_csr_device_*),
+  // in the handle's canonical buffers beside this one; this matrix itself when it is canonical already.  `report` (may be
+  // null) receives the report of THIS matrix.  Valid until the next canonicalize on the handle.
+  ResidentCsr canonicalize(CsrReport* report = nullptr) const {
+    ResidentCsr out(h_, m_, n_);
+    if (report) report->struct_size = (uint32_t)sizeof(*report);
+    check(ResidentAbi<T>::canonicalize(h_, m_, n_, nnz_, ptr_, idx_, val_, &out.nnz_, &out.ptr_, &out.idx_, &out.val_, report));
     return out;
   }
   uint64_t nrows() const { return m_; }

@@ -41,6 +41,23 @@ class Timings(C.Structure):
     ]
 
 
+# sapca_csr_report and its flags (sapca_check_csr_device_*, sapca_canonicalize_csr_device_*)
+CSR_BAD_OFFSETS, CSR_COL_RANGE, CSR_UNSORTED, CSR_DUPLICATES, CSR_NONFINITE = 1, 2, 4, 8, 16
+CSR_FLAG_NAMES = {CSR_BAD_OFFSETS: "BAD_OFFSETS", CSR_COL_RANGE: "COL_RANGE", CSR_UNSORTED: "UNSORTED",
+                  CSR_DUPLICATES: "DUPLICATES", CSR_NONFINITE: "NONFINITE"}
+
+
+class CsrReport(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_uint32),
+        ("first_bad_offset_row", C.c_uint64), ("cols_out_of_range", C.c_uint64), ("first_out_of_range_row", C.c_uint64),
+        ("unsorted_rows", C.c_uint64), ("first_unsorted_row", C.c_uint64),
+        ("duplicate_entries", C.c_uint64), ("first_duplicate_row", C.c_uint64),
+        ("nonfinite_values", C.c_uint64), ("first_nonfinite_row", C.c_uint64),
+        ("stored_zeros", C.c_uint64),
+    ]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p)
 
 # every symbol include/sapca.h declares (the CPU test checks the library exports each one)
@@ -54,7 +71,7 @@ _TYPED = [
     "sapca_normalize_panel", "sapca_generate_omega",
     "sapca_upload_csr", "sapca_normalize_csr_device", "sapca_log1p_csr_device", "sapca_stats_csr_device",
     "sapca_batch_stats_csr_device", "sapca_sum_row_n_top_csr_device", "sapca_masked_stats_csr_device",
-    "sapca_select_rows_csr_device",
+    "sapca_select_rows_csr_device", "sapca_check_csr_device", "sapca_canonicalize_csr_device",
     "sapca_multi_fit_csr", "sapca_multi_transform_csr", "sapca_multi_fit_transform_csr",
     "sapca_multi_upload_csr", "sapca_multi_transform_resident", "sapca_multi_fit_transform_resident",
 ]

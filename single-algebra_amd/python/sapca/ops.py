@@ -121,6 +121,36 @@ def _row_list(rows, m):
     return np.ascontiguousarray(a, dtype=np.uint64)
 
 
+class CsrReport:
+    """What sapca_check_csr_device_* / sapca_canonicalize_csr_device_* found in a device CSR (sapca_csr_report): the counts
+    and first rows as attributes (a first_*_row is None where its count is zero), `flags` as the tuple of the names of the
+    bits that are set (BAD_OFFSETS, COL_RANGE, UNSORTED, DUPLICATES, NONFINITE), `bits` as the number, and `canonical`:
+    none of the first four is set."""
+
+    _FIRSTS = ("first_bad_offset_row", "first_out_of_range_row", "first_unsorted_row", "first_duplicate_row", "first_nonfinite_row")
+    _COUNTS = ("cols_out_of_range", "unsorted_rows", "duplicate_entries", "nonfinite_values", "stored_zeros")
+
+    def __init__(self, raw):
+        self.bits = int(raw.flags)
+        self.flags = tuple(name for bit, name in sorted(L.CSR_FLAG_NAMES.items()) if self.bits & bit)
+        self.canonical = (self.bits & 15) == 0
+        for f in self._COUNTS:
+            setattr(self, f, int(getattr(raw, f)))
+        for f in self._FIRSTS:
+            v = int(getattr(raw, f))
+            setattr(self, f, None if v == 2 ** 64 - 1 else v)
+
+    def __repr__(self):
+        body = ", ".join(f"{f}={getattr(self, f)}" for f in self._COUNTS + self._FIRSTS if getattr(self, f) not in (0, None))
+        return f"CsrReport(flags={'|'.join(self.flags) or '0'}{', ' + body if body else ''})"
+
+
+def _new_report():
+    r = L.CsrReport()
+    r.struct_size = C.sizeof(L.CsrReport)
+    return r
+
+
 class ResidentCsr:
     """A CSR matrix uploaded once into buffers owned by a Session (sapca_upload_csr_*): normalize -> log1p ->
     statistics -> PCA on it without crossing PCIe again.  `as_device_csr()` gives the
@@ -370,6 +400,55 @@ class ResidentCsr:
             *self._args(), _p(r, C.c_uint64) if r.size else None, C.c_uint64(r.size), C.byref(nnz_out), C.byref(dp), C.byref(di),
             C.byref(dv)))
         return ResidentCsr(self._s, (r.size, self.shape[1]), nnz_out.value, self.dtype, dp.value or 0, di.value or 0, dv.value or 0)
+
+    @classmethod
+    def from_torch(cls, session, row_offsets, col_indices, values, shape):
+        """Adopt a caller's own device arrays -- three contiguous CUDA tensors: int64 offsets (m + 1), int32 column indices
+        and f32 / f64 values of equal length -- as a ResidentCsr of `session`, without copying.  The object keeps
+        references to the tensors.  Nothing is validated here: check() / canonicalize() are the gate, before anything else.
+        Stream order: the Session works on its own stream (or the one it was given), not on torch's.  Tensors that torch
+        kernels have just written on another stream must be complete first -- torch.cuda.current_stream().synchronize(),
+        or build the Session on torch's current stream -- or check() / canonicalize() race with their producer."""
+        import torch
+        m, n = (int(x) for x in shape)
+        want = {"row_offsets": (row_offsets, torch.int64), "col_indices": (col_indices, torch.int32)}
+        for name, (t, dt) in want.items():
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.dim() == 1 and t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous one-dimensional CUDA tensor of {dt}")
+        if not (isinstance(values, torch.Tensor) and values.is_cuda and values.dtype in (torch.float32, torch.float64)
+                and values.dim() == 1 and values.is_contiguous()):
+            raise ValueError("values must be a contiguous one-dimensional CUDA tensor of float32 or float64")
+        if row_offsets.numel() != m + 1 or col_indices.numel() != values.numel():
+            raise ValueError(f"shape {(m, n)} wants {m + 1} row offsets and as many column indices as values, got "
+                             f"{row_offsets.numel()}, {col_indices.numel()} and {values.numel()}")
+        dt = np.float32 if values.dtype == torch.float32 else np.float64
+        out = cls(session, (m, n), values.numel(), dt, row_offsets.data_ptr(), col_indices.data_ptr(), values.data_ptr())
+        out._keep = (row_offsets, col_indices, values)
+        return out
+
+    def check(self):
+        """sapca_check_csr_device_*: a CsrReport of these arrays (read-only, one pass on the GPU).  `.canonical` says
+        whether every entry point may take them as they are."""
+        suf, _ = _SUF[self.dtype]
+        rep = _new_report()
+        L.check(self._s._h, getattr(L.load(), f"sapca_check_csr_device_{suf}")(*self._args(), C.byref(rep)))
+        return CsrReport(rep)
+
+    def canonicalize(self):
+        """sapca_canonicalize_csr_device_*: (matrix, report) -- the same matrix with every row's columns ascending and equal
+        columns summed (left to right in stored order), and the CsrReport of THIS matrix (duplicate_entries exact).  The
+        matrix is `self` when nothing had to be done; otherwise it lives in the Session's canonical buffers, beside this
+        one, until the next canonicalize on the Session.  Broken offsets or a column out of range raise SapcaError."""
+        suf, _ = _SUF[self.dtype]
+        rep = _new_report()
+        nnz_out = C.c_uint64()
+        dp, di, dv = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        L.check(self._s._h, getattr(L.load(), f"sapca_canonicalize_csr_device_{suf}")(
+            *self._args(), C.byref(nnz_out), C.byref(dp), C.byref(di), C.byref(dv), C.byref(rep)))
+        got = (dp.value or 0, di.value or 0, dv.value or 0)
+        if got == (self.d_ptr, self.d_idx, self.d_val):
+            return self, CsrReport(rep)
+        return ResidentCsr(self._s, self.shape, nnz_out.value, self.dtype, *got), CsrReport(rep)
 
     def values(self):
         """the current (device) values, copied to the host"""

@@ -51,7 +51,8 @@ class SVDMethod:
 
 class DeviceCsr:
     """HBM-resident CSR: row_offsets int64 [m+1], col_indices int32 [nnz], values f32/f64 [nnz]
-    (torch CUDA tensors), columns ascending and unique per row."""
+    (torch CUDA tensors), columns ascending and unique per row.  Arrays of another origin go through
+    ops.ResidentCsr.from_torch(...).check() / .canonicalize() first (sapca_canonicalize_csr_device_*)."""
 
     def __init__(self, row_offsets, col_indices, values, shape):
         import torch

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Writes single-algebra_amd/host/rust/sapca-sys/src/lib.rs from include/sapca.h: one `extern "C"` item per function the
-header declares (same name, same argument count and order, C types mapped to their Rust FFI twins), the two POD structs and
-the enum constants.  Run it after editing the header; tests/test_abi_cpu.py::test_rust_sys_crate_declares_the_whole_header
+header declares (same name, same argument count and order, C types mapped to their Rust FFI twins), the POD structs, the
+enum constants and the SAPCA_CSR_* flags.  Run it after editing the header; tests/test_abi_cpu.py::test_rust_sys_crate_declares_the_whole_header
 regenerates in memory and compares with the committed file, and checks name + argument-count agreement independently.
 
     python tools/gen_sapca_sys.py            # rewrite the crate source
@@ -19,7 +19,7 @@ SCALARS = {
     "void": "c_void", "char": "c_char", "int": "c_int", "float": "f32", "double": "f64", "size_t": "usize",
     "uint8_t": "u8", "int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64",
     "sapca_status": "c_int", "sapca_handle": "sapca_handle", "sapca_multi": "sapca_multi",
-    "sapca_options": "sapca_options", "sapca_timings": "sapca_timings", "sapca_allreduce_fn": "sapca_allreduce_fn",
+    "sapca_options": "sapca_options", "sapca_timings": "sapca_timings", "sapca_csr_report": "sapca_csr_report", "sapca_allreduce_fn": "sapca_allreduce_fn",
 }
 
 
@@ -98,8 +98,10 @@ def parse_struct(header_text, name):
         if arr:
             fields.append((arr.group(2), "[%s; %s]" % (rust_type(arr.group(1)), arr.group(3))))
             continue
-        mm = re.match(r"(.*?)(\w+)$", decl)
+        names = [x.strip() for x in decl.split(",")]   # `uint64_t a, b, c`: one type, several fields
+        mm = re.match(r"(.*?)(\w+)$", names[0])
         fields.append((mm.group(2), rust_type(mm.group(1))))
+        fields.extend((x, rust_type(mm.group(1))) for x in names[1:])
     return fields
 
 
@@ -128,7 +130,9 @@ def render(header_text):
     w("")
     w("/// `int (*)(void* ctx, void* buf, uint64_t count, int32_t dtype, void* stream)`")
     w("pub type sapca_allreduce_fn = Option<unsafe extern \"C\" fn(*mut c_void, *mut c_void, u64, i32, *mut c_void) -> c_int>;")
-    for struct in ("sapca_options", "sapca_timings"):
+    for name, value in re.findall(r"^#define\s+(SAPCA_CSR_\w+)\s+(\d+)u\b", header_text, flags=re.M):
+        w("pub const %s: u32 = %s;" % (name, value))
+    for struct in ("sapca_options", "sapca_timings", "sapca_csr_report"):
         w("")
         w("#[repr(C)]")
         w("#[derive(Clone, Copy)]")
