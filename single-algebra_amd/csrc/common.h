@@ -63,6 +63,11 @@ struct DevBuf {
   U* as(size_t count) { return static_cast<U*>(ensure(count * sizeof(U))); }
   template <typename U>
   U* ptr() const { return static_cast<U*>(p); }
+  // q points into this buffer's allocation
+  bool contains(const void* q) const {
+    const char* c = static_cast<const char*>(q);
+    return p != nullptr && c >= static_cast<const char*>(p) && c < static_cast<const char*>(p) + cap;
+  }
 };
 
 // Non-owning view of a device CSR matrix (rows x cols).

@@ -124,18 +124,6 @@ double* stats_dev(H& h, int64_t n) { return h.stats.as<double>((size_t)3 * n + 1
 // (above 128 columns every panel is a multiple of 64 wide: column passes of the sweeps, 64 / 128-column blocks of the dense kernels)
 int panel_ld(int k, int ldp) { return k > 128 ? (int)round_up(k, 64) : std::max(ldp, k <= 64 ? 64 : 128); }
 
-// The three arrays of a CSR with `rows` rows and room for `cap` entries, in grow-only buffers of the handle.
-template <typename T>
-struct CsrBuf {
-  int64_t* ptr; int32_t* idx; T* val;
-  H::RawCsr raw(int64_t rows, int64_t cols, int64_t nnz) const { return {rows, cols, nnz, ptr, idx, val}; }
-};
-template <typename T>
-CsrBuf<T> csr_buffers(DevBuf& ptr, DevBuf& idx, DevBuf& val, int64_t rows, int64_t cap) {
-  const size_t entries = (size_t)std::max<int64_t>(cap, 1);
-  return {ptr.as<int64_t>((size_t)rows + 1), idx.as<int32_t>(entries), val.as<T>(entries)};
-}
-
 // The key of the preparation the handle would hold of A under its present mask.
 template <typename T>
 H::PrepKey prep_key_of(const H& h, const CsrView<T>& A) {

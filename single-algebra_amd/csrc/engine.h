@@ -106,13 +106,28 @@ struct sapca_handle_s {
     bool valid = false;
   } up_stats;
   hipEvent_t up_stats_done = nullptr;
+  // the values of the uploaded / the caller's matrix changed: under any cached preparation, and under the upload's statistics
+  void values_changed() { prep_key.valid = false; up_stats.valid = false; }
+  // a preparation cached for a result (selection, canonical) whose arrays are about to change describes them no longer; any other stays
+  template <typename R>
+  void drop_preparation_of(const R& result) {
+    if (prep_key.valid && (result.owns(prep_key.ptr) || result.owns(prep_key.idx) || result.owns(prep_key.val))) prep_key.valid = false;
+  }
   // the row selection of sapca_select_rows_csr_device_*: a CSR of its own beside the upload's, the row list on the device and the
   // scan's work space (nothing else lives in these, so a selection disturbs no cached preparation but one made OF it)
-  sapca::DevBuf sub_ptr, sub_idx, sub_val, sub_rows, sub_scan;
-  // the canonical form of sapca_canonicalize_csr_device_*: a third CSR beside the upload's and the selection's (canon_idx2 /
-  // canon_val2 hold it when duplicates merged: the fill's output), and the work space of the check and the sort: the counter
-  // block, per row {defect bits, distinct columns, three row lists} and the long rows' key offsets, their keys, the scan's
-  sapca::DevBuf canon_ptr, canon_idx, canon_val, canon_idx2, canon_val2, canon_ctr, canon_rows, canon_long, canon_keys, canon_scan;
+  struct Selection {
+    sapca::DevBuf ptr, idx, val, rows, scan;
+    bool owns(const void* q) const { return ptr.contains(q) || idx.contains(q) || val.contains(q); }   // the result's arrays, not the work space
+  } selection;
+  // the canonical form of sapca_canonicalize_csr_device_*: a third CSR beside the upload's and the selection's (idx2 / val2
+  // hold it when duplicates merged: the fill's output), and the work space of the check and the sort: the counter block,
+  // per row {defect bits, distinct columns, three row lists} and the long rows' key offsets, their keys, the scan's
+  struct Canonical {
+    sapca::DevBuf ptr, idx, val, idx2, val2, ctr, rows, long_off, keys, scan;
+    bool owns(const void* q) const {
+      return ptr.contains(q) || idx.contains(q) || val.contains(q) || idx2.contains(q) || val2.contains(q);
+    }
+  } canonical;
   sapca::DevBuf at_ptr, at_idx, at_val;                          // A^T
   sapca::DevBuf ca_ptr, ca_idx, ca_val, cat_ptr, cat_idx, cat_val;  // mask-compacted A, A^T
   sapca::DevBuf drop_stats, drop_tmp;                              // their sums (sum | sumsq, full width) and the sort's work space
@@ -164,6 +179,28 @@ struct SmallLayout {
   double* wsum() const { return base + 6 * W * W + 64 + 2 * W; }
   double* behind() const { return base + 6 * W * W + 64 + 4 * W; }
 };
+
+// The three arrays of a CSR with `rows` rows and room for `cap` entries, in grow-only buffers of the handle.
+template <typename T>
+struct CsrBuf {
+  int64_t* ptr; int32_t* idx; T* val;
+  sapca_handle_s::RawCsr raw(int64_t rows, int64_t cols, int64_t nnz) const { return {rows, cols, nnz, ptr, idx, val}; }
+};
+template <typename T>
+CsrBuf<T> csr_buffers(DevBuf& ptr, DevBuf& idx, DevBuf& val, int64_t rows, int64_t cap) {
+  const size_t entries = (size_t)std::max<int64_t>(cap, 1);
+  return {ptr.as<int64_t>((size_t)rows + 1), idx.as<int32_t>(entries), val.as<T>(entries)};
+}
+
+// A^T in natural row order in the handle's at_*, on the main stream; no wait.  Those buffers are shared with prepare(), so
+// whatever preparation the handle had cached is gone.
+template <typename T>
+CsrView<T> transpose_into_at(sapca_handle_s& h, const CsrView<T>& A) {
+  h.prep_key.valid = false;
+  const CsrBuf<T> at = csr_buffers<T>(h.at_ptr, h.at_idx, h.at_val, A.cols, A.nnz);
+  k::transpose_csr(A, at.ptr, at.idx, at.val, h.scratch, h.stream);
+  return CsrView<T>{A.cols, A.rows, A.nnz, at.ptr, at.idx, at.val};
+}
 
 // What a normalisation takes beyond its panel.
 template <typename T>

@@ -1,0 +1,54 @@
+// The operations on a device-resident CSR behind the sapca_*_csr_device_* entry points: preprocessing,
+// statistics, row selection, check / canonicalise.  Host side only: buffer layouts, launches, the finishing arithmetic.
+// They throw sapca::Error; api.cpp turns that into a status.
+#pragma once
+#include "engine.h"
+
+namespace sapca {
+
+// The caller's device arrays as a view, NOT checked: every operation below runs check_view() on it, at the point where its
+// argument checks reach the matrix (their order is part of the ABI's behaviour).
+template <typename T>
+CsrView<T> unchecked_view(uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v) {
+  CsrView<T> a;
+  a.rows = (int64_t)m; a.cols = (int64_t)n; a.nnz = (int64_t)nnz; a.ptr = p; a.idx = i; a.val = v;
+  return a;
+}
+template <typename T>
+void check_view(const CsrView<T>& a) {
+  SAPCA_CHECK(a.ptr != nullptr && (a.nnz == 0 || (a.idx && a.val)), SAPCA_ERR_ARG, "null CSR array");
+  SAPCA_CHECK((uint64_t)a.cols < (1ull << 31) && (uint64_t)a.rows < (1ull << 31), SAPCA_ERR_ARG,
+              "more than 2^31-1 rows or columns is not supported");
+}
+
+namespace resident {
+
+using H = sapca_handle_s;
+
+template <typename T>
+void normalize(H& h, const CsrView<T>& A, T* v, const double* sums, uint64_t sums_len, double target, int32_t direction);
+template <typename T>
+void log1p(H& h, uint64_t nnz, T* v);
+// direction 0: per row (sum_row, sum_row_squared, nonzero_row, min_max_row); 1: per column (the same on A^T)
+template <typename T>
+void stats(H& h, const CsrView<T>& A, int32_t direction, double* sum, double* sumsq, uint64_t* nonzero, T* minv, T* maxv);
+template <typename T>
+void batch_stats(H& h, const CsrView<T>& A, int32_t grouped_axis, const int32_t* codes, uint64_t codes_len, uint32_t n_batches,
+                 double* mean, double* var, uint64_t* count);
+template <typename T>
+void masked_stats(H& h, const CsrView<T>& A, int32_t direction, const uint8_t* mask, uint64_t mask_len, double* sum, double* sumsq,
+                  uint64_t* count, double* var);
+// MatrixNTop::sum_row_n_top (csr.rs:1347-1376) for several n in one pass over the rows: out[i * m + r]
+template <typename T>
+void top_n(H& h, const CsrView<T>& A, const uint64_t* ns, uint32_t n_ns, double* out);
+template <typename T>
+void select_rows(H& h, const CsrView<T>& A, const uint64_t* rows, uint64_t n_rows, uint64_t* nnz_out, const int64_t** d_ptr,
+                 const int32_t** d_idx, T** d_val);
+template <typename T>
+void check(H& h, const CsrView<T>& A, sapca_csr_report* report);
+template <typename T>
+void canonicalize(H& h, const CsrView<T>& A, uint64_t* nnz_out, const int64_t** d_ptr, const int32_t** d_idx, T** d_val,
+                  sapca_csr_report* report);
+
+}  // namespace resident
+}  // namespace sapca

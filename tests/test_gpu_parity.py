@@ -1334,6 +1334,77 @@ def test_transform_after_the_values_were_edited_in_place():
     assert np.abs(t - t_fit).max() > 0.1 * np.abs(t_fit).max()   # and it is not the projection of the fitted values
 
 
+def test_statistics_of_another_matrix_in_the_handle_leave_fit_and_projection_of_the_first_alone():
+    """Statistics of ANOTHER matrix run in the handle that holds a fitted matrix's preparation, and they share buffers with
+    it: the transposition of the column direction and of the per-batch statistics (codes on the rows) goes into at_*, the
+    row / column statistics write h.stats and out_tmp.  Each of them drops the cached preparation (transpose_into_at() in
+    csrc/engine.h; resident::stats in csrc/resident.cpp).  The other matrix is the first with its rows reversed -- same
+    m, n and nnz: anything stale would be wrong but never out of bounds.
+
+    Who reads the key: only transform() (select_projection_operator in csrc/engine.cpp, `pr.prepared`); fit() prepares
+    unconditionally.  A prepared unmasked projection reads A itself, A's tile-major format and the per-column counts (the
+    reference semantics' weights) at h.stats + 2n.  So
+      - the ROW statistics (m entries per array, m != n) leave sums where those counts were: with the line in
+        resident::stats removed, the last projection below is weighted by them and fails.  That line is what this guards;
+      - the per-batch and the COLUMN statistics overwrite nothing a projection reads today (at_* is read by the sweeps of a
+        fit only; the reversed rows have the first matrix's column counts): their projections pin that the result is the
+        same on either side of the key, not the line in transpose_into_at();
+      - the second fit gives mean_ byte for byte (the statistics gathered behind the upload stay valid through all of it)
+        and the same singular values because fit() prepares again whatever the key says.
+    f64 at this size: route `Transposed`, no tile-major format (below the staged sweep's floor)."""
+    import batch_stats_ref as B
+    m, n, k, p, q = 3000, 600, 6, 6, 2
+    ptr, idx, val = csr_np(synth.gapped_csr(m, n, 0.05, k, seed=42, dtype=torch.float64))
+    A = mat(ptr, idx, val, m, n)
+    A.sort_indices()
+    om = synth.gaussian_panel(n, k + p, 42).numpy()
+    est = _builder(k, p, q).build().set_omega(om)
+
+    class _InHandleOf:   # a Session-shaped view of the estimator's handle (not owned)
+        _h = est._h
+        _csr_args = ops.Session._csr_args
+        upload = ops.Session.upload
+    sess = _InHandleOf()
+    R = sess.upload(A.indptr, A.indices, A.data, m, n)
+    est.fit(R.as_device_csr())
+    mean0, sing0 = est.mean_(np.float64).copy(), est.singular_values_(np.float64).copy()
+    t0 = est.transform(R.as_device_csr()).cpu().numpy()                          # through the preparation the fit left
+    tw = O.transform_sparse(A.indptr.astype(np.int64), A.indices.astype(np.int64), A.data, m, n, est.components_(np.float64), mean0, True)
+    scale = max(1.0, float(np.abs(tw).max()))
+    np.testing.assert_allclose(t0, tw, atol=1e-9 * scale)                        # (the bar of the f64 projections in test_gpu_select_rows.py)
+
+    Bm = A[::-1].tocsr()
+    Bm.sort_indices()
+    assert Bm.shape == A.shape and Bm.nnz == A.nnz
+    bptr, bidx, bval = Bm.indptr.astype(np.int64), Bm.indices.astype(np.int64), Bm.data
+    dev = [torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (bptr, bidx.astype(np.int32), bval)]
+    torch.cuda.synchronize()
+    RB = ops.ResidentCsr.from_torch(sess, *dev, (m, n))
+
+    codes = np.random.default_rng(3).integers(0, 3, m).astype(np.int32)
+    bat = RB.batch_stats(0, codes, 3)                                            # transposes B into at_*: the helper's line alone
+    np.testing.assert_allclose(est.transform(R.as_device_csr()).cpu().numpy(), t0, rtol=0, atol=1e-9 * scale, err_msg="after the per-batch statistics")
+    col = RB.stats(ops.COLUMN)
+    np.testing.assert_allclose(est.transform(R.as_device_csr()).cpu().numpy(), t0, rtol=0, atol=1e-9 * scale, err_msg="after the column statistics")
+
+    est.fit(R.as_device_csr())
+    assert est.mean_(np.float64).tobytes() == mean0.tobytes()
+    np.testing.assert_allclose(est.singular_values_(np.float64), sing0, rtol=1e-5)
+    row = RB.stats(ops.ROW)                                                      # h.stats now holds m sums where the n counts were
+    np.testing.assert_allclose(est.transform(R.as_device_csr()).cpu().numpy(), t0, rtol=0, atol=1e-9 * scale, err_msg="after the row statistics")
+
+    for got, direction in ((col, ops.COLUMN), (row, ops.ROW)):
+        want = O.stats_csr(bptr, bidx, bval, m, n, direction)
+        for j, name in ((0, "sum"), (1, "sumsq")):
+            np.testing.assert_allclose(got[j], want[j], rtol=1e-12, atol=1e-12 * max(1.0, float(np.abs(want[j]).max())), err_msg=name)
+        for j in (2, 3, 4):
+            np.testing.assert_array_equal(got[j], want[j])
+    mean, var, cnt = B.batch_stats(bptr, bidx, bval, m, n, 0, codes, 3)
+    np.testing.assert_array_equal(bat["count"], cnt)
+    for name, w in (("mean", mean), ("var", var)):
+        np.testing.assert_allclose(bat[name], w, rtol=1e-9, atol=1e-9 * max(1.0, float(np.abs(w).max())), err_msg=name)
+
+
 def test_fit_after_the_uploaded_values_were_edited_in_place():
     """sapca_upload_csr_* on the ESTIMATOR's handle hands back a writable d_values; the statistics gathered behind that
     upload serve a fit of the arrays as uploaded.  A caller that edits the values with its own kernel calls
