@@ -415,12 +415,12 @@ sapca_status spmm_host(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, con
     if (!transposed) {
       if (mu) sapca::k::weighted_colsum(X, (int64_t)n, ld, d_mu, cvec, h->scratch, s);
       const sapca::TiledOp* top = nullptr;
-      if (want_tiled && sapca::k::build_tiled(A, 64, h->tiled_a, h->tb_a, s)) top = &h->tiled_a;   // else: row kernel
+      if (want_tiled && sapca::k::build_tiled(A, 64, h->tiled_a, h->tb_a, s, sapca::k::QuadSource::csr())) top = &h->tiled_a;   // else: row kernel
       sapca::k::spmm(A, top, X, ld, Y, ld, ld, mu ? cvec : nullptr, h->opt.spmm_variant, h->split_scratch, s);
     } else {
       const CsrView<T> At = sapca::transpose_into_at(*h, A);
       const sapca::TiledOp* top = nullptr;
-      if (want_tiled && sapca::k::build_tiled(At, 64, h->tiled_at, h->tb_at, s)) top = &h->tiled_at;
+      if (want_tiled && sapca::k::build_tiled(At, 64, h->tiled_at, h->tb_at, s, sapca::k::QuadSource::csr())) top = &h->tiled_at;
       sapca::k::spmm(At, top, X, ld, Y, ld, ld, (const T*)nullptr, h->opt.spmm_variant, h->split_scratch, s);
       if (mu) {
         sapca::k::weighted_colsum(X, (int64_t)m, ld, (const T*)nullptr, svec, h->scratch, s);

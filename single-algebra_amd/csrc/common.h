@@ -136,7 +136,7 @@ struct TiledOp {
   int64_t mid_row0 = -1;               // blk_row0[nrb / 2] on the host (the cut of a sweep in two pieces); -1: not recorded
   const uint32_t* row_perm = nullptr;  // [rows] slot position -> row (rows sorted by length, longest first); null = identity
   const int64_t* chunk_off = nullptr;  // [nrb*nct+1] entry offsets
-  const uint32_t* wave_off = nullptr;  // [nrb*nct][8]
+  const uint32_t* wave_off = nullptr;  // [nrb*nct][16] entry offset of every wave's first quad inside the chunk
   const uint8_t* steps = nullptr;      // [nrb*nct][256]
   const void* ent = nullptr;           // {u32 lds byte offset, f32 value} or {u32 offset, u32 pad, f64 value}
   // DPP-fed sweep (spmm_dq.hip): per (row block, wave, tile) {entry offset / 8, 16-step chunks}
@@ -144,7 +144,10 @@ struct TiledOp {
   const uint32_t* dq_info = nullptr;
 };
 struct TiledBuffers {
-  DevBuf blk, seg, steps, wave_off, chunk_off, ent, tmp, misc, run, rank, perm, lens, dq_info, bounds;
+  DevBuf blk, steps, wave_off, chunk_off, ent, tmp, misc, perm, lens, dq_info, bounds;
+  DevBuf seg;        // [row][tile + 1] per-row tile index; on the A -> A^T route the histogram instead: [tile][column] 16-bit entry counts
+  DevBuf quad_off;   // [row block][quad][tile] entry offset of the quad's segment inside its chunk
+  DevBuf raw;        // (A -> A^T) stored entries per chunk, scanned into the bucket offsets
   PinnedBuf host;   // page-locked staging of the builder's small host <-> device exchanges
   // the DPP-fed sweep's tables are a latency-bound kernel over the counts: it runs on this stream beside the
   // bandwidth-bound fill (fork / join events on the build's own stream)

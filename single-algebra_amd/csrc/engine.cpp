@@ -159,7 +159,7 @@ H::RawCsr compact_a(H& h, const CsrView<T>& A, const int32_t* d_o2m, int64_t n_u
 //  A^T                 | taken by                                   | what happens
 //  Nothing             | Lanczos, n_used <= m, m >= 4096, nnz > 0,  | no transposed operator: the second product of a step scatters into LDS (scatter.hip,
 //                      | k::scatter_fits (~19k columns: C3 has 18k) | fixed-point sums: reproducible); masked fits still compact A
-//  FormatFromA         | f32, staged sweep, unmasked                | A^T's tile-major format straight from A (spmm_tiled.hip, "bucket route"): no sort, no
+//  FormatFromA         | f32, staged sweep, unmasked                | A^T's tile-major format straight from A (tiled_build.hip, "bucket route"): no sort, no
 //                      |                                            | transposed CSR; outside its limits (more than 65536 columns, ...) refused: Transposed
 //  FormatFromCompacted | f32, staged sweep, masked, n_used <= 65536 | compaction, then the same builder on its result; refused: CompactedTransposed
 //  CompactedTransposed | every other masked fit                     | compaction, then its transposition into cat_*
@@ -334,7 +334,7 @@ void start_a_format_aside(H& h, const CsrView<T>& A, const PrepPlan& p, PrepOutc
     try {
       SAPCA_HIP(hipSetDevice(h.device));
       SAPCA_HIP(hipStreamWaitEvent(h.stream2, h.ev_fork, 0));
-      if (p.tiled_ldp != 0) out.ok_a = k::build_tiled(src, p.tiled_ldp, h.tiled_a, h.tb_a, h.stream2);
+      if (p.tiled_ldp != 0) out.ok_a = k::build_tiled(src, p.tiled_ldp, h.tiled_a, h.tb_a, h.stream2, k::QuadSource::csr());
       SAPCA_HIP(hipEventRecord(h.ev_join, h.stream2));
     } catch (...) {
       aside.err = std::current_exception();
@@ -489,15 +489,18 @@ void build_formats(H& h, const PrepPlan& p, PrepOutcome<T>& out, Aside& aside) {
   Scope sc(h, C_PREPARE);
   const CsrView<T> at = Engine<T>::view(h.at_used);
   bool ok_at = out.at_direct;
+  const k::QuadSource at_rows = p.at_nct != 0 ? k::QuadSource::tile_major() : k::QuadSource::csr();   // (how at_transpose ordered them)
   if constexpr (sizeof(T) == 4) {
-    if (!ok_at) ok_at = k::build_tiled(at, p.tiled_ldp, h.tiled_at, h.tb_at, s, p.at_nct != 0, out.at_packed, out.at_seg_ready);
+    if (!ok_at)
+      ok_at = k::build_tiled(at, p.tiled_ldp, h.tiled_at, h.tb_at, s,
+                             out.at_packed ? k::QuadSource::tile_major_packed(out.at_packed, out.at_seg_ready) : at_rows);
     if (out.at_packed && !ok_at) {   // someone needs the transposed CSR after all
       k::unpack_transposed(out.at_packed, p.nnz, const_cast<int32_t*>(out.At.idx), const_cast<float*>(out.At.val), s);
       out.at_packed = nullptr;
-      ok_at = k::build_tiled(at, p.tiled_ldp, h.tiled_at, h.tb_at, s, p.at_nct != 0);
+      ok_at = k::build_tiled(at, p.tiled_ldp, h.tiled_at, h.tb_at, s, at_rows);
     }
   } else {
-    ok_at = k::build_tiled(at, p.tiled_ldp, h.tiled_at, h.tb_at, s, p.at_nct != 0);
+    ok_at = k::build_tiled(at, p.tiled_ldp, h.tiled_at, h.tb_at, s, at_rows);
   }
   aside.join();
   const bool ok_a = out.ok_a;
@@ -571,7 +574,7 @@ void Engine<T>::prepare(H& h, const CsrView<T>& A) {
   if (!lz_scatter && !out.at_direct) at_transpose(h, A, p, maps, out);
   if (a_aside_late) {
     h.tiled_a = TiledOp();
-    out.ok_a = k::build_tiled(A, p.tiled_ldp, h.tiled_a, h.tb_a, h.stream2);
+    out.ok_a = k::build_tiled(A, p.tiled_ldp, h.tiled_a, h.tb_a, h.stream2, k::QuadSource::csr());
     SAPCA_HIP(hipEventRecord(h.ev_join, h.stream2));   // ...and the main stream waits for it at the end of prepare()
     out.a_aside = true;
   }
@@ -1276,7 +1279,7 @@ Projection<T> select_projection_operator(H& h, const CsrView<T>& A) {
       h.prep_key.valid = false;   // (tiled_a no longer belongs to the fitted matrix)
       h.tiled_at = TiledOp();
       h.tiled_a = TiledOp();
-      if (k::build_tiled(pr.Au, ldp_t, h.tiled_a, h.tb_a, s) && h.tiled_a.valid) pr.top = &h.tiled_a;
+      if (k::build_tiled(pr.Au, ldp_t, h.tiled_a, h.tb_a, s, k::QuadSource::csr()) && h.tiled_a.valid) pr.top = &h.tiled_a;
       else h.tiled_a = TiledOp();
     }
   }

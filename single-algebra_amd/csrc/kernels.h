@@ -189,18 +189,41 @@ template <typename T>
 void colstats_scatter(const CsrView<T>& A, const unsigned long long* amax_bits, double* sum, double* sumsq, double* cnt, DevBuf& scratch,
                       hipStream_t s);
 
-// ---- spmm_tiled.hip ---------------------------------------------------------------------
+// ---- tiled_build.hip: builders of the tile-major "quad" format the staged sweeps read ---------------------------
+// Where the rows of the operator come from, which decides the builder's route.
+struct AtDirectSrc;   // (tiled_build.hip: what build_tiled_at_direct hands the builder)
+struct QuadSource {
+  enum Kind {
+    Csr,               // S is a CSR with ascending columns
+    TileMajorCsr,      // S's rows were produced by transpose_csr(..., tile_major_nct = tiled_tile_count(S.cols, ldp))
+    TileMajorPacked,   // ... and left packed: S.idx / S.val are not filled, `packed` holds (row << 32 | value bits); f32 only
+    FromA              // A^T straight from A: build_tiled_at_direct's own
+  };
+  Kind kind = Csr;
+  const uint64_t* packed = nullptr;
+  bool seg_ready = false;                // TileMajorPacked: buf.seg already holds the per-row tile index (at_stats_index)
+  const AtDirectSrc* from_a = nullptr;   // FromA
+  static QuadSource csr() { return QuadSource(); }
+  static QuadSource tile_major() {
+    QuadSource q;
+    q.kind = TileMajorCsr;
+    return q;
+  }
+  static QuadSource tile_major_packed(const uint64_t* packed, bool seg_ready) {
+    QuadSource q;
+    q.kind = TileMajorPacked;
+    q.packed = packed;
+    q.seg_ready = seg_ready;
+    return q;
+  }
+};
 // Builds the tile-major format of an f32 operator for panels of leading dimension ldp (64).
-// Returns false (op.valid == false) when the operator does not fit the LDS staging; callers then
-// stay on the row kernel.
-// rows_tile_major: S's rows were produced by transpose_csr(..., tile_major_nct = tiled_tile_count(S.cols, ldp))
-bool build_tiled(const CsrView<float>& S, int ldp, TiledOp& op, TiledBuffers& buf, hipStream_t s,
-                 bool rows_tile_major = false, const uint64_t* packed_rows = nullptr,   // packed_rows: S.idx / S.val are not
-                                                                                         // filled, read (row << 32 | value) instead
-                 bool seg_ready = false);   // buf.seg already holds the per-row tile index (at_stats_index)
+// Returns false (op.valid == false) when the operator is outside the route's limits or does not fit the LDS staging;
+// callers then stay on the row kernel.  Synchronises with the host (the entry counts come back).
+bool build_tiled(const CsrView<float>& S, int ldp, TiledOp& op, TiledBuffers& buf, hipStream_t s, const QuadSource& src);
 // The same format with f64 values for panels of 64 f64 columns (512-byte rows: the tile geometry of the
-// 128-float panels); built from a CSR in natural row order by the direct fill.
-bool build_tiled(const CsrView<double>& S, int ldp, TiledOp& op, TiledBuffers& buf, hipStream_t s, bool rows_tile_major = false);
+// 128-float panels); from a CSR (LDS-staged fill, direct scatter as the fallback) or a tile-major CSR (streaming fill).
+bool build_tiled(const CsrView<double>& S, int ldp, TiledOp& op, TiledBuffers& buf, hipStream_t s, const QuadSource& src);
 // The format of A^T (op: A.cols x A.rows) straight from A, without a transposed CSR: a histogram per (tile of A rows,
 // column), a scatter of A's entries into per-chunk buckets, one workgroup per chunk for the format.  Byte-identical to
 // build_tiled on the tile-major transposition.  at_ptr (A.cols + 1) receives A^T's row offsets, stats (2 * A.cols, may
@@ -209,11 +232,13 @@ bool build_tiled(const CsrView<double>& S, int ldp, TiledOp& op, TiledBuffers& b
 bool build_tiled_at_direct(const CsrView<float>& A, int ldp, TiledOp& op, TiledBuffers& buf, int64_t* at_ptr, double* stats,
                            DevBuf& scratch, hipStream_t s);
 // Column statistics of A (row sums / sums of squares of the packed tile-major A^T rows, same summation order as
-// row_sums) and, in the same pass, the per-row tile index build_tiled(..., rows_tile_major, packed, ., seg_ready) needs.
+// row_sums) and, in the same pass, the per-row tile index build_tiled(..., QuadSource::tile_major_packed(packed, true)) needs.
 void at_stats_index(const int64_t* ptr, const uint64_t* packed, int64_t rows, int64_t cols, int ldp, TiledBuffers& buf,
                     double* sum, double* sumsq, hipStream_t s);
 // number of interleaved column tiles the format uses for an operator with `cols` columns
 int tiled_tile_count(int64_t cols, int ldp);
+
+// ---- spmm_tiled.hip: the staged-entry sweep over that format, and the dispatch to the DPP-fed one (spmm_dq.hip) ----
 void spmm_tiled(const TiledOp& op, const float* X, int ldx, float* Y, int ldy, int ncols, const float* cvec, DevBuf& scratch,
                 hipStream_t s, PanelSource<float>* keep = nullptr);
 // the DPP-fed sweep in pieces of its output rows (spmm_tiled.hip): can the operator be swept so, the pieces' row bounds, one piece

@@ -26,6 +26,7 @@
 #include "kernels.h"
 #include <algorithm>
 
+#include "quad_format.h"
 #include "spmm_dq.h"
 #ifdef DQ2_GEN_H   // experiment variants of the generated main loop (tools/dq2_variant.sh)
 #include DQ2_GEN_H
@@ -38,16 +39,15 @@ namespace k {
 
 namespace {
 
-constexpr int WAVE = 64;
 constexpr int DQ_WAVES = 16, DQ_THREADS = DQ_WAVES * WAVE;
-constexpr int DQ_BLOCK_QUADS = 256;           // stride of the per-chunk quad step table (= Q_BLOCK_QUADS of spmm_tiled.hip)
+static_assert(DQ_WAVES == QWAVES, "the format deals a block's quads to QWAVES streams (wave_off, q_first): this sweep walks sixteen");
+constexpr int DQ_BLOCK_QUADS = Q_BLOCK_QUADS;   // stride of the per-chunk quad step table
 constexpr int DQ_TILE_BYTES = DQ2_TILE_BYTES;
 constexpr int DQ_LDS = 2 * DQ_TILE_BYTES;
 static_assert((DQ2_ODD_STEPS != 0) == kOddSteps, "the generated main loop and the format disagree on odd step counts (DQ2_ODD / -DSAPCA_ODD_STEPS)");
 constexpr int DQ_OFF_UNIT = kOddSteps ? 4 : 8;   // entries per unit of a stream's offset in the info table
 static_assert(DQ2_ACC_BASE == 56, "the accumulator operands below are written out for row slots starting at v56");
 
-__host__ __device__ inline int dq_first(int wave, int nquads) { return wave * nquads / DQ_WAVES; }
 // Which of the sixteen streams of a row block a hardware wave walks.  Waves w, w + 4, w + 8, w + 12 share a SIMD, and a
 // block's quads are dealt to the streams s as [s nq / 16, (s + 1) nq / 16): when nq is not a multiple of 16 the longer streams
 // recur with a period that divides 16 (every fourth one for nq = 16 a + 4) -- walked by wave s they would all land on one SIMD
@@ -86,7 +86,7 @@ dq_info_kernel(const int32_t* __restrict__ blk_row0, int nct, const int64_t* __r
     const int nrows = blk_row0[rb + 1] - blk_row0[rb];
     const int nquads = (nrows + 3) / 4;
     const int wave = lane & (DQ_WAVES - 1);
-    const int quad0 = dq_first(wave, nquads), my_quads = dq_first(wave + 1, nquads) - quad0;   // <= 16
+    const int quad0 = q_first(wave, nquads), my_quads = q_first(wave + 1, nquads) - quad0;   // <= 16
     int n = 0;
     if (lane < DQ_WAVES)
       for (int j = 0; j < my_quads; ++j) n += (int)steps[cidx * DQ_BLOCK_QUADS + quad0 + j];
@@ -128,7 +128,7 @@ spmm_dq_kernel(const int32_t* __restrict__ blk_row0, const uint32_t* __restrict_
   const int g = lane / 16, q = lane % 16;
   const int row0 = blk_row0[rb], nrows = blk_row0[rb + 1] - row0;
   const int nquads = (nrows + 3) / 4;
-  const int quad0 = dq_first(wave, nquads), my_quads = dq_first(wave + 1, nquads) - quad0;   // <= RG
+  const int quad0 = q_first(wave, nquads), my_quads = q_first(wave + 1, nquads) - quad0;   // <= RG
   const int my_rows = min(nrows, 4 * (quad0 + my_quads)) - 4 * quad0;
 
   v8f a0, a1, a2, a3, a4, a5, a6, a7;   // row slots 2i, 2i+1 (RG = 8: a0..a3)
@@ -256,7 +256,7 @@ spmm_dq_f64_kernel(const int32_t* __restrict__ blk_row0, const uint32_t* __restr
   const int g = lane / 16, q = lane % 16;
   const int row0 = blk_row0[rb], nrows = blk_row0[rb + 1] - row0;
   const int nquads = (nrows + 3) / 4;
-  const int quad0 = dq_first(wave, nquads), my_quads = dq_first(wave + 1, nquads) - quad0;   // <= 4
+  const int quad0 = q_first(wave, nquads), my_quads = q_first(wave + 1, nquads) - quad0;   // <= 4
   const int my_rows = min(nrows, 4 * (quad0 + my_quads)) - 4 * quad0;
 
   v4d a0, a1, a2, a3, a4, a5, a6, a7;   // slot j: a(2j) = columns 2q, 2q+1 ; a(2j+1) = columns 32+2q, 32+2q+1

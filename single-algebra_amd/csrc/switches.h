@@ -13,8 +13,9 @@
 // The switches of the debug variant (name: effect), by file:
 //   engine.cpp   SAPCA_TILED_MIN_ENTRIES (floor of the staged sweep), SAPCA_AT_NATURAL, SAPCA_AT_UNPACK, SAPCA_AT_SORT,
 //                SAPCA_LANCZOS_TRANSPOSE, SAPCA_MASK_STATS_INLINE, SAPCA_Q3_ROWKERNEL
-//   spmm_tiled.hip  SAPCA_DQ_BLOCK_ROWS, SAPCA_SPLIT_WGS, SAPCA_QF_CAP_FIXED, SAPCA_NO_ROWSORT, SAPCA_ROWSORT_ALWAYS, SAPCA_FILL_DIRECT,
-//                SAPCA_AT_BUCKETS, SAPCA_AT_SORT, SAPCA_RUNS_SEG_LDS_MAX, SAPCA_SWEEP_STAGED, SAPCA_NO_DQ, SAPCA_DEBUG
+//   tiled_build.hip (BuildSwitches, read once per build)  SAPCA_DQ_BLOCK_ROWS, SAPCA_SPLIT_WGS, SAPCA_QF_CAP_FIXED, SAPCA_NO_ROWSORT,
+//                SAPCA_ROWSORT_ALWAYS, SAPCA_FILL_DIRECT, SAPCA_AT_BUCKETS, SAPCA_AT_SORT, SAPCA_RUNS_SEG_LDS_MAX, SAPCA_NO_DQ, SAPCA_DEBUG
+//   spmm_tiled.hip  SAPCA_SWEEP_STAGED
 //   spmm_dq.hip  SAPCA_NO_DQ, SAPCA_NO_DQ_F64      prep.hip  SAPCA_TRANSPOSE_GATHER
 //   dense.hip    SAPCA_CHOL_GENERAL, SAPCA_EIG_DEVICE
 //   lanczos.hip  SAPCA_SPMV_NO_LDS, SAPCA_SPMV_NO_SLICE_GRID, SAPCA_SPMV_IDX32, SAPCA_LANCZOS_CHECK

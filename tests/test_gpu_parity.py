@@ -1571,11 +1571,14 @@ def test_bucket_route_on_a_half_dense_matrix(debug_switches, monkeypatch):
     np.testing.assert_allclose(out[0][0], want.singular_values, rtol=2e-4)
 
 
-def test_tile_major_builder_with_and_without_its_lds_table(debug_switches, monkeypatch):
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_tile_major_builder_with_and_without_its_lds_table(debug_switches, monkeypatch, dtype):
     """A^T's format: the row-segment bounds staged in LDS (few tiles) or read from global memory one tile ahead
-    (many tiles, C4/C5) -- the same bytes, hence bit-identical fits"""
+    (many tiles, C4/C5) -- the same bytes, hence bit-identical fits.  f32 and f64 share the fill's dispatch (f64 fits
+    reach the streaming fill through the tile-major transposition: the same values in 16-byte entries)"""
     m, n, k, p, q = 9000, 700, 8, 6, 2
     ptr, idx, val = csr_np(synth.gapped_csr(m, n, 0.06, k, seed=12, dtype=torch.float32))
+    val = val.astype(dtype)
     om = synth.gaussian_panel(n, k + p, 3).numpy()
     out = []
     for lim in ("100000", "0"):
@@ -1589,16 +1592,18 @@ def test_tile_major_builder_with_and_without_its_lds_table(debug_switches, monke
     np.testing.assert_allclose(out[0][0], want.singular_values, rtol=1e-4)
 
 
-def test_staged_and_direct_format_fill_agree(debug_switches, monkeypatch):
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_staged_and_direct_format_fill_agree(debug_switches, monkeypatch, dtype):
     """the LDS-staged builder of A's tile-major format and the direct one write the same bytes: bit-identical
-    fits; a matrix with a few very long rows sends some quads down the direct route inside the staged kernel"""
+    fits; a matrix with a few very long rows sends some quads down the direct route inside the staged kernel.
+    f32 and f64 (the same values in 16-byte entries) share the fill's dispatch"""
     m, n, k, p, q = 5000, 3000, 10, 6, 2
     ptr, idx, val = csr_np(synth.gapped_csr(m, n, 0.04, k, seed=8, dtype=torch.float32))
     A = mat(ptr, idx, val, m, n).tolil()
     rng = np.random.default_rng(0)
     for r in (7, 1234, 4999):            # dense rows: 3000 entries each, a quad of > 6144 padded entries
         A[r, :] = rng.uniform(0.5, 1.5, n).astype(np.float32)
-    A = A.tocsr()
+    A = A.tocsr().astype(dtype)
     A.sort_indices()
     om = synth.gaussian_panel(n, k + p, 3).numpy()
     out = []
