@@ -62,7 +62,8 @@ extern "C" {
                                  additive, ABI 4: sapca_options.reserved0 became lanczos_center (same size and offsets;
                                                   0, the value every caller passed, is the behaviour of before)
                                  additive, ABI 4: sapca_select_rows_csr_device_*
-                                 additive, ABI 4: sapca_check_csr_device_*, sapca_canonicalize_csr_device_*           */
+                                 additive, ABI 4: sapca_check_csr_device_*, sapca_canonicalize_csr_device_*
+                                 additive, ABI 4: sapca_select_submatrix_csr_device_*                                 */
 
 typedef struct sapca_handle_s* sapca_handle;
 
@@ -417,6 +418,45 @@ sapca_status sapca_select_rows_csr_device_f64(sapca_handle h, uint64_t m, uint64
                                               const int64_t* row_offsets, const int32_t* col_indices, const double* values,
                                               const uint64_t* rows, uint64_t n_rows, uint64_t* nnz_out,
                                               const int64_t** d_row_offsets, const int32_t** d_col_indices, double** d_values);
+
+/* Rows AND columns of a device-resident CSR in one call: A[rows][:, col_mask] as a CSR of its own.  The column half is
+ * the reference's MaskedCSRMatrix::new(x, mask) -- cols_to_use ascending, a kept column renumbered by its rank among the
+ * kept ones (sparse_masked/mod.rs:264-271, 455-466) -- offered as a resident matrix instead of a private step of one fit:
+ * gene filters (min-cells, highly variable genes) then serve the statistics, normalisation and every fit of a sweep,
+ * the compaction is paid once, and the dropped columns need not stay in HBM.
+ *   rows      HOST; as in sapca_select_rows_csr_device_* (any order, repeats allowed); NULL = rows 0 .. n_rows-1 in
+ *             order (n_rows <= m).  Output row i is source row rows[i], its kept entries in stored order.
+ *   col_mask  HOST, mask_len == n entries, non-zero = kept; NULL = every column (mask_len ignored).  A kept column c
+ *             becomes the number of kept columns below c; *n_cols_out = the kept columns (n without a mask).  A mask,
+ *             not a list: ascending by construction, so a canonical source gives a canonical result.
+ *   flags     SAPCA_SELECT_DROP_STORED_ZEROS: entries whose value == 0 (either sign) are dropped as well -- the stored
+ *             zeros that sapca_check_csr_device_* counts and that the reference's nonzero_* and quirk Q2 count as
+ *             entries.  A NaN is kept.  Without the flag stored zeros survive.
+ * Values move bit for bit (NaN payloads, -0.0).  n_rows == 0, an all-false mask (*n_cols_out = 0, every offset 0) and a
+ * mask that keeps only columns without entries are valid.  With no mask (or one that keeps every column) and no flag the
+ * result is byte-identical to sapca_select_rows_csr_device_* of the same rows, by the same kernels.  The result is
+ * deterministic: the same bytes from call to call (no atomics; every output word has one writer).
+ * SAPCA_ERR_ARG, checked on the host before anything is enqueued (the previous selection stays intact, the handle usable):
+ * mask_len != n with a mask ("select_submatrix: the column mask has L entries, the matrix N columns"); rows[i] >= m
+ * ("select_submatrix: row index R at position I is out of range (m = M)"); rows == NULL with n_rows > m; unknown flag
+ * bits; a null output pointer; a source that is the handle's own selection buffers.
+ * The outputs live in the SAME buffers as those of sapca_select_rows_csr_device_*, with the same lifetime and "writable"
+ * contract: one selection per handle, either call replaces it.  The source, the column statistics gathered during its
+ * upload and any cached preparation not made of the previous selection are untouched.  On a handle that belongs to a
+ * communicator the call is local to the rank and issues no collective.                                               */
+#define SAPCA_SELECT_DROP_STORED_ZEROS 1u   /* drop entries whose value == 0 (either sign); NaN is kept */
+sapca_status sapca_select_submatrix_csr_device_f32(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz,
+                                                   const int64_t* row_offsets, const int32_t* col_indices, const float* values,
+                                                   const uint64_t* rows, uint64_t n_rows,
+                                                   const uint8_t* col_mask, uint64_t mask_len, uint32_t flags,
+                                                   uint64_t* n_cols_out, uint64_t* nnz_out,
+                                                   const int64_t** d_row_offsets, const int32_t** d_col_indices, float** d_values);
+sapca_status sapca_select_submatrix_csr_device_f64(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz,
+                                                   const int64_t* row_offsets, const int32_t* col_indices, const double* values,
+                                                   const uint64_t* rows, uint64_t n_rows,
+                                                   const uint8_t* col_mask, uint64_t mask_len, uint32_t flags,
+                                                   uint64_t* n_cols_out, uint64_t* nnz_out,
+                                                   const int64_t** d_row_offsets, const int32_t** d_col_indices, double** d_values);
 
 /* ---- the gate in front of the device entry points: check and canonicalise a device-resident CSR ----
  * Every kernel relies on offsets that start at 0, end at nnz and never decrease, on columns < n, and on rows whose

@@ -682,6 +682,16 @@ sapca_status sapca_set_omega_f64(sapca_handle h, const double* omega, size_t row
                                                   uint64_t* nnz_out, const int64_t** dp, const int32_t** di, T** dv) {     \
     return guarded(h, [&] { resident::select_rows<T>(*h, unchecked_view(m, n, nnz, p, i, v), rows, n_rows, nnz_out, dp, di, dv); }); \
   }                                                                                                                      \
+  sapca_status sapca_select_submatrix_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, \
+                                                       const int32_t* i, const T* v, const uint64_t* rows, uint64_t n_rows,    \
+                                                       const uint8_t* col_mask, uint64_t mask_len, uint32_t flags,              \
+                                                       uint64_t* n_cols_out, uint64_t* nnz_out, const int64_t** dp,             \
+                                                       const int32_t** di, T** dv) {                                            \
+    return guarded(h, [&] {                                                                                              \
+      resident::select_submatrix<T>(*h, unchecked_view(m, n, nnz, p, i, v), rows, n_rows, col_mask, mask_len, flags, n_cols_out, \
+                                    nnz_out, dp, di, dv);                                                                \
+    });                                                                                                                  \
+  }                                                                                                                      \
   sapca_status sapca_check_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p,        \
                                             const int32_t* i, const T* v, sapca_csr_report* report) {                      \
     return guarded(h, [&] { resident::check<T>(*h, unchecked_view(m, n, nnz, p, i, v), report); });                      \

@@ -115,8 +115,9 @@ struct sapca_handle_s {
   }
   // the row selection of sapca_select_rows_csr_device_*: a CSR of its own beside the upload's, the row list on the device and the
   // scan's work space (nothing else lives in these, so a selection disturbs no cached preparation but one made OF it)
+  // (gather / spans / cmap: the gathered offsets, the per-span counts and the column map of sapca_select_submatrix_csr_device_*)
   struct Selection {
-    sapca::DevBuf ptr, idx, val, rows, scan;
+    sapca::DevBuf ptr, idx, val, rows, scan, gather, spans, cmap;
     bool owns(const void* q) const { return ptr.contains(q) || idx.contains(q) || val.contains(q); }   // the result's arrays, not the work space
   } selection;
   // the canonical form of sapca_canonicalize_csr_device_*: a third CSR beside the upload's and the selection's (idx2 / val2

@@ -119,6 +119,22 @@ template <typename T>
 void select_rows_fill(const CsrView<T>& A, const uint64_t* rows, int64_t n_rows, const int64_t* out_ptr, int64_t total,
                       int32_t* out_idx, T* out_val, hipStream_t s);
 
+// Rows AND columns (sapca_select_submatrix_csr_device_*): the gathered rows -- goff (n_rows + 1) their offsets, gtotal =
+// goff[n_rows]; rows null: source rows 0 .. n_rows - 1, goff = A.ptr -- filtered by a column map and / or without stored zeros.
+// cmap (device, null: every column): bits[words] | before[words], words = ceil(A.cols / 32): bit c % 32 of bits[c / 32] is
+// set where column c is kept, before[w] = the kept columns below 32 w.  A workgroup per span of gathered positions:
+// select_submatrix_spans(gtotal) of them.  count: span_cnt[0 .. spans) = the kept entries of each span, span_cnt[spans] = 0;
+// after exclusive_scan_i64 over all spans + 1 the same array is the fill's span_base.  fill: out_ptr[0 .. n_rows], and the
+// kept entries in gathered order at out_idx / out_val, columns renumbered by rank, values bit for bit.  No atomics.
+int64_t select_submatrix_spans(int64_t gtotal);
+template <typename T>
+void select_submatrix_count(const CsrView<T>& A, const uint64_t* rows, int64_t n_rows, const int64_t* goff, int64_t gtotal,
+                            const uint32_t* cmap, bool drop_zeros, int64_t* span_cnt, hipStream_t s);
+template <typename T>
+void select_submatrix_fill(const CsrView<T>& A, const uint64_t* rows, int64_t n_rows, const int64_t* goff, int64_t gtotal,
+                           const uint32_t* cmap, bool drop_zeros, const int64_t* span_base, int64_t* out_ptr, int32_t* out_idx,
+                           T* out_val, hipStream_t s);
+
 // ---- canon.hip: check and canonicalise a device CSR (sapca_check_csr_device_*, sapca_canonicalize_csr_device_*) ----------
 // slots of the 64-bit counter block `ctr` (device, kCtrSlots words): first rows (start at all bits set), then counts
 enum CanonCtr {

@@ -236,24 +236,14 @@ void top_n(H& h, const CsrView<T>& A, const uint64_t* ns, uint32_t n_ns, double*
   SAPCA_HIP(hipStreamSynchronize(s));
 }
 
-// Rows `rows[0 .. n_rows)` of a device CSR (any order, repeats allowed) as a CSR in the handle's selection buffers: the
-// offsets through a scan (one synchronisation: the total sizes the output), then a fill balanced over output entries
-// (select.hip).  Everything that can be refused is refused before anything is enqueued or a buffer is touched.
+namespace {
+
+// rows[0 .. n_rows) (host, every entry below A.rows) of A into the selection's buffers: the offsets through a scan (one
+// synchronisation: the total sizes the output), then a fill balanced over output entries (select.hip)
 template <typename T>
-void select_rows(H& h, const CsrView<T>& A, const uint64_t* rows, uint64_t n_rows, uint64_t* nnz_out, const int64_t** d_ptr,
+void gather_rows(H& h, const CsrView<T>& A, const uint64_t* rows, uint64_t n_rows, uint64_t* nnz_out, const int64_t** d_ptr,
                  const int32_t** d_idx, T** d_val) {
-  SAPCA_CHECK(nnz_out && d_ptr && d_idx && d_val, SAPCA_ERR_ARG, "select_rows: null output pointer");
-  SAPCA_CHECK(rows != nullptr || n_rows == 0, SAPCA_ERR_ARG, "select_rows: rows is NULL with n_rows > 0");
-  check_view(A);
-  SAPCA_CHECK(n_rows < (1ull << 31), SAPCA_ERR_ARG, "more than 2^31-1 rows or columns is not supported");
   H::Selection& sel = h.selection;
-  SAPCA_CHECK(!sel.owns(A.ptr) && !sel.owns(A.idx) && !sel.owns(A.val), SAPCA_ERR_ARG,
-              "select_rows: the source is this handle's own selection, which the call overwrites (select from the uploaded matrix)");
-  const uint64_t m = (uint64_t)A.rows;
-  for (uint64_t j = 0; j < n_rows; ++j)
-    if (rows[j] >= m)
-      throw Error(SAPCA_ERR_ARG, "select_rows: row index " + std::to_string(rows[j]) + " at position " + std::to_string(j) +
-                                     " is out of range (m = " + std::to_string(m) + ")");
   hipStream_t s = h.stream;
   h.drop_preparation_of(sel);
   int64_t* o_ptr = sel.ptr.as<int64_t>(n_rows + 1);
@@ -271,6 +261,133 @@ void select_rows(H& h, const CsrView<T>& A, const uint64_t* rows, uint64_t n_row
   T* o_val = sel.val.as<T>(std::max<int64_t>(total, 1));
   k::select_rows_fill(A, d_rows, (int64_t)n_rows, o_ptr, total, o_idx, o_val, s);
   SAPCA_HIP(hipStreamSynchronize(s));   // the arrays are complete when the call returns, whatever stream reads them next
+  *nnz_out = (uint64_t)total;
+  *d_ptr = o_ptr;
+  *d_idx = o_idx;
+  *d_val = o_val;
+}
+
+void check_row_list(const char* who, const uint64_t* rows, uint64_t n_rows, uint64_t m) {
+  for (uint64_t j = 0; j < n_rows; ++j)
+    if (rows[j] >= m)
+      throw Error(SAPCA_ERR_ARG, std::string(who) + ": row index " + std::to_string(rows[j]) + " at position " + std::to_string(j) +
+                                     " is out of range (m = " + std::to_string(m) + ")");
+}
+
+}  // namespace
+
+// Rows `rows[0 .. n_rows)` of a device CSR (any order, repeats allowed) as a CSR in the handle's selection buffers.
+// Everything that can be refused is refused before anything is enqueued or a buffer is touched.
+template <typename T>
+void select_rows(H& h, const CsrView<T>& A, const uint64_t* rows, uint64_t n_rows, uint64_t* nnz_out, const int64_t** d_ptr,
+                 const int32_t** d_idx, T** d_val) {
+  SAPCA_CHECK(nnz_out && d_ptr && d_idx && d_val, SAPCA_ERR_ARG, "select_rows: null output pointer");
+  SAPCA_CHECK(rows != nullptr || n_rows == 0, SAPCA_ERR_ARG, "select_rows: rows is NULL with n_rows > 0");
+  check_view(A);
+  SAPCA_CHECK(n_rows < (1ull << 31), SAPCA_ERR_ARG, "more than 2^31-1 rows or columns is not supported");
+  const H::Selection& sel = h.selection;
+  SAPCA_CHECK(!sel.owns(A.ptr) && !sel.owns(A.idx) && !sel.owns(A.val), SAPCA_ERR_ARG,
+              "select_rows: the source is this handle's own selection, which the call overwrites (select from the uploaded matrix)");
+  check_row_list("select_rows", rows, n_rows, (uint64_t)A.rows);
+  gather_rows(h, A, rows, n_rows, nnz_out, d_ptr, d_idx, d_val);
+}
+
+// A[rows][:, col_mask], optionally without stored zeros, in the same buffers (MaskedCSRMatrix::new's column compaction,
+// sparse_masked/mod.rs:264-271, 455-466, fused with the row selection).  Without a mask that drops a column and without the
+// flag it IS the row selection: the same launches, the same bytes.  Otherwise the gathered rows are never materialised:
+// their offsets, a count per span of gathered positions, a scan (the one synchronisation: the total sizes the output) and
+// the fill (select.hip).  Refusals come first, as above.
+template <typename T>
+void select_submatrix(H& h, const CsrView<T>& A, const uint64_t* rows, uint64_t n_rows, const uint8_t* col_mask, uint64_t mask_len,
+                      uint32_t flags, uint64_t* n_cols_out, uint64_t* nnz_out, const int64_t** d_ptr, const int32_t** d_idx, T** d_val) {
+  SAPCA_CHECK(n_cols_out && nnz_out && d_ptr && d_idx && d_val, SAPCA_ERR_ARG, "select_submatrix: null output pointer");
+  SAPCA_CHECK((flags & ~(uint32_t)SAPCA_SELECT_DROP_STORED_ZEROS) == 0, SAPCA_ERR_ARG,
+              "select_submatrix: unknown flag bits " + std::to_string(flags & ~(uint32_t)SAPCA_SELECT_DROP_STORED_ZEROS));
+  check_view(A);
+  SAPCA_CHECK(n_rows < (1ull << 31), SAPCA_ERR_ARG, "more than 2^31-1 rows or columns is not supported");
+  H::Selection& sel = h.selection;
+  SAPCA_CHECK(!sel.owns(A.ptr) && !sel.owns(A.idx) && !sel.owns(A.val), SAPCA_ERR_ARG,
+              "select_submatrix: the source is this handle's own selection, which the call overwrites (select from the uploaded matrix)");
+  const uint64_t m = (uint64_t)A.rows, n = (uint64_t)A.cols;
+  if (rows == nullptr)
+    SAPCA_CHECK(n_rows <= m, SAPCA_ERR_ARG,
+                "select_submatrix: rows is NULL with n_rows = " + std::to_string(n_rows) + " > m = " + std::to_string(m));
+  else
+    check_row_list("select_submatrix", rows, n_rows, m);
+  if (col_mask != nullptr && mask_len != n)
+    throw Error(SAPCA_ERR_ARG, "select_submatrix: the column mask has " + std::to_string(mask_len) + " entries, the matrix " +
+                                   std::to_string(n) + " columns");
+  const bool drop_zeros = (flags & SAPCA_SELECT_DROP_STORED_ZEROS) != 0;
+  // the column map of select.hip: a bit per column, and per 32 columns the kept ones before them
+  const uint64_t words = (n + 31) / 32;
+  std::vector<uint32_t> cmap;
+  uint64_t kept = n;
+  if (col_mask != nullptr) {
+    cmap.assign(2 * words, 0u);
+    kept = 0;
+    for (uint64_t c = 0; c < n; ++c) {
+      if ((c & 31) == 0) cmap[words + (c >> 5)] = (uint32_t)kept;
+      if (col_mask[c]) {
+        cmap[c >> 5] |= 1u << (c & 31);
+        ++kept;
+      }
+    }
+  }
+  *n_cols_out = kept;
+  if (kept == n && !drop_zeros) {   // nothing to filter: the row selection itself
+    std::vector<uint64_t> all;
+    if (rows == nullptr) {
+      all.resize(n_rows);
+      for (uint64_t j = 0; j < n_rows; ++j) all[j] = j;
+      rows = all.data();
+    }
+    gather_rows(h, A, rows, n_rows, nnz_out, d_ptr, d_idx, d_val);   // (synchronises: `all` may go)
+    return;
+  }
+  hipStream_t s = h.stream;
+  h.drop_preparation_of(sel);
+  int64_t* o_ptr = sel.ptr.as<int64_t>(n_rows + 1);
+  const uint32_t* d_cmap = nullptr;
+  if (kept < n) {
+    uint32_t* dc = sel.cmap.as<uint32_t>(cmap.size());
+    SAPCA_HIP(hipMemcpyAsync(dc, cmap.data(), cmap.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    d_cmap = dc;
+  }
+  // the gathered offsets: the source's own for rows 0 .. n_rows - 1
+  const uint64_t* d_rows = nullptr;
+  const int64_t* goff = A.ptr;
+  int64_t gtotal = 0, total = 0;
+  if (rows != nullptr && n_rows > 0) {
+    uint64_t* dr = sel.rows.as<uint64_t>(n_rows);
+    SAPCA_HIP(hipMemcpyAsync(dr, rows, n_rows * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    d_rows = dr;
+    int64_t* g = sel.gather.as<int64_t>(n_rows + 1);
+    k::select_rows_offsets(A.ptr, d_rows, (int64_t)n_rows, g, &gtotal, sel.scan, s);
+    goff = g;
+  } else if (n_rows == m) {
+    gtotal = A.nnz;
+  } else if (n_rows > 0) {
+    SAPCA_HIP(hipMemcpyAsync(&gtotal, A.ptr + n_rows, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    SAPCA_HIP(hipStreamSynchronize(s));
+  }
+  int32_t* o_idx = nullptr;
+  T* o_val = nullptr;
+  if (n_rows == 0 || gtotal <= 0) {   // no entry to look at: every offset is 0
+    SAPCA_HIP(hipMemsetAsync(o_ptr, 0, (n_rows + 1) * sizeof(int64_t), s));
+    o_idx = sel.idx.as<int32_t>(1);
+    o_val = sel.val.as<T>(1);
+  } else {
+    const int64_t spans = k::select_submatrix_spans(gtotal);
+    int64_t* span = sel.spans.as<int64_t>(spans + 1);
+    k::select_submatrix_count(A, d_rows, (int64_t)n_rows, goff, gtotal, d_cmap, drop_zeros, span, s);
+    k::exclusive_scan_i64(span, spans + 1, sel.scan, 0, s);
+    SAPCA_HIP(hipMemcpyAsync(&total, span + spans, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    SAPCA_HIP(hipStreamSynchronize(s));
+    o_idx = sel.idx.as<int32_t>(std::max<int64_t>(total, 1));
+    o_val = sel.val.as<T>(std::max<int64_t>(total, 1));
+    k::select_submatrix_fill(A, d_rows, (int64_t)n_rows, goff, gtotal, d_cmap, drop_zeros, span, o_ptr, o_idx, o_val, s);
+  }
+  SAPCA_HIP(hipStreamSynchronize(s));   // complete when the call returns; cmap may go
   *nnz_out = (uint64_t)total;
   *d_ptr = o_ptr;
   *d_idx = o_idx;
@@ -430,6 +547,8 @@ void canonicalize(H& h, const CsrView<T>& A, uint64_t* nnz_out, const int64_t** 
   template void masked_stats<T>(H&, const CsrView<T>&, int32_t, const uint8_t*, uint64_t, double*, double*, uint64_t*, double*);  \
   template void top_n<T>(H&, const CsrView<T>&, const uint64_t*, uint32_t, double*);                                               \
   template void select_rows<T>(H&, const CsrView<T>&, const uint64_t*, uint64_t, uint64_t*, const int64_t**, const int32_t**, T**); \
+  template void select_submatrix<T>(H&, const CsrView<T>&, const uint64_t*, uint64_t, const uint8_t*, uint64_t, uint32_t, uint64_t*, \
+                                    uint64_t*, const int64_t**, const int32_t**, T**);                                             \
   template void check<T>(H&, const CsrView<T>&, sapca_csr_report*);                                                                \
   template void canonicalize<T>(H&, const CsrView<T>&, uint64_t*, const int64_t**, const int32_t**, T**, sapca_csr_report*);
 SAPCA_INSTANTIATE_RESIDENT(float)

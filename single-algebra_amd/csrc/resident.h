@@ -44,6 +44,10 @@ void top_n(H& h, const CsrView<T>& A, const uint64_t* ns, uint32_t n_ns, double*
 template <typename T>
 void select_rows(H& h, const CsrView<T>& A, const uint64_t* rows, uint64_t n_rows, uint64_t* nnz_out, const int64_t** d_ptr,
                  const int32_t** d_idx, T** d_val);
+// A[rows][:, col_mask] (rows null: rows 0 .. n_rows - 1; col_mask null: every column), flags: SAPCA_SELECT_*
+template <typename T>
+void select_submatrix(H& h, const CsrView<T>& A, const uint64_t* rows, uint64_t n_rows, const uint8_t* col_mask, uint64_t mask_len,
+                      uint32_t flags, uint64_t* n_cols_out, uint64_t* nnz_out, const int64_t** d_ptr, const int32_t** d_idx, T** d_val);
 template <typename T>
 void check(H& h, const CsrView<T>& A, sapca_csr_report* report);
 template <typename T>

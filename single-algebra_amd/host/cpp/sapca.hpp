@@ -76,6 +76,7 @@ template <typename T> struct ResidentAbi;
     static sapca_status check(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, sapca_csr_report* rep) { return sapca_check_csr_device_##SUF(h, m, n, nnz, p, i, v, rep); } \
     static sapca_status canonicalize(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, uint64_t* nnz_out, const int64_t** op, const int32_t** oi, T** ov, sapca_csr_report* rep) { return sapca_canonicalize_csr_device_##SUF(h, m, n, nnz, p, i, v, nnz_out, op, oi, ov, rep); } \
     static sapca_status select_rows(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, const uint64_t* rows, uint64_t nr, uint64_t* nnz_out, const int64_t** op, const int32_t** oi, T** ov) { return sapca_select_rows_csr_device_##SUF(h, m, n, nnz, p, i, v, rows, nr, nnz_out, op, oi, ov); } \
+    static sapca_status select(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, const uint64_t* rows, uint64_t nr, const uint8_t* mk, uint64_t ml, uint32_t flags, uint64_t* ncols_out, uint64_t* nnz_out, const int64_t** op, const int32_t** oi, T** ov) { return sapca_select_submatrix_csr_device_##SUF(h, m, n, nnz, p, i, v, rows, nr, mk, ml, flags, ncols_out, nnz_out, op, oi, ov); } \
   };
 SAPCA_RES(f32, float)
 SAPCA_RES(f64, double)
@@ -147,6 +148,20 @@ class ResidentCsr {
     check(ResidentAbi<T>::select_rows(h_, m_, n_, nnz_, ptr_, idx_, val_, rows.data(), rows.size(), &out.nnz_, &out.ptr_, &out.idx_, &out.val_));
     return out;
   }
+  // Rows AND columns in one call (sapca_select_submatrix_csr_device_*): this[rows][:, cols].  rows null: every row in order;
+  // cols null: every column, otherwise a mask of ncols() entries -- a kept column is renumbered by its rank among the kept
+  // ones (MaskedCSRMatrix::new, sparse_masked/mod.rs:264-271, 455-466), so gene filters serve statistics, normalisation and
+  // every fit alike.  drop_stored_zeros: entries whose value == 0 go as well (a NaN stays).  Same buffers and lifetime as
+  // select_rows: one selection per handle, either call replaces it.
+  ResidentCsr select(const std::vector<uint64_t>* rows, const std::vector<bool>* cols = nullptr, bool drop_stored_zeros = false) const {
+    std::vector<uint8_t> mk;
+    if (cols) mk.assign(cols->begin(), cols->end());
+    ResidentCsr out(h_, rows ? (uint64_t)rows->size() : m_, n_);
+    check(ResidentAbi<T>::select(h_, m_, n_, nnz_, ptr_, idx_, val_, rows ? rows->data() : nullptr, out.m_, cols ? mk.data() : nullptr,
+                                 mk.size(), drop_stored_zeros ? SAPCA_SELECT_DROP_STORED_ZEROS : 0u, &out.n_, &out.nnz_, &out.ptr_,
+                                 &out.idx_, &out.val_));
+    return out;
+  }
   // What the arrays are (sapca_check_csr_device_*): safe offsets and columns, rows ascending without repeats.  Read-only.
   CsrReport check_csr() const {
     CsrReport rep{};
@@ -171,7 +186,7 @@ class ResidentCsr {
   T* values() const { return val_; }
 
  private:
-  ResidentCsr(sapca_handle h, uint64_t m, uint64_t n) : h_(h), m_(m), n_(n), nnz_(0) {}   // (filled in by select_rows)
+  ResidentCsr(sapca_handle h, uint64_t m, uint64_t n) : h_(h), m_(m), n_(n), nnz_(0) {}   // (filled in by select_rows / select)
   void check(sapca_status st) const {
     if (st != SAPCA_OK) throw Error(st, sapca_last_error(h_));
   }

@@ -47,6 +47,10 @@ CSR_FLAG_NAMES = {CSR_BAD_OFFSETS: "BAD_OFFSETS", CSR_COL_RANGE: "COL_RANGE", CS
                   CSR_DUPLICATES: "DUPLICATES", CSR_NONFINITE: "NONFINITE"}
 
 
+# flags of sapca_select_submatrix_csr_device_*
+SELECT_DROP_STORED_ZEROS = 1
+
+
 class CsrReport(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("flags", C.c_uint32),
@@ -72,6 +76,7 @@ _TYPED = [
     "sapca_upload_csr", "sapca_normalize_csr_device", "sapca_log1p_csr_device", "sapca_stats_csr_device",
     "sapca_batch_stats_csr_device", "sapca_sum_row_n_top_csr_device", "sapca_masked_stats_csr_device",
     "sapca_select_rows_csr_device", "sapca_check_csr_device", "sapca_canonicalize_csr_device",
+    "sapca_select_submatrix_csr_device",
     "sapca_multi_fit_csr", "sapca_multi_transform_csr", "sapca_multi_fit_transform_csr",
     "sapca_multi_upload_csr", "sapca_multi_transform_resident", "sapca_multi_fit_transform_resident",
 ]
@@ -155,6 +160,13 @@ def _open(path):
         lib.sapca_comm_has_side_lane.argtypes = [C.c_void_p]
     if hasattr(lib, "sapca_measure_copy_gbs"):
         lib.sapca_measure_copy_gbs.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
+    for suf, ct in (("f32", C.c_float), ("f64", C.c_double)):
+        fn = getattr(lib, f"sapca_select_submatrix_csr_device_{suf}", None)   # (absent from an older build loaded for an A/B run)
+        if fn is not None:
+            fn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                           C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint8), C.c_uint64, C.c_uint32,
+                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                           C.POINTER(C.c_void_p)]
     return lib
 
 

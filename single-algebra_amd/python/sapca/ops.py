@@ -121,6 +121,40 @@ def _row_list(rows, m):
     return np.ascontiguousarray(a, dtype=np.uint64)
 
 
+def _col_mask(cols, n):
+    """The column selection of ResidentCsr.select as the uint8 mask of length n the C ABI takes: a boolean array of length
+    exactly n passes through; strictly ascending integer indices below n become the mask that is true at them (an empty
+    list: all false).  The ABI takes a mask, not a list, because the result must stay canonical: kept columns are
+    renumbered by rank, which is their order only when they ascend without repeats.  Pure host code (numpy only): a mask
+    of another length, a negative index, one >= n, repeated or descending indices, and input that is neither raise
+    ValueError."""
+    a = np.asarray(cols)
+    n = int(n)
+    if a.ndim != 1:
+        raise ValueError(f"cols must be one-dimensional, got shape {a.shape}")
+    if a.dtype == np.bool_:
+        if a.size != n:
+            raise ValueError(f"Column mask length ({a.size}) does not match number of columns ({n})")
+        return np.ascontiguousarray(a, dtype=np.uint8)
+    mask = np.zeros(n, dtype=np.uint8)
+    if a.size == 0:
+        return mask
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"cols must be a boolean mask or integer indices, got dtype {a.dtype}")
+    if a.dtype.kind == "i" and (a < 0).any():
+        j = int(np.flatnonzero(a < 0)[0])
+        raise ValueError(f"negative column index {int(a[j])} at position {j}")
+    a = a.astype(np.uint64)
+    if a.size > 1 and (a[1:] <= a[:-1]).any():
+        j = int(np.flatnonzero(a[1:] <= a[:-1])[0]) + 1
+        raise ValueError(f"column indices must be strictly ascending: {int(a[j])} at position {j} follows {int(a[j - 1])} "
+                         "(a mask keeps the result canonical; sort and deduplicate, or canonicalize a reordered matrix)")
+    if int(a[-1]) >= n:
+        raise ValueError(f"column index {int(a[-1])} is out of range (n = {n})")
+    mask[a.astype(np.int64)] = 1
+    return mask
+
+
 class CsrReport:
     """What sapca_check_csr_device_* / sapca_canonicalize_csr_device_* found in a device CSR (sapca_csr_report): the counts
     and first rows as attributes (a first_*_row is None where its count is zero), `flags` as the tuple of the names of the
@@ -400,6 +434,37 @@ class ResidentCsr:
             *self._args(), _p(r, C.c_uint64) if r.size else None, C.c_uint64(r.size), C.byref(nnz_out), C.byref(dp), C.byref(di),
             C.byref(dv)))
         return ResidentCsr(self._s, (r.size, self.shape[1]), nnz_out.value, self.dtype, dp.value or 0, di.value or 0, dv.value or 0)
+
+    def select(self, rows=None, cols=None, drop_stored_zeros=False):
+        """sapca_select_submatrix_csr_device_*: self[rows][:, cols] as a ResidentCsr in the same Session, in one call and
+        without crossing PCIe.  rows: as in select_rows (None: every row in order).  cols: a boolean mask of length n or
+        strictly ascending integer indices (None: every column); a kept column is renumbered by its rank among the kept
+        ones, as MaskedCSRMatrix::new does, so the result is an ordinary (m', n') matrix for every method here and every
+        fit -- the column compaction a masked fit repeats in each preparation is paid once.  drop_stored_zeros: entries
+        whose value == 0 are dropped too (check().stored_zeros of the result is 0; a NaN stays).  Values move bit for
+        bit.  The result shares the Session's selection buffers with select_rows: either call replaces it."""
+        suf, _ = _SUF[self.dtype]
+        m, n = self.shape
+        if rows is None:
+            rp, nr = None, m
+        else:
+            r = _row_list(rows, m)
+            rp, nr = (_p(r, C.c_uint64) if r.size else None), r.size   # (no rows: NULL with n_rows = 0 says the same)
+        if cols is None:
+            mp, ml = None, 0
+        else:
+            mk = _col_mask(cols, n)
+            mp, ml = (_p(mk, C.c_uint8) if mk.size else None), mk.size
+        ncols, nnz_out = C.c_uint64(), C.c_uint64()
+        dp, di, dv = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        L.check(self._s._h, getattr(L.load(), f"sapca_select_submatrix_csr_device_{suf}")(
+            *self._args(), rp, C.c_uint64(nr), mp, C.c_uint64(ml), C.c_uint32(L.SELECT_DROP_STORED_ZEROS if drop_stored_zeros else 0),
+            C.byref(ncols), C.byref(nnz_out), C.byref(dp), C.byref(di), C.byref(dv)))
+        return ResidentCsr(self._s, (nr, ncols.value), nnz_out.value, self.dtype, dp.value or 0, di.value or 0, dv.value or 0)
+
+    def select_cols(self, cols):
+        """select(cols=cols): every row, the columns `cols`"""
+        return self.select(cols=cols)
 
     @classmethod
     def from_torch(cls, session, row_offsets, col_indices, values, shape):
