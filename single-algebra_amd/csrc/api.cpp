@@ -52,6 +52,16 @@ sapca_status guarded(sapca_handle h, F&& f) {
 namespace {
 constexpr size_t kUpChunk = (size_t)16 << 20;   // indices per chunk (64 MiB of int32)
 
+// the chunk length of this upload: kUpChunk, or, in the debug variant, what SAPCA_UP_CHUNK says (>= 1; read on every upload
+// so that a test can put chunk boundaries where it wants them on a small matrix)
+size_t up_chunk_len() {
+  if (const char* e = sapca::dbg_env("SAPCA_UP_CHUNK")) {
+    const long long v = std::atoll(e);
+    if (v >= 1) return (size_t)v;
+  }
+  return kUpChunk;
+}
+
 // out[i] = (int32) in[i]; returns true if any in[i] >= n
 bool narrow_chunk(const uint64_t* in, int32_t* out, size_t count, uint64_t n, unsigned nthreads) {
   std::atomic<bool> bad{false};
@@ -117,7 +127,7 @@ CsrView<T> upload(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const ui
   if (nnz) {
     SAPCA_HIP(hipMemcpyAsync(d_val, values, nnz * sizeof(T), hipMemcpyHostToDevice, s));
     const unsigned nthreads = std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
-    const size_t chunk = std::min<size_t>(kUpChunk, nnz);
+    const size_t chunk = std::min<size_t>(up_chunk_len(), nnz);
     for (int b = 0; b < 2; ++b) {
       h->up_stage[b].ensure(chunk * sizeof(int32_t));
       if (!h->up_done[b]) SAPCA_HIP(hipEventCreateWithFlags(&h->up_done[b], hipEventDisableTiming));

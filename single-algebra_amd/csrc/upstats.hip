@@ -224,8 +224,22 @@ __device__ double limbs_to_double(const unsigned long long* L, int base) {
   uint64_t w = (uint64_t)(v >> (32 - lz));
   bool sticky = (v & (((unsigned __int128)1 << (32 - lz)) - 1)) != 0;
   for (int j = t - 3; j >= 0 && !sticky; --j) sticky = dig[j] != 0;
-  if (sticky) w |= 1ull;   // 64 -> 53 bits below: the sticky bit only has to make a tie not a tie
-  const double r = ldexp((double)w, 32 * (t - 1) - lz + base);
+  if (sticky) w |= 1ull;   // the sticky bit only has to make a tie not a tie
+  // |value| = w * 2^e with bit 63 of w set.  Round once, in integers, to the bits the result can hold: 53 for a normal
+  // double, fewer below 2^-1022, where the last place stays at 2^-1074 (rounding to 53 bits first and letting ldexp round
+  // again into the subnormal range would round twice).  q <= 2^53 and q * 2^(e + drop) is representable, or overflows to
+  // inf as the rounded sum does: the ldexp is exact.
+  const int e = 32 * (t - 1) - lz + base;
+  const int drop = max(11, -1074 - e);
+  if (drop > 64) return neg ? -0.0 : 0.0;   // less than half of the smallest subnormal
+  uint64_t q, rem, half;
+  if (drop == 64) {
+    q = 0, rem = w, half = 1ull << 63;
+  } else {
+    q = w >> drop, rem = w & ((1ull << drop) - 1), half = 1ull << (drop - 1);
+  }
+  if (rem > half || (rem == half && (q & 1ull))) ++q;
+  const double r = ldexp((double)q, e + drop);
   return neg ? -r : r;
 }
 

@@ -170,7 +170,7 @@ def test_release_library_reads_no_debug_switches():
     assert len(sites) <= 8, sites
     rel = open(L.LIB_PATH, "rb").read()
     for name in (b"SAPCA_AT_SORT", b"SAPCA_AT_NATURAL", b"SAPCA_TRANSPOSE_GATHER", b"SAPCA_FILL_DIRECT", b"SAPCA_COMM_FORCE_RCCL",
-                 b"SAPCA_RCCL_LIBRARY"):   # (the tests' stand-in for librccl is reachable from the debug build only)
+                 b"SAPCA_RCCL_LIBRARY", b"SAPCA_UP_CHUNK"):   # (the tests' stand-in for librccl is reachable from the debug build only)
         assert name not in rel, f"the release library carries the switch {name.decode()}"
     assert b"SAPCA_AT_OVERLAP" in rel
     if os.path.exists(L.DEBUG_LIB_PATH):

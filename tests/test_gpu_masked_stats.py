@@ -98,8 +98,16 @@ def test_every_masked_method_against_the_restatement(dt):
 def test_column_sums_are_exact_and_reproducible(dt):
     m, n = 3000, 1500     # (more than one 1,280-column tile of the accumulators)
     A = _mixed(m, n, 0.04, 5, dt)
-    ptr, idx, val = _arrays(A)
     mk = np.random.default_rng(4).random(m) < 0.5
+    if dt == np.float64:
+        # one more column, whose kept squares sum to 2.5 * 2^-1074 + 2^-1200: the correctly rounded sum is 3 * 2^-1074; rounding
+        # the long accumulator to 53 bits first and again into the subnormal range would give 2 * 2^-1074.  A dropped row
+        # holds a large value in it.
+        tiny = [2.0 ** -537, 2.0 ** -537, 2.0 ** -538, 2.0 ** -538, 2.0 ** -600, 1e100]
+        A = sp.hstack([A, sp.csr_matrix((tiny, (np.arange(6), np.zeros(6, int))), shape=(m, 1))], format="csr")
+        A.sort_indices()
+        mk[:5], mk[5], n = True, False, n + 1
+    ptr, idx, val = _arrays(A)
     sess, R = _resident(A)
     a, b = R.masked_stats(M.COLUMN, mk), R.masked_stats(M.COLUMN, mk)
     for x, y in zip(a, b):
@@ -107,6 +115,12 @@ def test_column_sums_are_exact_and_reproducible(dt):
     fs, fq = _fsum_cols(ptr, idx, val, n, mk)
     np.testing.assert_array_equal(a[0], fs)
     np.testing.assert_array_equal(a[1], fq)
+    if dt == np.float64:
+        ulp = 2.0 ** -1074
+        assert fq[-1] == 3 * ulp and a[2][-1] == 5
+        np.testing.assert_array_equal(R.sum_col_masked(mk), fs)
+        # sumsq / count - mean^2 in f64: 3 ulp / 5 rounds to 1 ulp (2 ulp / 5 would round to 0); mean^2 underflows to 0
+        assert R.var_col_masked(mk)[-1] == fq[-1] / 5 - (fs[-1] / 5) ** 2 == ulp
 
 
 @pytest.mark.parametrize("dt", [np.float32, np.float64])

@@ -12,6 +12,7 @@ import torch
 
 import sapca
 import sapca_oracle as O
+from exact_sums_ref import exact_column_sums as _exact_column_sums
 from sapca import _lib as L
 from sapca import ops, synth
 from sapca import PowerIterationNormalizer as PIN
@@ -52,18 +53,6 @@ def test_g1_colstats(golden, session, dtype, tol):
     np.testing.assert_allclose(s, g["sum_col"], rtol=tol, atol=tol)
     np.testing.assert_allclose(sq, g["sum_col_sq"], rtol=tol, atol=tol)
     assert cnt.tolist() == g["cnt"].tolist()
-
-
-def _exact_column_sums(idx, val, n):
-    """correctly rounded exact column sums and sums of squares (math.fsum; squares as exact fractions)"""
-    from fractions import Fraction
-    import math
-    cols = [[] for _ in range(n)]
-    for j, v in zip(idx.tolist(), val.tolist()):
-        cols[j].append(v)
-    s = np.array([math.fsum(c) for c in cols])
-    sq = np.array([float(sum((Fraction(v) * Fraction(v) for v in c), Fraction(0))) for c in cols])
-    return s, sq
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
