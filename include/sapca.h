@@ -303,8 +303,11 @@ sapca_status sapca_normalize_csr_device_f32(sapca_handle h, uint64_t m, uint64_t
 sapca_status sapca_normalize_csr_device_f64(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz,
                                             const int64_t* row_offsets, const int32_t* col_indices, double* values,
                                             const double* sums, uint64_t sums_len, double target, int32_t direction);
-/* <CsrMatrix<T> as Log1P<T>>::log1p_normalize (csr.rs:1069-1078): value = ln(1 + value) in T,
- * in place on the DEVICE value array.                                                           */
+/* <CsrMatrix<T> as Log1P<T>>::log1p_normalize (csr.rs:1069-1078): value = ln(1 + value), in
+ * place on the DEVICE value array.  The sum 1 + value is T's own, as in the reference (not a true
+ * log1p: |value| <= eps/4 and subnormals give +0.0); the logarithm is evaluated in f64 and rounded
+ * once to T, within 1 ulp of T of whatever a libm ln returns.  value = -1 gives -inf, value < -1
+ * and NaN give NaN, +inf stays +inf, -0.0 gives +0.0.                                            */
 sapca_status sapca_log1p_csr_device_f32(sapca_handle h, uint64_t nnz, float* values);
 sapca_status sapca_log1p_csr_device_f64(sapca_handle h, uint64_t nnz, double* values);
 /* d_values of sapca_upload_csr_* is writable: a caller that edits the uploaded values with its own
@@ -317,8 +320,18 @@ sapca_status sapca_upload_values_changed(sapca_handle h);
  * MatrixNonZero / MatrixMinMax traits in one call on a device-resident CSR: sum_row|col
  * (csr.rs:259-392), sum_row|col_squared (:558-630), nonzero_row|col (:23-134, stored entries),
  * min_max_row|col (:917-1008: over the stored entries; a row/column without any keeps
- * (T::MAX, -T::MAX), the reference's initial values).  Outputs are HOST arrays of length m or n;
- * any may be NULL.  Sums are accumulated in f64 (the reference accumulates in the caller's T, in
+ * (T::MAX, -T::MAX), the reference's initial values).  min/max compare with `<` and `>` as the
+ * reference does, so a NaN never wins a comparison, and each direction starts where the reference
+ * starts:
+ *   ROW (:987-1005)   from the row's FIRST stored value: a row that begins with a NaN is
+ *                     (NaN, NaN); a NaN later in a row is ignored; a row of +inf alone (or +inf
+ *                     followed by NaNs) has min +inf, a row of -inf alone has max -inf.
+ *   COLUMN (:921-922, :960-967) from (T::MAX, -T::MAX): NaNs are ignored wherever they sit (a
+ *                     column of NaNs alone keeps (MAX, -MAX)); a column of +inf alone keeps min
+ *                     T::MAX (max +inf), a column of -inf alone keeps max -T::MAX (min -inf).
+ * The sign of a zero min or max is not specified.  Sums over a line that holds an inf or a NaN
+ * propagate it as an f64 sum does; f32 subnormals are not flushed.  Outputs are HOST arrays of
+ * length m or n; any may be NULL.  Sums are accumulated in f64 (the reference accumulates in the caller's T, in
  * storage order).  var_row|col (csr.rs:632-726) is host arithmetic on these:
  *   var = (sumsq/N - (sum/N)^2) * N/(N-1), N = the other dimension.                             */
 sapca_status sapca_stats_csr_device_f32(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz,

@@ -405,15 +405,22 @@ def normalize_csr(indptr, indices, data, sums, target, direction):
 
 
 def log1p_csr(data):
-    """Log1P for CsrMatrix, src/sparse/csr.rs:1069-1078: value = (1 + value).ln() in T"""
+    """Log1P for CsrMatrix, src/sparse/csr.rs:1069-1078: value = (1 + value).ln() in T.  The addition is T's own (IEEE:
+    exact parity); the logarithm is evaluated in long double and rounded once to T, so this is the correctly rounded
+    value, which the reference's libm ln stays within 1 ulp of (numpy's f32 log alone strays up to 3 ulp from it)."""
     data = np.asarray(data)
-    return np.log((data.dtype.type(1) + data).astype(data.dtype)).astype(data.dtype)
+    with np.errstate(all="ignore"):
+        one = (data.dtype.type(1) + data).astype(data.dtype)
+        return np.log(one.astype(np.longdouble)).astype(data.dtype)
 
 
 def stats_csr(indptr, indices, data, m, n, direction):
     """(sum, sum_squared, nonzero, min, max) per row or per column: sum_row/col (csr.rs:259-392),
     sum_*_squared (:558-630), nonzero_row/col (:23-134: stored entries), min_max_row/col (:917-1008: over
-    the stored entries, empty rows/columns keep Item::max_value()/min_value() = (T::MAX, -T::MAX))."""
+    the stored entries, empty rows/columns keep Item::max_value()/min_value() = (T::MAX, -T::MAX)).
+    min/max compare as the reference does: COLUMN starts from (MAX, -MAX) and a NaN never wins (:960-967: a column
+    of +inf alone keeps min MAX); ROW starts from the row's first stored value (:987-1005), so a row that begins with
+    a NaN is (NaN, NaN), a NaN later in it never wins, and a row of +inf alone has min +inf."""
     indptr, indices, data = np.asarray(indptr), np.asarray(indices), np.asarray(data)
     ln = n if int(direction) == COLUMN else m
     key = indices if int(direction) == COLUMN else np.repeat(np.arange(m), np.diff(indptr))
@@ -424,8 +431,15 @@ def stats_csr(indptr, indices, data, m, n, direction):
     big = np.finfo(data.dtype).max
     lo = np.full(ln, big, dtype=data.dtype)
     hi = np.full(ln, -big, dtype=data.dtype)
-    np.minimum.at(lo, key, data)
-    np.maximum.at(hi, key, data)
+    if int(direction) == COLUMN:
+        np.fmin.at(lo, key, data)       # fmin / fmax skip a nan operand
+        np.fmax.at(hi, key, data)
+    else:
+        has = np.flatnonzero(np.diff(indptr) > 0)
+        if has.size:
+            first = data[indptr[has]]
+            lo[has] = np.where(np.isnan(first), first, np.fmin.reduceat(data, indptr[has]))
+            hi[has] = np.where(np.isnan(first), first, np.fmax.reduceat(data, indptr[has]))
     return sm, sq, nz, lo, hi
 
 

@@ -80,12 +80,14 @@ void column_counts_f64(const int32_t* idx, int64_t nnz, int64_t n, double* out, 
 template <typename T>
 void normalize_csr(const CsrView<T>& A, T* values, const double* d_sums, double target, bool by_column, double* d_scale,
                    hipStream_t s);
-// Log1P (csr.rs:1069-1078): values = ln(1 + values), in T.
+// Log1P (csr.rs:1069-1078): values = ln(1 + values): the sum in T, the logarithm in f64 and rounded once to T.
 template <typename T>
 void log1p_values(T* values, int64_t nnz, hipStream_t s);
 // sum_row, sum_row_squared, min_max_row of a CSR (applied to A^T: the column versions); any output may be null.
+// from_first_value: a row's min and max start from its first stored value (min_max_row_chunk); otherwise from
+// (MAX, -MAX) (min_max_col_chunk, for the rows of A^T).  A NaN never wins a comparison in either.
 template <typename T>
-void row_stats(const CsrView<T>& A, double* sum, double* sumsq, T* minv, T* maxv, hipStream_t s);
+void row_stats(const CsrView<T>& A, bool from_first_value, double* sum, double* sumsq, T* minv, T* maxv, hipStream_t s);
 
 // ---- batchstats.hip: per-batch statistics and top-n row sums (BatchMatrixVariance / BatchMatrixMean / MatrixNTop) ------
 // the most codes one batch_row_stats launch takes (its LDS budget)

@@ -57,12 +57,14 @@ __global__ void normalize_rows_kernel(const int64_t* __restrict__ ptr, T* __rest
   }
 }
 
-// csr.rs:1071-1076: val = (1 + val).ln(), in T
+// csr.rs:1071-1076: val = (1 + val).ln().  The sum is T's own (IEEE: parity with the reference); the logarithm is taken in
+// f64 and rounded once to T.  For f32 that is the correctly rounded value (the device's f32 log strays up to 2.06 ulp
+// from it, the reference's libm stays within 1: DESIGN.md); the kernel streams the values once and stays HBM-bound.
 template <typename T>
 __global__ void log1p_kernel(T* __restrict__ val, int64_t nnz) {
   int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; e < nnz; e += stride) val[e] = (T)log((T)1 + val[e]);
+  for (; e < nnz; e += stride) val[e] = (T)log((double)((T)1 + val[e]));
 }
 
 template <typename T> struct Lim;
@@ -74,8 +76,11 @@ template <> struct Lim<double> {
 };
 
 // per row: sum, sum of squares (f64 accumulation), min and max over the STORED entries (rows without entries
-// keep the reference's initial values Item::max_value() / Item::min_value(), csr.rs:932-933)
-template <typename T>
+// keep the reference's initial values Item::max_value() / Item::min_value(), csr.rs:932-933).
+// FIRST: min_max_row_chunk (csr.rs:987-1005) starts a row's min and max from its first stored value, so a row that
+// begins with a NaN is (NaN, NaN) and a row of +inf alone has min +inf; without it (the rows of A^T: min_max_col_chunk,
+// csr.rs:921-922, 960-967) both start from (MAX, -MAX).  In either mode a NaN never wins a comparison.
+template <typename T, bool FIRST>
 __global__ void row_stats_kernel(const int64_t* __restrict__ ptr, const T* __restrict__ val, int64_t rows,
                                  double* __restrict__ sum, double* __restrict__ sumsq, T* __restrict__ minv,
                                  T* __restrict__ maxv) {
@@ -85,8 +90,9 @@ __global__ void row_stats_kernel(const int64_t* __restrict__ ptr, const T* __res
   for (int64_t r = wave; r < rows; r += nwaves) {
     double a = 0, b = 0;
     T lo = Lim<T>::hi(), hi = -Lim<T>::hi();
-    const int64_t e1 = ptr[r + 1];
-    for (int64_t e = ptr[r] + lane; e < e1; e += WAVE) {
+    const int64_t e0 = ptr[r], e1 = ptr[r + 1];
+    if (FIRST && e0 < e1) lo = hi = val[e0];
+    for (int64_t e = e0 + lane; e < e1; e += WAVE) {
       const T x = val[e];
       const double v = (double)x;
       a += v;
@@ -154,17 +160,20 @@ void log1p_values(T* values, int64_t nnz, hipStream_t s) {
 }
 
 template <typename T>
-void row_stats(const CsrView<T>& A, double* sum, double* sumsq, T* minv, T* maxv, hipStream_t s) {
+void row_stats(const CsrView<T>& A, bool from_first_value, double* sum, double* sumsq, T* minv, T* maxv, hipStream_t s) {
   if (A.rows == 0) return;
-  hipLaunchKernelGGL((row_stats_kernel<T>), dim3(grid_for(A.rows * WAVE, 256, 4096)), dim3(256), 0, s, A.ptr, A.val, A.rows, sum,
-                     sumsq, minv, maxv);
+  const dim3 grid(grid_for(A.rows * WAVE, 256, 4096));
+  if (from_first_value)
+    hipLaunchKernelGGL((row_stats_kernel<T, true>), grid, dim3(256), 0, s, A.ptr, A.val, A.rows, sum, sumsq, minv, maxv);
+  else
+    hipLaunchKernelGGL((row_stats_kernel<T, false>), grid, dim3(256), 0, s, A.ptr, A.val, A.rows, sum, sumsq, minv, maxv);
   SAPCA_HIP(hipGetLastError());
 }
 
 #define INSTANTIATE(T)                                                                                        \
   template void normalize_csr<T>(const CsrView<T>&, T*, const double*, double, bool, double*, hipStream_t);  \
   template void log1p_values<T>(T*, int64_t, hipStream_t);                                                    \
-  template void row_stats<T>(const CsrView<T>&, double*, double*, T*, T*, hipStream_t);
+  template void row_stats<T>(const CsrView<T>&, bool, double*, double*, T*, T*, hipStream_t);
 INSTANTIATE(float)
 INSTANTIATE(double)
 #undef INSTANTIATE

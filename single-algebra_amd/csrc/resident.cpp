@@ -57,7 +57,7 @@ void stats(H& h, const CsrView<T>& A, int32_t direction, double* sum, double* su
   const CsrView<T> R = direction == 1 ? transpose_into_at(h, A) : A;
   double* d = h.stats.as<double>(3 * len + 1);
   T* dmm = h.out_tmp.as<T>(2 * len);
-  k::row_stats(R, d, d + len, dmm, dmm + len, s);
+  k::row_stats(R, direction == 0, d, d + len, dmm, dmm + len, s);   // ROW: min / max from the first stored value
   k::row_lengths_f64(R.ptr, (int64_t)len, d + 2 * len, s);
   std::vector<double> host(3 * len);
   std::vector<T> mm(2 * len);

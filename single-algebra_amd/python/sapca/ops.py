@@ -220,7 +220,10 @@ class ResidentCsr:
 
     def stats(self, direction):
         """(sum, sum_squared, nonzero, min, max) per row (ROW) or column (COLUMN): sum_row/col, sum_row/col_squared,
-        nonzero_row/col, min_max_row/col of the reference (csr.rs:23-134, 259-392, 558-630, 917-1008)"""
+        nonzero_row/col, min_max_row/col of the reference (csr.rs:23-134, 259-392, 558-630, 917-1008).  min / max compare
+        as the reference does: a NaN never wins; ROW starts from the row's first stored value (a row that begins with a
+        NaN is (NaN, NaN), a row of +inf alone has min +inf), COLUMN from (T::MAX, -T::MAX) (NaNs are ignored, a column
+        of +inf alone keeps min T::MAX).  Lines without entries keep (T::MAX, -T::MAX)."""
         suf, ct = _SUF[self.dtype]
         m, n = self.shape
         ln = n if int(direction) == COLUMN else m
@@ -393,8 +396,10 @@ class ResidentCsr:
 
     def min_max_col_chunk(self, reference):
         """MatrixMinMax::min_max_col_chunk (csr.rs:939-973): reference = (mins, maxs); each column's stored values narrow
-        mins[c] / maxs[c] (a nan in the arrays stays, nan values never win).  Every column with a stored entry must
-        lie inside both arrays."""
+        mins[c] / maxs[c] (a nan in the arrays stays, nan values never win: a column of NaNs alone changes nothing).
+        The column's own min / max come from stats(COLUMN), which start at (T::MAX, -T::MAX): a column holding only
+        +inf lowers a mins[c] above T::MAX to T::MAX (the reference leaves it), and the mirror for -inf.  Every column
+        with a stored entry must lie inside both arrays."""
         mins, maxs = reference
         _, _, nz, lo, hi = self.stats(COLUMN)
         has = np.flatnonzero(nz)
@@ -408,8 +413,9 @@ class ResidentCsr:
 
     def min_max_row_chunk(self, reference):
         """MatrixMinMax::min_max_row_chunk (csr.rs:975-1008): reference = (mins, maxs); rows with stored entries overwrite
-        mins[r] / maxs[r] with their own min / max, the others are left alone.  Every row with a stored entry must lie
-        inside both arrays."""
+        mins[r] / maxs[r] with their own min / max, the others are left alone.  The reference starts a row from its
+        first stored value: a row that begins with a NaN writes (NaN, NaN), a NaN later in a row is ignored, a row of
+        +inf alone writes min +inf (of -inf alone, max -inf).  Every row with a stored entry must lie inside both arrays."""
         mins, maxs = reference
         _, _, nz, lo, hi = self.stats(ROW)
         has = np.flatnonzero(nz)

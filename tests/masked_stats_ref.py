@@ -102,13 +102,26 @@ def var_row_chunk(ptr, idx, val, m, n, reference):
 
 
 def _min_max(ptr, idx, val, m, n, direction):
-    key = _rows(ptr) if direction == ROW else np.asarray(idx, np.int64)
-    ln = m if direction == ROW else n
+    """(has entries, min, max) per line over the stored values, compared as the reference compares (`<`, `>`: a NaN never
+    wins).  COLUMN: from (+inf, -inf), so that narrowing the caller's arrays with the result is the reference's loop;
+    ROW: from the row's first stored value -- a row that begins with a NaN is (NaN, NaN)."""
+    ptr = np.asarray(ptr, np.int64)
     x = np.asarray(val)
-    lo = np.full(ln, np.inf, x.dtype if x.dtype.kind == "f" else np.float64)
-    hi = np.full(ln, -np.inf, lo.dtype)
-    np.minimum.at(lo, key, x)
-    np.maximum.at(hi, key, x)
+    dt = x.dtype if x.dtype.kind == "f" else np.float64
+    x = x.astype(dt)
+    ln = m if direction == ROW else n
+    lo, hi = np.full(ln, np.inf, dt), np.full(ln, -np.inf, dt)
+    if direction == ROW:
+        has = np.diff(ptr) > 0
+        j = np.flatnonzero(has)
+        if j.size:
+            first = x[ptr[j]]
+            lo[j] = np.where(np.isnan(first), first, np.fmin.reduceat(x, ptr[j]))
+            hi[j] = np.where(np.isnan(first), first, np.fmax.reduceat(x, ptr[j]))
+        return has, lo, hi
+    key = np.asarray(idx, np.int64)
+    np.fmin.at(lo, key, x)      # fmin / fmax skip a nan operand
+    np.fmax.at(hi, key, x)
     return np.bincount(key, minlength=ln)[:ln] > 0, lo, hi
 
 
@@ -116,7 +129,7 @@ def min_max_col_chunk(ptr, idx, val, m, n, reference):
     mins, maxs = reference
     has, lo, hi = _min_max(ptr, idx, val, m, n, COLUMN)
     j = np.flatnonzero(has)
-    mins[j] = np.where(lo[j] < mins[j], lo[j], mins[j])
+    mins[j] = np.where(lo[j] < mins[j], lo[j], mins[j])     # (a nan in the caller's arrays stays: nothing is < or > it)
     maxs[j] = np.where(hi[j] > maxs[j], hi[j], maxs[j])
     return reference
 
