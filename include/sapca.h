@@ -63,7 +63,9 @@ extern "C" {
                                                   0, the value every caller passed, is the behaviour of before)
                                  additive, ABI 4: sapca_select_rows_csr_device_*
                                  additive, ABI 4: sapca_check_csr_device_*, sapca_canonicalize_csr_device_*
-                                 additive, ABI 4: sapca_select_submatrix_csr_device_*                                 */
+                                 additive, ABI 4: sapca_select_submatrix_csr_device_*
+                                 additive, ABI 4: sapca_covariate_basis, sapca_set_covariates, sapca_get_covariate_rank,
+                                                  sapca_project_out_panel_*                                           */
 
 typedef struct sapca_handle_s* sapca_handle;
 
@@ -163,6 +165,47 @@ sapca_status sapca_set_mask(sapca_handle h, const uint8_t* mask, size_t len);
  * stream is not reproducible, so parity is checked with a shared Omega.       */
 sapca_status sapca_set_omega_f32(sapca_handle h, const float* omega, size_t rows, size_t cols);
 sapca_status sapca_set_omega_f64(sapca_handle h, const double* omega, size_t rows, size_t cols);
+
+/* ---- per-row covariates, regressed out implicitly (opt-in; the reference has no counterpart: its consumers build the dense
+ * residual matrix on the host) ----
+ * A randomized fit with covariates set is the fit of R = (I - Q Q^T) A, where Q is an orthonormal basis of the design matrix
+ * D = [1 | z] (options.center = 1: the intercept IS the centring) or D = z (center = 0).  R is never formed: the sweeps run
+ * uncentred, every A-sweep's panel is projected (Y <- Y - Q (Q^T Y), csrc/covar.hip) and every A^T-sweep is corrected by
+ * G (Q^T Y), G = A^T Q, so that it is A^T (I - Q Q^T) Y whatever rounding left in Y.  Batch labels (one-hot columns),
+ * sequencing depth, any regress_out-style covariate and per-batch centring are designs of a few columns; collinear designs
+ * (one-hot codes of every batch plus the intercept) are legal: only the span matters.
+ *   fit        every fitted quantity is that of R under the same options -- singular values, components (with svd_flip),
+ *              explained_variance_ = sigma^2 / (m - 1), the ratios, importances -- except mean_, which stays the column means
+ *              of A (zeros for center = 0).  The total variance is sum_j (sumsq_j - |(Q^T A)_j|^2) / (m - 1) over the columns
+ *              the fit uses for center = 1, and the reference's quirk unchanged (sum sigma_i^2 / (m - 1), sparse/mod.rs:218-223)
+ *              for center = 0.  The denominator stays m - 1 (not m - rank): the results equal those of this library run on
+ *              the densified R.  n_components > min(m - rank, n_used) is SAPCA_ERR_SVD ("n_components exceeds the matrix
+ *              dimensions").
+ *   transform  (SAPCA_TRANSFORM_CENTERED only) scores = A V^T - Q_rows C with C = Q^T A V^T (rank x k, stored at fit) and
+ *              Q_rows = D_rows W built from the covariates set at the time of the call: the fitted matrix's (the result is
+ *              (I - Q Q^T) A V^T), or a new matrix's own rows for out-of-sample scoring, with `cols` as at fit.  Out-of-sample
+ *              results are unique when the new design rows lie in the row space of the fit's design; otherwise the
+ *              pivot-column solution W of sapca_covariate_basis applies (dependent design columns have zero coefficients).
+ * SAPCA_ERR_ARG, checked on the host before anything is enqueued (the handle stays usable, a fitted model stays fitted):
+ * more than SAPCA_MAX_DESIGN_COLUMNS design columns; a non-finite covariate; z == NULL with rows * cols > 0; rows != m at
+ * fit or transform ("covariates have R rows, the matrix M"); SAPCA_LANCZOS ("covariates need SVDMethod::Random": the
+ * reference's Lanczos branch does not centre at all, quirk Q1); SAPCA_TRANSFORM_REFERENCE at transform / fit_transform (quirks
+ * Q2 / Q3 have no meaning on residuals); a handle that belongs to a communicator, sapca_multi_* members included (the
+ * projection would need an all-reduce per sweep); a model fitted with covariates transformed without them, or the reverse;
+ * a different `cols` than at fit.  A handle on which covariates were never set, or were cleared, takes exactly the code
+ * paths it took before this feature existed and launches none of its kernels.                                          */
+#define SAPCA_MAX_DESIGN_COLUMNS 16   /* covariate columns + the intercept that center = 1 adds */
+/* Pure host code, no handle (like sapca_partition_rows).  z: rows x cols, row-major, finite.  Each design column is scaled to
+ * unit norm (a zero column is dropped), then a Householder QR with column pivoting in f64; rank r = #{j : |R_jj| >
+ * max(rows, design columns) eps_f64 |R_00|}.  q (rows x 16, row-major) receives the first r columns of Q, zero padded;
+ * w ((cols + center) x 16, zero padded) the map Q = D W: the basic solution on the pivot columns, dependent columns get zero
+ * rows.  Rank 0 is valid and means "no correction".                                                                    */
+sapca_status sapca_covariate_basis(const double* z, uint64_t rows, uint64_t cols, int32_t center, double* q, double* w, uint64_t* rank);
+/* Stores z (HOST, rows x cols f64 row-major, copied) on the handle, like sapca_set_mask and sapca_set_omega_*: the next fit or
+ * transform uses it, and rows must equal that call's m.  rows == 0 or cols == 0 clears.                                */
+sapca_status sapca_set_covariates(sapca_handle h, const double* z, uint64_t rows, uint64_t cols);
+/* design columns (cols + center) and rank of the basis of the fitted model; 0, 0 when it was fitted without covariates */
+sapca_status sapca_get_covariate_rank(sapca_handle h, uint64_t* design_cols, uint64_t* rank);
 
 /* SparsePCA::fit / MaskedSparsePCA::fit          sparse/mod.rs:102-242; masked :255-419
  * Host matrices: the column statistics of the fit (sum_col, sum_col_squared, csr.rs:259-312 and
@@ -274,6 +317,11 @@ sapca_status sapca_spmmt_csr_f64(sapca_handle h, uint64_t m, uint64_t n, uint64_
  * basis of the same span; LU: well-conditioned basis of the same span; NONE: untouched).     */
 sapca_status sapca_normalize_panel_f32(sapca_handle h, int32_t normalizer, uint64_t rows, uint64_t l, float* panel);
 sapca_status sapca_normalize_panel_f64(sapca_handle h, int32_t normalizer, uint64_t rows, uint64_t l, double* panel);
+/* The projection of the covariate route on a rows x l row-major panel in place: panel <- panel - Q (Q^T panel), with Q a
+ * rows x r panel (r <= 16) taken as given (orthonormal columns make it the orthogonal projection).  Q^T panel is summed in
+ * f64 in a fixed order: the same bytes from call to call.                                                             */
+sapca_status sapca_project_out_panel_f32(sapca_handle h, uint64_t rows, uint64_t l, float* panel, uint32_t r, const float* q);
+sapca_status sapca_project_out_panel_f64(sapca_handle h, uint64_t rows, uint64_t l, double* panel, uint32_t r, const double* q);
 /* The built-in Omega generator (rows x l standard normal from (seed)), for inspection.        */
 sapca_status sapca_generate_omega_f32(sapca_handle h, uint64_t rows, uint64_t l, float* out);
 sapca_status sapca_generate_omega_f64(sapca_handle h, uint64_t rows, uint64_t l, double* out);

@@ -254,7 +254,10 @@ void download_out(sapca_handle h, const T* d, T* out, size_t count) {
 template <typename T>
 sapca_status fit_host(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const uint64_t* ro, const uint64_t* ci,
                       const T* v) {
-  return guarded(h, [&] { Engine<T>::fit(*h, upload<T>(h, m, n, nnz, ro, ci, v, true)); });
+  return guarded(h, [&] {
+    sapca::covar_check(*h, m, true, false);
+    Engine<T>::fit(*h, upload<T>(h, m, n, nnz, ro, ci, v, true));
+  });
 }
 
 template <typename T>
@@ -267,6 +270,7 @@ sapca_status transform_host(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz
         throw Error(SAPCA_ERR_MASK_LEN, "The mask vector length and the number of features (columns) have to be the same!");
       if (!h->fitted) throw Error(SAPCA_ERR_NOT_FITTED, "Must be fitted before transform!");
     }
+    sapca::covar_check(*h, m, fit_first, fit_first);
     CsrView<T> A = upload<T>(h, m, n, nnz, ro, ci, v, fit_first);
     if (fit_first) Engine<T>::fit(*h, A, true);   // (its host-side tail runs once the projection is queued)
     try {
@@ -283,7 +287,10 @@ sapca_status transform_host(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz
 template <typename T>
 sapca_status fit_device(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i,
                         const T* v) {
-  return guarded(h, [&] { Engine<T>::fit(*h, device_view<T>(m, n, nnz, p, i, v)); });
+  return guarded(h, [&] {
+    sapca::covar_check(*h, m, true, false);
+    Engine<T>::fit(*h, device_view<T>(m, n, nnz, p, i, v));
+  });
 }
 
 template <typename T>
@@ -292,6 +299,7 @@ sapca_status transform_device(sapca_handle h, uint64_t m, uint64_t n, uint64_t n
   return guarded(h, [&] {
     SAPCA_CHECK(d_out != nullptr || m == 0, SAPCA_ERR_ARG, "null output buffer");
     CsrView<T> A = device_view<T>(m, n, nnz, p, i, v);
+    sapca::covar_check(*h, m, fit_first, fit_first);
     T* host_out = out_on_host ? d_out : nullptr;
     // (the staging holds what transform() writes and download_out() copies: m x k of the model that projects -- the one
     // being fitted here has at most n_components, a fitted one has h->k)
@@ -459,6 +467,31 @@ sapca_status normalize_host(sapca_handle h, int32_t normalizer, uint64_t rows, u
   });
 }
 
+// panel <- panel - Q (Q^T panel): the two kernels of the covariate route on host buffers
+template <typename T>
+sapca_status project_out_host(sapca_handle h, uint64_t rows, uint64_t l, T* panel, uint32_t r, const T* q) {
+  return guarded(h, [&] {
+    constexpr uint64_t kq = sapca::k::kCovarCols;
+    SAPCA_CHECK(l >= 1 && l <= (uint64_t)sapca::k::kMaxPanelWidth && panel && rows >= 1, SAPCA_ERR_ARG, "project_out: panel width must be in [1, 1024]");
+    SAPCA_CHECK(r >= 1 && r <= kq && q, SAPCA_ERR_ARG, "project_out: the basis must have 1 to 16 columns");
+    hipStream_t s = h->stream;
+    const int ld = (int)sapca::round_up((int64_t)l, l > 128 ? 64 : 16);
+    std::vector<T> q16(rows * kq, (T)0);
+    for (uint64_t i = 0; i < rows; ++i) std::copy(q + i * r, q + (i + 1) * r, q16.begin() + i * kq);
+    T* stage = h->scratch.as<T>(rows * l);
+    T* P = h->panel_y.as<T>(rows * ld);
+    T* Q = h->covar_q.as<T>(rows * kq);
+    double* S = h->covar_s.as<double>(kq * (uint64_t)ld);
+    SAPCA_HIP(hipMemcpyAsync(stage, panel, rows * l * sizeof(T), hipMemcpyHostToDevice, s));
+    SAPCA_HIP(hipMemcpyAsync(Q, q16.data(), rows * kq * sizeof(T), hipMemcpyHostToDevice, s));
+    sapca::k::add_padding(stage, (int64_t)rows, (int)l, P, ld, s);
+    sapca::k::panel_qt_y(P, Q, (int64_t)rows, ld, S, h->scratch2, s);
+    sapca::k::panel_sub_qs(P, Q, (int64_t)rows, ld, ld, S, ld, s);
+    sapca::k::strip_padding(P, (int64_t)rows, ld, (int)l, stage, s);
+    download_out(h, stage, panel, (size_t)(rows * l));   // (waits for the stream: q16 is still alive)
+  });
+}
+
 template <typename T>
 sapca_status omega_host(sapca_handle h, uint64_t rows, uint64_t l, T* out) {
   return guarded(h, [&] {
@@ -596,6 +629,45 @@ sapca_status sapca_set_omega_f64(sapca_handle h, const double* omega, size_t row
   return SAPCA_OK;
 }
 
+// z is copied: the next fit or transform reads it (their checks: engine.cpp, covar_check).  What does not depend on that call
+// is refused here: too many design columns for the handle's center option, a value that is not finite.
+sapca_status sapca_set_covariates(sapca_handle h, const double* z, uint64_t rows, uint64_t cols) {
+  if (!h) return SAPCA_ERR_ARG;
+  auto refuse = [&](const std::string& msg) { h->err = msg; return SAPCA_ERR_ARG; };
+  try {
+    if (rows == 0 || cols == 0) {
+      h->covar_z.clear();
+      h->covar_rows = h->covar_cols = 0;
+      h->err.clear();
+      return SAPCA_OK;
+    }
+    if (!z) return refuse("covariates: null array");
+    const uint64_t design = cols + (h->opt.center ? 1 : 0);
+    if (cols > SAPCA_MAX_DESIGN_COLUMNS || design > SAPCA_MAX_DESIGN_COLUMNS)
+      return refuse("covariates: " + std::to_string(design) + " design columns" + (h->opt.center ? " (the intercept included)" : "") +
+                    ", at most " + std::to_string(SAPCA_MAX_DESIGN_COLUMNS) + " are supported");
+    for (uint64_t i = 0; i < rows * cols; ++i)
+      if (!std::isfinite(z[i]))
+        return refuse("covariates: non-finite value at row " + std::to_string(i / cols) + ", column " + std::to_string(i % cols));
+    h->covar_z.assign(z, z + rows * cols);
+    h->covar_rows = rows;
+    h->covar_cols = cols;
+    h->err.clear();
+    return SAPCA_OK;
+  } catch (const std::bad_alloc&) {
+    h->err = "out of host memory";
+    return SAPCA_ERR_NOMEM;
+  }
+}
+
+sapca_status sapca_get_covariate_rank(sapca_handle h, uint64_t* design_cols, uint64_t* rank) {
+  return guarded(h, [&] {
+    need_fitted(h);
+    if (design_cols) *design_cols = h->covar.model.design;
+    if (rank) *rank = h->covar.model.rank;
+  });
+}
+
 #define SAPCA_DEFINE_TYPED(SUF, T)                                                                                       \
   sapca_status sapca_fit_csr_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const uint64_t* ro,             \
                                    const uint64_t* ci, const T* v) {                                                     \
@@ -729,6 +801,9 @@ sapca_status sapca_set_omega_f64(sapca_handle h, const double* omega, size_t row
   }                                                                                                                      \
   sapca_status sapca_generate_omega_##SUF(sapca_handle h, uint64_t rows, uint64_t l, T* out) {                           \
     return omega_host<T>(h, rows, l, out);                                                                               \
+  }                                                                                                                      \
+  sapca_status sapca_project_out_panel_##SUF(sapca_handle h, uint64_t rows, uint64_t l, T* panel, uint32_t r, const T* q) { \
+    return project_out_host<T>(h, rows, l, panel, r, q);                                                                 \
   }
 
 SAPCA_DEFINE_TYPED(f32, float)

@@ -722,6 +722,15 @@ namespace {
 //  GramDevice        | f32 under SAPCA_EIG_DEVICE=1              | opt-in experiment, slower (k::sym_eig_device_ok): one workgroup solves the
 //                    |                                           | eigenproblem and writes M itself -- no wait for the host anywhere in the small SVD
 //  QrJacobi          | f64                                       | R11 through a QR of B^T: B^T = Qz Rz, Rz = Ur S Vr^T  =>  vt = (Qz Ur)^T
+//  covariates        |                                           |
+//  cov               | sapca_set_covariates, basis of rank > 0   | the fit of R = (I - Q Q^T) A without forming it.  center is off for the sweeps (no c,
+//                    | (one rank, SAPCA_RANDOM)                  | mu, 1^T Y): the intercept is a column of the design.  Before the iterations one A^T
+//                    |                                           | sweep of the basis gives G = A^T Q; every A sweep is followed by Y -= Q (Q^T Y)
+//                    |                                           | (covar.hip), every A^T sweep by X -= G (Q^T Y): with it X = A^T (I - Q Q^T) Y whatever
+//                    |                                           | rounding left of Q in the normalised Y -- A^T amplifies that direction by |A^T Q| /
+//                    |                                           | sigma_k, two orders of magnitude where a few columns carry a large offset.  The
+//                    |                                           | A^T sweep sums its slabs itself (the correction needs X), and the small SVD is never
+//                    |                                           | held back: the fit's host tail computes C = G^T V^T, which the projection reads
 enum class AtSweep { OnePiece, TwoPieces };
 enum class SmallSvd { GramHost, GramHostHeldBack, GramDevice, QrJacobi };
 
@@ -735,6 +744,7 @@ struct RandomizedPlan {
   int l = 0, ld = 0, k = 0, ldk = 0, q = 0;
   int norm = 0, variant = 0;
   bool center = false, tiled = false;
+  bool cov = false;          // the covariate route: uncentred sweeps around the projection by the basis Q (see "covariates" below)
   SmallSvd small = SmallSvd::GramHost;
   AtPieces at;
 };
@@ -762,7 +772,9 @@ RandomizedPlan plan_randomized(H& h) {
   p.tiled = h.tiled_a.valid && h.tiled_at.valid;
   p.ld = (p.l > 128 || p.tiled || h.comm.active()) ? panel_ld(p.l, p.tiled ? h.tiled_a.ldp : 0) : (int)round_up(p.l, 16);
   p.q = (int)h.opt.n_power_iterations; p.norm = h.opt.normalizer;
-  p.center = h.opt.center != 0; p.variant = h.opt.spmm_variant;
+  p.cov = h.covar.active();
+  p.center = h.opt.center != 0 && !p.cov;   // (covariates: the intercept of the design is the centring, the sweeps run uncentred)
+  p.variant = h.opt.spmm_variant;
   p.small = sizeof(T) == 8 ? SmallSvd::QrJacobi : k::sym_eig_device_ok(p.l) ? SmallSvd::GramDevice
             : h.held_small.defer ? SmallSvd::GramHostHeldBack : SmallSvd::GramHost;
   return p;
@@ -835,6 +847,59 @@ void sweep_a(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
   k::spmm(Engine<T>::view(h.a_used), &h.tiled_a, f.X, p.ld, f.Y, p.ld, p.ld, p.center ? f.cvec : nullptr, p.variant, h.split_scratch, s);
 }
 
+// ---- covariates: the three steps the route adds to a fit (RandomizedPlan's table) ----
+template <typename T>
+double* covar_s(H& h, int ld) { return h.covar_s.as<double>((size_t)k::kCovarCols * (size_t)std::max(ld, 16)); }
+
+// Q on the device (m x 16, T) and G = A^T Q (n_used x 16, T).  Y carries the basis through the sweep as a panel of the fit's
+// own width -- it is free until the first A sweep -- so the sweep is the one every iteration runs, tile-major formats included.
+template <typename T>
+void covar_basis_sweep(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
+  hipStream_t s = h.stream;
+  constexpr int kq = k::kCovarCols;
+  T* Q = h.covar_q.as<T>((size_t)p.m * kq);
+  SAPCA_HIP(hipMemcpyAsync(Q, h.covar.q_t.data(), (size_t)p.m * kq * sizeof(T), hipMemcpyHostToDevice, s));   // (q_t: a member, alive)
+  T* Gp = h.panel_xs.as<T>(((size_t)std::max<int64_t>(p.n_used, 1) + 1) * p.ld);
+  T* G = h.covar_g.as<T>((size_t)p.n_used * kq);
+  k::add_padding(Q, p.m, kq, f.Y, p.ld, s);
+  {
+    Scope sc(h, C_SPMMT);
+    k::spmm(Engine<T>::view(h.at_used), &h.tiled_at, f.Y, p.ld, Gp, p.ld, p.ld, (const T*)nullptr, p.variant, h.split_scratch, s);
+  }
+  k::strip_padding(Gp, p.n_used, p.ld, kq, G, s);
+}
+
+// What the fitted model keeps of G once the components exist: C = G^T V^T (16 x ldc, f64, stays on the device for the
+// projections) and G^T G (16 x 16, to the host: its trace is what the regression takes out of the total variance).  Both are
+// panel_qt_y with G in the basis' place; V^T as the n_used x ldc panel project_with_components builds, too.
+template <typename T>
+void covar_model_products(H& h, const RandomizedPlan& p) {
+  hipStream_t s = h.stream;
+  constexpr int kq = k::kCovarCols;
+  Scope sc(h, C_ORTHO);
+  const int ldc = (int)round_up(p.k, p.k > 128 ? 64 : 16);
+  h.covar.ldc = ldc;
+  T* W = h.panel_w.as<T>((size_t)std::max<int64_t>(p.n_used, 1) * ldc);
+  double* C = h.covar_c.as<double>((size_t)kq * ldc);
+  double* GG = covar_s<T>(h, kq);
+  const T* G = h.covar_g.ptr<T>();
+  k::scaled_transpose(h.components_dev.ptr<T>(), p.n_used, p.k, nullptr, W, ldc, s);
+  k::panel_qt_y(W, G, p.n_used, ldc, C, h.scratch2, s);
+  k::panel_qt_y(G, G, p.n_used, kq, GG, h.scratch2, s);
+  void* host = h.covar_host.ensure((size_t)kq * kq * sizeof(double));
+  SAPCA_HIP(hipMemcpyAsync(host, GG, (size_t)kq * kq * sizeof(double), hipMemcpyDeviceToHost, s));
+}
+
+// P -= B (Q^T Y) for the m x ld panel Y: B = Q, P = Y behind an A sweep; B = G, P = X behind an A^T sweep.
+template <typename T>
+void covar_project(H& h, const RandomizedPlan& p, FitPanels<T>& f, bool behind_at) {
+  Scope sc(h, C_ORTHO);
+  double* S = covar_s<T>(h, p.ld);
+  k::panel_qt_y(f.Y, h.covar_q.ptr<T>(), p.m, p.ld, S, h.scratch2, h.stream);
+  if (behind_at) k::panel_sub_qs(f.X, h.covar_g.ptr<T>(), p.n_used, p.ld, p.ld, S, p.ld, h.stream);
+  else k::panel_sub_qs(f.Y, h.covar_q.ptr<T>(), p.m, p.ld, p.ld, S, p.ld, h.stream);
+}
+
 // X = Ac^T Y   (R9); partial products are summed over ranks.  The panel is left as the sweep produced it: f.src says what the
 // next pass over X -- the Gram of its normalisation, or of the small SVD -- still has to apply (slabs of a sweep whose tile
 // range was split over workgroups, the centring term mu (1^T Y)^T; the normaliser of Y delivered 1^T Y into f.sv).
@@ -846,7 +911,7 @@ void sweep_at_one_piece(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
     Scope sc(h, C_SPMMT);
     // (one rank: the slabs may stay unsummed; several: the collective needs the sum)
     k::spmm(Engine<T>::view(h.at_used), &h.tiled_at, f.Y, p.ld, f.X, p.ld, p.ld, (const T*)nullptr, p.variant, h.split_scratch, s,
-            h.comm.active() ? nullptr : &f.src);
+            h.comm.active() || p.cov ? nullptr : &f.src);
   }
   if (!f.src.parts) { f.src.parts = f.X; f.src.nsplit = 1; }
   if (h.comm.active()) {
@@ -883,6 +948,7 @@ void sweep_at_two_pieces(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
 template <typename T>
 void sweep_at(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
   p.at.sweep == AtSweep::TwoPieces ? sweep_at_two_pieces(h, p, f) : sweep_at_one_piece(h, p, f);
+  if (p.cov) covar_project(h, p, f, true);
 }
 
 // R8-R10: q power iterations, then Q = qr(Ac X) and X = B^T = Ac^T Q (n_used x l), completed by the small SVD's first pass.
@@ -892,6 +958,7 @@ void power_iterations(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
   T* const sv_out = p.center ? f.sv : nullptr;
   for (int it = 0; it < p.q; ++it) {
     sweep_a(h, p, f);
+    if (p.cov) covar_project(h, p, f, false);
     Engine<T>::normalize(h, f.Y, p.m, p.l, p.ld, p.norm, true, Extras{.passes = 1, .vec_out = sv_out});
     sweep_at(h, p, f);
     Engine<T>::normalize(h, f.X, p.n_used, p.l, p.ld, p.norm, false,
@@ -899,6 +966,7 @@ void power_iterations(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
     f.cvec_current = p.center;
   }
   sweep_a(h, p, f);
+  if (p.cov) covar_project(h, p, f, false);
   Engine<T>::normalize(h, f.Y, p.m, p.l, p.ld, SAPCA_NORM_QR, true, Extras{.vec_out = sv_out});   // Q = qr(Y): always orthonormal
   sweep_at(h, p, f);
 }
@@ -1010,12 +1078,14 @@ void Engine<T>::fit_randomized(H& h) {
   SAPCA_HIP(hipMemsetAsync(lay.info(), 0, sizeof(int), h.stream));
   load_omega(h, p, f);
   p.at = agree_on_at_pieces<T>(h, p);   // (several ranks: a collective and a host wait, at this point of the stream)
+  if (p.cov) covar_basis_sweep(h, p, f);
   power_iterations(h, p, f);
   switch (p.small) {
     case SmallSvd::GramDevice: small_svd_gram_device(h, p, f); break;
     case SmallSvd::QrJacobi: small_svd_qr_jacobi(h, p, f); break;
     default: small_svd_gram_host(h, p, f); break;
   }
+  if (p.cov) covar_model_products<T>(h, p);   // (the components exist: with covariates no small SVD is held back)
 }
 
 // R11 (f32), host half: eigen-decomposition of the l x l Gram staged in small_host by small_svd_gram_host, the factor
@@ -1081,18 +1151,100 @@ void Engine<T>::fit_lanczos(H& h, bool centred) {
 }
 
 // ------------------------------------------------------------------------------------------
+// covariates (sapca_set_covariates): what a fit or a transform settles on the host before it enqueues anything
+// ------------------------------------------------------------------------------------------
+void covar_check(H& h, uint64_t m, bool fit, bool then_transform) {
+  const bool set = !h.covar_z.empty();
+  const bool model = h.covar.model.design > 0;
+  if (!fit) {
+    if (!h.fitted || (!set && !model)) return;   // (not fitted: the reference's own error follows; neither: nothing to do)
+    SAPCA_CHECK(model, SAPCA_ERR_ARG, "transform: covariates are set, but the model was fitted without covariates");
+    SAPCA_CHECK(set, SAPCA_ERR_ARG, "transform: the model was fitted with covariates, but none are set");
+    SAPCA_CHECK(h.covar_cols == h.covar.model.cols, SAPCA_ERR_ARG,
+                "transform: covariates have " + std::to_string(h.covar_cols) + " columns, the fitted model's " + std::to_string(h.covar.model.cols));
+  }
+  if (!set) return;
+  SAPCA_CHECK(!h.comm.active(), SAPCA_ERR_ARG, "covariates are not supported on a handle that belongs to a communicator");
+  SAPCA_CHECK(h.opt.method == SAPCA_RANDOM, SAPCA_ERR_ARG, "covariates need SVDMethod::Random");
+  SAPCA_CHECK(!(then_transform || !fit) || h.opt.transform_semantics == SAPCA_TRANSFORM_CENTERED, SAPCA_ERR_ARG,
+              "covariates need SAPCA_TRANSFORM_CENTERED: the reference's transform semantics have no meaning on residuals");
+  SAPCA_CHECK(h.covar_rows == m, SAPCA_ERR_ARG,
+              "covariates have " + std::to_string(h.covar_rows) + " rows, the matrix " + std::to_string(m));
+}
+
+namespace {
+
+// the orthonormal basis Q of this fit's design and the map W (Q = D W), on the host; Q rounded to T for the device
+template <typename T>
+void covar_fit_basis(H& h) {
+  constexpr size_t kq = k::kCovarCols;
+  H::Covar& c = h.covar;
+  c.fit = {};
+  if (h.covar_z.empty()) return;
+  const size_t m = (size_t)h.covar_rows, design = (size_t)h.covar_cols + (h.opt.center ? 1 : 0);
+  c.q.resize(m * kq);
+  c.w.resize(design * kq);
+  uint64_t rank = 0;
+  SAPCA_CHECK(sapca_covariate_basis(h.covar_z.data(), h.covar_rows, h.covar_cols, h.opt.center ? 1 : 0, c.q.data(), c.w.data(), &rank) == SAPCA_OK,
+              SAPCA_ERR_ARG, "covariates: the design matrix was refused");
+  c.fit = {h.covar_cols, (uint64_t)design, rank};
+  c.q_t.resize(m * kq * sizeof(T));
+  T* qt = reinterpret_cast<T*>(c.q_t.data());
+  for (size_t i = 0; i < m * kq; ++i) qt[i] = (T)c.q[i];
+}
+
+// Q_rows = D_rows W of the fitted model for the rows of the covariates set now, rounded to T (transform)
+template <typename T>
+void covar_rows_basis(H& h) {
+  constexpr size_t kq = k::kCovarCols;
+  H::Covar& c = h.covar;
+  const size_t m = (size_t)h.covar_rows, cols = (size_t)h.covar_cols, off = h.opt.center ? 1 : 0;
+  c.q_t.resize(m * kq * sizeof(T));
+  T* qt = reinterpret_cast<T*>(c.q_t.data());
+  for (size_t i = 0; i < m; ++i)
+    for (size_t j = 0; j < kq; ++j) {
+      double acc = off ? c.w_model[j] : 0.0;
+      for (size_t t = 0; t < cols; ++t) acc += h.covar_z[i * cols + t] * c.w_model[(off + t) * kq + j];
+      qt[i * kq + j] = (T)acc;
+    }
+}
+
+// The host tail of a fit with covariates: W for the projections to come and, for center = 1, the total variance of the
+// residual, sum_j (sumsq_j - |G_j|^2) / (m - 1) over the columns the fit used; sum_j |G_j|^2 = trace(G^T G), which
+// covar_model_products sent to covar_host.  The caller has waited for the stream.
+void covar_finish_fit(H& h) {
+  constexpr size_t kq = k::kCovarCols;
+  H::Covar& c = h.covar;
+  if (c.fit.design == 0) return;
+  c.w_model = c.w;
+  if (!c.active() || !h.opt.center) return;
+  const double* GG = static_cast<const double*>(h.covar_host.p);
+  const double* sums = static_cast<const double*>(h.stats_host.p);
+  const size_t n = (size_t)h.stats_cols;
+  double raw = 0, taken = 0;
+  if (h.has_mask_maps) for (uint64_t j : h.cols_to_use) raw += sums[n + (size_t)j];
+  else for (size_t j = 0; j < n; ++j) raw += sums[n + j];
+  for (size_t i = 0; i < kq; ++i) taken += GG[i * kq + i];
+  h.total_var = (raw - taken) / (double)(h.m_fit - 1);
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------
 // fit
 // ------------------------------------------------------------------------------------------
 template <typename T>
 void Engine<T>::fit(H& h, const CsrView<T>& A, bool defer_finish) {
   hipStream_t s = h.stream;
+  covar_check(h, (uint64_t)A.rows, true, false);   // (first: a refused fit leaves the handle as it was)
   h.held_tail.reset();
   h.held_small.reset();
+  covar_fit_basis<T>(h);
   {
     // GramHostHeldBack (RandomizedPlan's route table has the break-even)
     const double lw = (double)(h.opt.n_components + h.opt.n_oversamples) <= 64 ? 64.0 : 128.0;
     h.held_small.defer = defer_finish && h.mask.empty() && h.opt.method == SAPCA_RANDOM && sizeof(T) == 4 &&
-                         (h.comm.active() || (double)A.rows * lw * lw <= 400e3 * 64.0 * 64.0);
+                         (h.comm.active() || (double)A.rows * lw * lw <= 400e3 * 64.0 * 64.0) && !h.covar.active();
   }
   h.spans.clear();
   h.comm.host_ms = 0;
@@ -1104,7 +1256,7 @@ void Engine<T>::fit(H& h, const CsrView<T>& A, bool defer_finish) {
   SAPCA_CHECK(A.rows > 0 && A.cols > 0, SAPCA_ERR_ARG, "empty matrix");
   prepare(h, A);   // (throws where the mask selects no feature)
   const int64_t n_used = h.a_used.cols;
-  if ((int64_t)h.opt.n_components > std::min<int64_t>((int64_t)h.m_global, n_used))
+  if ((int64_t)h.opt.n_components > std::min<int64_t>((int64_t)h.m_global - (int64_t)h.covar.fit.rank, n_used))
     throw Error(SAPCA_ERR_SVD, std::string(h.opt.method == SAPCA_RANDOM ? "Randomized SVD" : "SVD") +
                                    " computation failed: n_components exceeds the matrix dimensions");
   SAPCA_CHECK(h.m_global >= 2, SAPCA_ERR_ARG, "need at least two samples");
@@ -1148,13 +1300,15 @@ void Engine<T>::fit(H& h, const CsrView<T>& A, bool defer_finish) {
   h.m_fit = h.m_global;
   h.dtype = kDtype;
   h.fitted = true;
+  h.covar.model = h.covar.fit;   // (now, not in the tail: a held-back tail runs behind the projection, whose checks read this)
   h.timer.stop(total_ev);
   h.held_tail.total_ev = total_ev;
   h.held_tail.pending = true;
   // fit_transform: the host-side tail (statistics, timings: two waits for the device) runs once the projection is queued --
   // the model the projection reads is all on the device by now
   // (masked fits finish first: their projection asks the finished statistics whether its two sweeps would cancel, Q3)
-  if (!defer_finish || !h.mask.empty()) finish_fit(h);
+  // (covariates: the projection reads C = G^T V^T, which the tail computes)
+  if (!defer_finish || !h.mask.empty() || h.covar.fit.design > 0) finish_fit(h);
 }
 
 namespace {
@@ -1220,6 +1374,7 @@ void Engine<T>::finish_fit(H& h) {
     for (uint64_t i = 0; i < h.k; ++i) h.total_var += h.expl_var[i];
   }
   SAPCA_HIP(hipStreamSynchronize(s));
+  covar_finish_fit(h);
   collect_timings(h, true);
   if (total_ev >= 0) h.timings.fit_total_ms = h.timer.ms(total_ev);
   describe_sweeps<T>(h);
@@ -1315,12 +1470,13 @@ void project_unrotated(H& h, const Projection<T>& pr, T* d_out) {
 //  Q2 (sparse/mod.rs:268-282), unmasked:            t_ik = sum_j cnt_j (x_ij - [center] mu_j) V_kj
 //  Q3 (sparse_masked/mod.rs:488-529), masked:       the mean is subtracted at stored, kept entries only
 //  centred (opt-in, SAPCA_TRANSFORM_CENTERED):      the mathematically centred projection (A - 1 mu^T) V^T
+//  uncentred (a model fitted with covariates):      A V^T through the centred semantics' one sweep; project_residual_scores finishes it
 template <typename T>
-void project_with_components(H& h, const Projection<T>& pr, T* d_out) {
+void project_with_components(H& h, const Projection<T>& pr, T* d_out, bool uncentred = false) {
   hipStream_t s = h.stream;
   const int k = (int)h.k, ldk = pr.ldk, variant = h.opt.spmm_variant;
   const int64_t m = pr.Au.rows, n_used = (int64_t)h.n_used;
-  const bool center = h.opt.center != 0, masked = !h.mask.empty(), ref_sem = h.opt.transform_semantics == SAPCA_TRANSFORM_REFERENCE;
+  const bool center = h.opt.center != 0 && !uncentred, masked = !h.mask.empty(), ref_sem = h.opt.transform_semantics == SAPCA_TRANSFORM_REFERENCE;
   const T* mu = h.mean_used_dev.ptr<T>();
   T* cvec = SmallLayout(h.small, ldk).c<T>();
   T* W = h.panel_w.as<T>((size_t)n_used * ldk);
@@ -1347,6 +1503,21 @@ void project_with_components(H& h, const Projection<T>& pr, T* d_out) {
   if (route == Q3::Plain) k::spmm(pr.Au, pr.top, W, ldk, d_out, k, k, (const T*)nullptr, variant, h.split_scratch, s);
 }
 
+// A model fitted with covariates: scores = A V^T - Q_rows C, with Q_rows = D_rows W from the covariates set now (the fitted
+// matrix's, or a new matrix's own rows) and C = Q^T A V^T from the fit (covar_c, on the device).  The host array the copy reads is a member.
+template <typename T>
+void project_residual_scores(H& h, const Projection<T>& pr, T* d_out) {
+  hipStream_t s = h.stream;
+  constexpr int kq = k::kCovarCols;
+  const int k = (int)h.k;
+  const int64_t m = pr.Au.rows;
+  project_with_components(h, pr, d_out, true);
+  covar_rows_basis<T>(h);
+  T* Q = h.covar_q.as<T>((size_t)m * kq);
+  SAPCA_HIP(hipMemcpyAsync(Q, h.covar.q_t.data(), (size_t)m * kq * sizeof(T), hipMemcpyHostToDevice, s));
+  k::panel_sub_qs(d_out, Q, m, k, k, h.covar_c.ptr<double>(), h.covar.ldc, s);
+}
+
 }  // namespace
 
 template <typename T>
@@ -1359,6 +1530,7 @@ void Engine<T>::transform(H& h, const CsrView<T>& A, T* d_out) {
   SAPCA_CHECK(h.dtype == kDtype, SAPCA_ERR_ARG, "transform dtype differs from the fitted model's");
   SAPCA_CHECK((uint64_t)A.cols == h.n_cols, SAPCA_ERR_ARG, "transform: column count differs from the fitted matrix");
   SAPCA_CHECK(masked == h.has_mask_maps, SAPCA_ERR_ARG, "transform: mask changed since fit");
+  covar_check(h, (uint64_t)A.rows, false, false);
   // keep the fit's spans (their events stay valid); drop those of an earlier transform
   h.spans.erase(std::remove_if(h.spans.begin(), h.spans.end(), [](const std::pair<int, int>& p) { return p.first == C_TRANSFORM; }),
                 h.spans.end());
@@ -1374,7 +1546,8 @@ void Engine<T>::transform(H& h, const CsrView<T>& A, T* d_out) {
       project_unrotated(h, pr, d_out);
     } else {
       if (h.held_small.pending) finish_small_svd(h, nullptr);   // (a held-back small SVD whose projection cannot take the un-rotated route)
-      project_with_components(h, pr, d_out);
+      if (h.covar.model.rank > 0) project_residual_scores(h, pr, d_out);
+      else project_with_components(h, pr, d_out);
     }
   }
   SAPCA_HIP(hipStreamSynchronize(s));

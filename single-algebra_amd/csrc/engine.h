@@ -31,6 +31,24 @@ struct sapca_handle_s {
   std::vector<double> omega;  // injected test matrix (rows x cols, row-major)
   size_t omega_rows = 0, omega_cols = 0;
 
+  // per-row covariates (sapca_set_covariates): z as given, rows x cols; empty: none, and nothing below is touched
+  std::vector<double> covar_z;
+  uint64_t covar_rows = 0, covar_cols = 0;
+  // The covariate route of a fit or transform in flight and of the fitted model (engine.cpp, "covariates").  `fit` / `model`
+  // describe the design: its columns (z's + the intercept) and the rank of its basis; design == 0: no covariates.
+  struct Covar {
+    struct Shape { uint64_t cols = 0, design = 0, rank = 0; };
+    Shape fit, model;
+    std::vector<double> q, w;        // this fit's basis (rows x 16) and its map Q = D W ((cols + center) x 16)
+    std::vector<double> w_model;     // ... of the fit that made the model
+    int ldc = 0;                     // row stride of covar_c
+    std::vector<unsigned char> q_t;  // q, or D_rows W of a transform, in T: what the device copy reads (alive here: no wait for the copy)
+    bool active() const { return fit.rank > 0; }   // this fit runs the uncentred sweeps with the projection
+  } covar;
+  sapca::DevBuf covar_q, covar_g, covar_s;   // Q (m x 16, T), G = A^T Q (n_used x 16, T), S = Q^T Y of a sweep (f64)
+  sapca::DevBuf covar_c;                     // C = Q^T A V^T = G^T V^T of the fitted model (16 x ldc, f64)
+  sapca::PinnedBuf covar_host;               // G^T G (16 x 16) on its way to the host tail of the fit
+
   // fitted state
   bool fitted = false;
   int dtype = 0;  // 0 = f32, 1 = f64
@@ -202,6 +220,10 @@ CsrView<T> transpose_into_at(sapca_handle_s& h, const CsrView<T>& A) {
   k::transpose_csr(A, at.ptr, at.idx, at.val, h.scratch, h.stream);
   return CsrView<T>{A.cols, A.rows, A.nnz, at.ptr, at.idx, at.val};
 }
+
+// Covariates: the host-side checks of a fit (fit = true; then_transform: a fit_transform) or a transform of an m-row matrix
+// against the covariates set on the handle and those of the fitted model.  Enqueues nothing; throws SAPCA_ERR_ARG.
+void covar_check(sapca_handle_s& h, uint64_t m, bool fit, bool then_transform);
 
 // What a normalisation takes beyond its panel.
 template <typename T>

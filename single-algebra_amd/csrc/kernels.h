@@ -323,6 +323,18 @@ void strip_padding(const T* in, int64_t rows, int ld, int ncols, T* out, hipStre
 template <typename T>
 void add_padding(const T* in, int64_t rows, int ncols, T* out, int ld, hipStream_t s);
 
+// ---- covar.hip: implicit row-side correction by an orthonormal covariate basis (sapca_set_covariates) --------------------
+// columns of the basis panel Q (rows x kCovarCols of T, zero beyond the basis' rank) = SAPCA_MAX_DESIGN_COLUMNS
+constexpr int kCovarCols = 16;
+// S (kCovarCols x ld, f64) = Q^T Y for a rows x ld panel Y, ld % 16 == 0 (ld <= 128) or ld % 64 == 0 (ld <= 1024).  Per-workgroup
+// partial sums (in `scratch`) added in block order by a second kernel: no atomics, the same bits from run to run.
+template <typename T>
+void panel_qt_y(const T* Y, const T* Q, int64_t rows, int ld, double* S, DevBuf& scratch, hipStream_t s);
+// Y[i][c] = T(Y[i][c] - sum_j Q[i][j] S[j * lds + c]) for c < ncols (f64 arithmetic, one rounding).  Y has row stride ld; a full
+// panel (ncols == ld, a width panel_qt_y takes) moves in 16-byte vectors, anything else -- the m x k projection -- by elements.
+template <typename T>
+void panel_sub_qs(T* Y, const T* Q, int64_t rows, int ld, int ncols, const double* S, int lds, hipStream_t s);
+
 // ---- rng.hip ---------------------------------------------------------------------------
 // Omega[r][j] ~ N(0,1) for j < l (zero for l <= j < ld), a pure function of (seed, r*l+j).
 template <typename T>

@@ -281,6 +281,13 @@ class SparsePCA {
   SparsePCA(const SparsePCA&) = delete;
   SparsePCA& operator=(const SparsePCA&) = delete;
 
+  // Per-row covariates of the next fit / transform, regressed out implicitly (sapca_set_covariates; no reference counterpart):
+  // z is rows x cols, row-major; rows == 0 or cols == 0 clears.  SVDMethod::Random only.
+  SparsePCA& set_covariates(const std::vector<double>& z, size_t rows, size_t cols) {
+    if (z.size() != rows * cols) throw Error(SAPCA_ERR_ARG, "covariates: z must hold rows x cols values");
+    check(sapca_set_covariates(h_, z.data(), rows, cols));
+    return *this;
+  }
   SparsePCA& fit(const CsrRef<T>& x) { mask_check(x); check(Abi<T>::fit(h_, x)); return *this; }
   std::vector<T> transform(const CsrRef<T>& x) const {                     // m x k row-major
     mask_check(x);

@@ -210,6 +210,15 @@ impl<T: SapcaFloat> SparsePCA<T> {
     }
     /// for the `&self` methods: no handle yet means nothing was fitted -- the reference's own messages
     fn handle(&self, msg: &'static str) -> Result<&Handle> { self.h.as_ref().ok_or_else(|| anyhow!(msg)) }
+    /// Per-row covariates of the next fit / transform, regressed out implicitly (`sapca_set_covariates`; no reference
+    /// counterpart): `z` is rows x cols, row-major; an empty slice or `cols == 0` clears.  SVDMethod::Random on one device only.
+    pub fn set_covariates(&mut self, z: &[f64], cols: usize) -> Result<&mut Self> {
+        let rows = if cols == 0 { 0 } else { z.len() / cols };
+        if rows * cols != z.len() { return Err(anyhow!("covariates: {} values do not fill rows of {} columns", z.len(), cols)); }
+        let h = self.handle_mut()?;
+        check(h.0, unsafe { ffi::sapca_set_covariates(h.0, z.as_ptr(), rows as u64, cols as u64) })?;
+        Ok(self)
+    }
     /// sparse/mod.rs:102-242
     pub fn fit(&mut self, x: &CsrMatrix<T>) -> Result<&mut Self> {
         let (ro, ci, v) = (x.row_offsets(), x.col_indices(), x.values());

@@ -73,6 +73,18 @@ class Session:
             self._h, C.c_int32(int(normalizer)), C.c_uint64(P.shape[0]), C.c_uint64(P.shape[1]), _p(P, ct)))
         return P
 
+    def project_out_panel(self, P, Q):
+        """sapca_project_out_panel_*: P - Q (Q^T P) for a rows x l panel and a rows x r basis (r <= 16), by the two kernels of
+        the covariate route (csrc/covar.hip)"""
+        P = np.array(P, order="C", copy=True)
+        Q = np.ascontiguousarray(Q, dtype=P.dtype)
+        if Q.ndim != 2 or P.ndim != 2 or Q.shape[0] != P.shape[0]:
+            raise ValueError(f"panel {P.shape} and basis {Q.shape} must be two-dimensional with the same number of rows")
+        suf, ct = _SUF[P.dtype]
+        L.check(self._h, getattr(L.load(), f"sapca_project_out_panel_{suf}")(
+            self._h, C.c_uint64(P.shape[0]), C.c_uint64(P.shape[1]), _p(P, ct), C.c_uint32(Q.shape[1]), _p(Q, ct)))
+        return P
+
     def generate_omega(self, rows, l, dtype=np.float64):
         out = np.zeros((rows, l), dtype=dtype)
         suf, ct = _SUF[np.dtype(dtype)]
@@ -549,6 +561,26 @@ def _upload(self, indptr, indices, data, m, n):
 
 
 Session.upload = _upload
+
+
+def covariate_basis(Z, center=True):
+    """sapca_covariate_basis (host-only code path of the library): (Q, W, rank) for the design D = [1 | Z] (center) or Z.
+    Q: rows x rank, orthonormal columns spanning D's; W: (cols + center) x rank with Q = D W (zero rows for the design
+    columns the pivoted QR found dependent).  Rank 0 gives empty Q and W."""
+    z = np.ascontiguousarray(np.asarray(Z, dtype=np.float64))
+    if z.ndim == 1:
+        z = np.ascontiguousarray(z[:, None])
+    rows, cols = z.shape
+    design = cols + int(bool(center))
+    q = np.zeros((rows, L.MAX_DESIGN_COLUMNS))
+    w = np.zeros((design, L.MAX_DESIGN_COLUMNS))
+    rank = C.c_uint64()
+    st = L.load().sapca_covariate_basis(_p(z, C.c_double) if z.size else None, C.c_uint64(rows), C.c_uint64(cols), C.c_int32(int(bool(center))),
+                                        _p(q, C.c_double), _p(w, C.c_double), C.byref(rank))
+    if st != L.OK:
+        raise L.SapcaError(st, "sapca_covariate_basis refused the design (more than 16 design columns, or a non-finite value)")
+    r = int(rank.value)
+    return q[:, :r].copy(), w[:, :r].copy(), r
 
 
 def partition_rows(indptr, nparts):

@@ -146,7 +146,55 @@ class _Estimator:
                                                       C.c_size_t(om.shape[0]), C.c_size_t(om.shape[1])))
         return self
 
+    # -- per-row covariates, regressed out implicitly (no reference counterpart) ---------------
+    def set_covariates(self, Z=None, batch=None):
+        """Per-row covariates of the next fit / transform (sapca_set_covariates): SVDMethod.Random fits then factor the
+        residual (I - Q Q^T) A of the regression on the design [1 | batch one-hot | Z] (the intercept with center(True))
+        without forming it, and transform (TRANSFORM_CENTERED) scores A V^T - Q_rows C.  Z: (m, c) or (m,) floats; batch:
+        m labels of any hashable kind, expanded to one-hot columns in order of first appearance.  At most 16 design columns,
+        the intercept included; collinear designs are fine.  No arguments clears.  ValueError, before any library call, for
+        a wrong row count (Z against batch), too many columns or a non-finite value."""
+        from .ops import _dense_codes
+        cols = []
+        if batch is not None:
+            labels, codes = _dense_codes(batch)
+            cols.append(np.eye(len(labels), dtype=np.float64)[codes] if len(labels) else np.zeros((0, 0)))
+        if Z is not None:
+            z = np.asarray(Z, dtype=np.float64)
+            if z.ndim == 1:
+                z = z[:, None]
+            if z.ndim != 2:
+                raise ValueError(f"Z must be one- or two-dimensional, got shape {z.shape}")
+            if cols and cols[0].shape[0] != z.shape[0]:
+                raise ValueError(f"covariates have {z.shape[0]} rows, batch {cols[0].shape[0]} labels")
+            cols.append(z)
+        d = np.ascontiguousarray(np.hstack(cols)) if cols else np.zeros((0, 0))
+        if d.size:
+            design = d.shape[1] + int(self.center)
+            if design > L.MAX_DESIGN_COLUMNS:
+                raise ValueError(f"covariates: {design} design columns{' (the intercept included)' if self.center else ''}, "
+                                 f"at most {L.MAX_DESIGN_COLUMNS} are supported")
+            if not np.isfinite(d).all():
+                i, j = np.argwhere(~np.isfinite(d))[0]
+                raise ValueError(f"covariates: non-finite value at row {i}, column {j}")
+        self._covariates = d if d.size else None
+        L.check(self._h, L.load().sapca_set_covariates(self._h, _np_ptr(d, C.c_double) if d.size else None,
+                                                       C.c_uint64(d.shape[0] if d.size else 0), C.c_uint64(d.shape[1] if d.size else 0)))
+        return self
+
+    @property
+    def covariate_rank_(self):
+        """rank of the covariate basis of the fitted model (0: fitted without covariates, or a design of rank 0)"""
+        dc, r = C.c_uint64(), C.c_uint64()
+        L.check(self._h, L.load().sapca_get_covariate_rank(self._h, C.byref(dc), C.byref(r)))
+        return int(r.value)
+
     # -- marshalling ---------------------------------------------------------------------
+    def _covariate_check(self, m):
+        z = getattr(self, "_covariates", None)
+        if z is not None and z.shape[0] != m:
+            raise ValueError(f"covariates have {z.shape[0]} rows, the matrix {m}")
+
     def _mask_check(self, ncols):
         # MaskedSparsePCA raises on ANY length mismatch, including an empty mask (masked :258-262)
         if self._mask is not None and self._mask.size != ncols:
@@ -160,6 +208,7 @@ class _Estimator:
             suf = "f32" if x.values.dtype == torch.float32 else "f64"
             m, n = x.shape
             self._mask_check(n)
+            self._covariate_check(m)
             args = [self._h, C.c_uint64(m), C.c_uint64(n), C.c_uint64(x.nnz),
                     C.c_void_p(x.row_offsets.data_ptr()), C.c_void_p(x.col_indices.data_ptr()),
                     C.c_void_p(x.values.data_ptr())]
@@ -181,6 +230,7 @@ class _Estimator:
         suf, ct = _SUF[dt]
         m, n = x.shape
         self._mask_check(n)
+        self._covariate_check(m)
         ro = as_u64(x.indptr)     # nalgebra_sparse usize layout
         ci = as_u64(x.indices)
         va = np.ascontiguousarray(x.data)
