@@ -65,7 +65,8 @@ extern "C" {
                                  additive, ABI 4: sapca_check_csr_device_*, sapca_canonicalize_csr_device_*
                                  additive, ABI 4: sapca_select_submatrix_csr_device_*
                                  additive, ABI 4: sapca_covariate_basis, sapca_set_covariates, sapca_get_covariate_rank,
-                                                  sapca_project_out_panel_*                                           */
+                                                  sapca_project_out_panel_*
+                                 additive, ABI 4: sapca_knn_device_*                                                  */
 
 typedef struct sapca_handle_s* sapca_handle;
 
@@ -589,6 +590,55 @@ sapca_status sapca_canonicalize_csr_device_f64(sapca_handle h, uint64_t m, uint6
                                                const int64_t* row_offsets, const int32_t* col_indices, const double* values,
                                                uint64_t* nnz_out, const int64_t** d_row_offsets, const int32_t** d_col_indices,
                                                double** d_values, sapca_csr_report* report);
+
+/* ---- the step behind PCA: exact k-nearest neighbours of device-resident score rows ----
+ * The fit and the projection leave the m x n_components scores in HBM; the neighbour graph of those rows feeds clustering,
+ * UMAP / t-SNE and label transfer.  The reference has no such call: its notion of "near" is the SimilarityMeasure trait of
+ * src/similarity/mod.rs (a file its lib.rs does not compile), and this is the neighbour search built on three of its
+ * measures, an opt-in superset like row selection and covariates.
+ * Both inputs are row-major DEVICE panels of d columns with row strides ldq, ldc >= d (a slice of a wider buffer is legal;
+ * nothing beyond column d of a row is read).  d_queries == d_corpus is the usual case, neighbours within one fitted
+ * matrix; another query panel is the out-of-sample case.  Row i of the outputs (DEVICE, mq x n_neighbors each) holds the
+ * n_neighbors corpus rows nearest to query i, best first: d_indices the corpus row numbers, d_values
+ *   SAPCA_KNN_EUCLIDEAN  the distance |a - b| (EuclideanSimilarity's `dist`, similarity/mod.rs:59-64, before its exp(-gamma .));
+ *   SAPCA_KNN_COSINE     CosineSimilarity::calculate, similarity/mod.rs:14-36: <a, b> / sqrt(|a|^2 |b|^2);
+ *   SAPCA_KNN_PEARSON    PearsonSimilarity::calculate, similarity/mod.rs:69-101: the same on the rows minus their own means.
+ * The order is part of the contract: by value (ascending distance, descending similarity), then by ascending corpus index.
+ * The result is deterministic, the same bytes from call to call and whatever the launch geometry (no atomics decide an
+ * order; every output word has one writer).
+ * The search ranks by alpha <a, b> + bias on the f32 / f64 matrix cores and keeps the best n_neighbors under the key
+ * (score, -index); the values are then recomputed for the selected pairs from the rows as given, in f64, rounded once to T,
+ * and each list is sorted again by (value, index).  The selection is exact up to the rounding of its inner products: where
+ * two candidates' scores differ by less than about 4 d eps_T (|a| + max |b|)^2 either may be kept.
+ * SAPCA_KNN_EXCLUDE_SELF skips corpus row j == i for query i: by index, not by distance, so a duplicate of a point is still
+ * a neighbour at distance 0.
+ * Deviation from the reference (the only one): it compares the PAIR's norm product with T::epsilon() (similarity/mod.rs:30,
+ * :95); here a ROW whose norm (after centring, for PEARSON) is <= sqrt(eps_T) is the zero vector, and its similarity to
+ * everything is 0 -- a property of the row, so that the search can scale every row once.
+ * The norm is summed in f64 in one order where the rows are scaled and in another where the values are recomputed: a row
+ * whose norm lies within f64 rounding (a relative 1e-15) of sqrt(eps_T) may be zero for one and not for the other -- it is
+ * then ranked as the zero vector and reported with its true similarity, or the reverse; the lists stay sorted by value.
+ * A non-finite input value gives unspecified neighbours for the rows it touches; a list slot that was never filled holds
+ * index -1 and NaN; no index outside [-1, mc) is ever written.
+ * Outputs are complete when the call returns.  The call runs on the handle's stream, works in buffers of its own (a fitted
+ * model, a cached preparation and the upload's statistics are untouched) and, on a handle that belongs to a communicator,
+ * is local to the rank and issues no collective.  mq == 0 is valid and writes nothing (the sizes are still checked, the
+ * pointers are not looked at).
+ * SAPCA_ERR_ARG, checked on the host before anything is enqueued (the handle stays usable), each with a message that names
+ * the offending number: an unknown metric; unknown flag bits; n_neighbors == 0; n_neighbors > SAPCA_KNN_MAX_NEIGHBORS;
+ * d == 0 or d > 1024; ldq < d or ldc < d (or a stride >= 2^28); mc >= 2^31 (or mq); n_neighbors > mc - (EXCLUDE_SELF ? 1 : 0); a null pointer
+ * with a non-empty shape.                                                                                              */
+typedef enum sapca_knn_metric { SAPCA_KNN_EUCLIDEAN = 0, SAPCA_KNN_COSINE = 1, SAPCA_KNN_PEARSON = 2 } sapca_knn_metric;
+#define SAPCA_KNN_EXCLUDE_SELF 1u
+#define SAPCA_KNN_MAX_NEIGHBORS 128
+sapca_status sapca_knn_device_f32(sapca_handle h, uint64_t mq, const float* d_queries, uint64_t ldq,
+                                  uint64_t mc, const float* d_corpus, uint64_t ldc,
+                                  uint64_t d, int32_t metric, uint32_t n_neighbors, uint32_t flags,
+                                  int32_t* d_indices, float* d_values);
+sapca_status sapca_knn_device_f64(sapca_handle h, uint64_t mq, const double* d_queries, uint64_t ldq,
+                                  uint64_t mc, const double* d_corpus, uint64_t ldc,
+                                  uint64_t d, int32_t metric, uint32_t n_neighbors, uint32_t flags,
+                                  int32_t* d_indices, double* d_values);
 
 /* Measurement support: the rate (GB/s, read + write counted) of a 16-byte-per-lane streaming copy of `bytes`
  * bytes on the handle's device, best of `reps` -- the HBM rate a kernel of this library can attain, reported by

@@ -783,6 +783,11 @@ sapca_status sapca_get_covariate_rank(sapca_handle h, uint64_t* design_cols, uin
                                                    const int32_t** di, T** dv, sapca_csr_report* report) {                 \
     return guarded(h, [&] { resident::canonicalize<T>(*h, unchecked_view(m, n, nnz, p, i, v), nnz_out, dp, di, dv, report); }); \
   }                                                                                                                      \
+  sapca_status sapca_knn_device_##SUF(sapca_handle h, uint64_t mq, const T* dq, uint64_t ldq, uint64_t mc, const T* dc,    \
+                                      uint64_t ldc, uint64_t d, int32_t metric, uint32_t n_neighbors, uint32_t flags,      \
+                                      int32_t* d_indices, T* d_values) {                                                   \
+    return guarded(h, [&] { resident::knn<T>(*h, mq, dq, ldq, mc, dc, ldc, d, metric, n_neighbors, flags, d_indices, d_values); }); \
+  }                                                                                                                      \
   sapca_status sapca_sum_row_n_top_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, \
                                                     const int32_t* i, const T* v, const uint64_t* ns, uint32_t n_ns,        \
                                                     double* out) {                                                          \

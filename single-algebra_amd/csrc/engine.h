@@ -147,6 +147,11 @@ struct sapca_handle_s {
       return ptr.contains(q) || idx.contains(q) || val.contains(q) || idx2.contains(q) || val2.contains(q);
     }
   } canonical;
+  // sapca_knn_device_*: the unit rows of the two panels, the corpus bias, the per-split lists and the merged selection
+  // (nothing else lives in these: a search disturbs no fitted model, preparation or statistics)
+  struct Knn {
+    sapca::DevBuf unit_q, unit_c, bias, part_sc, part_ix, merged;
+  } knn;
   sapca::DevBuf at_ptr, at_idx, at_val;                          // A^T
   sapca::DevBuf ca_ptr, ca_idx, ca_val, cat_ptr, cat_idx, cat_val;  // mask-compacted A, A^T
   sapca::DevBuf drop_stats, drop_tmp;                              // their sums (sum | sumsq, full width) and the sort's work space

@@ -335,6 +335,32 @@ void panel_qt_y(const T* Y, const T* Q, int64_t rows, int ld, double* S, DevBuf&
 template <typename T>
 void panel_sub_qs(T* Y, const T* Q, int64_t rows, int ld, int ncols, const double* S, int lds, hipStream_t s);
 
+// ---- knn.hip: exact k-nearest neighbours of dense row panels (sapca_knn_device_*) ----------------------------------------
+// The launch geometry of the selection: query rows per workgroup (64 * mt), corpus splits per query block, LDS per workgroup.
+struct KnnPlan {
+  int mt = 1, nsplit = 1, tiles_per_split = 1;
+  size_t lds_bytes = 0;
+};
+template <typename T>
+KnnPlan knn_plan(int64_t mq, int64_t mc, int k, int n_cus);
+// EUCLIDEAN: bias[r] = -|x_r|^2 (unit unused).  COSINE / PEARSON: unit (rows x d, row stride d) = the rows (centred for
+// PEARSON) scaled to unit norm, a row of norm <= sqrt(eps_T) as zeros (bias unused).  Reads x[r * ld + t] for t < d only.
+template <typename T>
+void knn_prepare(const T* x, int64_t ld, int64_t rows, int d, int metric, T* unit, T* bias, hipStream_t s);
+// per (query, split) the k best corpus rows of the split's range by (alpha <a, b> + bias, -index), sorted:
+// part_sc / part_ix [mq][plan.nsplit][k]; an unfilled slot holds (-inf, INT_MAX).  bias null: 0.
+template <typename T>
+void knn_select(const T* q, int64_t ldq, int64_t mq, const T* c, int64_t ldc, int64_t mc, const T* bias, int d, int metric, int k,
+                bool exclude_self, const KnnPlan& plan, T* part_sc, int32_t* part_ix, hipStream_t s);
+// merged [mq][k] = the corpus rows of the k best entries of a query's nsplit (<= 64) lists, by the same key
+template <typename T>
+void knn_merge(const T* part_sc, const int32_t* part_ix, int64_t mq, int nsplit, int k, int32_t* merged, hipStream_t s);
+// the values of the selected pairs (sel[query * sel_stride + slot]) from the original rows in f64, rounded once to T, each
+// list sorted by (value ascending for EUCLIDEAN / descending otherwise, index); an unfilled slot gives (-1, NaN), last
+template <typename T>
+void knn_refine(const T* q, int64_t ldq, int64_t mq, const T* c, int64_t ldc, int64_t mc, int d, int metric, const int32_t* sel,
+                int64_t sel_stride, int k, int32_t* out_ix, T* out_val, hipStream_t s);
+
 // ---- rng.hip ---------------------------------------------------------------------------
 // Omega[r][j] ~ N(0,1) for j < l (zero for l <= j < ld), a pure function of (seed, r*l+j).
 template <typename T>

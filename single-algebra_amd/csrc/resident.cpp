@@ -555,5 +555,82 @@ SAPCA_INSTANTIATE_RESIDENT(float)
 SAPCA_INSTANTIATE_RESIDENT(double)
 #undef SAPCA_INSTANTIATE_RESIDENT
 
+// ---- sapca_knn_device_*: the exact k-nearest neighbours of device-resident score rows (the kernels are knn.hip's) --------
+// Everything that can be refused is refused before anything is enqueued or a buffer is touched.
+template <typename T>
+void knn(H& h, uint64_t mq, const T* dq, uint64_t ldq, uint64_t mc, const T* dc, uint64_t ldc, uint64_t d, int32_t metric,
+         uint32_t n_neighbors, uint32_t flags, int32_t* d_indices, T* d_values) {
+  const auto num = [](uint64_t v) { return std::to_string(v); };
+  SAPCA_CHECK(metric == SAPCA_KNN_EUCLIDEAN || metric == SAPCA_KNN_COSINE || metric == SAPCA_KNN_PEARSON, SAPCA_ERR_ARG,
+              "knn: unknown metric " + std::to_string(metric) + " (0 EUCLIDEAN, 1 COSINE, 2 PEARSON)");
+  SAPCA_CHECK((flags & ~(uint32_t)SAPCA_KNN_EXCLUDE_SELF) == 0, SAPCA_ERR_ARG,
+              "knn: unknown flag bits " + num(flags & ~(uint32_t)SAPCA_KNN_EXCLUDE_SELF));
+  const bool exclude_self = (flags & SAPCA_KNN_EXCLUDE_SELF) != 0;
+  SAPCA_CHECK(n_neighbors != 0, SAPCA_ERR_ARG, "knn: n_neighbors is 0");
+  SAPCA_CHECK(n_neighbors <= SAPCA_KNN_MAX_NEIGHBORS, SAPCA_ERR_ARG,
+              "knn: n_neighbors = " + num(n_neighbors) + " exceeds SAPCA_KNN_MAX_NEIGHBORS = " + num(SAPCA_KNN_MAX_NEIGHBORS));
+  SAPCA_CHECK(d != 0, SAPCA_ERR_ARG, "knn: d is 0");
+  SAPCA_CHECK(d <= 1024, SAPCA_ERR_ARG, "knn: d = " + num(d) + " exceeds 1024 columns");
+  SAPCA_CHECK(ldq >= d, SAPCA_ERR_ARG, "knn: ldq = " + num(ldq) + " is less than d = " + num(d));
+  SAPCA_CHECK(ldc >= d, SAPCA_ERR_ARG, "knn: ldc = " + num(ldc) + " is less than d = " + num(d));
+  SAPCA_CHECK(ldq < (1ull << 28) && ldc < (1ull << 28), SAPCA_ERR_ARG,
+              "knn: a row stride of " + num(ldq < (1ull << 28) ? ldc : ldq) + " elements; 2^28 or more are not supported");
+  SAPCA_CHECK(mc < (1ull << 31), SAPCA_ERR_ARG, "knn: mc = " + num(mc) + " corpus rows; 2^31 or more are not supported");
+  SAPCA_CHECK(mq < (1ull << 31), SAPCA_ERR_ARG, "knn: mq = " + num(mq) + " query rows; 2^31 or more are not supported");
+  if ((uint64_t)n_neighbors + (exclude_self ? 1 : 0) > mc)
+    throw Error(SAPCA_ERR_ARG, "knn: n_neighbors = " + num(n_neighbors) + " exceeds the " + num(mc - (exclude_self && mc ? 1 : 0)) +
+                                   " corpus rows a query can have (mc = " + num(mc) + (exclude_self ? ", itself excluded)" : ")"));
+  if (mq == 0) return;   // valid, nothing is read or written: no pointer is looked at
+  SAPCA_CHECK(dc != nullptr, SAPCA_ERR_ARG, "knn: d_corpus is NULL with mc = " + num(mc));
+  SAPCA_CHECK(dq != nullptr, SAPCA_ERR_ARG, "knn: d_queries is NULL with mq = " + num(mq));
+  SAPCA_CHECK(d_indices != nullptr && d_values != nullptr, SAPCA_ERR_ARG, "knn: a NULL output with mq = " + num(mq));
+
+  hipStream_t s = h.stream;
+  const int nn = (int)n_neighbors, dd = (int)d;
+  int n_cus = 0;
+  SAPCA_HIP(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, h.device));
+  const k::KnnPlan plan = k::knn_plan<T>((int64_t)mq, (int64_t)mc, nn, n_cus);
+  H::Knn& w = h.knn;
+  // prepare: what the ranking s(i, j) = alpha <a_i, b_j> + bias_j runs on
+  const T *sq = dq, *sc = dc, *bias = nullptr;
+  int64_t sldq = (int64_t)ldq, sldc = (int64_t)ldc;
+  if (metric == SAPCA_KNN_EUCLIDEAN) {
+    T* b = w.bias.as<T>(mc);
+    k::knn_prepare<T>(dc, (int64_t)ldc, (int64_t)mc, dd, metric, nullptr, b, s);
+    bias = b;
+  } else {
+    T* uc = w.unit_c.as<T>(mc * d);
+    k::knn_prepare<T>(dc, (int64_t)ldc, (int64_t)mc, dd, metric, uc, nullptr, s);
+    sc = uc;
+    sldc = dd;
+    if (dq == dc && ldq == ldc && mq == mc) {   // neighbours within one panel: one set of unit rows
+      sq = uc;
+    } else {
+      T* uq = w.unit_q.as<T>(mq * d);
+      k::knn_prepare<T>(dq, (int64_t)ldq, (int64_t)mq, dd, metric, uq, nullptr, s);
+      sq = uq;
+    }
+    sldq = dd;
+  }
+  const size_t lists = (size_t)mq * plan.nsplit * nn;
+  T* part_sc = w.part_sc.as<T>(lists);
+  int32_t* part_ix = w.part_ix.as<int32_t>(lists);
+  k::knn_select<T>(sq, sldq, (int64_t)mq, sc, sldc, (int64_t)mc, bias, dd, metric, nn, exclude_self, plan, part_sc, part_ix, s);
+  const int32_t* sel = part_ix;
+  if (plan.nsplit > 1) {
+    int32_t* merged = w.merged.as<int32_t>((size_t)mq * nn);
+    k::knn_merge<T>(part_sc, part_ix, (int64_t)mq, plan.nsplit, nn, merged, s);
+    sel = merged;
+  }
+  // refine: the values from the rows as the caller gave them
+  k::knn_refine<T>(dq, (int64_t)ldq, (int64_t)mq, dc, (int64_t)ldc, (int64_t)mc, dd, metric, sel, nn, nn, d_indices, d_values, s);
+  SAPCA_HIP(hipStreamSynchronize(s));   // the outputs are complete when the call returns, whatever stream reads them next
+}
+
+template void knn<float>(H&, uint64_t, const float*, uint64_t, uint64_t, const float*, uint64_t, uint64_t, int32_t, uint32_t, uint32_t,
+                         int32_t*, float*);
+template void knn<double>(H&, uint64_t, const double*, uint64_t, uint64_t, const double*, uint64_t, uint64_t, int32_t, uint32_t, uint32_t,
+                          int32_t*, double*);
+
 }  // namespace resident
 }  // namespace sapca

@@ -54,5 +54,10 @@ template <typename T>
 void canonicalize(H& h, const CsrView<T>& A, uint64_t* nnz_out, const int64_t** d_ptr, const int32_t** d_idx, T** d_val,
                   sapca_csr_report* report);
 
+// sapca_knn_device_*: the n_neighbors nearest corpus rows of every query row of two dense device panels
+template <typename T>
+void knn(H& h, uint64_t mq, const T* d_queries, uint64_t ldq, uint64_t mc, const T* d_corpus, uint64_t ldc, uint64_t d, int32_t metric,
+         uint32_t n_neighbors, uint32_t flags, int32_t* d_indices, T* d_values);
+
 }  // namespace resident
 }  // namespace sapca

@@ -82,6 +82,22 @@ SAPCA_RES(f32, float)
 SAPCA_RES(f64, double)
 #undef SAPCA_RES
 
+// Exact k-nearest neighbours of device-resident rows (sapca_knn_device_*): for each of the mq query rows the n_neighbors
+// nearest of the mc corpus rows, best first, ties by ascending corpus index, into d_indices / d_values (DEVICE, mq x
+// n_neighbors each).  The panels are row-major DEVICE arrays of d columns with row strides ldq, ldc >= d -- the scores a
+// fit_transform left in HBM, taken in place.  Values: the distance (EUCLIDEAN) or the similarity of the reference's
+// similarity/mod.rs (COSINE, PEARSON).  exclude_self skips corpus row i for query i.
+template <typename T> struct KnnAbi;
+template <> struct KnnAbi<float> { static constexpr auto call = &sapca_knn_device_f32; };
+template <> struct KnnAbi<double> { static constexpr auto call = &sapca_knn_device_f64; };
+template <typename T>
+inline void knn_device(sapca_handle h, uint64_t mq, const T* d_queries, uint64_t ldq, uint64_t mc, const T* d_corpus, uint64_t ldc,
+                       uint64_t d, sapca_knn_metric metric, uint32_t n_neighbors, bool exclude_self, int32_t* d_indices, T* d_values) {
+  const sapca_status st = KnnAbi<T>::call(h, mq, d_queries, ldq, mc, d_corpus, ldc, d, (int32_t)metric, n_neighbors,
+                                          exclude_self ? SAPCA_KNN_EXCLUDE_SELF : 0u, d_indices, d_values);
+  if (st != SAPCA_OK) throw Error(st, sapca_last_error(h));
+}
+
 template <typename T>
 class ResidentCsr {
  public:

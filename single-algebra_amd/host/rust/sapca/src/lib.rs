@@ -38,6 +38,10 @@ pub enum SVDMethod {
 }
 impl Default for SVDMethod { fn default() -> Self { Self::Lanczos } }
 
+/// What "near" means to `knn_device`: the Euclidean distance, or the cosine / Pearson similarity of similarity/mod.rs
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum KnnMetric { Euclidean, Cosine, Pearson }
+
 mod sealed { pub trait Sealed {} impl Sealed for f32 {} impl Sealed for f64 {} }
 
 /// The value types libsapca is built for.  One associated function per typed entry point of the C ABI.
@@ -60,10 +64,13 @@ pub trait SapcaFloat: sealed::Sealed + Copy + Default + num_traits::Zero + 'stat
     unsafe fn components(h: ffi::sapca_handle, out: *mut Self, cap: usize) -> i32;
     unsafe fn explained_variance(h: ffi::sapca_handle, out: *mut Self, cap: usize) -> i32;
     unsafe fn mean(h: ffi::sapca_handle, out: *mut Self, cap: usize) -> i32;
+    #[allow(clippy::too_many_arguments)]
+    unsafe fn knn_device(h: ffi::sapca_handle, mq: u64, q: *const Self, ldq: u64, mc: u64, c: *const Self, ldc: u64, d: u64,
+                         metric: i32, n_neighbors: u32, flags: u32, indices: *mut i32, values: *mut Self) -> i32;
 }
 
 macro_rules! impl_sapca_float {
-    ($t:ty, $fit:ident, $transform:ident, $fit_transform:ident, $mfit:ident, $mtransform:ident, $mfit_transform:ident, $fi:ident, $evr:ident, $cevr:ident, $comp:ident, $ev:ident, $mean:ident) => {
+    ($t:ty, $fit:ident, $transform:ident, $fit_transform:ident, $mfit:ident, $mtransform:ident, $mfit_transform:ident, $fi:ident, $evr:ident, $cevr:ident, $comp:ident, $ev:ident, $mean:ident, $knn:ident) => {
         impl SapcaFloat for $t {
             fn to_f64(self) -> f64 { self as f64 }
             unsafe fn fit(h: ffi::sapca_handle, m: u64, n: u64, nnz: u64, ro: *const u64, ci: *const u64, v: *const Self) -> i32 {
@@ -96,17 +103,21 @@ macro_rules! impl_sapca_float {
             unsafe fn components(h: ffi::sapca_handle, out: *mut Self, cap: usize) -> i32 { ffi::$comp(h, out, cap) }
             unsafe fn explained_variance(h: ffi::sapca_handle, out: *mut Self, cap: usize) -> i32 { ffi::$ev(h, out, cap) }
             unsafe fn mean(h: ffi::sapca_handle, out: *mut Self, cap: usize) -> i32 { ffi::$mean(h, out, cap) }
+            unsafe fn knn_device(h: ffi::sapca_handle, mq: u64, q: *const Self, ldq: u64, mc: u64, c: *const Self, ldc: u64, d: u64,
+                                 metric: i32, n_neighbors: u32, flags: u32, indices: *mut i32, values: *mut Self) -> i32 {
+                ffi::$knn(h, mq, q, ldq, mc, c, ldc, d, metric, n_neighbors, flags, indices, values)
+            }
         }
     };
 }
 impl_sapca_float!(f32, sapca_fit_csr_f32, sapca_transform_csr_f32, sapca_fit_transform_csr_f32, sapca_multi_fit_csr_f32,
                   sapca_multi_transform_csr_f32, sapca_multi_fit_transform_csr_f32, sapca_get_feature_importances_f32,
                   sapca_get_explained_variance_ratio_f32, sapca_get_cumulative_explained_variance_ratio_f32,
-                  sapca_get_components_f32, sapca_get_explained_variance_f32, sapca_get_mean_f32);
+                  sapca_get_components_f32, sapca_get_explained_variance_f32, sapca_get_mean_f32, sapca_knn_device_f32);
 impl_sapca_float!(f64, sapca_fit_csr_f64, sapca_transform_csr_f64, sapca_fit_transform_csr_f64, sapca_multi_fit_csr_f64,
                   sapca_multi_transform_csr_f64, sapca_multi_fit_transform_csr_f64, sapca_get_feature_importances_f64,
                   sapca_get_explained_variance_ratio_f64, sapca_get_cumulative_explained_variance_ratio_f64,
-                  sapca_get_components_f64, sapca_get_explained_variance_f64, sapca_get_mean_f64);
+                  sapca_get_components_f64, sapca_get_explained_variance_f64, sapca_get_mean_f64, sapca_knn_device_f64);
 
 /// `.0`: the handle the getters read (with several devices: member 0 -- the fitted state is replicated on all members);
 /// `.1`: the sapca_multi that owns the members, null for a single device.
@@ -218,6 +229,27 @@ impl<T: SapcaFloat> SparsePCA<T> {
         let h = self.handle_mut()?;
         check(h.0, unsafe { ffi::sapca_set_covariates(h.0, z.as_ptr(), rows as u64, cols as u64) })?;
         Ok(self)
+    }
+    /// Exact k-nearest neighbours of device-resident rows (`sapca_knn_device_*`; the neighbour search built on three measures of
+    /// the reference's similarity/mod.rs): for each of the `mq` query rows the `n_neighbors` nearest of the `mc` corpus rows,
+    /// best first, ties by ascending index, into `d_indices` / `d_values` (mq x n_neighbors each).  Every pointer is a DEVICE
+    /// pointer; the panels are row-major with `d` columns and row strides `ldq`, `ldc`.  On a several-device estimator the
+    /// call runs on member 0.
+    ///
+    /// # Safety
+    /// The pointers must be valid device allocations of the stated shapes on the handle's device.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn knn_device(&mut self, mq: usize, d_queries: *const T, ldq: usize, mc: usize, d_corpus: *const T, ldc: usize,
+                             d: usize, metric: KnnMetric, n_neighbors: u32, exclude_self: bool, d_indices: *mut i32,
+                             d_values: *mut T) -> Result<()> {
+        let h = self.handle_mut()?;
+        let code = match metric {
+            KnnMetric::Euclidean => ffi::SAPCA_KNN_EUCLIDEAN,
+            KnnMetric::Cosine => ffi::SAPCA_KNN_COSINE,
+            KnnMetric::Pearson => ffi::SAPCA_KNN_PEARSON,
+        };
+        check(h.0, T::knn_device(h.0, mq as u64, d_queries, ldq as u64, mc as u64, d_corpus, ldc as u64, d as u64, code, n_neighbors,
+                                 exclude_self as u32, d_indices, d_values))
     }
     /// sparse/mod.rs:102-242
     pub fn fit(&mut self, x: &CsrMatrix<T>) -> Result<&mut Self> {

@@ -49,6 +49,11 @@ CSR_FLAG_NAMES = {CSR_BAD_OFFSETS: "BAD_OFFSETS", CSR_COL_RANGE: "COL_RANGE", CS
 
 # flags of sapca_select_submatrix_csr_device_*
 SELECT_DROP_STORED_ZEROS = 1
+# sapca_knn_device_*: metrics, flags, the longest list
+KNN_EUCLIDEAN, KNN_COSINE, KNN_PEARSON = 0, 1, 2
+KNN_METRICS = {"euclidean": KNN_EUCLIDEAN, "cosine": KNN_COSINE, "pearson": KNN_PEARSON}
+KNN_EXCLUDE_SELF = 1
+KNN_MAX_NEIGHBORS = 128
 # covariate columns + the intercept that center = 1 adds (sapca_set_covariates)
 MAX_DESIGN_COLUMNS = 16
 
@@ -78,7 +83,7 @@ _TYPED = [
     "sapca_upload_csr", "sapca_normalize_csr_device", "sapca_log1p_csr_device", "sapca_stats_csr_device",
     "sapca_batch_stats_csr_device", "sapca_sum_row_n_top_csr_device", "sapca_masked_stats_csr_device",
     "sapca_select_rows_csr_device", "sapca_check_csr_device", "sapca_canonicalize_csr_device",
-    "sapca_select_submatrix_csr_device",
+    "sapca_select_submatrix_csr_device", "sapca_knn_device",
     "sapca_multi_fit_csr", "sapca_multi_transform_csr", "sapca_multi_fit_transform_csr",
     "sapca_multi_upload_csr", "sapca_multi_transform_resident", "sapca_multi_fit_transform_resident",
 ]
@@ -178,6 +183,11 @@ def _open(path):
                            C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint8), C.c_uint64, C.c_uint32,
                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                            C.POINTER(C.c_void_p)]
+    for suf in ("f32", "f64"):
+        fn = getattr(lib, f"sapca_knn_device_{suf}", None)   # (absent from an older build loaded for an A/B run)
+        if fn is not None:
+            fn.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64,
+                           C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     return lib
 
 

@@ -17,6 +17,26 @@ def _p(a, ct):
     return a.ctypes.data_as(C.POINTER(ct))
 
 
+def _knn_panel(name, t):
+    """(rows, d, row stride, torch dtype) of a panel for Session.knn: a two-dimensional tensor of float32 / float64 whose
+    rows are contiguous (stride(1) == 1, or a single column) and at least d elements apart -- a slice of a wider buffer
+    is fine.  Pure host checks: ValueError otherwise."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor on the device, got {type(t).__name__}")
+    if t.dim() != 2:
+        raise ValueError(f"{name} must be two-dimensional (rows x d), got shape {tuple(t.shape)}")
+    if t.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{name} must be float32 or float64, got {t.dtype}")
+    rows, d = int(t.shape[0]), int(t.shape[1])
+    if d > 1 and t.stride(1) != 1:
+        raise ValueError(f"{name}: the elements of a row must be contiguous (stride(1) == 1), got strides {tuple(t.stride())}")
+    ld = int(t.stride(0)) if rows > 1 else d
+    if ld < d:
+        raise ValueError(f"{name}: rows overlap (row stride {ld} < d = {d})")
+    return rows, d, ld, t.dtype
+
+
 class Session:
     """A bare handle (default options) to run stage-level operators on."""
 
@@ -90,6 +110,60 @@ class Session:
         suf, ct = _SUF[np.dtype(dtype)]
         L.check(self._h, getattr(L.load(), f"sapca_generate_omega_{suf}")(self._h, C.c_uint64(rows), C.c_uint64(l), _p(out, ct)))
         return out
+
+    def knn(self, queries, corpus=None, n_neighbors=15, metric="euclidean", exclude_self=None):
+        """sapca_knn_device_*: (indices, values), two device tensors of shape (rows of queries, n_neighbors) -- for every query row
+        the n_neighbors nearest rows of `corpus`, best first: int32 corpus row numbers, and the Euclidean distance or the
+        cosine / Pearson similarity of the reference's src/similarity/mod.rs.  Ordered by value (ascending distance,
+        descending similarity), then by ascending index; the same bytes from call to call.  corpus None: the queries
+        themselves, with a row's own index left out unless exclude_self=False.  Both panels are CUDA tensors of one dtype with
+        contiguous rows (a column slice of a wider score buffer is taken in place).  A row of norm <= sqrt(eps) -- after centring,
+        for Pearson -- is the zero vector: similarity 0 to everything.
+        Stream order: the Session works on its own stream (or the one it was given); torch's current stream is synchronised
+        first, and the outputs are complete on return.  Bad arguments raise ValueError here, before any device work."""
+        import torch
+        if isinstance(metric, str):
+            if metric.lower() not in L.KNN_METRICS:
+                raise ValueError(f"unknown metric {metric!r}: one of {sorted(L.KNN_METRICS)}")
+            code = L.KNN_METRICS[metric.lower()]
+        else:
+            code = int(metric)
+            if code not in L.KNN_METRICS.values():
+                raise ValueError(f"unknown metric {metric!r}: one of {sorted(L.KNN_METRICS)}")
+        mq, d, ldq, dt = _knn_panel("queries", queries)
+        if corpus is None:
+            corpus = queries
+            if exclude_self is None:
+                exclude_self = True
+        mc, dc, ldc, dtc = _knn_panel("corpus", corpus)
+        if dc != d:
+            raise ValueError(f"queries have {d} columns, the corpus {dc}")
+        if dtc != dt or corpus.device != queries.device:
+            raise ValueError(f"queries ({dt}, {queries.device}) and corpus ({dtc}, {corpus.device}) must share dtype and device")
+        exclude_self = bool(exclude_self)
+        k = int(n_neighbors)
+        if k < 1:
+            raise ValueError(f"n_neighbors must be at least 1, got {n_neighbors}")
+        if k > L.KNN_MAX_NEIGHBORS:
+            raise ValueError(f"n_neighbors = {k} exceeds the {L.KNN_MAX_NEIGHBORS} the library keeps per query")
+        if k > mc - int(exclude_self):
+            raise ValueError(f"n_neighbors = {k} exceeds the {max(mc - int(exclude_self), 0)} corpus rows a query can have "
+                             f"(corpus rows {mc}{', itself excluded' if exclude_self else ''})")
+        if d < 1 or d > 1024:
+            raise ValueError(f"the panels have {d} columns; 1 .. 1024 are supported")
+        for name, t in (("queries", queries), ("corpus", corpus)):   # (last: everything above is checked without a device)
+            if not t.is_cuda:
+                raise ValueError(f"{name} must live on the device (a CUDA tensor), got a tensor on {t.device}")
+        idx = torch.empty((mq, k), dtype=torch.int32, device=queries.device)
+        val = torch.empty((mq, k), dtype=dt, device=queries.device)
+        suf = "f32" if dt == torch.float32 else "f64"
+        torch.cuda.current_stream().synchronize()   # what torch has queued for the panels is complete before the handle's stream reads them
+        L.check(self._h, getattr(L.load(), f"sapca_knn_device_{suf}")(
+            self._h, C.c_uint64(mq), C.c_void_p(queries.data_ptr() if mq else None), C.c_uint64(ldq), C.c_uint64(mc),
+            C.c_void_p(corpus.data_ptr()), C.c_uint64(ldc), C.c_uint64(d), C.c_int32(code), C.c_uint32(k),
+            C.c_uint32(L.KNN_EXCLUDE_SELF if exclude_self else 0), C.c_void_p(idx.data_ptr() if mq else None),
+            C.c_void_p(val.data_ptr() if mq else None)))
+        return idx, val
 
 
 ROW, COLUMN = 0, 1   # Direction of the reference's Normalize / statistics traits (src/utils.rs)
