@@ -66,7 +66,9 @@ extern "C" {
                                  additive, ABI 4: sapca_select_submatrix_csr_device_*
                                  additive, ABI 4: sapca_covariate_basis, sapca_set_covariates, sapca_get_covariate_rank,
                                                   sapca_project_out_panel_*
-                                 additive, ABI 4: sapca_knn_device_*                                                  */
+                                 additive, ABI 4: sapca_knn_device_*
+                                 additive, ABI 4: sapca_set_column_scaling, sapca_get_column_scale,
+                                                  sapca_scale_panel_rows_*                                            */
 
 typedef struct sapca_handle_s* sapca_handle;
 
@@ -208,6 +210,42 @@ sapca_status sapca_set_covariates(sapca_handle h, const double* z, uint64_t rows
 /* design columns (cols + center) and rank of the basis of the fitted model; 0, 0 when it was fitted without covariates */
 sapca_status sapca_get_covariate_rank(sapca_handle h, uint64_t* design_cols, uint64_t* rank);
 
+/* ---- column scaling, applied implicitly (opt-in; the reference has no counterpart: standardising a sparse matrix on the host
+ * makes it dense) ----
+ * A randomized fit with a scaling set is the fit of S = (A - 1 mu^T) diag(d) (options.center = 1) or S = A diag(d) (center = 0)
+ * over the columns the fit uses (under a mask d is compacted like the columns).  S is never formed and no value of A is
+ * rewritten: A (D X) and D (A^T Y) only touch the thin column-side panels (csrc/colscale.hip); the sweeps, the formats, the
+ * preparation cache and the statistics gathered at upload do not depend on d.
+ *   d          SAPCA_SCALE_WEIGHTS: d_j = weights[j]; a weight of 0 drops the column from the fit.
+ *              SAPCA_SCALE_UNIT_VARIANCE: from the fit's own f64 column sums, ss_j = sumsq_j - sum_j^2 / m, var_j = ss_j / (m - 1),
+ *              d_j = 1 / sqrt(var_j), and d_j = 0 where ss_j <= 4 m eps_f64 sumsq_j: empty columns, columns constant over all
+ *              rows and what rounding leaves of a constant column (ss may even come out negative there).  The variance is
+ *              taken about the mean whatever `center` is; m is the global row count on a communicator.
+ *   fit        singular values, components (k x n_used, right singular vectors of S, with svd_flip), explained_variance_ =
+ *              sigma^2 / (m - 1), the ratios and importances are those of S; mean_ stays the column means of A.  The total
+ *              variance for center = 1 is sum_j d_j^2 var_j (under UNIT_VARIANCE: the number of columns with d_j > 0); for
+ *              center = 0 the reference's quirk is unchanged.  A component's entry at a column with d_j = 0 is exactly 0.
+ *   transform  (SAPCA_TRANSFORM_CENTERED only) scores = (A - 1 mu^T) diag(d) V^T with the d and mu stored at the fit, for the
+ *              fitted matrix and for out-of-sample rows alike; what is set on the handle then only concerns the next fit.
+ *   with       masks; host, device-resident and *_to_host entry points; handles of a communicator and sapca_multi members
+ *              (every rank derives the same d from the all-reduced statistics; no collective is added or changes size; like
+ *              sapca_set_omega_*, the setting has to be applied to every member); SAPCA_SCALE_WEIGHTS with covariates, the
+ *              operator being (I - Q Q^T) A diag(d) and the total variance (sum_j d_j^2 sumsq_j - |Q^T A D|_F^2) / (m - 1).
+ * SAPCA_ERR_ARG, checked on the host before anything is enqueued (the handle stays usable, a fitted model stays fitted): an
+ * unknown mode; weights == NULL with mode 2 and len > 0, or a weights pointer with mode 1; a negative or non-finite weight
+ * ("column scaling: weight W at column J"); len != n at fit ("column scaling has L weights, the matrix N columns");
+ * SAPCA_LANCZOS ("column scaling needs SVDMethod::Random"); SAPCA_TRANSFORM_REFERENCE at transform / fit_transform of a scaled
+ * model ("column scaling needs SAPCA_TRANSFORM_CENTERED": quirks Q2 / Q3 have no meaning on scaled columns); UNIT_VARIANCE with
+ * m < 2; UNIT_VARIANCE together with covariates ("pass explicit weights").  A handle on which scaling was never set, or was
+ * reset to SAPCA_SCALE_NONE, launches none of this feature's kernels and gives bit-identical results.                      */
+typedef enum sapca_column_scaling { SAPCA_SCALE_NONE = 0, SAPCA_SCALE_UNIT_VARIANCE = 1, SAPCA_SCALE_WEIGHTS = 2 } sapca_column_scaling;
+/* Stored on the handle like the mask and the covariates; used by the NEXT fit.  weights: HOST, f64, len = n (all columns of the
+ * matrix, like the mask), copied; only for SAPCA_SCALE_WEIGHTS.  SAPCA_SCALE_NONE clears.                                  */
+sapca_status sapca_set_column_scaling(sapca_handle h, int32_t mode, const double* weights, uint64_t len);
+/* Of the FITTED model: its mode and the n_used factors the fit applied (aligned with the components' columns).  mode and out
+ * may be NULL; a model fitted without scaling reports mode 0 and writes nothing.                                          */
+sapca_status sapca_get_column_scale(sapca_handle h, int32_t* mode, double* out, size_t cap);
+
 /* SparsePCA::fit / MaskedSparsePCA::fit          sparse/mod.rs:102-242; masked :255-419
  * Host matrices: the column statistics of the fit (sum_col, sum_col_squared, csr.rs:259-312 and
  * 558-608, and the per-column counts) are gathered behind the upload's DMA as exact sums rounded
@@ -323,6 +361,10 @@ sapca_status sapca_normalize_panel_f64(sapca_handle h, int32_t normalizer, uint6
  * f64 in a fixed order: the same bytes from call to call.                                                             */
 sapca_status sapca_project_out_panel_f32(sapca_handle h, uint64_t rows, uint64_t l, float* panel, uint32_t r, const float* q);
 sapca_status sapca_project_out_panel_f64(sapca_handle h, uint64_t rows, uint64_t l, double* panel, uint32_t r, const double* q);
+/* The row scaling of the column-scaling route on a rows x l row-major panel in place: panel[r][:] *= T(scale[r]); the factor
+ * is rounded once to T, each product once (csrc/colscale.hip).                                                           */
+sapca_status sapca_scale_panel_rows_f32(sapca_handle h, uint64_t rows, uint64_t l, float* panel, const double* scale);
+sapca_status sapca_scale_panel_rows_f64(sapca_handle h, uint64_t rows, uint64_t l, double* panel, const double* scale);
 /* The built-in Omega generator (rows x l standard normal from (seed)), for inspection.        */
 sapca_status sapca_generate_omega_f32(sapca_handle h, uint64_t rows, uint64_t l, float* out);
 sapca_status sapca_generate_omega_f64(sapca_handle h, uint64_t rows, uint64_t l, double* out);

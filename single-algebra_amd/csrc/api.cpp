@@ -256,6 +256,7 @@ sapca_status fit_host(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, cons
                       const T* v) {
   return guarded(h, [&] {
     sapca::covar_check(*h, m, true, false);
+    sapca::scale_check(*h, m, n, true, false);
     Engine<T>::fit(*h, upload<T>(h, m, n, nnz, ro, ci, v, true));
   });
 }
@@ -271,6 +272,7 @@ sapca_status transform_host(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz
       if (!h->fitted) throw Error(SAPCA_ERR_NOT_FITTED, "Must be fitted before transform!");
     }
     sapca::covar_check(*h, m, fit_first, fit_first);
+    sapca::scale_check(*h, m, n, fit_first, fit_first);
     CsrView<T> A = upload<T>(h, m, n, nnz, ro, ci, v, fit_first);
     if (fit_first) Engine<T>::fit(*h, A, true);   // (its host-side tail runs once the projection is queued)
     try {
@@ -289,6 +291,7 @@ sapca_status fit_device(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, co
                         const T* v) {
   return guarded(h, [&] {
     sapca::covar_check(*h, m, true, false);
+    sapca::scale_check(*h, m, n, true, false);
     Engine<T>::fit(*h, device_view<T>(m, n, nnz, p, i, v));
   });
 }
@@ -300,6 +303,7 @@ sapca_status transform_device(sapca_handle h, uint64_t m, uint64_t n, uint64_t n
     SAPCA_CHECK(d_out != nullptr || m == 0, SAPCA_ERR_ARG, "null output buffer");
     CsrView<T> A = device_view<T>(m, n, nnz, p, i, v);
     sapca::covar_check(*h, m, fit_first, fit_first);
+    sapca::scale_check(*h, m, n, fit_first, fit_first);
     T* host_out = out_on_host ? d_out : nullptr;
     // (the staging holds what transform() writes and download_out() copies: m x k of the model that projects -- the one
     // being fitted here has at most n_components, a fitted one has h->k)
@@ -492,6 +496,28 @@ sapca_status project_out_host(sapca_handle h, uint64_t rows, uint64_t l, T* pane
   });
 }
 
+// panel[r][:] *= T(scale[r]): the row-scaling kernel of the column-scaling route on host buffers
+template <typename T>
+sapca_status scale_rows_host(sapca_handle h, uint64_t rows, uint64_t l, T* panel, const double* scale) {
+  return guarded(h, [&] {
+    SAPCA_CHECK(l >= 1 && l <= (uint64_t)sapca::k::kMaxPanelWidth && panel && scale && rows >= 1, SAPCA_ERR_ARG,
+                "scale_panel_rows: panel width must be in [1, 1024]");
+    hipStream_t s = h->stream;
+    const int ld = (int)sapca::round_up((int64_t)l, l > 128 ? 64 : 16);
+    std::vector<T> dt(rows);
+    for (uint64_t i = 0; i < rows; ++i) dt[i] = (T)scale[i];
+    T* stage = h->scratch.as<T>(rows * l);
+    T* P = h->panel_y.as<T>(rows * ld);
+    T* d = h->scratch2.as<T>(rows);
+    SAPCA_HIP(hipMemcpyAsync(stage, panel, rows * l * sizeof(T), hipMemcpyHostToDevice, s));
+    SAPCA_HIP(hipMemcpyAsync(d, dt.data(), rows * sizeof(T), hipMemcpyHostToDevice, s));
+    sapca::k::add_padding(stage, (int64_t)rows, (int)l, P, ld, s);
+    sapca::k::scale_panel_rows(P, (int64_t)rows, ld, d, s);
+    sapca::k::strip_padding(P, (int64_t)rows, ld, (int)l, stage, s);
+    download_out(h, stage, panel, (size_t)(rows * l));   // (waits for the stream: dt is still alive)
+  });
+}
+
 template <typename T>
 sapca_status omega_host(sapca_handle h, uint64_t rows, uint64_t l, T* out) {
   return guarded(h, [&] {
@@ -668,6 +694,47 @@ sapca_status sapca_get_covariate_rank(sapca_handle h, uint64_t* design_cols, uin
   });
 }
 
+// Stored like the mask and the covariates: the next fit reads it (its checks: engine.cpp, scale_check).  What does not depend
+// on that fit is refused here: an unknown mode, weights where none belong or none where they do, a weight below 0 or not finite.
+sapca_status sapca_set_column_scaling(sapca_handle h, int32_t mode, const double* weights, uint64_t len) {
+  if (!h) return SAPCA_ERR_ARG;
+  auto refuse = [&](const std::string& msg) { h->err = msg; return SAPCA_ERR_ARG; };
+  try {
+    if (mode != SAPCA_SCALE_NONE && mode != SAPCA_SCALE_UNIT_VARIANCE && mode != SAPCA_SCALE_WEIGHTS)
+      return refuse("column scaling: unknown mode " + std::to_string(mode));
+    if (mode == SAPCA_SCALE_UNIT_VARIANCE && weights)
+      return refuse("column scaling: unit variance takes no weights (" + std::to_string(len) + " given)");
+    if (mode == SAPCA_SCALE_WEIGHTS) {
+      if (!weights && len > 0) return refuse("column scaling: null array of " + std::to_string(len) + " weights");
+      for (uint64_t j = 0; j < len; ++j)
+        if (!(weights[j] >= 0.0) || !std::isfinite(weights[j])) {
+          char w[40];
+          snprintf(w, sizeof w, "%g", weights[j]);
+          return refuse(std::string("column scaling: weight ") + w + " at column " + std::to_string(j));
+        }
+      h->scale_weights.assign(weights, weights + len);
+    } else {
+      h->scale_weights.clear();
+    }
+    h->scale_mode = mode;
+    h->err.clear();
+    return SAPCA_OK;
+  } catch (const std::bad_alloc&) {
+    h->err = "out of host memory";
+    return SAPCA_ERR_NOMEM;
+  }
+}
+
+sapca_status sapca_get_column_scale(sapca_handle h, int32_t* mode, double* out, size_t cap) {
+  return guarded(h, [&] {
+    need_fitted(h);
+    if (mode) *mode = h->scale_model;
+    if (!out || h->scale_model == SAPCA_SCALE_NONE) return;
+    SAPCA_CHECK(cap >= h->n_used, SAPCA_ERR_ARG, "output buffer too small");
+    download_out(h, h->scale_d64.ptr<double>(), out, (size_t)h->n_used);
+  });
+}
+
 #define SAPCA_DEFINE_TYPED(SUF, T)                                                                                       \
   sapca_status sapca_fit_csr_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const uint64_t* ro,             \
                                    const uint64_t* ci, const T* v) {                                                     \
@@ -809,6 +876,9 @@ sapca_status sapca_get_covariate_rank(sapca_handle h, uint64_t* design_cols, uin
   }                                                                                                                      \
   sapca_status sapca_project_out_panel_##SUF(sapca_handle h, uint64_t rows, uint64_t l, T* panel, uint32_t r, const T* q) { \
     return project_out_host<T>(h, rows, l, panel, r, q);                                                                 \
+  }                                                                                                                      \
+  sapca_status sapca_scale_panel_rows_##SUF(sapca_handle h, uint64_t rows, uint64_t l, T* panel, const double* scale) {  \
+    return scale_rows_host<T>(h, rows, l, panel, scale);                                                                 \
   }
 
 SAPCA_DEFINE_TYPED(f32, float)

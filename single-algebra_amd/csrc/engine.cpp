@@ -731,6 +731,16 @@ namespace {
 //                    |                                           | sigma_k, two orders of magnitude where a few columns carry a large offset.  The
 //                    |                                           | A^T sweep sums its slabs itself (the correction needs X), and the small SVD is never
 //                    |                                           | held back: the fit's host tail computes C = G^T V^T, which the projection reads
+//  column scaling    |                                           |
+//  scale             | sapca_set_column_scaling, SAPCA_RANDOM    | the fit of S = (A - 1 mu^T) D, D = diag(d), without forming it or touching A, the
+//                    | (any rank count, masks, covariates with   | sweeps or the formats: only the n_used-row panels meet d (colscale.hip).  X <- D X in
+//                    | explicit weights)                         | front of every A sweep (Omega included), its centring vector c = (D X)^T mu = X^T (D mu)
+//                    |                                           | still from the Gram pass of X's normalisation (w = D mu in mu's place); behind every
+//                    |                                           | A^T sweep -- and its all-reduce -- one finishing pass writes Z = D (sum of slabs -
+//                    |                                           | mu sv^T) and the panel's next reader finds it plain.  A kernel of its own rather than
+//                    |                                           | a row factor in PanelSource: gram() and materialize() stay byte for byte what an
+//                    |                                           | unscaled fit runs.  With covariates G = A^T Q is scaled once to D G.  The small SVD is
+//                    |                                           | never held back (the un-rotated projection would need D as well)
 enum class AtSweep { OnePiece, TwoPieces };
 enum class SmallSvd { GramHost, GramHostHeldBack, GramDevice, QrJacobi };
 
@@ -744,7 +754,8 @@ struct RandomizedPlan {
   int l = 0, ld = 0, k = 0, ldk = 0, q = 0;
   int norm = 0, variant = 0;
   bool center = false, tiled = false;
-  bool cov = false;          // the covariate route: uncentred sweeps around the projection by the basis Q (see "covariates" below)
+  bool cov = false;          // the covariate route: uncentred sweeps around the projection by the basis Q (see "covariates" above)
+  bool scale = false;        // the fit of (A - 1 mu^T) D (see "column scaling" above)
   SmallSvd small = SmallSvd::GramHost;
   AtPieces at;
 };
@@ -758,6 +769,7 @@ struct FitPanels {
   T *cvec, *sv;             // c = X^T mu of sweep_a; the column sums 1^T Y of the A^T sweep
   bool cvec_current = false;   // the normaliser of X delivered c
   k::PanelSource<T> src;    // what the next pass over X still has to apply
+  const T *d = nullptr, *dmu = nullptr;   // column scaling: the factors d and d mu in T (null: none)
 };
 
 // Enqueues nothing.
@@ -773,6 +785,7 @@ RandomizedPlan plan_randomized(H& h) {
   p.ld = (p.l > 128 || p.tiled || h.comm.active()) ? panel_ld(p.l, p.tiled ? h.tiled_a.ldp : 0) : (int)round_up(p.l, 16);
   p.q = (int)h.opt.n_power_iterations; p.norm = h.opt.normalizer;
   p.cov = h.covar.active();
+  p.scale = h.scale_fit != 0;
   p.center = h.opt.center != 0 && !p.cov;   // (covariates: the intercept of the design is the centring, the sweeps run uncentred)
   p.variant = h.opt.spmm_variant;
   p.small = sizeof(T) == 8 ? SmallSvd::QrJacobi : k::sym_eig_device_ok(p.l) ? SmallSvd::GramDevice
@@ -841,6 +854,10 @@ void load_omega(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
 template <typename T>
 void sweep_a(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
   hipStream_t s = h.stream;
+  if (p.scale) {   // X <- D X (a normalised X brought c = X^T (D mu) along: the same vector)
+    Scope sc(h, C_ORTHO);
+    k::scale_panel_rows(f.X, p.n_used, p.ld, f.d, s);
+  }
   if (p.center && !f.cvec_current) k::weighted_colsum(f.X, p.n_used, p.ld, f.mu, f.cvec, h.scratch2, s);
   f.cvec_current = false;
   Scope sc(h, C_SPMM);
@@ -867,6 +884,7 @@ void covar_basis_sweep(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
     k::spmm(Engine<T>::view(h.at_used), &h.tiled_at, f.Y, p.ld, Gp, p.ld, p.ld, (const T*)nullptr, p.variant, h.split_scratch, s);
   }
   k::strip_padding(Gp, p.n_used, p.ld, kq, G, s);
+  if (p.scale) k::scale_panel_rows(G, p.n_used, kq, f.d, s);   // D G: the A^T-side correction, C and trace(G^T G) are those of A D
 }
 
 // What the fitted model keeps of G once the components exist: C = G^T V^T (16 x ldc, f64, stays on the device for the
@@ -948,6 +966,12 @@ void sweep_at_two_pieces(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
 template <typename T>
 void sweep_at(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
   p.at.sweep == AtSweep::TwoPieces ? sweep_at_two_pieces(h, p, f) : sweep_at_one_piece(h, p, f);
+  if (p.scale) {   // Z = D (sum of slabs - mu sv^T), behind the all-reduce: the panel is plain from here on
+    Scope sc(h, C_ORTHO);
+    k::finish_scaled_panel(f.X, p.n_used, p.ld, f.src, f.d, h.stream);
+    f.src = k::PanelSource<T>();
+    f.src.parts = f.X; f.src.nsplit = 1;
+  }
   if (p.cov) covar_project(h, p, f, true);
 }
 
@@ -962,7 +986,7 @@ void power_iterations(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
     Engine<T>::normalize(h, f.Y, p.m, p.l, p.ld, p.norm, true, Extras{.passes = 1, .vec_out = sv_out});
     sweep_at(h, p, f);
     Engine<T>::normalize(h, f.X, p.n_used, p.l, p.ld, p.norm, false,
-                         Extras{.passes = 1, .src = &f.src, .w = f.mu, .vec_out = p.center ? f.cvec : nullptr});
+                         Extras{.passes = 1, .src = &f.src, .w = p.scale ? f.dmu : f.mu, .vec_out = p.center ? f.cvec : nullptr});
     f.cvec_current = p.center;
   }
   sweep_a(h, p, f);
@@ -1075,6 +1099,7 @@ void Engine<T>::fit_randomized(H& h) {
   // one collective carries the l column sums of this rank's Y too: they live in the row behind the panel then
   T* sv = h.comm.active() ? X + (size_t)p.n_used * p.ld : lay.s<T>();
   FitPanels<T> f{X, Y, lay, p.center ? h.mean_used_dev.ptr<T>() : nullptr, lay.c<T>(), sv};
+  if (p.scale) { f.d = h.scale_dt.ptr<T>(); f.dmu = h.scale_w.ptr<T>(); }
   SAPCA_HIP(hipMemsetAsync(lay.info(), 0, sizeof(int), h.stream));
   load_omega(h, p, f);
   p.at = agree_on_at_pieces<T>(h, p);   // (several ranks: a collective and a host wait, at this point of the stream)
@@ -1172,7 +1197,51 @@ void covar_check(H& h, uint64_t m, bool fit, bool then_transform) {
               "covariates have " + std::to_string(h.covar_rows) + " rows, the matrix " + std::to_string(m));
 }
 
+// ------------------------------------------------------------------------------------------
+// column scaling (sapca_set_column_scaling): what a fit or a transform settles on the host before it enqueues anything
+// ------------------------------------------------------------------------------------------
+void scale_check(H& h, uint64_t m, uint64_t n, bool fit, bool then_transform) {
+  const int mode = fit ? h.scale_mode : (h.fitted ? h.scale_model : 0);
+  if (mode == SAPCA_SCALE_NONE) return;
+  if (fit) {
+    SAPCA_CHECK(h.opt.method == SAPCA_RANDOM, SAPCA_ERR_ARG, "column scaling needs SVDMethod::Random");
+    if (mode == SAPCA_SCALE_WEIGHTS)
+      SAPCA_CHECK(h.scale_weights.size() == n, SAPCA_ERR_ARG,
+                  "column scaling has " + std::to_string(h.scale_weights.size()) + " weights, the matrix " + std::to_string(n) + " columns");
+    if (mode == SAPCA_SCALE_UNIT_VARIANCE) {
+      SAPCA_CHECK(m >= 2 || h.comm.active(), SAPCA_ERR_ARG,
+                  "column scaling: unit variance needs at least two rows, the matrix has " + std::to_string(m));
+      SAPCA_CHECK(h.covar_z.empty(), SAPCA_ERR_ARG,
+                  "column scaling: unit variance of covariate residuals is not supported (" + std::to_string(h.covar_cols) +
+                      " covariate columns are set): pass explicit weights");
+    }
+  }
+  SAPCA_CHECK(!(then_transform || !fit) || h.opt.transform_semantics == SAPCA_TRANSFORM_CENTERED, SAPCA_ERR_ARG,
+              "column scaling needs SAPCA_TRANSFORM_CENTERED: the reference's transform semantics have no meaning on scaled columns");
+}
+
 namespace {
+
+// The factors of this fit on the device, from the column sums prepare() left there (all-reduced on a communicator, so every
+// rank derives the same d): d in f64 and T, d mu in T, and sum_j d_j^2 var_j on its way to the host tail.  Main stream, no wait.
+template <typename T>
+void column_scale_factors(H& h, int64_t n_used) {
+  hipStream_t s = h.stream;
+  const int64_t n = h.stats_cols;
+  const double* weights = nullptr;
+  if (h.scale_fit == SAPCA_SCALE_WEIGHTS) {   // (scale_weights: a member, alive while the copy reads it)
+    double* w = h.scale_in.as<double>((size_t)std::max<int64_t>(n, 1));
+    SAPCA_HIP(hipMemcpyAsync(w, h.scale_weights.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
+    weights = w;
+  }
+  const size_t cap = (size_t)std::max<int64_t>(n_used, 1), parts = k::column_scale_partials(n_used);
+  double* red = h.scale_red.as<double>(parts + 1);
+  const double* stats = h.stats.ptr<double>();
+  k::column_scale_factors<T>(stats, stats + n, (double)h.m_global, h.has_mask_maps ? h.sel_rows_dev.ptr<int32_t>() : nullptr, weights, n_used,
+                             h.scale_d64.as<double>(cap), h.scale_dt.as<T>(cap), h.scale_w.as<T>(cap), red, red + parts, s);
+  void* host = h.scale_host.ensure(sizeof(double));
+  SAPCA_HIP(hipMemcpyAsync(host, red + parts, sizeof(double), hipMemcpyDeviceToHost, s));
+}
 
 // the orthonormal basis Q of this fit's design and the map W (Q = D W), on the host; Q rounded to T for the device
 template <typename T>
@@ -1222,8 +1291,11 @@ void covar_finish_fit(H& h) {
   const double* sums = static_cast<const double*>(h.stats_host.p);
   const size_t n = (size_t)h.stats_cols;
   double raw = 0, taken = 0;
-  if (h.has_mask_maps) for (uint64_t j : h.cols_to_use) raw += sums[n + (size_t)j];
-  else for (size_t j = 0; j < n; ++j) raw += sums[n + j];
+  // (column scaling, explicit weights only on this route: the raw second moment of A D; G is D G already)
+  const bool scaled = h.scale_model == SAPCA_SCALE_WEIGHTS && h.scale_weights.size() == n;
+  auto moment = [&](size_t j) { return scaled ? h.scale_weights[j] * h.scale_weights[j] * sums[n + j] : sums[n + j]; };
+  if (h.has_mask_maps) for (uint64_t j : h.cols_to_use) raw += moment((size_t)j);
+  else for (size_t j = 0; j < n; ++j) raw += moment(j);
   for (size_t i = 0; i < kq; ++i) taken += GG[i * kq + i];
   h.total_var = (raw - taken) / (double)(h.m_fit - 1);
 }
@@ -1237,6 +1309,8 @@ template <typename T>
 void Engine<T>::fit(H& h, const CsrView<T>& A, bool defer_finish) {
   hipStream_t s = h.stream;
   covar_check(h, (uint64_t)A.rows, true, false);   // (first: a refused fit leaves the handle as it was)
+  scale_check(h, (uint64_t)A.rows, (uint64_t)A.cols, true, false);
+  h.scale_fit = h.scale_mode;
   h.held_tail.reset();
   h.held_small.reset();
   covar_fit_basis<T>(h);
@@ -1244,7 +1318,7 @@ void Engine<T>::fit(H& h, const CsrView<T>& A, bool defer_finish) {
     // GramHostHeldBack (RandomizedPlan's route table has the break-even)
     const double lw = (double)(h.opt.n_components + h.opt.n_oversamples) <= 64 ? 64.0 : 128.0;
     h.held_small.defer = defer_finish && h.mask.empty() && h.opt.method == SAPCA_RANDOM && sizeof(T) == 4 &&
-                         (h.comm.active() || (double)A.rows * lw * lw <= 400e3 * 64.0 * 64.0) && !h.covar.active();
+                         (h.comm.active() || (double)A.rows * lw * lw <= 400e3 * 64.0 * 64.0) && !h.covar.active() && h.scale_fit == 0;
   }
   h.spans.clear();
   h.comm.host_ms = 0;
@@ -1272,6 +1346,7 @@ void Engine<T>::fit(H& h, const CsrView<T>& A, bool defer_finish) {
 
   if (h.opt.method == SAPCA_RANDOM) {
     device_means();
+    if (h.scale_fit) column_scale_factors<T>(h, n_used);
     fit_randomized(h);
   } else {
     // the Lanczos branch does not centre (Q1) unless asked to: only transform reads the means.  On the scatter route the
@@ -1300,6 +1375,7 @@ void Engine<T>::fit(H& h, const CsrView<T>& A, bool defer_finish) {
   h.m_fit = h.m_global;
   h.dtype = kDtype;
   h.fitted = true;
+  h.scale_model = h.scale_fit;
   h.covar.model = h.covar.fit;   // (now, not in the tail: a held-back tail runs behind the projection, whose checks read this)
   h.timer.stop(total_ev);
   h.held_tail.total_ev = total_ev;
@@ -1374,6 +1450,8 @@ void Engine<T>::finish_fit(H& h) {
     for (uint64_t i = 0; i < h.k; ++i) h.total_var += h.expl_var[i];
   }
   SAPCA_HIP(hipStreamSynchronize(s));
+  // column scaling: the total variance of (A - 1 mu^T) D is sum_j d_j^2 var_j, reduced on the device beside the factors
+  if (h.scale_model && h.opt.center) h.total_var = *static_cast<const double*>(h.scale_host.p);
   covar_finish_fit(h);
   collect_timings(h, true);
   if (total_ev >= 0) h.timings.fit_total_ms = h.timer.ms(total_ev);
@@ -1481,6 +1559,7 @@ void project_with_components(H& h, const Projection<T>& pr, T* d_out, bool uncen
   T* cvec = SmallLayout(h.small, ldk).c<T>();
   T* W = h.panel_w.as<T>((size_t)n_used * ldk);
   k::scaled_transpose(h.components_dev.ptr<T>(), n_used, k, ref_sem && !masked ? pr.d_cnt : nullptr, W, ldk, s);
+  if (h.scale_model) k::scale_panel_rows(W, n_used, ldk, h.scale_dt.ptr<T>(), s);   // W = D V^T, with the d (and mu) of the fit
   if (!(ref_sem && masked)) {   // Q2, centred: one sweep, centred through c = W^T mu
     if (center) k::weighted_colsum(W, n_used, ldk, mu, cvec, h.scratch2, s);
     k::spmm(pr.Au, pr.top, W, ldk, d_out, k, k, center ? cvec : nullptr, variant, h.split_scratch, s);
@@ -1531,6 +1610,7 @@ void Engine<T>::transform(H& h, const CsrView<T>& A, T* d_out) {
   SAPCA_CHECK((uint64_t)A.cols == h.n_cols, SAPCA_ERR_ARG, "transform: column count differs from the fitted matrix");
   SAPCA_CHECK(masked == h.has_mask_maps, SAPCA_ERR_ARG, "transform: mask changed since fit");
   covar_check(h, (uint64_t)A.rows, false, false);
+  scale_check(h, (uint64_t)A.rows, (uint64_t)A.cols, false, false);
   // keep the fit's spans (their events stay valid); drop those of an earlier transform
   h.spans.erase(std::remove_if(h.spans.begin(), h.spans.end(), [](const std::pair<int, int>& p) { return p.first == C_TRANSFORM; }),
                 h.spans.end());

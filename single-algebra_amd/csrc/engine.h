@@ -49,6 +49,15 @@ struct sapca_handle_s {
   sapca::DevBuf covar_c;                     // C = Q^T A V^T = G^T V^T of the fitted model (16 x ldc, f64)
   sapca::PinnedBuf covar_host;               // G^T G (16 x 16) on its way to the host tail of the fit
 
+  // column scaling (sapca_set_column_scaling): what the NEXT fit applies.  SAPCA_SCALE_NONE: nothing below is touched
+  int scale_mode = 0;
+  std::vector<double> scale_weights;   // SAPCA_SCALE_WEIGHTS: one per column of the matrix, as given
+  // ... of the fit in flight and of the fitted model (engine.cpp, "column scaling"): the factors of the n_used columns stay on the
+  // device -- d in f64 (sapca_get_column_scale), d and d mu in T (the sweeps, the projection) -- and only sum_j d_j^2 var_j crosses
+  int scale_fit = 0, scale_model = 0;
+  sapca::DevBuf scale_in, scale_d64, scale_dt, scale_w, scale_red;   // the weights (full width); d; T(d); T(d mu); partial sums | their total
+  sapca::PinnedBuf scale_host;                                        // that total on its way to the host tail of the fit
+
   // fitted state
   bool fitted = false;
   int dtype = 0;  // 0 = f32, 1 = f64
@@ -229,6 +238,8 @@ CsrView<T> transpose_into_at(sapca_handle_s& h, const CsrView<T>& A) {
 // Covariates: the host-side checks of a fit (fit = true; then_transform: a fit_transform) or a transform of an m-row matrix
 // against the covariates set on the handle and those of the fitted model.  Enqueues nothing; throws SAPCA_ERR_ARG.
 void covar_check(sapca_handle_s& h, uint64_t m, bool fit, bool then_transform);
+// Column scaling: the same for the scaling set on the handle (a fit of an m x n matrix) or the fitted model's (a transform).
+void scale_check(sapca_handle_s& h, uint64_t m, uint64_t n, bool fit, bool then_transform);
 
 // What a normalisation takes beyond its panel.
 template <typename T>

@@ -335,6 +335,22 @@ void panel_qt_y(const T* Y, const T* Q, int64_t rows, int ld, double* S, DevBuf&
 template <typename T>
 void panel_sub_qs(T* Y, const T* Q, int64_t rows, int ld, int ncols, const double* S, int lds, hipStream_t s);
 
+// ---- colscale.hip: implicit column scaling S = (A - 1 mu^T) diag(d) of a randomized fit (sapca_set_column_scaling) ------------
+// The factors of the n_used columns a fit uses (column j sits at sel[j] of the full-width sums; sel null: at j), from the f64
+// column sums: weights (full width, f64) null: d = 1 / sqrt(var) about the mean, 0 where ss = sumsq - sum^2 / m <= 4 m eps_f64 sumsq;
+// else d = weights.  d64 / dt: d in f64 and rounded once to T; w = T(d * sum / m); *total = sum_j d_j^2 var_j, added in a fixed
+// order through part (column_scale_partials(n_used) doubles).  No atomics.
+size_t column_scale_partials(int64_t n_used);
+template <typename T>
+void column_scale_factors(const double* sum, const double* sumsq, double m, const int32_t* sel, const double* weights, int64_t n_used,
+                          double* d64, T* dt, T* w, double* part, double* total, hipStream_t s);
+// P[r][c] = P[r][c] * d[r] in place for a rows x ld panel whose rows are 16-byte vectors (ld % (16 / sizeof(T)) == 0, P aligned)
+template <typename T>
+void scale_panel_rows(T* P, int64_t rows, int ld, const T* d, hipStream_t s);
+// P[r][c] = d[r] * (sum of src's slabs - src.mu[r] src.sv[c]): what materialize() writes, times d, in one pass (P may be src.parts)
+template <typename T>
+void finish_scaled_panel(T* P, int64_t rows, int ld, const PanelSource<T>& src, const T* d, hipStream_t s);
+
 // ---- knn.hip: exact k-nearest neighbours of dense row panels (sapca_knn_device_*) ----------------------------------------
 // The launch geometry of the selection: query rows per workgroup (64 * mt), corpus splits per query block, LDS per workgroup.
 struct KnnPlan {

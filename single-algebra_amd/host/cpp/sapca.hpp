@@ -304,6 +304,25 @@ class SparsePCA {
     check(sapca_set_covariates(h_, z.data(), rows, cols));
     return *this;
   }
+  // Column scaling of the next fit, applied implicitly (sapca_set_column_scaling; no reference counterpart): the fit is that of
+  // (A - 1 mu^T) diag(d).  SAPCA_SCALE_UNIT_VARIANCE takes no weights; SAPCA_SCALE_WEIGHTS one per column of the matrix;
+  // SAPCA_SCALE_NONE clears.  SVDMethod::Random only.
+  SparsePCA& set_column_scaling(sapca_column_scaling mode, const std::vector<double>& weights = {}) {
+    check(sapca_set_column_scaling(h_, (int32_t)mode, mode == SAPCA_SCALE_WEIGHTS && !weights.empty() ? weights.data() : nullptr,
+                                   mode == SAPCA_SCALE_WEIGHTS ? weights.size() : 0));
+    return *this;
+  }
+  // the factors the fitted model applied, one per column the fit used; empty for a model fitted without scaling
+  std::vector<double> column_scale() const {
+    int32_t mode = 0;
+    check(sapca_get_column_scale(h_, &mode, nullptr, 0));
+    if (mode == SAPCA_SCALE_NONE) return {};
+    uint64_t k = 0, n_used = 0, n_cols = 0;
+    check(sapca_get_dims(h_, &k, &n_used, &n_cols));
+    std::vector<double> d(n_used);
+    check(sapca_get_column_scale(h_, &mode, d.data(), d.size()));
+    return d;
+  }
   SparsePCA& fit(const CsrRef<T>& x) { mask_check(x); check(Abi<T>::fit(h_, x)); return *this; }
   std::vector<T> transform(const CsrRef<T>& x) const {                     // m x k row-major
     mask_check(x);

@@ -230,6 +230,18 @@ impl<T: SapcaFloat> SparsePCA<T> {
         check(h.0, unsafe { ffi::sapca_set_covariates(h.0, z.as_ptr(), rows as u64, cols as u64) })?;
         Ok(self)
     }
+    /// Column scaling of the next fit, applied implicitly (`sapca_set_column_scaling`; no reference counterpart): the fit is
+    /// that of (A - 1 mu^T) diag(d).  `Some(weights)`: one non-negative weight per column of the matrix; `None` with
+    /// `unit_variance`: d = 1 / std from the fit's own column statistics; `None` without: clears.  SVDMethod::Random only.
+    pub fn set_column_scaling(&mut self, unit_variance: bool, weights: Option<&[f64]>) -> Result<&mut Self> {
+        let h = self.handle_mut()?;
+        let st = match weights {
+            Some(w) => unsafe { ffi::sapca_set_column_scaling(h.0, 2, w.as_ptr(), w.len() as u64) },
+            None => unsafe { ffi::sapca_set_column_scaling(h.0, if unit_variance { 1 } else { 0 }, std::ptr::null(), 0) },
+        };
+        check(h.0, st)?;
+        Ok(self)
+    }
     /// Exact k-nearest neighbours of device-resident rows (`sapca_knn_device_*`; the neighbour search built on three measures of
     /// the reference's similarity/mod.rs): for each of the `mq` query rows the `n_neighbors` nearest of the `mc` corpus rows,
     /// best first, ties by ascending index, into `d_indices` / `d_values` (mq x n_neighbors each).  Every pointer is a DEVICE

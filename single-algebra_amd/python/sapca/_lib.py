@@ -56,6 +56,8 @@ KNN_EXCLUDE_SELF = 1
 KNN_MAX_NEIGHBORS = 128
 # covariate columns + the intercept that center = 1 adds (sapca_set_covariates)
 MAX_DESIGN_COLUMNS = 16
+# sapca_column_scaling (sapca_set_column_scaling)
+SCALE_NONE, SCALE_UNIT_VARIANCE, SCALE_WEIGHTS = 0, 1, 2
 
 
 class CsrReport(C.Structure):
@@ -79,7 +81,7 @@ _TYPED = [
     "sapca_get_components", "sapca_get_singular_values", "sapca_get_explained_variance", "sapca_get_mean",
     "sapca_get_explained_variance_ratio", "sapca_get_cumulative_explained_variance_ratio",
     "sapca_get_feature_importances", "sapca_colstats_csr", "sapca_spmm_csr", "sapca_spmmt_csr",
-    "sapca_normalize_panel", "sapca_generate_omega", "sapca_project_out_panel",
+    "sapca_normalize_panel", "sapca_generate_omega", "sapca_project_out_panel", "sapca_scale_panel_rows",
     "sapca_upload_csr", "sapca_normalize_csr_device", "sapca_log1p_csr_device", "sapca_stats_csr_device",
     "sapca_batch_stats_csr_device", "sapca_sum_row_n_top_csr_device", "sapca_masked_stats_csr_device",
     "sapca_select_rows_csr_device", "sapca_check_csr_device", "sapca_canonicalize_csr_device",
@@ -96,6 +98,7 @@ _PLAIN = [
     "sapca_multi_create", "sapca_multi_destroy", "sapca_multi_last_error", "sapca_multi_n_devices", "sapca_multi_member",
     "sapca_multi_uses_rccl", "sapca_multi_set_mask",
     "sapca_covariate_basis", "sapca_set_covariates", "sapca_get_covariate_rank",
+    "sapca_set_column_scaling", "sapca_get_column_scale",
 ]
 EXPORTED_SYMBOLS = _PLAIN + [f"{n}_{s}" for n in _TYPED for s in ("f32", "f64")]
 
@@ -176,6 +179,12 @@ def _open(path):
         for suf, ct in (("f32", C.c_float), ("f64", C.c_double)):
             getattr(lib, f"sapca_project_out_panel_{suf}").argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(ct), C.c_uint32,
                                                                        C.POINTER(ct)]
+    if hasattr(lib, "sapca_set_column_scaling"):   # (absent from an older build loaded for an A/B run)
+        lib.sapca_set_column_scaling.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_uint64]
+        lib.sapca_get_column_scale.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_size_t]
+        for suf, ct in (("f32", C.c_float), ("f64", C.c_double)):
+            getattr(lib, f"sapca_scale_panel_rows_{suf}").argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(ct),
+                                                                      C.POINTER(C.c_double)]
     for suf, ct in (("f32", C.c_float), ("f64", C.c_double)):
         fn = getattr(lib, f"sapca_select_submatrix_csr_device_{suf}", None)   # (absent from an older build loaded for an A/B run)
         if fn is not None:

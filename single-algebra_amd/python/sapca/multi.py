@@ -69,6 +69,12 @@ class MultiDevice:
             m.set_omega(omega)
         return self
 
+    def set_column_scaling(self, scaling=None):
+        """the column scaling of the next fit, applied to every member (sapca_set_column_scaling; like set_omega)"""
+        for m in self._members:
+            m.set_column_scaling(scaling)
+        return self
+
     def _call(self, op, x, want_out):
         import scipy.sparse as sp
         if not sp.isspmatrix_csr(x):

@@ -105,6 +105,18 @@ class Session:
             self._h, C.c_uint64(P.shape[0]), C.c_uint64(P.shape[1]), _p(P, ct), C.c_uint32(Q.shape[1]), _p(Q, ct)))
         return P
 
+    def scale_panel_rows(self, P, scale):
+        """sapca_scale_panel_rows_*: P[r, :] * dtype(scale[r]) for a rows x l panel, by the row-scaling kernel of the
+        column-scaling route (csrc/colscale.hip)"""
+        P = np.array(P, order="C", copy=True)
+        d = np.ascontiguousarray(scale, dtype=np.float64)
+        if P.ndim != 2 or d.ndim != 1 or d.shape[0] != P.shape[0]:
+            raise ValueError(f"panel {P.shape} must be two-dimensional and scale {d.shape} hold one factor per row")
+        suf, ct = _SUF[P.dtype]
+        L.check(self._h, getattr(L.load(), f"sapca_scale_panel_rows_{suf}")(
+            self._h, C.c_uint64(P.shape[0]), C.c_uint64(P.shape[1]), _p(P, ct), _p(d, C.c_double)))
+        return P
+
     def generate_omega(self, rows, l, dtype=np.float64):
         out = np.zeros((rows, l), dtype=dtype)
         suf, ct = _SUF[np.dtype(dtype)]

@@ -189,6 +189,54 @@ class _Estimator:
         L.check(self._h, L.load().sapca_get_covariate_rank(self._h, C.byref(dc), C.byref(r)))
         return int(r.value)
 
+    # -- column scaling, applied implicitly (no reference counterpart) -------------------------
+    def set_column_scaling(self, scaling=None):
+        """Column scaling of the next fit (sapca_set_column_scaling): SVDMethod.Random fits then factor (A - 1 mu^T) diag(d)
+        without forming it, and transform (TRANSFORM_CENTERED) scores with the fitted d and mu.  "unit_variance": d_j =
+        1 / std_j from the fit's own column statistics (0 for empty and constant columns) -- the PCA of standardised
+        features; an array of one non-negative weight per column of the matrix (0 drops the column); None clears.
+        ValueError, before any library call, for an unknown name, a wrong shape or a negative or non-finite weight."""
+        lib = L.load()
+        if scaling is None:
+            self._scale_weights = None
+            L.check(self._h, lib.sapca_set_column_scaling(self._h, C.c_int32(L.SCALE_NONE), None, C.c_uint64(0)))
+            return self
+        if isinstance(scaling, str):
+            if scaling != "unit_variance":
+                raise ValueError(f"column scaling: unknown mode {scaling!r} (\"unit_variance\", an array of weights or None)")
+            self._scale_weights = None
+            L.check(self._h, lib.sapca_set_column_scaling(self._h, C.c_int32(L.SCALE_UNIT_VARIANCE), None, C.c_uint64(0)))
+            return self
+        w = np.ascontiguousarray(scaling, dtype=np.float64)
+        if w.ndim != 1:
+            raise ValueError(f"column scaling: weights must be one-dimensional, got shape {w.shape}")
+        bad = ~(np.isfinite(w) & (w >= 0))
+        if bad.any():
+            j = int(np.argmax(bad))
+            raise ValueError(f"column scaling: weight {w[j]:g} at column {j}")
+        self._scale_weights = w
+        L.check(self._h, lib.sapca_set_column_scaling(self._h, C.c_int32(L.SCALE_WEIGHTS), _np_ptr(w, C.c_double) if w.size else None,
+                                                      C.c_uint64(w.size)))
+        return self
+
+    @property
+    def column_scale_(self):
+        """the factors d the fitted model applied, one per column the fit used (aligned with components_); None for a model
+        fitted without scaling"""
+        mode = C.c_int32()
+        L.check(self._h, L.load().sapca_get_column_scale(self._h, C.byref(mode), None, C.c_size_t(0)))
+        if mode.value == L.SCALE_NONE:
+            return None
+        _, nu, _ = self._dims()
+        out = np.empty(nu, dtype=np.float64)
+        L.check(self._h, L.load().sapca_get_column_scale(self._h, C.byref(mode), _np_ptr(out, C.c_double), C.c_size_t(out.size)))
+        return out
+
+    def _scale_check(self, n):
+        w = getattr(self, "_scale_weights", None)
+        if w is not None and w.size != n:
+            raise ValueError(f"column scaling has {w.size} weights, the matrix {n} columns")
+
     # -- marshalling ---------------------------------------------------------------------
     def _covariate_check(self, m):
         z = getattr(self, "_covariates", None)
@@ -209,6 +257,8 @@ class _Estimator:
             m, n = x.shape
             self._mask_check(n)
             self._covariate_check(m)
+            if op != "transform":
+                self._scale_check(n)
             args = [self._h, C.c_uint64(m), C.c_uint64(n), C.c_uint64(x.nnz),
                     C.c_void_p(x.row_offsets.data_ptr()), C.c_void_p(x.col_indices.data_ptr()),
                     C.c_void_p(x.values.data_ptr())]
@@ -231,6 +281,8 @@ class _Estimator:
         m, n = x.shape
         self._mask_check(n)
         self._covariate_check(m)
+        if op != "transform":
+            self._scale_check(n)
         ro = as_u64(x.indptr)     # nalgebra_sparse usize layout
         ci = as_u64(x.indices)
         va = np.ascontiguousarray(x.data)
