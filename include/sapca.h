@@ -68,7 +68,10 @@ extern "C" {
                                                   sapca_project_out_panel_*
                                  additive, ABI 4: sapca_knn_device_*
                                  additive, ABI 4: sapca_set_column_scaling, sapca_get_column_scale,
-                                                  sapca_scale_panel_rows_*                                            */
+                                                  sapca_scale_panel_rows_*
+                                 additive, ABI 4: sapca_tsne_options_default, sapca_tsne_affinities_device_*,
+                                                  sapca_tsne_gradient_device_*, sapca_tsne_embed_device_*,
+                                                  sapca_tsne_device_*, sapca_tsne_*                                   */
 
 typedef struct sapca_handle_s* sapca_handle;
 
@@ -681,6 +684,106 @@ sapca_status sapca_knn_device_f64(sapca_handle h, uint64_t mq, const double* d_q
                                   uint64_t mc, const double* d_corpus, uint64_t ldc,
                                   uint64_t d, int32_t metric, uint32_t n_neighbors, uint32_t flags,
                                   int32_t* d_indices, double* d_values);
+
+/* ---- the second half of the reference's dimred: t-SNE of device-resident score rows (dimred::tsne) ----
+ * The reference's src/dimred/tsne/mod.rs:7-66 holds TSNEConfig { output_dim, perplexity, epochs, theta } and run_f32 /
+ * run_f64, which hand a dense row-major panel to bhtsne's Barnes-Hut t-SNE with a Euclidean metric.  These calls replace
+ * them on the scores a fit_transform left in HBM.  PARITY STATUS: UNPINNED, as for the PCA: the source of bhtsne is not
+ * available to this project, so the algorithm is van der Maaten's bh_tsne (which the crate ports), stated here in full and
+ * pinned by a numpy restatement (tests/tsne_ref.py) and by scikit-learn's t-SNE gradient, not by the crate.
+ *   1. K = floor(3 perplexity) Euclidean nearest neighbours of every row, itself excluded (sapca_knn_device_*).
+ *   2. Per row i, with D_k the squared distances: beta_i from 1, bounds -inf / +inf, doubled or halved while the far bound
+ *      is infinite, else bisected, at most 200 steps; a step takes p_k = exp(-beta D_k), s = sum p + DBL_MIN,
+ *      H = ln s + beta sum(D_k p_k) / s and stops when |H - ln perplexity| < 1e-5 (H larger: beta rises).  p_k|i = p_k / s
+ *      at the beta the search ended on.  All f64 whatever T is.  A slot whose index is outside [0, m) (the search's -1)
+ *      contributes nothing.
+ *   3. P_ij = (p_j|i + p_i|j) / (2 m), the sum in f64, rounded once to T: bh_tsne's symmetrise-then-divide-by-the-total,
+ *      since every conditional row sums to 1.  A canonical CSR: int64 offsets, int32 columns ascending without repeats.
+ *   4. q_ij = 1 / (1 + |y_i - y_j|^2), Z = sum_{i != j} q_ij,
+ *      g_i = e sum_j P_ij q_ij (y_i - y_j) - (1 / Z) sum_{j != i} q_ij^2 (y_i - y_j)   (the Barnes-Hut form, no factor 4),
+ *      KL = sum over stored P_ij of P_ij ln(P_ij Z / q_ij) with the unexaggerated P.  The pair i == j is left out by
+ *      index; coincident rows i != j count q = 1 and exert no force.
+ *   5. Per epoch t: e = exaggeration for t < stop_lying_epoch, else 1; mu = momentum for t < momentum_switch_epoch, else
+ *      final_momentum; gain += 0.2 where sign(g) != sign(v) (sign in {-1, 0, +1}), else gain *= 0.8, then max(gain, 0.01);
+ *      v = mu v - learning_rate gain g; y += v; every column of y re-centred to mean zero (the mean summed in f64 in a
+ *      fixed order).  Start: gain 1, v 0, y = 1e-4 N(0, 1) from the built-in generator (sapca_generate_omega's, on an
+ *      m x output_dim panel) under random_seed, or the caller's panel (init_given), re-centred first.
+ * Deviations from the reference:
+ *   1. The repulsive term is evaluated exactly, the limit theta -> 0 of the tree: theta is accepted and stored for drop-in
+ *      and not read; results are those of barnes_hut(0.0, ..).
+ *   2. For T = f32 the affinities (stages 2-3) are computed in f64 and rounded once, and the repulsion folds its f32
+ *      per-lane sums into f64 once per 1024 rows j; the crate works in T throughout.
+ *   3. The initial embedding comes from this library's counter-based generator, not from the crate's rand stream.
+ *   4. Re-centring in f32: the column mean is summed in f64 and y_i - mean is rounded to f32 once, so a stored f32 column has
+ *      mean 0 only up to the mean of those roundings, at most 2^-24 max|y| (eps_f32 / 2); an f64 column to f64 rounding.
+ * A single row (m == 1) has no pair: Z = 0, and the stage calls define the repulsion and the KL as 0 (no 0 / 0); its embedding
+ * is the origin.
+ * Deterministic: the same bytes from call to call.  Integer atomics count and hand out positions in stage 3, the rows are
+ * then sorted by column and a pair's two terms added (a + b == b + a), so no order reaches a value; every floating-point sum
+ * that crosses lanes or workgroups is added in an order fixed by the shape (the rows j are dealt into chunks by m alone,
+ * every chunk summed from zero, the chunks added in order, whether one workgroup walks them or one takes each).
+ * Outputs are complete when the call returns.  Every call runs on the handle's stream in buffers of its own: a fitted
+ * model, a cached preparation, the upload's statistics, the selection and the canonical buffers are untouched; on a handle
+ * that belongs to a communicator the call is local to the rank and issues no collective.  The epoch loop enqueues kernels
+ * only (Z, the means and the KL terms stay on the device).
+ * No index outside the arrays is touched: a neighbour slot or a column of P outside [0, m) is skipped where it is read (the
+ * search's contract writes -1 only), the emitted positions are counted before they are written, and the offsets of a
+ * caller's P are trusted as in every *_csr_device_* call.  Non-finite input values give an unspecified embedding.
+ * SAPCA_ERR_ARG, checked on the host before anything is enqueued (the handle stays usable), each with a message that names
+ * the offending number: a wrong struct_size; output_dim outside 1 .. 3; perplexity non-finite or < 1; K = floor(3 perplexity)
+ * > SAPCA_KNN_MAX_NEIGHBORS ("perplexity P needs N neighbours, at most 128"); K > m - 1 ("perplexity too large for the number
+ * of rows"); m >= 2^31; the d / stride limits of sapca_knn_device_*; a non-finite or negative constant; a null pointer with
+ * a non-empty shape.  epochs == 0 is valid: the initial embedding, re-centred, and its KL.                              */
+typedef struct sapca_tsne_options {
+  uint32_t struct_size;            /* sizeof(sapca_tsne_options)                                       */
+  uint32_t random_seed;            /* default 42                                                       */
+  uint32_t output_dim;             /* TSNEConfig.output_dim (tsne/mod.rs:8), default 2; 1 .. 3         */
+  uint32_t init_given;             /* 1: d_y / y holds the initial embedding                           */
+  double perplexity;               /* TSNEConfig.perplexity (tsne/mod.rs:9), default 20 (bhtsne's)     */
+  double theta;                    /* TSNEConfig.theta (tsne/mod.rs:11), default 0.5: stored, not read */
+  uint64_t epochs;                 /* TSNEConfig.epochs (tsne/mod.rs:10), default 1000                 */
+  uint64_t stop_lying_epoch;       /* default 250                                                      */
+  uint64_t momentum_switch_epoch;  /* default 250                                                      */
+  double exaggeration;             /* default 12                                                       */
+  double learning_rate;            /* default 200                                                      */
+  double momentum;                 /* default 0.5                                                      */
+  double final_momentum;           /* default 0.8                                                      */
+} sapca_tsne_options;
+void sapca_tsne_options_default(sapca_tsne_options* opts);
+/* Stages 2-3 on neighbour lists laid out as sapca_knn_device_* writes them (m x K, DEVICE; d_dist holds distances, not
+ * squares; 1 <= K <= SAPCA_KNN_MAX_NEIGHBORS).  The symmetric P comes back in handle-owned DEVICE arrays like the selection's
+ * and the canonical result's: valid until the next affinity call (sapca_tsne_device_* and sapca_tsne_* make one) or destroy,
+ * and accepted by every *_csr_device_* entry point.  d_beta (m f64, DEVICE, may be NULL) receives beta_i.                  */
+sapca_status sapca_tsne_affinities_device_f32(sapca_handle h, uint64_t m, const int32_t* d_indices, const float* d_dist, uint32_t K,
+                                              double perplexity, uint64_t* nnz_out, const int64_t** d_row_offsets,
+                                              const int32_t** d_col_indices, float** d_values, double* d_beta);
+sapca_status sapca_tsne_affinities_device_f64(sapca_handle h, uint64_t m, const int32_t* d_indices, const double* d_dist, uint32_t K,
+                                              double perplexity, uint64_t* nnz_out, const int64_t** d_row_offsets,
+                                              const int32_t** d_col_indices, double** d_values, double* d_beta);
+/* One evaluation of stage 4 (a stage-level operator for parity tests, like sapca_spmm_csr_*): P an m x m DEVICE CSR, d_y the
+ * m x output_dim embedding with row stride ldy, d_grad m x output_dim packed (DEVICE); *Z and *kl on the HOST (may be NULL).  */
+sapca_status sapca_tsne_gradient_device_f32(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                            const float* values, const float* d_y, uint64_t ldy, uint32_t output_dim,
+                                            double exaggeration, float* d_grad, double* Z, double* kl);
+sapca_status sapca_tsne_gradient_device_f64(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                            const double* values, const double* d_y, uint64_t ldy, uint32_t output_dim,
+                                            double exaggeration, double* d_grad, double* Z, double* kl);
+/* Stage 5 on a given P: d_y (m x output_dim packed, DEVICE) is read when opts->init_given and receives the embedding; *kl
+ * (HOST, may be NULL) its Kullback-Leibler divergence.  perplexity is not read here.                                       */
+sapca_status sapca_tsne_embed_device_f32(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                         const float* values, const sapca_tsne_options* opts, float* d_y, double* kl);
+sapca_status sapca_tsne_embed_device_f64(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                         const double* values, const sapca_tsne_options* opts, double* d_y, double* kl);
+/* Stages 1-5 on a resident m x d panel with row stride ldx (the scores of sapca_fit_transform_csr_device_*, searched in
+ * place): exactly sapca_knn_device_* (EUCLIDEAN, EXCLUDE_SELF, K), sapca_tsne_affinities_device_*, sapca_tsne_embed_device_*.  */
+sapca_status sapca_tsne_device_f32(sapca_handle h, uint64_t m, const float* d_x, uint64_t ldx, uint64_t d,
+                                   const sapca_tsne_options* opts, float* d_y, double* kl);
+sapca_status sapca_tsne_device_f64(sapca_handle h, uint64_t m, const double* d_x, uint64_t ldx, uint64_t d,
+                                   const sapca_tsne_options* opts, double* d_y, double* kl);
+/* The same with HOST arrays in and out (x: m x d row-major; y: m x output_dim): the drop-in for run_f32 / run_f64
+ * (tsne/mod.rs:14-39, :41-66).                                                                                            */
+sapca_status sapca_tsne_f32(sapca_handle h, uint64_t m, uint64_t d, const float* x, const sapca_tsne_options* opts, float* y, double* kl);
+sapca_status sapca_tsne_f64(sapca_handle h, uint64_t m, uint64_t d, const double* x, const sapca_tsne_options* opts, double* y, double* kl);
 
 /* Measurement support: the rate (GB/s, read + write counted) of a 16-byte-per-lane streaming copy of `bytes`
  * bytes on the handle's device, best of `reps` -- the HBM rate a kernel of this library can attain, reported by

@@ -855,6 +855,30 @@ sapca_status sapca_get_column_scale(sapca_handle h, int32_t* mode, double* out, 
                                       int32_t* d_indices, T* d_values) {                                                   \
     return guarded(h, [&] { resident::knn<T>(*h, mq, dq, ldq, mc, dc, ldc, d, metric, n_neighbors, flags, d_indices, d_values); }); \
   }                                                                                                                      \
+  sapca_status sapca_tsne_affinities_device_##SUF(sapca_handle h, uint64_t m, const int32_t* d_indices, const T* d_dist,   \
+                                                  uint32_t K, double perplexity, uint64_t* nnz_out, const int64_t** dp,    \
+                                                  const int32_t** di, T** dv, double* d_beta) {                            \
+    return guarded(h, [&] { resident::tsne_affinities<T>(*h, m, d_indices, d_dist, K, perplexity, nnz_out, dp, di, dv, d_beta); }); \
+  }                                                                                                                      \
+  sapca_status sapca_tsne_gradient_device_##SUF(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* p, const int32_t* i, \
+                                                const T* v, const T* d_y, uint64_t ldy, uint32_t output_dim,               \
+                                                double exaggeration, T* d_grad, double* Z, double* kl) {                   \
+    return guarded(h, [&] {                                                                                              \
+      resident::tsne_gradient<T>(*h, unchecked_view(m, m, nnz, p, i, v), d_y, ldy, output_dim, exaggeration, d_grad, Z, kl); \
+    });                                                                                                                  \
+  }                                                                                                                      \
+  sapca_status sapca_tsne_embed_device_##SUF(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* p, const int32_t* i,  \
+                                             const T* v, const sapca_tsne_options* opts, T* d_y, double* kl) {            \
+    return guarded(h, [&] { resident::tsne_embed<T>(*h, unchecked_view(m, m, nnz, p, i, v), opts, d_y, kl); });          \
+  }                                                                                                                      \
+  sapca_status sapca_tsne_device_##SUF(sapca_handle h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d,                 \
+                                       const sapca_tsne_options* opts, T* d_y, double* kl) {                              \
+    return guarded(h, [&] { resident::tsne_device<T>(*h, m, d_x, ldx, d, opts, d_y, kl); });                             \
+  }                                                                                                                      \
+  sapca_status sapca_tsne_##SUF(sapca_handle h, uint64_t m, uint64_t d, const T* x, const sapca_tsne_options* opts, T* y,  \
+                                double* kl) {                                                                             \
+    return guarded(h, [&] { resident::tsne_host<T>(*h, m, d, x, opts, y, kl); });                                        \
+  }                                                                                                                      \
   sapca_status sapca_sum_row_n_top_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, \
                                                     const int32_t* i, const T* v, const uint64_t* ns, uint32_t n_ns,        \
                                                     double* out) {                                                          \
@@ -884,6 +908,23 @@ sapca_status sapca_get_column_scale(sapca_handle h, int32_t* mode, double* out, 
 SAPCA_DEFINE_TYPED(f32, float)
 SAPCA_DEFINE_TYPED(f64, double)
 #undef SAPCA_DEFINE_TYPED
+
+void sapca_tsne_options_default(sapca_tsne_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  o->struct_size = (uint32_t)sizeof(sapca_tsne_options);
+  o->random_seed = 42;
+  o->output_dim = 2;
+  o->perplexity = 20.0;
+  o->theta = 0.5;
+  o->epochs = 1000;
+  o->stop_lying_epoch = 250;
+  o->momentum_switch_epoch = 250;
+  o->exaggeration = 12.0;
+  o->learning_rate = 200.0;
+  o->momentum = 0.5;
+  o->final_momentum = 0.8;
+}
 
 sapca_status sapca_get_dims(sapca_handle h, uint64_t* k, uint64_t* n_used, uint64_t* n_cols) {
   return guarded(h, [&] {

@@ -161,6 +161,16 @@ struct sapca_handle_s {
   struct Knn {
     sapca::DevBuf unit_q, unit_c, bias, part_sc, part_ix, merged;
   } knn;
+  // sapca_tsne_*: the conditional affinities and the emitted entries (raw_*), the row sort's work space and output (as in
+  // Canonical), the symmetric P handed back (one of raw_ptr / out_ptr, one of raw_idx / sort_idx, out_val), the optimiser's
+  // state and sums, and the panels of the host and one-call routes.  Nothing else lives in these.
+  struct Tsne {
+    sapca::DevBuf p, raw_ptr, nvalid, cursor, raw_idx, raw_val, scan, ctr, rows, long_off, keys, sort_idx, sort_val, out_ptr, out_val;
+    sapca::DevBuf part, rep, sum_part, scal, klrow, grad, v, gain, colpart, knn_idx, knn_dist, x, y;
+    bool owns(const void* q) const {
+      return raw_ptr.contains(q) || out_ptr.contains(q) || raw_idx.contains(q) || sort_idx.contains(q) || out_val.contains(q);
+    }
+  } tsne;
   sapca::DevBuf at_ptr, at_idx, at_val;                          // A^T
   sapca::DevBuf ca_ptr, ca_idx, ca_val, cat_ptr, cat_idx, cat_val;  // mask-compacted A, A^T
   sapca::DevBuf drop_stats, drop_tmp;                              // their sums (sum | sumsq, full width) and the sort's work space

@@ -377,6 +377,50 @@ template <typename T>
 void knn_refine(const T* q, int64_t ldq, int64_t mq, const T* c, int64_t ldc, int64_t mc, int d, int metric, const int32_t* sel,
                 int64_t sel_stride, int k, int32_t* out_ix, T* out_val, hipStream_t s);
 
+// ---- tsne.hip: t-SNE on dense row panels (sapca_tsne_*); include/sapca.h states the algorithm ------------------------------
+// p[i * K + slot] = p_{slot|i} (f64) and beta[i] (nullable) from the K neighbour distances of row i (dist, NOT squared); a slot
+// whose index is outside [0, m) contributes nothing and gets 0.  One wave per row, K <= 128.
+template <typename T>
+void tsne_perplexity(const int32_t* idx, const T* dist, int64_t m, int K, double perplexity, double* p, double* beta, hipStream_t s);
+// len[0 .. m] (zeroed here) = per row its valid slots + the rows that list it, len[m] = 0; nvalid[i] = the former
+void tsne_count(const int32_t* idx, int64_t m, int K, int64_t* len, int32_t* nvalid, hipStream_t s);
+// the unsorted CSR of the 2 m K emitted entries at offsets ptr (the scan of len): row i's own (j, p_j|i) first, in slot order,
+// then (j, p_i|j) of the rows j that list i in the order an integer cursor (m words, zeroed here) hands out
+void tsne_emit(const int32_t* idx, const double* p, int64_t m, int K, const int64_t* ptr, const int32_t* nvalid, int32_t* cursor,
+               int32_t* out_idx, double* out_val, hipStream_t s);
+// out[e] = T(in[e] * inv)
+template <typename T>
+void tsne_scale(const double* in, int64_t nnz, double inv, T* out, hipStream_t s);
+// The repulsion's geometry: the j tiles are dealt into nchunk chunks by m alone, and every chunk's sums are formed from zero
+// and added in chunk order whether one workgroup walks them all or (split) one workgroup takes each: the same bits.
+struct TsnePlan {
+  int nchunk = 1, tiles_per_chunk = 1;
+  bool split = false;   // by default where the i blocks alone leave CUs idle (debug builds: SAPCA_TSNE_SPLIT=0|1)
+};
+TsnePlan tsne_plan(int64_t m, int n_cus);
+size_t tsne_sum_parts(int64_t n);   // doubles of work space tsne_sum / tsne_repulsion need for n addends
+// rep[i * (D + 1) + c] = sum_{j != i} q_ij^2 (y_i - y_j)[c] (c < D), [.. + D] = sum_{j != i} q_ij; *z = the sum of the latter
+// over i.  part: plan.nchunk * m * (D + 1) doubles when plan.split.  y: m rows of D values, row stride ldy.  D in 1..3.
+template <typename T>
+void tsne_repulsion(const T* y, int64_t ldy, int64_t m, int D, const TsnePlan& plan, double* part, double* rep, double* sum_part, double* z,
+                    hipStream_t s);
+// grad (m x D, packed) = T(exaggeration * sum_j P_ij q_ij (y_i - y_j) - rep_i / *z); klrow[i] = sum_j P_ij ln(P_ij *z / q_ij)
+template <typename T>
+void tsne_attraction(const CsrView<T>& P, const T* y, int64_t ldy, int D, double exaggeration, const double* rep, const double* z, T* grad,
+                     double* klrow, hipStream_t s);
+// *out = in[0] + .. + in[n - 1] in an order fixed by n
+void tsne_sum(const double* in, int64_t n, double* sum_part, double* out, hipStream_t s);
+// gains, velocity and step of one epoch on packed m x D arrays, then every column of y re-centred (tsne_center)
+template <typename T>
+void tsne_update(T* y, T* v, T* gain, const T* grad, int64_t m, int D, double momentum, double rate, double* colpart, double* mean,
+                 hipStream_t s);
+// y[:, c] -= its mean (f64, per-block sums in colpart -- ceil(m / 256) * D doubles -- then one workgroup; sum_first: form them here)
+template <typename T>
+void tsne_center(T* y, int64_t m, int D, double* colpart, double* mean, bool sum_first, hipStream_t s);
+// v = 0, gain = 1, and, y non-null, y = 1e-4 N(0, 1) from gaussian_panel under `seed`
+template <typename T>
+void tsne_init_state(T* y_or_null, T* v, T* gain, int64_t m, int D, uint32_t seed, hipStream_t s);
+
 // ---- rng.hip ---------------------------------------------------------------------------
 // Omega[r][j] ~ N(0,1) for j < l (zero for l <= j < ld), a pure function of (seed, r*l+j).
 template <typename T>

@@ -59,5 +59,20 @@ template <typename T>
 void knn(H& h, uint64_t mq, const T* d_queries, uint64_t ldq, uint64_t mc, const T* d_corpus, uint64_t ldc, uint64_t d, int32_t metric,
          uint32_t n_neighbors, uint32_t flags, int32_t* d_indices, T* d_values);
 
+// sapca_tsne_* (tsne.cpp): the affinity graph of neighbour lists, one gradient evaluation, the optimiser, and the whole chain
+// on a device panel or on host arrays
+template <typename T>
+void tsne_affinities(H& h, uint64_t m, const int32_t* d_indices, const T* d_dist, uint32_t K, double perplexity, uint64_t* nnz_out,
+                     const int64_t** d_ptr, const int32_t** d_idx, T** d_val, double* d_beta);
+template <typename T>
+void tsne_gradient(H& h, const CsrView<T>& P, const T* d_y, uint64_t ldy, uint32_t output_dim, double exaggeration, T* d_grad, double* Z,
+                   double* kl);
+template <typename T>
+void tsne_embed(H& h, const CsrView<T>& P, const sapca_tsne_options* opts, T* d_y, double* kl);
+template <typename T>
+void tsne_device(H& h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d, const sapca_tsne_options* opts, T* d_y, double* kl);
+template <typename T>
+void tsne_host(H& h, uint64_t m, uint64_t d, const T* x, const sapca_tsne_options* opts, T* y, double* kl);
+
 }  // namespace resident
 }  // namespace sapca

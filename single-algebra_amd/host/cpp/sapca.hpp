@@ -98,6 +98,75 @@ inline void knn_device(sapca_handle h, uint64_t mq, const T* d_queries, uint64_t
   if (st != SAPCA_OK) throw Error(st, sapca_last_error(h));
 }
 
+// t-SNE of device-resident rows (sapca_tsne_*; the reference's dimred::tsne, src/dimred/tsne/mod.rs:7-66).  TsneOptions()
+// holds the library's defaults (TSNEConfig's output_dim, perplexity, epochs, theta and van der Maaten's constants); theta is
+// stored and not read: the repulsive term is evaluated exactly.  Every pointer but `kl` and the options is a DEVICE pointer
+// unless the name says host.  Each function returns the Kullback-Leibler divergence of the embedding it wrote.
+struct TsneOptions : sapca_tsne_options {
+  TsneOptions() { sapca_tsne_options_default(this); }
+};
+// the symmetric affinity matrix a call left in the handle's t-SNE buffers (valid until the next affinity call)
+template <typename T>
+struct TsneGraph {
+  uint64_t m = 0, nnz = 0;
+  const int64_t* row_offsets = nullptr;
+  const int32_t* col_indices = nullptr;
+  T* values = nullptr;
+};
+template <typename T> struct TsneAbi;
+template <> struct TsneAbi<float> {
+  static constexpr auto affinities = &sapca_tsne_affinities_device_f32;
+  static constexpr auto gradient = &sapca_tsne_gradient_device_f32;
+  static constexpr auto embed = &sapca_tsne_embed_device_f32;
+  static constexpr auto device = &sapca_tsne_device_f32;
+  static constexpr auto host = &sapca_tsne_f32;
+};
+template <> struct TsneAbi<double> {
+  static constexpr auto affinities = &sapca_tsne_affinities_device_f64;
+  static constexpr auto gradient = &sapca_tsne_gradient_device_f64;
+  static constexpr auto embed = &sapca_tsne_embed_device_f64;
+  static constexpr auto device = &sapca_tsne_device_f64;
+  static constexpr auto host = &sapca_tsne_f64;
+};
+inline void tsne_check(sapca_handle h, sapca_status st) {
+  if (st != SAPCA_OK) throw Error(st, sapca_last_error(h));
+}
+// stages 2-3 on neighbour lists as knn_device writes them (distances, not squares); d_beta (m doubles) may be null
+template <typename T>
+inline TsneGraph<T> tsne_affinities_device(sapca_handle h, uint64_t m, const int32_t* d_indices, const T* d_dist, uint32_t K,
+                                           double perplexity, double* d_beta = nullptr) {
+  TsneGraph<T> g;
+  g.m = m;
+  tsne_check(h, TsneAbi<T>::affinities(h, m, d_indices, d_dist, K, perplexity, &g.nnz, &g.row_offsets, &g.col_indices, &g.values, d_beta));
+  return g;
+}
+// one evaluation of the gradient (m x output_dim, packed) at d_y (row stride ldy); Z and kl may be null
+template <typename T>
+inline void tsne_gradient_device(sapca_handle h, const TsneGraph<T>& P, const T* d_y, uint64_t ldy, uint32_t output_dim,
+                                 double exaggeration, T* d_grad, double* Z, double* kl) {
+  tsne_check(h, TsneAbi<T>::gradient(h, P.m, P.nnz, P.row_offsets, P.col_indices, P.values, d_y, ldy, output_dim, exaggeration, d_grad, Z, kl));
+}
+template <typename T>
+inline double tsne_embed_device(sapca_handle h, const TsneGraph<T>& P, const sapca_tsne_options& opts, T* d_y) {
+  double kl = 0.0;
+  tsne_check(h, TsneAbi<T>::embed(h, P.m, P.nnz, P.row_offsets, P.col_indices, P.values, &opts, d_y, &kl));
+  return kl;
+}
+// neighbours, affinities and embedding of an m x d panel (row stride ldx) in one call; d_y: m x output_dim
+template <typename T>
+inline double tsne_device(sapca_handle h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d, const sapca_tsne_options& opts, T* d_y) {
+  double kl = 0.0;
+  tsne_check(h, TsneAbi<T>::device(h, m, d_x, ldx, d, &opts, d_y, &kl));
+  return kl;
+}
+// the same with host arrays: the drop-in for run_f32 / run_f64
+template <typename T>
+inline double tsne(sapca_handle h, uint64_t m, uint64_t d, const T* host_x, const sapca_tsne_options& opts, T* host_y) {
+  double kl = 0.0;
+  tsne_check(h, TsneAbi<T>::host(h, m, d, host_x, &opts, host_y, &kl));
+  return kl;
+}
+
 template <typename T>
 class ResidentCsr {
  public:

@@ -464,6 +464,87 @@ impl<T: SapcaFloat> MaskedSparsePCABuilder<T> {
     }
 }
 
+/// `single_algebra::dimred::tsne` (src/dimred/tsne/mod.rs:7-66): `TSNEConfig` and `run_f32` / `run_f64` on a dense row-major
+/// panel, through `sapca_tsne_f32` / `_f64`.  The repulsive term is evaluated exactly, so `theta` is stored and not read
+/// (include/sapca.h, deviation 1: the results are those of `barnes_hut(0.0, ..)`).  The reference's fields are private and it
+/// has no constructor; `TSNEConfig::new` and public fields are this crate's.  Its type parameter `T: FloatOpsTS` is unused
+/// there and unbounded here.
+pub mod tsne {
+    use super::{check, ffi};
+    use anyhow::{anyhow, Result};
+    use ndarray::{Array2, ArrayD, ArrayViewD};
+    use sapca_sys::sapca_tsne_options as RawOptions;
+
+    /// tsne/mod.rs:7-12
+    #[derive(Clone, Copy, Debug)]
+    pub struct TSNEConfig {
+        pub output_dim: u8,
+        pub perplexity: f32,
+        pub epochs: usize,
+        pub theta: f32,
+    }
+    impl TSNEConfig {
+        pub fn new(output_dim: u8, perplexity: f32, epochs: usize, theta: f32) -> Self { Self { output_dim, perplexity, epochs, theta } }
+    }
+    impl Default for TSNEConfig {
+        /// bhtsne's defaults: 2 dimensions, perplexity 20, 1000 epochs, theta 0.5
+        fn default() -> Self { Self { output_dim: 2, perplexity: 20.0, epochs: 1000, theta: 0.5 } }
+    }
+
+    fn options(config: &TSNEConfig) -> RawOptions {
+        let mut o: RawOptions = unsafe { std::mem::zeroed() };
+        unsafe { ffi::sapca_tsne_options_default(&mut o) };
+        o.output_dim = config.output_dim as u32;
+        o.perplexity = config.perplexity as f64;
+        o.epochs = config.epochs as u64;
+        o.theta = config.theta as f64;
+        o
+    }
+
+    fn with_handle<R>(f: impl FnOnce(ffi::sapca_handle) -> Result<R>) -> Result<R> {
+        let mut o: ffi::sapca_options = unsafe { std::mem::zeroed() };
+        unsafe { ffi::sapca_options_default(&mut o) };
+        let mut h: ffi::sapca_handle = std::ptr::null_mut();
+        if unsafe { ffi::sapca_create(&o, &mut h) } != ffi::SAPCA_OK {
+            return Err(anyhow!("sapca_create failed (no usable GPU?)"));
+        }
+        let r = f(h);
+        unsafe { ffi::sapca_destroy(h) };
+        r
+    }
+
+    fn shape_of(shape: &[usize]) -> Result<(usize, usize)> {
+        if shape.len() != 2 { return Err(anyhow!("t-SNE wants a two-dimensional array, got {} axes", shape.len())); }
+        Ok((shape[0], shape[1]))
+    }
+
+    /// tsne/mod.rs:14-39
+    pub fn run_f32<T>(x: ArrayViewD<f32>, config: TSNEConfig) -> Result<ArrayD<f32>> {
+        let (n_obs, n_dim) = shape_of(x.shape())?;
+        let x = x.as_standard_layout();
+        let o = options(&config);
+        let mut y = vec![0f32; n_obs * config.output_dim as usize];
+        let mut kl = 0f64;
+        with_handle(|h| check(h, unsafe {
+            ffi::sapca_tsne_f32(h, n_obs as u64, n_dim as u64, x.as_ptr(), &o, y.as_mut_ptr(), &mut kl)
+        }))?;
+        Ok(Array2::from_shape_vec((n_obs, config.output_dim as usize), y)?.into_dyn())
+    }
+
+    /// tsne/mod.rs:41-66
+    pub fn run_f64<T>(x: ArrayViewD<f64>, config: TSNEConfig) -> Result<ArrayD<f64>> {
+        let (n_obs, n_dim) = shape_of(x.shape())?;
+        let x = x.as_standard_layout();
+        let o = options(&config);
+        let mut y = vec![0f64; n_obs * config.output_dim as usize];
+        let mut kl = 0f64;
+        with_handle(|h| check(h, unsafe {
+            ffi::sapca_tsne_f64(h, n_obs as u64, n_dim as u64, x.as_ptr(), &o, y.as_mut_ptr(), &mut kl)
+        }))?;
+        Ok(Array2::from_shape_vec((n_obs, config.output_dim as usize), y)?.into_dyn())
+    }
+}
+
 /// The reference's module tree (src/dimred/pca/mod.rs:36-42; README.md:51-53 imports
 /// `dimred::pca::{SparsePCABuilder, SVDMethod}` and `dimred::pca::sparse::PowerIterationNormalizer`).
 pub mod dimred {
@@ -472,6 +553,8 @@ pub mod dimred {
         pub mod sparse { pub use crate::{PowerIterationNormalizer, SparsePCA, SparsePCABuilder}; }
         pub mod sparse_masked { pub use crate::{MaskedSparsePCA, MaskedSparsePCABuilder}; }
     }
+    /// src/dimred/mod.rs:21
+    pub mod tsne { pub use crate::tsne::{run_f32, run_f64, TSNEConfig}; }
 }
 
 /// Type aliases for callers that used the two instantiations by name.

@@ -41,6 +41,16 @@ class Timings(C.Structure):
     ]
 
 
+class TsneOptions(C.Structure):
+    """sapca_tsne_options"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("random_seed", C.c_uint32), ("output_dim", C.c_uint32), ("init_given", C.c_uint32),
+        ("perplexity", C.c_double), ("theta", C.c_double), ("epochs", C.c_uint64),
+        ("stop_lying_epoch", C.c_uint64), ("momentum_switch_epoch", C.c_uint64),
+        ("exaggeration", C.c_double), ("learning_rate", C.c_double), ("momentum", C.c_double), ("final_momentum", C.c_double),
+    ]
+
+
 # sapca_csr_report and its flags (sapca_check_csr_device_*, sapca_canonicalize_csr_device_*)
 CSR_BAD_OFFSETS, CSR_COL_RANGE, CSR_UNSORTED, CSR_DUPLICATES, CSR_NONFINITE = 1, 2, 4, 8, 16
 CSR_FLAG_NAMES = {CSR_BAD_OFFSETS: "BAD_OFFSETS", CSR_COL_RANGE: "COL_RANGE", CSR_UNSORTED: "UNSORTED",
@@ -86,6 +96,7 @@ _TYPED = [
     "sapca_batch_stats_csr_device", "sapca_sum_row_n_top_csr_device", "sapca_masked_stats_csr_device",
     "sapca_select_rows_csr_device", "sapca_check_csr_device", "sapca_canonicalize_csr_device",
     "sapca_select_submatrix_csr_device", "sapca_knn_device",
+    "sapca_tsne_affinities_device", "sapca_tsne_gradient_device", "sapca_tsne_embed_device", "sapca_tsne_device", "sapca_tsne",
     "sapca_multi_fit_csr", "sapca_multi_transform_csr", "sapca_multi_fit_transform_csr",
     "sapca_multi_upload_csr", "sapca_multi_transform_resident", "sapca_multi_fit_transform_resident",
 ]
@@ -99,6 +110,7 @@ _PLAIN = [
     "sapca_multi_uses_rccl", "sapca_multi_set_mask",
     "sapca_covariate_basis", "sapca_set_covariates", "sapca_get_covariate_rank",
     "sapca_set_column_scaling", "sapca_get_column_scale",
+    "sapca_tsne_options_default",
 ]
 EXPORTED_SYMBOLS = _PLAIN + [f"{n}_{s}" for n in _TYPED for s in ("f32", "f64")]
 
@@ -197,7 +209,28 @@ def _open(path):
         if fn is not None:
             fn.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64,
                            C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "sapca_tsne_options_default"):   # (absent from an older build loaded for an A/B run)
+        lib.sapca_tsne_options_default.argtypes = [C.POINTER(TsneOptions)]
+        lib.sapca_tsne_options_default.restype = None
+        csr = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]   # h, m, nnz, offsets, columns, values
+        for suf in ("f32", "f64"):
+            getattr(lib, f"sapca_tsne_affinities_device_{suf}").argtypes = [
+                C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.POINTER(C.c_uint64),
+                C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]
+            getattr(lib, f"sapca_tsne_gradient_device_{suf}").argtypes = csr + [
+                C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+            getattr(lib, f"sapca_tsne_embed_device_{suf}").argtypes = csr + [C.POINTER(TsneOptions), C.c_void_p, C.POINTER(C.c_double)]
+            getattr(lib, f"sapca_tsne_device_{suf}").argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64,
+                                                                 C.POINTER(TsneOptions), C.c_void_p, C.POINTER(C.c_double)]
+            getattr(lib, f"sapca_tsne_{suf}").argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(TsneOptions),
+                                                          C.c_void_p, C.POINTER(C.c_double)]
     return lib
+
+
+def default_tsne_options() -> TsneOptions:
+    o = TsneOptions()
+    load().sapca_tsne_options_default(C.byref(o))
+    return o
 
 
 def default_options() -> Options:

@@ -44,6 +44,7 @@ class Session:
         self._h = C.c_void_p()
         o = L.default_options()
         o.random_seed = seed
+        self._seed, self._owned = seed, True
         o.spmm_variant = spmm_variant
         if stream is not None:   # a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream): the handle's work goes there
             o.stream = C.c_void_p(int(stream))
@@ -51,9 +52,22 @@ class Session:
         if st != L.OK:
             raise L.SapcaError(st, (L.load().sapca_last_error(None) or b"").decode())
 
+    @classmethod
+    def borrow(cls, handle, seed=42):
+        """A Session on a handle that something else owns (an estimator's: `SparsePCA.session()`): the stage-level operators
+        run on that handle, in its stream and buffers; it is not destroyed with this object."""
+        self = cls.__new__(cls)
+        self._h, self._seed, self._owned = handle, int(seed), False
+        return self
+
+    def _device(self):
+        """the torch device of the handle's GPU (a handle is created on the current device)"""
+        import torch
+        return torch.device("cuda", torch.cuda.current_device())
+
     def __del__(self):
         try:
-            if self._h:
+            if self._h and getattr(self, "_owned", False):
                 L.load().sapca_destroy(self._h)
                 self._h = C.c_void_p()
         except Exception:
@@ -176,6 +190,125 @@ class Session:
             C.c_uint32(L.KNN_EXCLUDE_SELF if exclude_self else 0), C.c_void_p(idx.data_ptr() if mq else None),
             C.c_void_p(val.data_ptr() if mq else None)))
         return idx, val
+
+    # ---- t-SNE (sapca_tsne_*): the affinity graph, one gradient evaluation, the embedding ----
+    def _tsne_options(self, perplexity, epochs, output_dim, init_given, seed, constants):
+        o = L.default_tsne_options()
+        o.random_seed = int(self._seed if seed is None else seed)
+        o.perplexity, o.epochs, o.output_dim, o.init_given = float(perplexity), int(epochs), int(output_dim), int(bool(init_given))
+        for name, value in constants.items():
+            if name not in ("theta", "stop_lying_epoch", "momentum_switch_epoch", "exaggeration", "learning_rate", "momentum",
+                            "final_momentum"):
+                raise ValueError(f"unknown t-SNE constant {name!r}")
+            setattr(o, name, type(getattr(o, name))(value))
+        return o
+
+    def tsne_affinities(self, indices, dist, perplexity):
+        """sapca_tsne_affinities_device_*: (P, beta) from neighbour lists as knn() returns them (m x K device tensors, int32
+        indices and f32 / f64 distances).  P is the symmetric affinity matrix (p_j|i + p_i|j) / (2 m) as a canonical
+        ResidentCsr in the Session's t-SNE buffers (valid until the next affinity call on the Session), beta the m precisions
+        of the perplexity search (f64 device tensor)."""
+        import torch
+        m, K, ld, dt = _knn_panel("dist", dist)
+        if not (isinstance(indices, torch.Tensor) and indices.dtype == torch.int32 and tuple(indices.shape) == (m, K)
+                and indices.is_contiguous() and dist.is_contiguous()):
+            raise ValueError("indices must be a contiguous int32 tensor of the shape of dist, dist contiguous")
+        if not (indices.is_cuda and dist.is_cuda):
+            raise ValueError("indices and dist must live on the device")
+        beta = torch.empty((m,), dtype=torch.float64, device=dist.device)
+        suf = "f32" if dt == torch.float32 else "f64"
+        nnz = C.c_uint64()
+        dp, di, dv = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_tsne_affinities_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_void_p(indices.data_ptr() if m else None), C.c_void_p(dist.data_ptr() if m else None),
+            C.c_uint32(K), C.c_double(float(perplexity)), C.byref(nnz), C.byref(dp), C.byref(di), C.byref(dv),
+            C.c_void_p(beta.data_ptr() if m else None)))
+        P = ResidentCsr(self, (m, m), nnz.value, np.float32 if suf == "f32" else np.float64, dp.value or 0, di.value or 0, dv.value or 0)
+        return P, beta
+
+    def tsne_gradient(self, P, Y, exaggeration=1.0):
+        """sapca_tsne_gradient_device_*: (grad, Z, kl) at the embedding Y (m x output_dim device tensor of P's dtype) for the
+        affinity matrix P (a ResidentCsr): grad a device tensor of Y's shape, Z and kl Python floats."""
+        import torch
+        m, D, ld, dt = _knn_panel("Y", Y)
+        if not Y.is_cuda:
+            raise ValueError("Y must live on the device")
+        if np.dtype(np.float32 if dt == torch.float32 else np.float64) != P.dtype or P.shape != (m, m):
+            raise ValueError(f"P {P.shape} {P.dtype} and Y {tuple(Y.shape)} {dt} do not belong together")
+        grad = torch.empty((m, D), dtype=dt, device=Y.device)
+        Z, kl = C.c_double(), C.c_double()
+        suf = "f32" if dt == torch.float32 else "f64"
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_tsne_gradient_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_uint64(P.nnz), C.c_void_p(P.d_ptr), C.c_void_p(P.d_idx), C.c_void_p(P.d_val),
+            C.c_void_p(Y.data_ptr() if m else None), C.c_uint64(ld), C.c_uint32(D), C.c_double(float(exaggeration)),
+            C.c_void_p(grad.data_ptr() if m else None), C.byref(Z), C.byref(kl)))
+        return grad, Z.value, kl.value
+
+    def tsne_embed(self, P, epochs=1000, output_dim=2, init=None, seed=None, **constants):
+        """sapca_tsne_embed_device_*: (Y, kl) for the affinity matrix P (a ResidentCsr): the optimiser alone.  init: an
+        m x output_dim device tensor to start from (copied), or None for 1e-4 N(0, 1) under the seed."""
+        import torch
+        m = P.shape[0]
+        o = self._tsne_options(20.0, epochs, output_dim, init is not None, seed, constants)
+        dt = torch.float32 if P.dtype == np.float32 else torch.float64
+        if init is not None:
+            if not (isinstance(init, torch.Tensor) and init.is_cuda and init.dtype == dt and tuple(init.shape) == (m, int(output_dim))):
+                raise ValueError(f"init must be a device tensor of shape {(m, int(output_dim))} and dtype {dt}")
+            Y = init.contiguous().clone()
+        else:
+            Y = torch.empty((m, int(output_dim)), dtype=dt, device=self._device())
+        kl = C.c_double()
+        suf = "f32" if dt == torch.float32 else "f64"
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_tsne_embed_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_uint64(P.nnz), C.c_void_p(P.d_ptr), C.c_void_p(P.d_idx), C.c_void_p(P.d_val), C.byref(o),
+            C.c_void_p(Y.data_ptr() if m else None), C.byref(kl)))
+        return Y, kl.value
+
+    def tsne(self, X, perplexity=20.0, epochs=1000, output_dim=2, init=None, seed=None, **constants):
+        """sapca_tsne_device_* / sapca_tsne_*: (Y, kl), the t-SNE embedding of the rows of X and its Kullback-Leibler
+        divergence.  X: an m x d torch device tensor of float32 / float64 with contiguous rows (a column slice of the scores
+        is searched in place; Y is a device tensor), or a numpy array (the host route, the drop-in for the reference's
+        run_f32 / run_f64; Y is a numpy array).  init: the initial embedding in the same kind of array, else 1e-4 N(0, 1)
+        under `seed` (the Session's by default).  constants: theta (stored, not read), stop_lying_epoch,
+        momentum_switch_epoch, exaggeration, learning_rate, momentum, final_momentum.  The same bytes from call to call."""
+        o = self._tsne_options(perplexity, epochs, output_dim, init is not None, seed, constants)
+        D = int(output_dim)
+        kl = C.c_double()
+        if isinstance(X, np.ndarray):
+            if X.ndim != 2 or X.dtype not in _SUF:
+                raise ValueError(f"X must be a two-dimensional float32 / float64 array, got {X.dtype} {X.shape}")
+            X = np.ascontiguousarray(X)
+            m, d = X.shape
+            Y = np.zeros((m, D), dtype=X.dtype)
+            if init is not None:
+                init = np.asarray(init)
+                if init.shape != (m, D):
+                    raise ValueError(f"init must have shape {(m, D)}, got {init.shape}")
+                Y[...] = init
+            suf, ct = _SUF[X.dtype]
+            L.check(self._h, getattr(L.load(), f"sapca_tsne_{suf}")(
+                self._h, C.c_uint64(m), C.c_uint64(d), X.ctypes.data_as(C.c_void_p), C.byref(o), Y.ctypes.data_as(C.c_void_p),
+                C.byref(kl)))
+            return Y, kl.value
+        import torch
+        m, d, ld, dt = _knn_panel("X", X)
+        if not X.is_cuda:
+            raise ValueError(f"X must live on the device (a CUDA tensor) or be a numpy array, got a tensor on {X.device}")
+        if init is not None:
+            if not (isinstance(init, torch.Tensor) and init.is_cuda and init.dtype == dt and tuple(init.shape) == (m, D)):
+                raise ValueError(f"init must be a device tensor of shape {(m, D)} and dtype {dt}")
+            Y = init.contiguous().clone()
+        else:
+            Y = torch.empty((m, D), dtype=dt, device=X.device)
+        suf = "f32" if dt == torch.float32 else "f64"
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_tsne_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_void_p(X.data_ptr() if m else None), C.c_uint64(ld), C.c_uint64(d), C.byref(o),
+            C.c_void_p(Y.data_ptr() if m else None), C.byref(kl)))
+        return Y, kl.value
 
 
 ROW, COLUMN = 0, 1   # Direction of the reference's Normalize / statistics traits (src/utils.rs)

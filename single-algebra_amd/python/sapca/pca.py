@@ -139,6 +139,14 @@ class _Estimator:
             pass
 
     # -- test hook -----------------------------------------------------------------------
+    def session(self):
+        """An ops.Session on THIS estimator's handle (not owned): `est.session().knn(scores)`, `est.session().tsne(scores)` run
+        the steps behind the fit in the estimator's own stream and buffers, and leave the fitted model as it is."""
+        from .ops import Session
+        s = Session.borrow(self._h, self.random_seed & 0xFFFFFFFF)
+        s._keep = self      # the handle lives as long as the estimator
+        return s
+
     def set_omega(self, omega):
         """Inject the Gaussian test matrix of the next randomized fit (parity tests)."""
         om = np.ascontiguousarray(omega, dtype=np.float64)
@@ -531,3 +539,36 @@ class MaskedSparsePCABuilder(_BuilderBase):
         return MaskedSparsePCA(self._n_components, self._alpha, self._tolerance,
                                42 if self._random_seed is None else self._random_seed, self._mask,
                                self._center, self._verbose, self._svdmethod, **self._ext)
+
+
+class TSNE:
+    """t-SNE of dense rows on the GPU (sapca_tsne_*): the reference's dimred::tsne -- TSNEConfig { output_dim, perplexity,
+    epochs, theta } with run_f32 / run_f64 (src/dimred/tsne/mod.rs:7-66) -- as an estimator.  The repulsive term is evaluated
+    exactly: theta is kept for drop-in and not read (include/sapca.h, deviation 1).
+
+        emb = sapca.TSNE(perplexity=30, epochs=500).fit_transform(scores)      # a torch device tensor, or a numpy array
+
+    `scores` is usually what SparsePCA.fit_transform left on the device; it is searched in place.  After the call
+    `embedding_` holds the result and `kl_divergence_` its Kullback-Leibler divergence.  constants: stop_lying_epoch,
+    momentum_switch_epoch, exaggeration, learning_rate, momentum, final_momentum."""
+
+    def __init__(self, output_dim=2, perplexity=20.0, epochs=1000, theta=0.5, random_seed=42, **constants):
+        self.output_dim, self.perplexity, self.epochs, self.theta = int(output_dim), float(perplexity), int(epochs), float(theta)
+        self.random_seed = int(random_seed)
+        self.constants = dict(constants)
+        self.embedding_ = None
+        self.kl_divergence_ = None
+        self._session = None
+
+    def fit_transform(self, X, init=None):
+        from .ops import Session
+        if self._session is None:
+            self._session = Session(seed=self.random_seed)
+        self.embedding_, self.kl_divergence_ = self._session.tsne(
+            X, perplexity=self.perplexity, epochs=self.epochs, output_dim=self.output_dim, init=init, seed=self.random_seed,
+            theta=self.theta, **self.constants)
+        return self.embedding_
+
+    def fit(self, X, init=None):
+        self.fit_transform(X, init)
+        return self
