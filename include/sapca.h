@@ -71,7 +71,10 @@ extern "C" {
                                                   sapca_scale_panel_rows_*
                                  additive, ABI 4: sapca_tsne_options_default, sapca_tsne_affinities_device_*,
                                                   sapca_tsne_gradient_device_*, sapca_tsne_embed_device_*,
-                                                  sapca_tsne_device_*, sapca_tsne_*                                   */
+                                                  sapca_tsne_device_*, sapca_tsne_*
+                                 additive, ABI 4: sapca_kmeans_options_default, sapca_kmeans_seed_device_*,
+                                                  sapca_kmeans_assign_device_*, sapca_kmeans_update_device_*,
+                                                  sapca_kmeans_device_*, sapca_kmeans_*                               */
 
 typedef struct sapca_handle_s* sapca_handle;
 
@@ -784,6 +787,101 @@ sapca_status sapca_tsne_device_f64(sapca_handle h, uint64_t m, const double* d_x
  * (tsne/mod.rs:14-39, :41-66).                                                                                            */
 sapca_status sapca_tsne_f32(sapca_handle h, uint64_t m, uint64_t d, const float* x, const sapca_tsne_options* opts, float* y, double* kl);
 sapca_status sapca_tsne_f64(sapca_handle h, uint64_t m, uint64_t d, const double* x, const sapca_tsne_options* opts, double* y, double* kl);
+
+/* ---- clustering of device-resident score rows: k-means (Lloyd) with k-means++ seeding ----
+ * The reference has no k-means: like the neighbour search, the covariates and the column scaling this is an opt-in superset,
+ * the third consumer of the score rows a fit_transform left in HBM.  The algorithm is stated here in full and pinned by a
+ * numpy restatement (tests/kmeans_ref.py) that is itself held to scikit-learn's KMeans(algorithm="lloyd"), not by a crate.
+ * The input x is a row-major DEVICE panel, m x d, with row stride ldx >= d: nothing beyond column d of a row is read, so a
+ * slice of the score buffer is clustered in place.  The centroids C are k x d, packed, of type T; labels are int32.
+ *   1. Seeding (init = SAPCA_KMEANS_PLUSPLUS): plain k-means++ (Arthur & Vassilvitskii), one trial per centre.  u_t =
+ *      hash_u01(random_seed, 21, t), the counter generator behind sapca_generate_omega_* -- sapca.synth.hash_u01 -- on a
+ *      stream of its own.  c_0 = row floor(u_0 m).  For t = 1 .. k-1: D_i = min_{s<t} |x_i - c_s|^2 by the direct formula in f64, S the
+ *      inclusive prefix sums of D in f64, c_t = the first row i with S_i > u_t S_{m-1}; S_{m-1} == 0 (every row coincides with
+ *      a chosen centre): c_t = row floor(u_t m).  The prefix sums are associated in an order fixed by m alone (blocks of 1024
+ *      rows, doubling strides inside a wave), not the running order, so a row whose boundary S_i lies within m eps_f64 S_{m-1}
+ *      of u_t S_{m-1} may give way to its neighbour.  Everything stays on the device: no index is read back between centres.
+ *      init = SAPCA_KMEANS_GIVEN uses the caller's k x d centroids as they are.
+ *   2. Assignment: label_i = argmin_c |x_i - c|^2, ties to the lower c.  The labels are those of the direct formula in f64;
+ *      where a row's two smallest squared distances differ by less than 64 d eps_f64 (|x_i| + max_c |c|)^2 either may win.
+ *      Mechanism: the rows are ranked by 2 <x, c> - |c|^2 on the f32 / f64 matrix cores, every row keeping its best and its
+ *      second-best score; a row whose runner-up lies within 4 d eps_T (|x_i| + max |c|)^2 of its best (the bound of the
+ *      neighbour search for an FMA chain of length d) is AMBIGUOUS and is decided by a second pass that evaluates all k direct
+ *      distances in f64 and takes the least (distance, index).  The distance of every row to its chosen centroid is then
+ *      recomputed by the direct formula in f64 and rounded once to T (d_dist2); the inertia is the f64 sum of the unrounded
+ *      values in an order fixed by m.
+ *   3. Update: c = (sum_{label_i = c} x_i) / n_c, the sum and the division in f64 whatever T is, rounded once to T.
+ *      DEVIATION from scikit-learn: a cluster with no rows keeps its centroid (scikit-learn relocates it).  The rows are
+ *      sorted by (label, row) with a counting sort and each cluster's list is summed over fixed slices that are added in
+ *      order: the order of every sum is fixed by (m, k, d) and the labels alone; no floating-point atomic is used.
+ *   4. The loop, scikit-learn's Lloyd rule:
+ *        for i in 0 .. max_iter-1:
+ *          labels = assign(C);  C_new = update(labels);  shift = sum |C_new - C|^2 (f64, on the stored T values);  C = C_new
+ *          if i > 0 and labels == labels_prev: strict = true; break
+ *          if shift <= tol_abs: break
+ *        n_iter = i + 1 (0 when max_iter == 0);  if not strict: labels = assign(C)
+ *        inertia = sum_i |x_i - C[labels_i]|^2
+ *      tol_abs = tol x (the mean over the columns of the column's population variance), computed once on the device in f64
+ *      in two passes; tol == 0 gives tol_abs = 0, which leaves the strict test (and a shift of exactly 0).  The loop enqueues
+ *      kernels only: convergence sets a device flag that turns the iterations still enqueued into no-ops.  The host looks at
+ *      the flag every 8 iterations to stop enqueueing; the result does not depend on when it looks.
+ * Deterministic: the same bytes from call to call.  The labels do not depend on the launch geometry (a pair's score is the
+ * same k-ordered FMA chain wherever it falls); integer atomics count rows, no order reaches a value.
+ * Outputs are complete when the call returns.  Every call runs on the handle's stream in buffers of its own: a fitted model,
+ * a cached preparation, the upload's statistics, the selection, the canonical and the t-SNE buffers are untouched; on a
+ * handle that belongs to a communicator the call is local to the rank and issues no collective.
+ * No address outside the arrays is touched: a label outside [0, n_clusters) given to the update call is skipped where it is
+ * read (its row belongs to no cluster).  Non-finite input values give unspecified labels inside [0, n_clusters).
+ * SAPCA_ERR_ARG, checked on the host before anything is enqueued (the handle stays usable), each with a message that names the
+ * offending number: a wrong struct_size; n_clusters == 0; n_clusters > SAPCA_KMEANS_MAX_CLUSTERS; n_clusters > m when m > 0
+ * (seeding and the whole run); an unknown init; tol negative or not finite; the d and stride limits of sapca_knn_device_*
+ * (d in 1 .. 1024, ldx >= d, ldx < 2^28); m >= 2^31; a null pointer with a non-empty shape.  m == 0 is valid and writes
+ * nothing (*inertia = 0, *n_iter = 0).                                                                                   */
+typedef enum sapca_kmeans_init { SAPCA_KMEANS_PLUSPLUS = 0, SAPCA_KMEANS_GIVEN = 1 } sapca_kmeans_init;
+#define SAPCA_KMEANS_MAX_CLUSTERS 1024
+typedef struct sapca_kmeans_options {
+  uint32_t struct_size;   /* sizeof(sapca_kmeans_options)                                         */
+  uint32_t random_seed;   /* default 42                                                           */
+  uint32_t n_clusters;    /* default 8; 1 .. SAPCA_KMEANS_MAX_CLUSTERS                            */
+  uint32_t init;          /* sapca_kmeans_init, default SAPCA_KMEANS_PLUSPLUS                     */
+  uint64_t max_iter;      /* default 300                                                          */
+  double tol;             /* default 1e-4, relative to the mean column variance (scikit-learn's)  */
+} sapca_kmeans_options;
+void sapca_kmeans_options_default(sapca_kmeans_options* opts);
+/* Stage 1 alone (a stage-level operator for the parity tests, like sapca_tsne_gradient_device_*): d_centroids (k x d, DEVICE)
+ * receives the chosen rows, d_rows (k int32, DEVICE, may be NULL) their row numbers.                                      */
+sapca_status sapca_kmeans_seed_device_f32(sapca_handle h, uint64_t m, const float* d_x, uint64_t ldx, uint64_t d, uint32_t n_clusters,
+                                          uint32_t random_seed, float* d_centroids, int32_t* d_rows);
+sapca_status sapca_kmeans_seed_device_f64(sapca_handle h, uint64_t m, const double* d_x, uint64_t ldx, uint64_t d, uint32_t n_clusters,
+                                          uint32_t random_seed, double* d_centroids, int32_t* d_rows);
+/* Stage 2 alone, which is also the out-of-sample `predict`: d_labels (m int32, DEVICE), d_dist2 (m, DEVICE, may be NULL) the
+ * squared distance of every row to its centroid; *inertia and *n_ambiguous (the rows the second pass decided) on the HOST,
+ * may be NULL.  n_clusters may exceed m here.                                                                             */
+sapca_status sapca_kmeans_assign_device_f32(sapca_handle h, uint64_t m, const float* d_x, uint64_t ldx, uint64_t d, uint32_t n_clusters,
+                                            const float* d_centroids, int32_t* d_labels, float* d_dist2, double* inertia,
+                                            uint64_t* n_ambiguous);
+sapca_status sapca_kmeans_assign_device_f64(sapca_handle h, uint64_t m, const double* d_x, uint64_t ldx, uint64_t d, uint32_t n_clusters,
+                                            const double* d_centroids, int32_t* d_labels, double* d_dist2, double* inertia,
+                                            uint64_t* n_ambiguous);
+/* Stage 3 alone: d_centroids (k x d, DEVICE) is read for the clusters without rows, which keep theirs, and receives the
+ * means; d_counts (k int64, DEVICE, may be NULL) the rows of every cluster.                                               */
+sapca_status sapca_kmeans_update_device_f32(sapca_handle h, uint64_t m, const float* d_x, uint64_t ldx, uint64_t d, uint32_t n_clusters,
+                                            const int32_t* d_labels, float* d_centroids, int64_t* d_counts);
+sapca_status sapca_kmeans_update_device_f64(sapca_handle h, uint64_t m, const double* d_x, uint64_t ldx, uint64_t d, uint32_t n_clusters,
+                                            const int32_t* d_labels, double* d_centroids, int64_t* d_counts);
+/* Stages 1-4 on a resident panel: d_centroids (n_clusters x d, DEVICE) is read when opts->init == SAPCA_KMEANS_GIVEN and
+ * receives the centroids, d_labels (m int32, DEVICE) the labels; *inertia and *n_iter on the HOST, may be NULL.            */
+sapca_status sapca_kmeans_device_f32(sapca_handle h, uint64_t m, const float* d_x, uint64_t ldx, uint64_t d,
+                                     const sapca_kmeans_options* opts, float* d_centroids, int32_t* d_labels, double* inertia,
+                                     uint64_t* n_iter);
+sapca_status sapca_kmeans_device_f64(sapca_handle h, uint64_t m, const double* d_x, uint64_t ldx, uint64_t d,
+                                     const sapca_kmeans_options* opts, double* d_centroids, int32_t* d_labels, double* inertia,
+                                     uint64_t* n_iter);
+/* The same with HOST arrays in and out (x: m x d row-major; centroids: n_clusters x d; labels: m).                          */
+sapca_status sapca_kmeans_f32(sapca_handle h, uint64_t m, uint64_t d, const float* x, const sapca_kmeans_options* opts, float* centroids,
+                              int32_t* labels, double* inertia, uint64_t* n_iter);
+sapca_status sapca_kmeans_f64(sapca_handle h, uint64_t m, uint64_t d, const double* x, const sapca_kmeans_options* opts, double* centroids,
+                              int32_t* labels, double* inertia, uint64_t* n_iter);
 
 /* Measurement support: the rate (GB/s, read + write counted) of a 16-byte-per-lane streaming copy of `bytes`
  * bytes on the handle's device, best of `reps` -- the HBM rate a kernel of this library can attain, reported by

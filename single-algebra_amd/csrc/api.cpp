@@ -879,6 +879,31 @@ sapca_status sapca_get_column_scale(sapca_handle h, int32_t* mode, double* out, 
                                 double* kl) {                                                                             \
     return guarded(h, [&] { resident::tsne_host<T>(*h, m, d, x, opts, y, kl); });                                        \
   }                                                                                                                      \
+  sapca_status sapca_kmeans_seed_device_##SUF(sapca_handle h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d,           \
+                                              uint32_t n_clusters, uint32_t random_seed, T* d_centroids, int32_t* d_rows) { \
+    return guarded(h, [&] { resident::kmeans_seed<T>(*h, m, d_x, ldx, d, n_clusters, random_seed, d_centroids, d_rows); }); \
+  }                                                                                                                      \
+  sapca_status sapca_kmeans_assign_device_##SUF(sapca_handle h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d,         \
+                                                uint32_t n_clusters, const T* d_centroids, int32_t* d_labels, T* d_dist2,   \
+                                                double* inertia, uint64_t* n_ambiguous) {                                  \
+    return guarded(h, [&] {                                                                                              \
+      resident::kmeans_assign<T>(*h, m, d_x, ldx, d, n_clusters, d_centroids, d_labels, d_dist2, inertia, n_ambiguous);  \
+    });                                                                                                                  \
+  }                                                                                                                      \
+  sapca_status sapca_kmeans_update_device_##SUF(sapca_handle h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d,         \
+                                                uint32_t n_clusters, const int32_t* d_labels, T* d_centroids,              \
+                                                int64_t* d_counts) {                                                       \
+    return guarded(h, [&] { resident::kmeans_update<T>(*h, m, d_x, ldx, d, n_clusters, d_labels, d_centroids, d_counts); }); \
+  }                                                                                                                      \
+  sapca_status sapca_kmeans_device_##SUF(sapca_handle h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d,                \
+                                         const sapca_kmeans_options* opts, T* d_centroids, int32_t* d_labels,              \
+                                         double* inertia, uint64_t* n_iter) {                                              \
+    return guarded(h, [&] { resident::kmeans_device<T>(*h, m, d_x, ldx, d, opts, d_centroids, d_labels, inertia, n_iter); }); \
+  }                                                                                                                      \
+  sapca_status sapca_kmeans_##SUF(sapca_handle h, uint64_t m, uint64_t d, const T* x, const sapca_kmeans_options* opts,     \
+                                  T* centroids, int32_t* labels, double* inertia, uint64_t* n_iter) {                      \
+    return guarded(h, [&] { resident::kmeans_host<T>(*h, m, d, x, opts, centroids, labels, inertia, n_iter); });         \
+  }                                                                                                                      \
   sapca_status sapca_sum_row_n_top_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, \
                                                     const int32_t* i, const T* v, const uint64_t* ns, uint32_t n_ns,        \
                                                     double* out) {                                                          \
@@ -908,6 +933,17 @@ sapca_status sapca_get_column_scale(sapca_handle h, int32_t* mode, double* out, 
 SAPCA_DEFINE_TYPED(f32, float)
 SAPCA_DEFINE_TYPED(f64, double)
 #undef SAPCA_DEFINE_TYPED
+
+void sapca_kmeans_options_default(sapca_kmeans_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  o->struct_size = (uint32_t)sizeof(sapca_kmeans_options);
+  o->random_seed = 42;
+  o->n_clusters = 8;
+  o->init = SAPCA_KMEANS_PLUSPLUS;
+  o->max_iter = 300;
+  o->tol = 1e-4;
+}
 
 void sapca_tsne_options_default(sapca_tsne_options* o) {
   if (!o) return;

@@ -171,6 +171,13 @@ struct sapca_handle_s {
       return raw_ptr.contains(q) || out_ptr.contains(q) || raw_idx.contains(q) || sort_idx.contains(q) || out_val.contains(q);
     }
   } tsne;
+  // sapca_kmeans_*: the norms of the centroids and the rows, the list of ambiguous rows, the two label generations of the loop, the
+  // counting sort's counts, offsets, scan space and row order, the slices' sums, the control block and the scalars, the seeding's
+  // distances and block sums, and the arrays of the host route.  Nothing else lives in these.
+  struct Kmeans {
+    sapca::DevBuf bias, xb, amb, lab0, lab1, cnt, tab, scan, order, partial, shiftpart, ctl, scal, rowd, sum_part, colpart, cols;
+    sapca::DevBuf rows, seed_dist, seed_bsum, x, cen, labels;
+  } kmeans;
   sapca::DevBuf at_ptr, at_idx, at_val;                          // A^T
   sapca::DevBuf ca_ptr, ca_idx, ca_val, cat_ptr, cat_idx, cat_val;  // mask-compacted A, A^T
   sapca::DevBuf drop_stats, drop_tmp;                              // their sums (sum | sumsq, full width) and the sort's work space

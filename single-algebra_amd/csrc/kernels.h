@@ -110,7 +110,8 @@ void masked_row_stats(const CsrView<T>& A, const uint32_t* col_bits, double* sum
 
 // ---- select.hip: rows of a CSR, in any order and with repeats, as a new CSR (sapca_select_rows_csr_device_*) ----------
 // data[0 .. count) <- its exclusive prefix sums, in place (prep.hip); work space from `scratch` at scratch_offset
-void exclusive_scan_i64(int64_t* data, int64_t count, DevBuf& scratch, size_t scratch_offset, hipStream_t s);
+void exclusive_scan_i64(int64_t* data, int64_t count, DevBuf& scratch, size_t scratch_offset, hipStream_t s,
+                        int64_t* out = nullptr);   // (out: the offsets go there and data stays; null: in place)
 // out_ptr[0 .. n_rows] = the offsets of the selection (row i = source row rows[i]; rows: device, every entry below the source's
 // row count); *total_host = out_ptr[n_rows], on the host when the call returns (one synchronisation, like compact_columns)
 void select_rows_offsets(const int64_t* ptr, const uint64_t* rows, int64_t n_rows, int64_t* out_ptr, int64_t* total_host,
@@ -420,6 +421,61 @@ void tsne_center(T* y, int64_t m, int D, double* colpart, double* mean, bool sum
 // v = 0, gain = 1, and, y non-null, y = 1e-4 N(0, 1) from gaussian_panel under `seed`
 template <typename T>
 void tsne_init_state(T* y_or_null, T* v, T* gain, int64_t m, int D, uint32_t seed, hipStream_t s);
+
+// ---- kmeans.hip: k-means on dense row panels (sapca_kmeans_*); include/sapca.h states the algorithm ------------------------
+// The control block of a run (device, unsigned 64-bit words).  Every kernel below that takes `skip` returns at once when
+// *skip != 0 (null: never): the loop's kernels watch kKmDone, the closing assignment watches kKmStrict.
+enum { kKmDone = 0, kKmStrict = 1, kKmIter = 2, kKmChanged = 3, kKmAmbiguous = 4, kKmCtlWords = 8 };
+// The geometry of the update, fixed by (m, k): a wave counts and places rows_per_wave consecutive rows (nwaves of them), and
+// every cluster's sorted list is summed in `slices` consecutive pieces that are then added in order.
+struct KmeansPlan {
+  int64_t rows_per_wave = 256, nwaves = 1;
+  int slices = 1;
+};
+KmeansPlan kmeans_plan(int64_t m, int k);
+int kmeans_column_slices(int64_t m);   // pieces of the rows in the column sums behind tol_abs
+// k-means++ from the uniforms hash_u01(seed, 21, t): cen (k x d, packed) = the chosen rows, rows[t] their numbers (k words).
+// dist: m doubles, bsum: ceil(m / 1024) doubles of work space.  Nothing is read back.
+template <typename T>
+void kmeans_seed(const T* x, int64_t ldx, int64_t m, int d, int k, uint32_t seed, T* cen, int32_t* rows, double* dist, double* bsum,
+                 hipStream_t s);
+// labels[i] = argmax_c 2 <x_i, c> + bias[c] on the matrix cores (bias = -|c|^2 and xb[i] = -|x_i|^2 from knn_prepare), ties to
+// the lower c; a row whose runner-up lies within 4 d eps_T (|x_i| + max |c|)^2 of the best is appended to amb_list (m words,
+// in no particular order) and counted in ctl[kKmAmbiguous], which the caller (or kmeans_step) has set to 0
+template <typename T>
+void kmeans_rank(const unsigned long long* skip, const T* x, int64_t ldx, int64_t m, const T* cen, int k, const T* bias, const T* xb, int d,
+                 int32_t* labels, int32_t* amb_list, unsigned long long* ctl, hipStream_t s);
+// the ctl[kKmAmbiguous] listed rows decided by the k direct distances in f64 under (distance, index)
+template <typename T>
+void kmeans_refine(const unsigned long long* skip, const T* x, int64_t ldx, int64_t m, const T* cen, int k, int d, int32_t* labels,
+                   const int32_t* amb_list, const unsigned long long* ctl, hipStream_t s);
+// rowd[i] = |x_i - cen[labels[i]]|^2 by the direct formula in f64 (0 for a label outside [0, k)), dist2[i] (nullable) = T(rowd[i])
+template <typename T>
+void kmeans_distances(const T* x, int64_t ldx, int64_t m, const T* cen, int k, int d, const int32_t* labels, T* dist2, double* rowd,
+                      hipStream_t s);
+// the rows sorted by (label, row): cnt (k * plan.nwaves + 1 words) = the rows of every (cluster, wave) run, tab (as many) =
+// their offsets, so cluster c's list is order[tab[c * nwaves] .. tab[(c + 1) * nwaves]); a label outside [0, k) is left out.
+// The scan between the two passes cannot be skipped; it reads cnt and writes tab, so behind a skipped count it writes the
+// same offsets again.  prev non-null: the rows whose
+// label differs from prev[i] are counted into ctl[kKmChanged] by the counting pass.
+void kmeans_sort(const unsigned long long* skip, const int32_t* labels, int64_t m, int k, const KmeansPlan& plan, int64_t* cnt,
+                 int64_t* tab, int32_t* order, DevBuf& scan, const int32_t* prev, unsigned long long* ctl, hipStream_t s);
+// partial[(c * slices + s) * d + t] = the f64 sum over slice s of cluster c's list of x[row][t] (center null) or of
+// (x[row][t] - center[t])^2.  order / tab null: one cluster, the rows 0 .. m - 1 in order (k == 1).
+template <typename T>
+void kmeans_sums(const unsigned long long* skip, const T* x, int64_t ldx, int64_t m, int d, const int32_t* order, const int64_t* tab,
+                 int64_t nwaves, int k, int slices, const double* center, double* partial, hipStream_t s);
+// cen[c] = T(sum of its slices / n_c) where n_c > 0 (kept otherwise); counts[c] (nullable) = n_c; shiftpart[c] = |new - old|^2
+template <typename T>
+void kmeans_finalize(const unsigned long long* skip, const double* partial, const int64_t* tab, int64_t nwaves, int k, int d, int slices,
+                     T* cen, int64_t* counts, double* shiftpart, hipStream_t s);
+// the end of iteration `iter` of the loop: n_iter, the strict test (no label changed, iter > 0), shift <= *tol_abs; the counts
+// of changed and of ambiguous rows go back to 0
+void kmeans_step(unsigned long long* ctl, const double* shiftpart, int k, const double* tol_abs, unsigned long long iter, hipStream_t s);
+// cols[t] = sum_s partial[s * d + t] / m; scalar (nullable): *scalar = scale * mean_t cols[t]
+void kmeans_fold_columns(const double* partial, int slices, int d, int64_t m, double* cols, double scale, double* scalar, hipStream_t s);
+// a strict run's labels are those of its last iteration: out = (ctl[kKmIter] - 1) & 1 ? lab1 : lab0 when ctl[kKmStrict]
+void kmeans_take_labels(const unsigned long long* ctl, const int32_t* lab0, const int32_t* lab1, int32_t* out, int64_t m, hipStream_t s);
 
 // ---- rng.hip ---------------------------------------------------------------------------
 // Omega[r][j] ~ N(0,1) for j < l (zero for l <= j < ld), a pure function of (seed, r*l+j).

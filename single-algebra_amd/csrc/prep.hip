@@ -388,12 +388,13 @@ inline int grid_for(int64_t work_items, int block, int cap = 8192) {
 
 }  // namespace
 
-void exclusive_scan_i64(int64_t* data, int64_t count, DevBuf& scratch, size_t scratch_offset, hipStream_t s) {
+void exclusive_scan_i64(int64_t* data, int64_t count, DevBuf& scratch, size_t scratch_offset, hipStream_t s, int64_t* out) {
+  if (out == nullptr) out = data;
   size_t bytes = 0;
-  SAPCA_HIP(rocprim::exclusive_scan(nullptr, bytes, data, data, (int64_t)0, (size_t)count,
+  SAPCA_HIP(rocprim::exclusive_scan(nullptr, bytes, data, out, (int64_t)0, (size_t)count,
                                     rocprim::plus<int64_t>(), s));
   char* base = static_cast<char*>(scratch.ensure(scratch_offset + bytes + 256));
-  SAPCA_HIP(rocprim::exclusive_scan(base + scratch_offset, bytes, data, data, (int64_t)0, (size_t)count,
+  SAPCA_HIP(rocprim::exclusive_scan(base + scratch_offset, bytes, data, out, (int64_t)0, (size_t)count,
                                     rocprim::plus<int64_t>(), s));
 }
 

@@ -74,5 +74,21 @@ void tsne_device(H& h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d, const
 template <typename T>
 void tsne_host(H& h, uint64_t m, uint64_t d, const T* x, const sapca_tsne_options* opts, T* y, double* kl);
 
+// sapca_kmeans_* (kmeans.cpp): seeding, one assignment, one update, and the whole run on a device panel or on host arrays
+template <typename T>
+void kmeans_seed(H& h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d, uint32_t k, uint32_t seed, T* d_centroids, int32_t* d_rows);
+template <typename T>
+void kmeans_assign(H& h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d, uint32_t k, const T* d_centroids, int32_t* d_labels, T* d_dist2,
+                   double* inertia, uint64_t* n_ambiguous);
+template <typename T>
+void kmeans_update(H& h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d, uint32_t k, const int32_t* d_labels, T* d_centroids,
+                   int64_t* d_counts);
+template <typename T>
+void kmeans_device(H& h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d, const sapca_kmeans_options* opts, T* d_centroids,
+                   int32_t* d_labels, double* inertia, uint64_t* n_iter);
+template <typename T>
+void kmeans_host(H& h, uint64_t m, uint64_t d, const T* x, const sapca_kmeans_options* opts, T* centroids, int32_t* labels, double* inertia,
+                 uint64_t* n_iter);
+
 }  // namespace resident
 }  // namespace sapca

@@ -167,6 +167,70 @@ inline double tsne(sapca_handle h, uint64_t m, uint64_t d, const T* host_x, cons
   return kl;
 }
 
+// K-means of device-resident rows (sapca_kmeans_*; include/sapca.h states the algorithm).  KmeansOptions() holds the library's
+// defaults.  Every pointer is a DEVICE pointer unless the name says host.
+struct KmeansOptions : sapca_kmeans_options {
+  KmeansOptions() { sapca_kmeans_options_default(this); }
+};
+struct KmeansResult {
+  double inertia = 0.0;
+  uint64_t n_iter = 0;
+};
+template <typename T> struct KmeansAbi;
+template <> struct KmeansAbi<float> {
+  static constexpr auto seed = &sapca_kmeans_seed_device_f32;
+  static constexpr auto assign = &sapca_kmeans_assign_device_f32;
+  static constexpr auto update = &sapca_kmeans_update_device_f32;
+  static constexpr auto device = &sapca_kmeans_device_f32;
+  static constexpr auto host = &sapca_kmeans_f32;
+};
+template <> struct KmeansAbi<double> {
+  static constexpr auto seed = &sapca_kmeans_seed_device_f64;
+  static constexpr auto assign = &sapca_kmeans_assign_device_f64;
+  static constexpr auto update = &sapca_kmeans_update_device_f64;
+  static constexpr auto device = &sapca_kmeans_device_f64;
+  static constexpr auto host = &sapca_kmeans_f64;
+};
+inline void kmeans_check(sapca_handle h, sapca_status st) {
+  if (st != SAPCA_OK) throw Error(st, sapca_last_error(h));
+}
+// k-means++ centres (k x d) of an m x d panel with row stride ldx; d_rows (k) may be null
+template <typename T>
+inline void kmeans_seed_device(sapca_handle h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d, uint32_t k, uint32_t seed,
+                               T* d_centroids, int32_t* d_rows = nullptr) {
+  kmeans_check(h, KmeansAbi<T>::seed(h, m, d_x, ldx, d, k, seed, d_centroids, d_rows));
+}
+// the nearest centroid of every row (also `predict`); returns the inertia; d_dist2 and n_ambiguous may be null
+template <typename T>
+inline double kmeans_assign_device(sapca_handle h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d, uint32_t k, const T* d_centroids,
+                                   int32_t* d_labels, T* d_dist2 = nullptr, uint64_t* n_ambiguous = nullptr) {
+  double inertia = 0.0;
+  kmeans_check(h, KmeansAbi<T>::assign(h, m, d_x, ldx, d, k, d_centroids, d_labels, d_dist2, &inertia, n_ambiguous));
+  return inertia;
+}
+// the means of the rows under d_labels into d_centroids (a cluster without rows keeps its own); d_counts (k) may be null
+template <typename T>
+inline void kmeans_update_device(sapca_handle h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d, uint32_t k, const int32_t* d_labels,
+                                 T* d_centroids, int64_t* d_counts = nullptr) {
+  kmeans_check(h, KmeansAbi<T>::update(h, m, d_x, ldx, d, k, d_labels, d_centroids, d_counts));
+}
+// the whole run on a resident panel; d_centroids (n_clusters x d) is read when opts.init == SAPCA_KMEANS_GIVEN
+template <typename T>
+inline KmeansResult kmeans_device(sapca_handle h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d, const sapca_kmeans_options& opts,
+                                  T* d_centroids, int32_t* d_labels) {
+  KmeansResult r;
+  kmeans_check(h, KmeansAbi<T>::device(h, m, d_x, ldx, d, &opts, d_centroids, d_labels, &r.inertia, &r.n_iter));
+  return r;
+}
+// the same with host arrays
+template <typename T>
+inline KmeansResult kmeans(sapca_handle h, uint64_t m, uint64_t d, const T* host_x, const sapca_kmeans_options& opts, T* host_centroids,
+                           int32_t* host_labels) {
+  KmeansResult r;
+  kmeans_check(h, KmeansAbi<T>::host(h, m, d, host_x, &opts, host_centroids, host_labels, &r.inertia, &r.n_iter));
+  return r;
+}
+
 template <typename T>
 class ResidentCsr {
  public:

@@ -545,6 +545,86 @@ pub mod tsne {
     }
 }
 
+/// K-means of dense rows (`sapca_kmeans_f32` / `_f64`): Lloyd's iteration under scikit-learn's stopping rule with k-means++
+/// seeding, deterministic under `random_seed`; a cluster that loses all its rows keeps its centroid (include/sapca.h).  The
+/// reference has no clustering: this is the crate's own, beside `tsne`.
+pub mod kmeans {
+    use super::{check, ffi};
+    use anyhow::{anyhow, Result};
+    use ndarray::{Array1, Array2, ArrayView2};
+    use sapca_sys::sapca_kmeans_options as RawOptions;
+
+    #[derive(Clone, Copy, Debug)]
+    pub struct KMeansConfig {
+        pub n_clusters: u32,
+        pub max_iter: usize,
+        pub tol: f64,
+        pub random_seed: u32,
+    }
+    impl KMeansConfig {
+        pub fn new(n_clusters: u32, max_iter: usize, tol: f64, random_seed: u32) -> Self { Self { n_clusters, max_iter, tol, random_seed } }
+    }
+    impl Default for KMeansConfig {
+        /// the library's defaults: 8 clusters, 300 iterations, tol 1e-4, seed 42
+        fn default() -> Self { Self { n_clusters: 8, max_iter: 300, tol: 1e-4, random_seed: 42 } }
+    }
+
+    pub struct KMeansFit<T> {
+        pub labels: Array1<i32>,
+        pub cluster_centers: Array2<T>,
+        pub inertia: f64,
+        pub n_iter: u64,
+    }
+
+    fn options(config: &KMeansConfig, init_given: bool) -> RawOptions {
+        let mut o: RawOptions = unsafe { std::mem::zeroed() };
+        unsafe { ffi::sapca_kmeans_options_default(&mut o) };
+        o.n_clusters = config.n_clusters;
+        o.max_iter = config.max_iter as u64;
+        o.tol = config.tol;
+        o.random_seed = config.random_seed;
+        o.init = if init_given { ffi::SAPCA_KMEANS_GIVEN as u32 } else { ffi::SAPCA_KMEANS_PLUSPLUS as u32 };
+        o
+    }
+
+    fn with_handle<R>(f: impl FnOnce(ffi::sapca_handle) -> Result<R>) -> Result<R> {
+        let mut o: ffi::sapca_options = unsafe { std::mem::zeroed() };
+        unsafe { ffi::sapca_options_default(&mut o) };
+        let mut h: ffi::sapca_handle = std::ptr::null_mut();
+        if unsafe { ffi::sapca_create(&o, &mut h) } != ffi::SAPCA_OK {
+            return Err(anyhow!("sapca_create failed (no usable GPU?)"));
+        }
+        let r = f(h);
+        unsafe { ffi::sapca_destroy(h) };
+        r
+    }
+
+    macro_rules! run {
+        ($name:ident, $t:ty, $ffi:ident) => {
+            /// `init`: `n_clusters x d` centroids to start from, or `None` for k-means++ under `config.random_seed`
+            pub fn $name(x: ArrayView2<$t>, config: KMeansConfig, init: Option<ArrayView2<$t>>) -> Result<KMeansFit<$t>> {
+                let (m, d) = x.dim();
+                let k = config.n_clusters as usize;
+                let x = x.as_standard_layout();
+                let mut centers = match init {
+                    Some(c) if c.dim() == (k, d) => c.as_standard_layout().iter().copied().collect::<Vec<$t>>(),
+                    Some(c) => return Err(anyhow!("init has shape {:?}, expected ({}, {})", c.dim(), k, d)),
+                    None => vec![0 as $t; k * d],
+                };
+                let o = options(&config, init.is_some());
+                let mut labels = vec![0i32; m];
+                let (mut inertia, mut n_iter) = (0f64, 0u64);
+                with_handle(|h| check(h, unsafe {
+                    ffi::$ffi(h, m as u64, d as u64, x.as_ptr(), &o, centers.as_mut_ptr(), labels.as_mut_ptr(), &mut inertia, &mut n_iter)
+                }))?;
+                Ok(KMeansFit { labels: Array1::from_vec(labels), cluster_centers: Array2::from_shape_vec((k, d), centers)?, inertia, n_iter })
+            }
+        };
+    }
+    run!(run_f32, f32, sapca_kmeans_f32);
+    run!(run_f64, f64, sapca_kmeans_f64);
+}
+
 /// The reference's module tree (src/dimred/pca/mod.rs:36-42; README.md:51-53 imports
 /// `dimred::pca::{SparsePCABuilder, SVDMethod}` and `dimred::pca::sparse::PowerIterationNormalizer`).
 pub mod dimred {

@@ -51,6 +51,14 @@ class TsneOptions(C.Structure):
     ]
 
 
+class KmeansOptions(C.Structure):
+    """sapca_kmeans_options"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("random_seed", C.c_uint32), ("n_clusters", C.c_uint32), ("init", C.c_uint32),
+        ("max_iter", C.c_uint64), ("tol", C.c_double),
+    ]
+
+
 # sapca_csr_report and its flags (sapca_check_csr_device_*, sapca_canonicalize_csr_device_*)
 CSR_BAD_OFFSETS, CSR_COL_RANGE, CSR_UNSORTED, CSR_DUPLICATES, CSR_NONFINITE = 1, 2, 4, 8, 16
 CSR_FLAG_NAMES = {CSR_BAD_OFFSETS: "BAD_OFFSETS", CSR_COL_RANGE: "COL_RANGE", CSR_UNSORTED: "UNSORTED",
@@ -64,6 +72,9 @@ KNN_EUCLIDEAN, KNN_COSINE, KNN_PEARSON = 0, 1, 2
 KNN_METRICS = {"euclidean": KNN_EUCLIDEAN, "cosine": KNN_COSINE, "pearson": KNN_PEARSON}
 KNN_EXCLUDE_SELF = 1
 KNN_MAX_NEIGHBORS = 128
+# sapca_kmeans_*: the seeding rules, the most clusters
+KMEANS_PLUSPLUS, KMEANS_GIVEN = 0, 1
+KMEANS_MAX_CLUSTERS = 1024
 # covariate columns + the intercept that center = 1 adds (sapca_set_covariates)
 MAX_DESIGN_COLUMNS = 16
 # sapca_column_scaling (sapca_set_column_scaling)
@@ -97,6 +108,7 @@ _TYPED = [
     "sapca_select_rows_csr_device", "sapca_check_csr_device", "sapca_canonicalize_csr_device",
     "sapca_select_submatrix_csr_device", "sapca_knn_device",
     "sapca_tsne_affinities_device", "sapca_tsne_gradient_device", "sapca_tsne_embed_device", "sapca_tsne_device", "sapca_tsne",
+    "sapca_kmeans_seed_device", "sapca_kmeans_assign_device", "sapca_kmeans_update_device", "sapca_kmeans_device", "sapca_kmeans",
     "sapca_multi_fit_csr", "sapca_multi_transform_csr", "sapca_multi_fit_transform_csr",
     "sapca_multi_upload_csr", "sapca_multi_transform_resident", "sapca_multi_fit_transform_resident",
 ]
@@ -110,7 +122,7 @@ _PLAIN = [
     "sapca_multi_uses_rccl", "sapca_multi_set_mask",
     "sapca_covariate_basis", "sapca_set_covariates", "sapca_get_covariate_rank",
     "sapca_set_column_scaling", "sapca_get_column_scale",
-    "sapca_tsne_options_default",
+    "sapca_tsne_options_default", "sapca_kmeans_options_default",
 ]
 EXPORTED_SYMBOLS = _PLAIN + [f"{n}_{s}" for n in _TYPED for s in ("f32", "f64")]
 
@@ -224,7 +236,27 @@ def _open(path):
                                                                  C.POINTER(TsneOptions), C.c_void_p, C.POINTER(C.c_double)]
             getattr(lib, f"sapca_tsne_{suf}").argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(TsneOptions),
                                                           C.c_void_p, C.POINTER(C.c_double)]
+    if hasattr(lib, "sapca_kmeans_options_default"):   # (absent from an older build loaded for an A/B run)
+        lib.sapca_kmeans_options_default.argtypes = [C.POINTER(KmeansOptions)]
+        lib.sapca_kmeans_options_default.restype = None
+        panel = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64]   # h, m, d_x, ldx, d
+        for suf in ("f32", "f64"):
+            getattr(lib, f"sapca_kmeans_seed_device_{suf}").argtypes = panel + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+            getattr(lib, f"sapca_kmeans_assign_device_{suf}").argtypes = panel + [
+                C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+            getattr(lib, f"sapca_kmeans_update_device_{suf}").argtypes = panel + [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+            getattr(lib, f"sapca_kmeans_device_{suf}").argtypes = panel + [
+                C.POINTER(KmeansOptions), C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+            getattr(lib, f"sapca_kmeans_{suf}").argtypes = [
+                C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(KmeansOptions), C.c_void_p, C.c_void_p,
+                C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     return lib
+
+
+def default_kmeans_options() -> KmeansOptions:
+    o = KmeansOptions()
+    load().sapca_kmeans_options_default(C.byref(o))
+    return o
 
 
 def default_tsne_options() -> TsneOptions:

@@ -310,6 +310,145 @@ class Session:
             C.c_void_p(Y.data_ptr() if m else None), C.byref(kl)))
         return Y, kl.value
 
+    # ---- k-means (sapca_kmeans_*): seeding, one assignment, one update, the whole run ----
+    @staticmethod
+    def _kmeans_shape(name, X, n_clusters, at_most_rows):
+        """(m, d, ld, torch dtype, suffix) of a device panel and a number of clusters, checked on the host: ValueError."""
+        import torch
+        m, d, ld, dt = _knn_panel(name, X)
+        k = int(n_clusters)
+        if k < 1:
+            raise ValueError(f"n_clusters must be at least 1, got {n_clusters}")
+        if k > L.KMEANS_MAX_CLUSTERS:
+            raise ValueError(f"n_clusters = {k} exceeds the {L.KMEANS_MAX_CLUSTERS} the library supports")
+        if at_most_rows and m and k > m:
+            raise ValueError(f"n_clusters = {k} exceeds the {m} rows of {name}")
+        if d < 1 or d > 1024:
+            raise ValueError(f"{name} has {d} columns; 1 .. 1024 are supported")
+        if not X.is_cuda:   # (last: everything above is checked without a device)
+            raise ValueError(f"{name} must live on the device (a CUDA tensor), got a tensor on {X.device}")
+        return m, d, ld, dt, "f32" if dt == torch.float32 else "f64"
+
+    @staticmethod
+    def _kmeans_centroids(C_, k, d, dt, device):
+        import torch
+        if not (isinstance(C_, torch.Tensor) and C_.dtype == dt and tuple(C_.shape) == (k, d) and C_.device == device):
+            raise ValueError(f"centroids must be a device tensor of shape {(k, d)} and dtype {dt} beside the rows")
+        return C_.contiguous()
+
+    def kmeans_seed(self, X, n_clusters, seed=None):
+        """sapca_kmeans_seed_device_*: (centroids, rows) -- the k-means++ centres of the rows of the device panel X under the
+        uniforms hash_u01(seed, 21, t) (the Session's seed by default): n_clusters x d copies of rows of X, and their int32
+        row numbers."""
+        import torch
+        m, d, ld, dt, suf = self._kmeans_shape("X", X, n_clusters, True)
+        k = int(n_clusters)
+        cen = torch.empty((k, d), dtype=dt, device=X.device)
+        rows = torch.empty((k,), dtype=torch.int32, device=X.device)
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_kmeans_seed_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_void_p(X.data_ptr() if m else None), C.c_uint64(ld), C.c_uint64(d), C.c_uint32(k),
+            C.c_uint32(int(self._seed if seed is None else seed)), C.c_void_p(cen.data_ptr()), C.c_void_p(rows.data_ptr())))
+        return cen, rows
+
+    def kmeans_assign(self, X, centroids):
+        """sapca_kmeans_assign_device_* (also the out-of-sample predict): (labels, dist2, inertia, n_ambiguous) -- for every row
+        of the device panel X the nearest of the centroids (k x d device tensor), ties to the lower index, as an int32 device
+        tensor; its squared distance (the direct formula in f64, rounded once); their f64 sum; and the number of rows the
+        matrix-core ranking left to the f64 pass."""
+        import torch
+        if not isinstance(centroids, torch.Tensor) or centroids.dim() != 2:
+            raise ValueError("centroids must be a two-dimensional device tensor")
+        m, d, ld, dt, suf = self._kmeans_shape("X", X, centroids.shape[0], False)
+        k = int(centroids.shape[0])
+        cen = self._kmeans_centroids(centroids, k, d, dt, X.device)
+        labels = torch.empty((m,), dtype=torch.int32, device=X.device)
+        dist2 = torch.empty((m,), dtype=dt, device=X.device)
+        inertia, namb = C.c_double(), C.c_uint64()
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_kmeans_assign_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_void_p(X.data_ptr() if m else None), C.c_uint64(ld), C.c_uint64(d), C.c_uint32(k),
+            C.c_void_p(cen.data_ptr()), C.c_void_p(labels.data_ptr() if m else None), C.c_void_p(dist2.data_ptr() if m else None),
+            C.byref(inertia), C.byref(namb)))
+        return labels, dist2, inertia.value, namb.value
+
+    def kmeans_update(self, X, labels, centroids):
+        """sapca_kmeans_update_device_*: (centroids, counts) -- the means of the rows of X under `labels` (int32 device tensor;
+        a label outside [0, k) belongs to no cluster), summed and divided in f64 and rounded once; a cluster without rows keeps
+        its row of `centroids` (k x d device tensor, not modified: a copy is updated).  counts: int64 device tensor."""
+        import torch
+        if not isinstance(centroids, torch.Tensor) or centroids.dim() != 2:
+            raise ValueError("centroids must be a two-dimensional device tensor")
+        m, d, ld, dt, suf = self._kmeans_shape("X", X, centroids.shape[0], False)
+        k = int(centroids.shape[0])
+        if not (isinstance(labels, torch.Tensor) and labels.dtype == torch.int32 and tuple(labels.shape) == (m,)
+                and labels.is_contiguous() and labels.device == X.device):
+            raise ValueError(f"labels must be a contiguous int32 device tensor of {m} entries beside the rows")
+        cen = self._kmeans_centroids(centroids, k, d, dt, X.device).clone()
+        counts = torch.zeros((k,), dtype=torch.int64, device=X.device)
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_kmeans_update_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_void_p(X.data_ptr() if m else None), C.c_uint64(ld), C.c_uint64(d), C.c_uint32(k),
+            C.c_void_p(labels.data_ptr() if m else None), C.c_void_p(cen.data_ptr()), C.c_void_p(counts.data_ptr())))
+        return cen, counts
+
+    def kmeans(self, X, n_clusters=8, init="k-means++", max_iter=300, tol=1e-4, seed=None):
+        """sapca_kmeans_device_* / sapca_kmeans_*: (labels, centroids, inertia, n_iter) -- Lloyd's k-means of the rows of X
+        (include/sapca.h states the algorithm; scikit-learn's rule, n_iter included, except that an empty cluster keeps its
+        centroid).  X: an m x d torch device tensor of float32 / float64 with contiguous rows (a column slice of the scores is
+        clustered in place; labels and centroids are device tensors), or a numpy array (the host route; numpy arrays back).
+        init: "k-means++" (seeded by `seed`, the Session's by default) or an n_clusters x d array of centroids (a numpy
+        array, or beside device rows a device tensor).  The same bytes from call to call."""
+        o = L.default_kmeans_options()
+        o.random_seed = int(self._seed if seed is None else seed)
+        k = int(n_clusters)
+        given = not isinstance(init, str)
+        if not given and init != "k-means++":
+            raise ValueError(f"unknown init {init!r}: 'k-means++' or an array of centroids")
+        if int(max_iter) < 0:
+            raise ValueError(f"max_iter must not be negative, got {max_iter}")
+        if not (float(tol) >= 0.0 and np.isfinite(float(tol))):
+            raise ValueError(f"tol must be finite and not negative, got {tol}")
+        o.init, o.max_iter, o.tol = (L.KMEANS_GIVEN if given else L.KMEANS_PLUSPLUS), int(max_iter), float(tol)
+        inertia, n_iter = C.c_double(), C.c_uint64()
+        if isinstance(X, np.ndarray):
+            if X.ndim != 2 or X.dtype not in _SUF:
+                raise ValueError(f"X must be a two-dimensional float32 / float64 array, got {X.dtype} {X.shape}")
+            X = np.ascontiguousarray(X)
+            m, d = X.shape
+            if k < 1 or k > L.KMEANS_MAX_CLUSTERS or (m and k > m):
+                raise ValueError(f"n_clusters = {n_clusters} must lie in 1 .. min({L.KMEANS_MAX_CLUSTERS}, the {m} rows)")
+            if d < 1 or d > 1024:
+                raise ValueError(f"X has {d} columns; 1 .. 1024 are supported")
+            o.n_clusters = k
+            cen = np.zeros((k, d), dtype=X.dtype)
+            if given:
+                init = np.asarray(init)
+                if init.shape != (k, d):
+                    raise ValueError(f"init must have shape {(k, d)}, got {init.shape}")
+                cen[...] = init
+            labels = np.zeros((m,), dtype=np.int32)
+            suf, ct = _SUF[X.dtype]
+            L.check(self._h, getattr(L.load(), f"sapca_kmeans_{suf}")(
+                self._h, C.c_uint64(m), C.c_uint64(d), X.ctypes.data_as(C.c_void_p), C.byref(o), cen.ctypes.data_as(C.c_void_p),
+                labels.ctypes.data_as(C.c_void_p), C.byref(inertia), C.byref(n_iter)))
+            return labels, cen, inertia.value, n_iter.value
+        import torch
+        m, d, ld, dt, suf = self._kmeans_shape("X", X, k, True)
+        o.n_clusters = k
+        if given and not isinstance(init, torch.Tensor):   # a host array of centroids beside device rows: uploaded
+            init = np.asarray(init)
+            if init.shape != (k, d):
+                raise ValueError(f"init must have shape {(k, d)}, got {init.shape}")
+            init = torch.as_tensor(init, device=X.device).to(dt)
+        cen = self._kmeans_centroids(init, k, d, dt, X.device).clone() if given else torch.empty((k, d), dtype=dt, device=X.device)
+        labels = torch.empty((m,), dtype=torch.int32, device=X.device)
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_kmeans_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_void_p(X.data_ptr() if m else None), C.c_uint64(ld), C.c_uint64(d), C.byref(o),
+            C.c_void_p(cen.data_ptr()), C.c_void_p(labels.data_ptr() if m else None), C.byref(inertia), C.byref(n_iter)))
+        return labels, cen, inertia.value, n_iter.value
+
 
 ROW, COLUMN = 0, 1   # Direction of the reference's Normalize / statistics traits (src/utils.rs)
 

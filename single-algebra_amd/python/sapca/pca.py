@@ -572,3 +572,47 @@ class TSNE:
     def fit(self, X, init=None):
         self.fit_transform(X, init)
         return self
+
+
+class KMeans:
+    """K-means clustering of dense rows on the GPU (sapca_kmeans_*): Lloyd's iteration under scikit-learn's stopping rule with
+    k-means++ seeding, deterministic under `seed`; a cluster that loses all its rows keeps its centroid.
+
+        km = sapca.KMeans(n_clusters=12).fit(scores)       # a torch device tensor (clustered in place), or a numpy array
+        km.labels_, km.cluster_centers_, km.inertia_, km.n_iter_
+        km.predict(other_scores)
+
+    `scores` is usually what SparsePCA.fit_transform left on the device.  init: "k-means++" or an n_clusters x d array of
+    centroids.  One run per fit: callers who want scikit-learn's n_init loop over seeds and keep the least inertia_."""
+
+    def __init__(self, n_clusters=8, init="k-means++", max_iter=300, tol=1e-4, seed=42):
+        self.n_clusters, self.init, self.max_iter, self.tol, self.seed = int(n_clusters), init, int(max_iter), float(tol), int(seed)
+        self.labels_ = self.cluster_centers_ = self.inertia_ = self.n_iter_ = None
+        self._session = None
+
+    def _ops(self):
+        from .ops import Session
+        if self._session is None:
+            self._session = Session(seed=self.seed)
+        return self._session
+
+    def fit(self, X):
+        self.labels_, self.cluster_centers_, self.inertia_, self.n_iter_ = self._ops().kmeans(
+            X, n_clusters=self.n_clusters, init=self.init, max_iter=self.max_iter, tol=self.tol, seed=self.seed)
+        return self
+
+    def fit_predict(self, X):
+        return self.fit(X).labels_
+
+    def predict(self, X):
+        """the nearest of cluster_centers_ for every row of X: a device tensor (labels on the device), or a numpy array (labels
+        as a numpy array)"""
+        if self.cluster_centers_ is None:
+            raise RuntimeError("KMeans.predict: fit first")
+        import torch
+        ops = self._ops()
+        host = isinstance(X, np.ndarray)
+        Xd = torch.as_tensor(np.ascontiguousarray(X), device=ops._device()) if host else X
+        cen = torch.as_tensor(self.cluster_centers_, device=Xd.device).to(Xd.dtype)
+        labels = ops.kmeans_assign(Xd, cen)[0]
+        return labels.cpu().numpy() if host else labels

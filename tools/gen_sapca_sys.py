@@ -20,7 +20,8 @@ SCALARS = {
     "uint8_t": "u8", "int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64",
     "sapca_status": "c_int", "sapca_handle": "sapca_handle", "sapca_multi": "sapca_multi",
     "sapca_options": "sapca_options", "sapca_timings": "sapca_timings", "sapca_csr_report": "sapca_csr_report",
-    "sapca_tsne_options": "sapca_tsne_options", "sapca_allreduce_fn": "sapca_allreduce_fn",
+    "sapca_tsne_options": "sapca_tsne_options", "sapca_kmeans_options": "sapca_kmeans_options",
+    "sapca_allreduce_fn": "sapca_allreduce_fn",
 }
 
 
@@ -133,7 +134,7 @@ def render(header_text):
     w("pub type sapca_allreduce_fn = Option<unsafe extern \"C\" fn(*mut c_void, *mut c_void, u64, i32, *mut c_void) -> c_int>;")
     for name, value in re.findall(r"^#define\s+(SAPCA_CSR_\w+)\s+(\d+)u\b", header_text, flags=re.M):
         w("pub const %s: u32 = %s;" % (name, value))
-    for struct in ("sapca_options", "sapca_timings", "sapca_csr_report", "sapca_tsne_options"):
+    for struct in ("sapca_options", "sapca_timings", "sapca_csr_report", "sapca_tsne_options", "sapca_kmeans_options"):
         w("")
         w("#[repr(C)]")
         w("#[derive(Clone, Copy)]")
