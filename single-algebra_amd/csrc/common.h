@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/sapca.h"
@@ -168,43 +169,57 @@ struct Stream {
   bool owned = false;
 };
 
-// HIP-event stopwatch on a stream; a no-op unless enabled.
+// HIP-event stopwatch on a stream; a no-op unless enabled.  A span is two events of the pool; a span that opens where the
+// one before it closed (start_behind_last) shares that event instead of recording a second one right behind it.
 struct EventTimer {
   bool enabled = false;
   hipStream_t s = nullptr;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
+  std::vector<hipEvent_t> pool;
   size_t used = 0;
-  struct Span { size_t i; };
+  std::vector<std::pair<int, int>> spans;   // (opening, closing) event of the pool; closing -1: still open
+  int last_closed = -1;                     // the span whose closing event was the last one recorded
   void begin_collect(hipStream_t st, bool on) {
     enabled = on;
     s = st;
     used = 0;
+    spans.clear();
+    last_closed = -1;
+  }
+  int record() {
+    if (used == pool.size()) {
+      hipEvent_t e;
+      SAPCA_HIP(hipEventCreate(&e));
+      pool.push_back(e);
+    }
+    SAPCA_HIP(hipEventRecord(pool[used], s));
+    return (int)used++;
   }
   int start() {
     if (!enabled) return -1;
-    if (used == pool.size()) {
-      hipEvent_t a, b;
-      SAPCA_HIP(hipEventCreate(&a));
-      SAPCA_HIP(hipEventCreate(&b));
-      pool.emplace_back(a, b);
-    }
-    SAPCA_HIP(hipEventRecord(pool[used].first, s));
-    return (int)used++;
+    spans.emplace_back(record(), -1);
+    return (int)spans.size() - 1;
+  }
+  // The caller states that nothing was queued on the stream since the last span closed: that span's closing event opens
+  // this one (the same point of the stream).  No span closed yet: an event of its own.
+  int start_behind_last() {
+    if (!enabled) return -1;
+    if (last_closed < 0) return start();
+    spans.emplace_back(spans[(size_t)last_closed].second, -1);
+    return (int)spans.size() - 1;
   }
   void stop(int i) {
-    if (i >= 0) SAPCA_HIP(hipEventRecord(pool[i].second, s));
+    if (i < 0) return;
+    spans[(size_t)i].second = record();
+    last_closed = i;
   }
   double ms(int i) {
-    if (i < 0) return 0.0;
+    if (i < 0 || spans[(size_t)i].second < 0) return 0.0;
     float t = 0;
-    SAPCA_HIP(hipEventElapsedTime(&t, pool[i].first, pool[i].second));
+    SAPCA_HIP(hipEventElapsedTime(&t, pool[(size_t)spans[(size_t)i].first], pool[(size_t)spans[(size_t)i].second]));
     return t;
   }
   ~EventTimer() {
-    for (auto& p : pool) {
-      (void)hipEventDestroy(p.first);
-      (void)hipEventDestroy(p.second);
-    }
+    for (hipEvent_t e : pool) (void)hipEventDestroy(e);
   }
 };
 

@@ -231,25 +231,77 @@ __device__ __forceinline__ void gramv_wave(T* P, int64_t rows, int ld, double* _
 #pragma unroll
       for (int hh = 0; hh < NH; ++hh) Four<T>::load(src.sv + 64 * hh + 4 * c, &sv[4 * hh]);
     }
+    // A wave runs only a few chunks (2048 waves share a panel's rows), so what it waits for is the slabs of ONE chunk: U of
+    // them are loaded into registers of their own before the first is added (a round trip per U slabs, not per slab), and
+    // the head of the next chunk -- slab 0, the first U further slabs, mu and the weight -- is in flight while this chunk's
+    // MFMAs run.  The adds keep their order: slab 1 .. nsplit - 1 onto slab 0, then - mu sv.
+    constexpr int U = NT * sizeof(T) <= 16 ? 4 : NT * sizeof(T) <= 32 ? 2 : 1;   // (64 bytes of slabs per lane at a time: registers)
+    const int nsplit = src.nsplit;
+    const int64_t ss = src.slab_stride;
+    auto load_slab = [&](const T* p, int sp, T (&y)[NT]) {
+#pragma unroll
+      for (int hh = 0; hh < NH; ++hh) Four<T>::load(p + sp * ss + 64 * hh, &y[4 * hh]);
+    };
+    T hx[NT], hy[U][NT], hm = (T)0;
+    double hw = 0;
+    auto head = [&](int64_t r) {
+      if (r < rows) {
+        const T* p = src.parts + r * ld + 4 * c;
+        load_slab(p, 0, hx);
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+          if (1 + u < nsplit) load_slab(p, 1 + u, hy[u]);
+        if (src.mu) hm = src.mu[r];
+        hw = wgt ? (double)wgt[r] : 1.0;
+      }
+    };
+    head(r0 + g);
     for (; r0 < rows; r0 += stride) {
       const int64_t r = r0 + g;
+      const bool live = r < rows;
       T x[NT];
 #pragma unroll
       for (int t = 0; t < NT; ++t) x[t] = (T)0;
       double wr = 0;
-      if (r < rows) {
+      T m = (T)0;
+      if (live) {
         const T* p = src.parts + r * ld + 4 * c;
 #pragma unroll
-        for (int hh = 0; hh < NH; ++hh) Four<T>::load(p + 64 * hh, &x[4 * hh]);
-        for (int sp = 1; sp < src.nsplit; ++sp) {
-          T y[NT];
+        for (int t = 0; t < NT; ++t) x[t] = hx[t];
 #pragma unroll
-          for (int hh = 0; hh < NH; ++hh) Four<T>::load(p + sp * src.slab_stride + 64 * hh, &y[4 * hh]);
+        for (int u = 0; u < U; ++u)
+          if (1 + u < nsplit) {
 #pragma unroll
-          for (int t = 0; t < NT; ++t) x[t] += y[t];
+            for (int t = 0; t < NT; ++t) x[t] += hy[u][t];
+          }
+        m = hm;
+        wr = hw;
+        int sp = 1 + U;
+        for (; sp + U <= nsplit; sp += U) {
+          T y[U][NT];
+#pragma unroll
+          for (int u = 0; u < U; ++u) load_slab(p, sp + u, y[u]);
+#pragma unroll
+          for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) x[t] += y[u][t];
         }
+        if constexpr (U > 1) if (sp < nsplit) {   // the remainder: up to U - 1 slabs, loaded together as well
+          T y[U > 1 ? U - 1 : 1][NT];
+#pragma unroll
+          for (int u = 0; u < U - 1; ++u)
+            if (sp + u < nsplit) load_slab(p, sp + u, y[u]);
+#pragma unroll
+          for (int u = 0; u < U - 1; ++u)
+            if (sp + u < nsplit) {
+#pragma unroll
+              for (int t = 0; t < NT; ++t) x[t] += y[u][t];
+            }
+        }
+      }
+      head(r0 + stride + g);   // (another row: in place, too, it is not the one stored below)
+      if (live) {
         if (src.mu) {
-          const T m = src.mu[r];
 #pragma unroll
           for (int t = 0; t < NT; ++t) x[t] -= m * sv[t];
         }
@@ -257,7 +309,6 @@ __device__ __forceinline__ void gramv_wave(T* P, int64_t rows, int ld, double* _
 #pragma unroll
           for (int hh = 0; hh < NH; ++hh) Four<T>::store(P + r * ld + 64 * hh + 4 * c, &x[4 * hh]);
         }
-        wr = wgt ? (double)wgt[r] : 1.0;
       }
       mma(x, wr);
     }
@@ -333,7 +384,7 @@ __device__ __forceinline__ void gramv_wave(T* P, int64_t rows, int ld, double* _
 }
 
 template <typename T, int NT, bool SRC>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256, 2)   // (two workgroups per CU: 256 registers a lane, accumulators included)
 gramv_kernel(T* P, int64_t rows, int ld, double* __restrict__ slabs, PanelSource<T> src, const T* __restrict__ wgt, int want_sum) {
   constexpr int NPAIR = NT * (NT + 1) / 2;
   extern __shared__ double lds[];   // NT <= 6: NPAIR * 256 + 16 NT doubles
@@ -389,8 +440,18 @@ gram_reduce_kernel(const double* __restrict__ slabs, int nslabs, int nt, int ld,
   const int e = threadIdx.x & 15, grp = threadIdx.x >> 4;
   const int i = blockIdx.x * 16 + e;
   double sum = 0;
-  if (i < slab_len)
-    for (int b = grp; b < nslabs; b += 16) sum += slabs[(int64_t)b * slab_len + i];
+  if (i < slab_len) {
+    // eight of the group's slabs are loaded before the first is added: a round trip per eight slabs, the order of the adds kept
+    int b = grp;
+    for (; b + 16 * 7 < nslabs; b += 16 * 8) {
+      double v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = slabs[(int64_t)(b + 16 * u) * slab_len + i];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) sum += v[u];
+    }
+    for (; b < nslabs; b += 16) sum += slabs[(int64_t)b * slab_len + i];
+  }
   part[grp][e] = sum;
   __syncthreads();
   if (grp != 0 || i >= slab_len) return;
@@ -871,7 +932,21 @@ panel_gemm_kernel(const T* P, int64_t rows, int ld, const double* __restrict__ M
   //  diagonal are skipped: output tile tb stands upper - 1 tiles to the right of K tile 0's diagonal block.  10 of 16
   //  block products at 64 columns, 36 of 64 at 128, where this kernel is bound by the f64 MFMA rate)
   extern __shared__ double Ms[];  // ld x ldo
-  for (int i = threadIdx.x; i < ld * ldo; i += blockDim.x) Ms[i] = M[(i / ldo) * ldm_stride + (i % ldo)];
+  {
+    // eight loads of the factor in flight per thread (two round trips at 64 columns, not sixteen), no division where M is dense
+    const int nel = ld * ldo, step = blockDim.x;
+    const bool dense = ldm_stride == ldo;
+    auto at = [&](int i) { return dense ? i : (i / ldo) * ldm_stride + (i % ldo); };
+    int i = threadIdx.x;
+    for (; i + 7 * step < nel; i += 8 * step) {
+      double v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = M[at(i + u * step)];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) Ms[i + u * step] = v[u];
+    }
+    for (; i < nel; i += step) Ms[i] = M[at(i)];
+  }
   __syncthreads();
   const int lane = threadIdx.x & (WAVE - 1);
   const int wave = threadIdx.x / WAVE;
@@ -1333,7 +1408,10 @@ void launch_panel_gemm(const T* P, int64_t rows, int ld, const double* M, int ld
   if constexpr (NTO == 4) {
     // the 64-column panels of the headline configurations: eight waves per workgroup under a 128-register bound (the
     // 256-thread build takes 228 VGPRs: two waves per SIMD, and the kernel waits on one tile's round trip after another)
-    if (ntiles >= 4096) {
+    // From 1024 tiles on (below, a grid of eight-tile workgroups covers less than half of the CUs).  The n-side panel of the
+    // headline (1250 tiles) takes 8 us here against 17 us on the 256-thread build; the m-side one (12500 tiles) is no
+    // faster with 512 workgroups that loop longer than with these 1024.
+    if (ntiles >= 1024) {
       static LdsAttrState attr8;
       if (lds > 48 * 1024) ensure_dynamic_lds(reinterpret_cast<const void*>(&panel_gemm_kernel<T, NTO, 512>), lds, attr8);
       int blocks = (int)((ntiles + 7) / 8);

@@ -48,7 +48,10 @@ enum Cat { C_PREPARE, C_STATS, C_SPMM, C_SPMMT, C_ORTHO, C_SMALL, C_LANCZOS, C_T
 struct Scope {
   sapca_handle_s& h;
   int ev;
-  Scope(sapca_handle_s& h_, int cat) : h(h_), ev(h_.timer.start()) {
+  // behind_last: the caller has queued nothing on the stream since the Scope before this one closed -- the two share that
+  // point of the stream, and one event (two records back to back leave the GPU idle for about 10 us between the kernels
+  // either side of them; a fit step has two such boundaries per sweep)
+  Scope(sapca_handle_s& h_, int cat, bool behind_last = false) : h(h_), ev(behind_last ? h_.timer.start_behind_last() : h_.timer.start()) {
     if (ev >= 0) h.spans.emplace_back(cat, ev);
   }
   ~Scope() {
@@ -642,7 +645,7 @@ void Engine<T>::normalize(H& h, T* P, int64_t rows, int l, int ld, int normalize
     if (x.vec_out) k::weighted_colsum(P, rows, ld, x.w, x.vec_out, h.scratch2, s);
     return;
   }
-  Scope sc(h, C_ORTHO);
+  Scope sc(h, C_ORTHO, x.behind_sweep);
   const SmallLayout lay(h.small, ld);
   double *G = lay.gram(), *wsum = x.vec_out ? lay.wsum() : nullptr;
   // QR -> CholeskyQR2 (orthonormal to working precision); LU -> one pass: a well-conditioned
@@ -851,16 +854,20 @@ void load_omega(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
 // Y = Ac X   (R8).  The centring vectors -- c = X^T mu here, the column sums 1^T Y of the A^T sweep -- belong to a panel that
 // has just been normalised: normalize() delivers them from sums gathered in its Gram pass (vec_out), so no kernel re-reads
 // the normalised panel for them; only the very first c (of Omega) is summed here.
+// behind_normalize: the Scope of X's normalisation was the last thing on the stream (timings: see Scope).
 template <typename T>
-void sweep_a(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
+void sweep_a(H& h, const RandomizedPlan& p, FitPanels<T>& f, bool behind_normalize) {
   hipStream_t s = h.stream;
   if (p.scale) {   // X <- D X (a normalised X brought c = X^T (D mu) along: the same vector)
-    Scope sc(h, C_ORTHO);
+    Scope sc(h, C_ORTHO, behind_normalize);
     k::scale_panel_rows(f.X, p.n_used, p.ld, f.d, s);
   }
-  if (p.center && !f.cvec_current) k::weighted_colsum(f.X, p.n_used, p.ld, f.mu, f.cvec, h.scratch2, s);
+  if (p.center && !f.cvec_current) {
+    k::weighted_colsum(f.X, p.n_used, p.ld, f.mu, f.cvec, h.scratch2, s);
+    behind_normalize = false;
+  }
   f.cvec_current = false;
-  Scope sc(h, C_SPMM);
+  Scope sc(h, C_SPMM, behind_normalize);
   k::spmm(Engine<T>::view(h.a_used), &h.tiled_a, f.X, p.ld, f.Y, p.ld, p.ld, p.center ? f.cvec : nullptr, p.variant, h.split_scratch, s);
 }
 
@@ -922,11 +929,11 @@ void covar_project(H& h, const RandomizedPlan& p, FitPanels<T>& f, bool behind_a
 // next pass over X -- the Gram of its normalisation, or of the small SVD -- still has to apply (slabs of a sweep whose tile
 // range was split over workgroups, the centring term mu (1^T Y)^T; the normaliser of Y delivered 1^T Y into f.sv).
 template <typename T>
-void sweep_at_one_piece(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
+void sweep_at_one_piece(H& h, const RandomizedPlan& p, FitPanels<T>& f, bool behind_normalize) {
   hipStream_t s = h.stream;
   f.src = k::PanelSource<T>();
   {
-    Scope sc(h, C_SPMMT);
+    Scope sc(h, C_SPMMT, behind_normalize);
     // (one rank: the slabs may stay unsummed; several: the collective needs the sum)
     k::spmm(Engine<T>::view(h.at_used), &h.tiled_at, f.Y, p.ld, f.X, p.ld, p.ld, (const T*)nullptr, p.variant, h.split_scratch, s,
             h.comm.active() || p.cov ? nullptr : &f.src);
@@ -963,9 +970,10 @@ void sweep_at_two_pieces(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
   }
 }
 
+// behind_normalize: the Scope of Y's normalisation was the last thing on the stream (timings: see Scope).
 template <typename T>
-void sweep_at(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
-  p.at.sweep == AtSweep::TwoPieces ? sweep_at_two_pieces(h, p, f) : sweep_at_one_piece(h, p, f);
+void sweep_at(H& h, const RandomizedPlan& p, FitPanels<T>& f, bool behind_normalize) {
+  p.at.sweep == AtSweep::TwoPieces ? sweep_at_two_pieces(h, p, f) : sweep_at_one_piece(h, p, f, behind_normalize);
   if (p.scale) {   // Z = D (sum of slabs - mu sv^T), behind the all-reduce: the panel is plain from here on
     Scope sc(h, C_ORTHO);
     k::finish_scaled_panel(f.X, p.n_used, p.ld, f.src, f.d, h.stream);
@@ -980,19 +988,25 @@ template <typename T>
 void power_iterations(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
   using Extras = NormalizeExtras<T>;
   T* const sv_out = p.center ? f.sv : nullptr;
+  // Timings: sweep -> normalise -> sweep, each Scope opening at the event that closed the one before wherever nothing is
+  // queued between the two.  (A normaliser of NONE opens no Scope; covariates, column scaling and collectives queue work of
+  // their own behind a sweep.)
+  const bool y_behind = !p.cov, x_behind = !p.cov && !p.scale && !h.comm.active() && p.at.sweep != AtSweep::TwoPieces;
+  const bool normalises = p.norm != SAPCA_NORM_NONE;
   for (int it = 0; it < p.q; ++it) {
-    sweep_a(h, p, f);
+    sweep_a(h, p, f, it > 0 && normalises);
     if (p.cov) covar_project(h, p, f, false);
-    Engine<T>::normalize(h, f.Y, p.m, p.l, p.ld, p.norm, true, Extras{.passes = 1, .vec_out = sv_out});
-    sweep_at(h, p, f);
+    Engine<T>::normalize(h, f.Y, p.m, p.l, p.ld, p.norm, true, Extras{.passes = 1, .vec_out = sv_out, .behind_sweep = y_behind});
+    sweep_at(h, p, f, normalises);
     Engine<T>::normalize(h, f.X, p.n_used, p.l, p.ld, p.norm, false,
-                         Extras{.passes = 1, .src = &f.src, .w = p.scale ? f.dmu : f.mu, .vec_out = p.center ? f.cvec : nullptr});
+                         Extras{.passes = 1, .src = &f.src, .w = p.scale ? f.dmu : f.mu, .vec_out = p.center ? f.cvec : nullptr,
+                                .behind_sweep = x_behind});
     f.cvec_current = p.center;
   }
-  sweep_a(h, p, f);
+  sweep_a(h, p, f, p.q > 0 && normalises);
   if (p.cov) covar_project(h, p, f, false);
-  Engine<T>::normalize(h, f.Y, p.m, p.l, p.ld, SAPCA_NORM_QR, true, Extras{.vec_out = sv_out});   // Q = qr(Y): always orthonormal
-  sweep_at(h, p, f);
+  Engine<T>::normalize(h, f.Y, p.m, p.l, p.ld, SAPCA_NORM_QR, true, Extras{.vec_out = sv_out, .behind_sweep = y_behind});   // Q = qr(Y): always orthonormal
+  sweep_at(h, p, f, true);
 }
 
 // vt = (B^T M)^T with the sign convention of svd_flip (R13): the components, from the un-rotated panel X = B^T (panel_x,

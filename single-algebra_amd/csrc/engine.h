@@ -266,6 +266,7 @@ struct NormalizeExtras {
   const k::PanelSource<T>* src = nullptr;    // the panel is still as its producer left it: the first Gram applies the rest
   const T* w = nullptr;                      // weights of vec_out (null: ones)
   T* vec_out = nullptr;                      // receives sum_r w[r] Q[r][:] of the normalised panel
+  bool behind_sweep = false;                 // timings: nothing was queued since the sweep's Scope closed (Scope, behind_last)
 };
 
 template <typename T>
