@@ -308,7 +308,11 @@ sapca_status sapca_fit_transform_csr_device_to_host_f64(sapca_handle h, uint64_t
 /* Fitted state.  The reference keeps components_/explained_variance_/mean_ private
  * (sparse/mod.rs:41-43); a Rust wrapper needs them to populate those fields.
  * dims: k = n_components, n_used = columns seen by the SVD (n, or n' under a mask),
- * n_cols = columns of the fitted matrix (length of mean_).                                    */
+ * n_cols = columns of the fitted matrix (length of mean_).
+ * mean_ and the total variance come from f64 column sums of a and a^2.  The sums of a Lanczos fit on the scatter route
+ * (n_used <= m, m >= 4096, n_used doubles fit LDS: csrc/scatter.hip) are fixed-point: exact to rows * max|a| * 2^-61 per stored
+ * entry (rows * max|a|^2 * 2^-61 for the squares), max|a| taken over the whole matrix.  That is absolute, not relative to the
+ * column: a column whose values are many orders of magnitude below max|a| keeps fewer digits than a floating-point sum would.  */
 sapca_status sapca_get_dims(sapca_handle h, uint64_t* k, uint64_t* n_used, uint64_t* n_cols);
 sapca_status sapca_get_components_f32(sapca_handle h, float* out, size_t cap);            /* k x n_used   sparse/mod.rs:208 */
 sapca_status sapca_get_components_f64(sapca_handle h, double* out, size_t cap);

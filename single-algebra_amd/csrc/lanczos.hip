@@ -124,7 +124,12 @@ spmv_ldsx_kernel(const int64_t* __restrict__ ptr, const I* __restrict__ idx, con
 // rows (rpw per wave) slice by slice.  The column indices of a CSR row ascend, so the entries of a slice are a
 // contiguous run; the run limits of all (row, slice) pairs of a wave are found up front, one binary search per
 // lane, and handed out with shuffles.
+// Rows whose columns do NOT ascend (include/sapca.h: wrong numbers, not stray accesses): the searches still end inside the row,
+// so every entry read is the row's own, but a run can then hold a column of another slice, and k - c0 would index LDS below
+// xs or past the slice that was staged.  slice_x() therefore checks the position against the staged length; an entry outside
+// contributes nothing.  On sorted rows every position passes and the sums are what they were.
 constexpr int SLICE_WAVES = 16, SLICE_MAX_RPW = 8;
+__device__ inline double slice_x(const double* xs, int pos, int nc) { return (unsigned)pos < (unsigned)nc ? xs[pos] : 0.0; }
 template <typename T>
 __global__ void __launch_bounds__(SLICE_WAVES * WAVE)
 spmv_sliced_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx, const T* __restrict__ val, int64_t rows,
@@ -153,6 +158,7 @@ spmv_sliced_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ 
   for (int j = 0; j < SLICE_MAX_RPW; ++j) acc[j] = 0;
   for (int t = 0; t < nslices; ++t) {
     const int64_t c0 = (int64_t)t * slice, c1 = min(cols, c0 + (int64_t)slice);
+    const int nc = (int)(c1 - c0), b0 = (int)c0;
     __syncthreads();   // the previous slice's readers are done
     for (int64_t i = threadIdx.x; i < c1 - c0; i += blockDim.x) xs[i] = x[c0 + i];
     __syncthreads();
@@ -167,12 +173,12 @@ spmv_sliced_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ 
           const int k2 = __builtin_nontemporal_load(idx + e + 2 * WAVE), k3 = __builtin_nontemporal_load(idx + e + 3 * WAVE);
           const T v0 = __builtin_nontemporal_load(val + e), v1 = __builtin_nontemporal_load(val + e + WAVE);
           const T v2 = __builtin_nontemporal_load(val + e + 2 * WAVE), v3 = __builtin_nontemporal_load(val + e + 3 * WAVE);
-          a0 = fma((double)v0, xs[k0 - c0], a0);
-          a1 = fma((double)v1, xs[k1 - c0], a1);
-          a2 = fma((double)v2, xs[k2 - c0], a2);
-          a3 = fma((double)v3, xs[k3 - c0], a3);
+          a0 = fma((double)v0, slice_x(xs, k0 - b0, nc), a0);
+          a1 = fma((double)v1, slice_x(xs, k1 - b0, nc), a1);
+          a2 = fma((double)v2, slice_x(xs, k2 - b0, nc), a2);
+          a3 = fma((double)v3, slice_x(xs, k3 - b0, nc), a3);
         }
-        for (; e < e1; e += WAVE) a0 = fma((double)val[e], xs[idx[e] - c0], a0);
+        for (; e < e1; e += WAVE) a0 = fma((double)val[e], slice_x(xs, idx[e] - b0, nc), a0);
         acc[j] += (a0 + a1) + (a2 + a3);
       }
     }
@@ -192,6 +198,9 @@ spmv_sliced_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ 
 // second kernel adds them in slice order.  Lane j of a wave holds the run limits of the wave's j-th row.
 // REL16: the entry stream reads `rel` = column mod slice as 2-byte values (the position inside the staged slice) instead of
 // the 4-byte columns; the run limits are still searched in `idx`.
+// Unsorted rows: REL16 positions are column mod slice, below the `slice` doubles of LDS the launch asks for whatever the row
+// looks like (in the last, shorter slice such a position can read a stale element: a wrong number); the 4-byte columns
+// go through slice_x() as above.
 template <typename T, bool REL16>
 __global__ void __launch_bounds__(SLICE_WAVES * WAVE)
 spmv_slice_grid_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx, const uint16_t* __restrict__ rel,
@@ -202,6 +211,7 @@ spmv_slice_grid_kernel(const int64_t* __restrict__ ptr, const int32_t* __restric
   const int t = blockIdx.x % nslices;
   const int64_t g0 = (int64_t)(blockIdx.x / nslices) * rows_per_group;
   const int64_t c0 = (int64_t)t * slice, c1 = min(cols, c0 + (int64_t)slice);
+  const int nc = (int)(c1 - c0);
   // rows g0 + wave, g0 + wave + 16, ...: lane j searches the limits of the j-th of them (<= 64 rows per wave)
   int64_t e0l = 0, e1l = 0;
   {
@@ -242,12 +252,12 @@ spmv_slice_grid_kernel(const int64_t* __restrict__ ptr, const int32_t* __restric
       }
       const T v0 = __builtin_nontemporal_load(val + e), v1 = __builtin_nontemporal_load(val + e + WAVE);
       const T v2 = __builtin_nontemporal_load(val + e + 2 * WAVE), v3 = __builtin_nontemporal_load(val + e + 3 * WAVE);
-      a0 = fma((double)v0, xs[k0], a0);
-      a1 = fma((double)v1, xs[k1], a1);
-      a2 = fma((double)v2, xs[k2], a2);
-      a3 = fma((double)v3, xs[k3], a3);
+      a0 = fma((double)v0, REL16 ? xs[k0] : slice_x(xs, k0, nc), a0);
+      a1 = fma((double)v1, REL16 ? xs[k1] : slice_x(xs, k1, nc), a1);
+      a2 = fma((double)v2, REL16 ? xs[k2] : slice_x(xs, k2, nc), a2);
+      a3 = fma((double)v3, REL16 ? xs[k3] : slice_x(xs, k3, nc), a3);
     }
-    for (; e < e1; e += WAVE) a0 = fma((double)val[e], xs[REL16 ? (int)rel[e] : idx[e] - (int)c0], a0);
+    for (; e < e1; e += WAVE) a0 = fma((double)val[e], REL16 ? xs[rel[e]] : slice_x(xs, idx[e] - (int)c0, nc), a0);
     double a = (a0 + a1) + (a2 + a3);
 #pragma unroll
     for (int off = WAVE / 2; off > 0; off >>= 1) a += __shfl_xor(a, off);
@@ -450,10 +460,20 @@ inline unsigned grid1(int64_t n, int block = 256, int64_t cap = 1 << 30) {
 
 // which kernel spmv_launch takes for an operator, and the slice of x its 2-byte index copy is relative to (0: absolute)
 enum SpmvKind { SPMV_ROW = 0, SPMV_LDSX, SPMV_SLICE_GRID, SPMV_SLICED };
+
+// The three route switches of the debug build, read ONCE per fit and handed to the plan, the index narrowing and every launch
+// of that fit: one fit is always consistent (the 2-byte "column mod slice" copy made for the slice-grid kernel can reach no other
+// kernel) and the next fit sees the environment it was given.  A release build has dbg_env() == nullptr: three constant falses.
+struct SpmvSwitches {
+  bool no_lds = false, no_grid = false, idx32 = false;
+  static SpmvSwitches read() {
+    return {dbg_env("SAPCA_SPMV_NO_LDS") != nullptr, dbg_env("SAPCA_SPMV_NO_SLICE_GRID") != nullptr, dbg_env("SAPCA_SPMV_IDX32") != nullptr};
+  }
+};
+
 template <typename T>
-SpmvKind spmv_plan(const CsrView<T>& A, bool has_scratch, int* slice_out = nullptr, int* nslices_out = nullptr) {
-  static const bool no_lds = dbg_env("SAPCA_SPMV_NO_LDS") != nullptr;
-  static const bool no_grid = dbg_env("SAPCA_SPMV_NO_SLICE_GRID") != nullptr;
+SpmvKind spmv_plan(const CsrView<T>& A, bool has_scratch, const SpmvSwitches& sw, int* slice_out = nullptr, int* nslices_out = nullptr) {
+  const bool no_lds = sw.no_lds, no_grid = sw.no_grid;
   const size_t xbytes = (size_t)A.cols * sizeof(double);
   if (A.rows == 0 || no_lds) return SPMV_ROW;
   if (xbytes <= 150 * 1024 && A.rows >= 4096) return SPMV_LDSX;
@@ -477,10 +497,10 @@ __global__ void narrow_idx16_kernel(const int32_t* __restrict__ idx, int64_t cou
 
 // the 2-byte index copy an operator's Lanczos kernel reads (nullptr: that kernel takes the 4-byte columns)
 template <typename T>
-const uint16_t* spmv_narrow_indices(const CsrView<T>& A, bool has_scratch, DevBuf& buf, hipStream_t s) {
-  static const bool off = dbg_env("SAPCA_SPMV_IDX32") != nullptr;
+const uint16_t* spmv_narrow_indices(const CsrView<T>& A, bool has_scratch, const SpmvSwitches& sw, DevBuf& buf, hipStream_t s) {
+  const bool off = sw.idx32;
   int slice = 0, nslices = 0;
-  const SpmvKind kind = spmv_plan(A, has_scratch, &slice, &nslices);
+  const SpmvKind kind = spmv_plan(A, has_scratch, sw, &slice, &nslices);
   if (off || A.nnz == 0 || (kind != SPMV_LDSX && kind != SPMV_SLICE_GRID)) return nullptr;
   if (kind == SPMV_LDSX && A.cols > 65536) return nullptr;
   if (kind == SPMV_SLICE_GRID && slice > 65536) return nullptr;
@@ -492,14 +512,14 @@ const uint16_t* spmv_narrow_indices(const CsrView<T>& A, bool has_scratch, DevBu
 }
 
 template <typename T>
-void spmv_launch(const CsrView<T>& A, const double* x, double* y, hipStream_t s, DevBuf* scratch = nullptr,
+void spmv_launch(const CsrView<T>& A, const double* x, double* y, hipStream_t s, const SpmvSwitches& sw, DevBuf* scratch = nullptr,
                  const uint16_t* idx16 = nullptr, unsigned long long* ymax_bits = nullptr, bool* ymax_done = nullptr,
                  const double* shift = nullptr, const double* rowscale = nullptr) {
   // shift (device scalar, null: none): y[r] -= *shift * rowscale[r] (null rowscale: ones) where the product writes y
   if (ymax_done) *ymax_done = false;   // (only the kernel with x in LDS gathers max |y| on the way)
   if (A.rows == 0) return;
   const size_t xbytes = (size_t)A.cols * sizeof(double);
-  static const bool no_lds = dbg_env("SAPCA_SPMV_NO_LDS") != nullptr;
+  const bool no_lds = sw.no_lds;
   if (!no_lds && xbytes <= 150 * 1024 && A.rows >= 4096) {
     static LdsAttrState attr, attr16;   // one per instantiation of this function template
     if (idx16) {
@@ -517,7 +537,7 @@ void spmv_launch(const CsrView<T>& A, const double* x, double* y, hipStream_t s,
     const int nslices = (int)((A.cols + max_slice - 1) / max_slice);
     const int slice = (int)((A.cols + nslices - 1) / nslices);
     // (slice, row group) grid when the caller lends a buffer for the per-slice partial sums
-    static const bool no_grid = dbg_env("SAPCA_SPMV_NO_SLICE_GRID") != nullptr;
+    const bool no_grid = sw.no_grid;
     if (scratch && !no_grid && nslices > 1) {
       const int64_t groups_one_round = std::max<int64_t>(1, 256 / nslices);
       const int rows_per_group = (int)std::min<int64_t>(SLICE_WAVES * WAVE, (A.rows + groups_one_round - 1) / groups_one_round);
@@ -560,7 +580,7 @@ void spmv_launch(const CsrView<T>& A, const double* x, double* y, hipStream_t s,
 namespace k {
 template <typename T>
 void spmv(const CsrView<T>& A, const double* x, double* y, hipStream_t s) {
-  spmv_launch(A, x, y, s);
+  spmv_launch(A, x, y, s, SpmvSwitches::read());
   SAPCA_HIP(hipGetLastError());
 }
 template void spmv<float>(const CsrView<float>&, const double*, double*, hipStream_t);
@@ -570,6 +590,7 @@ template void spmv<double>(const CsrView<double>&, const double*, double*, hipSt
 template <typename T>
 void lanczos_fit(sapca_handle_s& h, bool centred) {
   hipStream_t s = h.stream;
+  const SpmvSwitches sw = SpmvSwitches::read();   // (once: the plan, the 2-byte indices and every product of this fit agree)
   const CsrView<T> A = Engine<T>::view(h.a_used), At = Engine<T>::view(h.at_used);
   const int64_t m = A.rows, n_used = A.cols;
   const int64_t m_global = (int64_t)h.m_global;
@@ -612,7 +633,7 @@ void lanczos_fit(sapca_handle_s& h, bool centred) {
   if (centred && right_side) d0 = mu;
   if (centred && !right_side) {
     hipLaunchKernelGGL(dot_kernel, dim3(1), dim3(256), 0, s, mu, mu, n_used, dots + 2);
-    spmv_launch(A, mu, g, s, nullptr, nullptr, nullptr, nullptr, dots + 2);   // g = A mu - ||mu||^2 1
+    spmv_launch(A, mu, g, s, sw, nullptr, nullptr, nullptr, nullptr, dots + 2);   // g = A mu - ||mu||^2 1
     d1 = g;
   }
 
@@ -640,25 +661,25 @@ void lanczos_fit(sapca_handle_s& h, bool centred) {
   if (scatter) SAPCA_HIP(hipMemsetAsync(sc + 1, 0, 2 * sizeof(unsigned long long), s));
   int64_t product = 0;
   // 2-byte index copies for the two products of a step (one pass over the indices each, paid back in a few steps)
-  const uint16_t* first16 = spmv_narrow_indices(right_side ? A : At, false, h.idx16_a, s);
-  const uint16_t* second16 = scatter ? nullptr : spmv_narrow_indices(right_side ? At : A, true, h.idx16_b, s);
+  const uint16_t* first16 = spmv_narrow_indices(right_side ? A : At, false, sw, h.idx16_a, s);
+  const uint16_t* second16 = scatter ? nullptr : spmv_narrow_indices(right_side ? At : A, true, sw, h.idx16_b, s);
   const double* shift = centred ? dots : nullptr;   // (of the v a step multiplies: written by the scale_kernel that wrote v)
   auto apply_B = [&](const double* v, double* out) {  // out = A^T A v  (or A A^T v); centred: A_c for A
     if (scatter) {
       unsigned long long* ymax = sc + 1 + (product & 1), *next = sc + 1 + ((product + 1) & 1);
       ++product;
       bool have_max = false;
-      spmv_launch(A, v, tmp, s, nullptr, first16, ymax, &have_max, shift);
+      spmv_launch(A, v, tmp, s, sw, nullptr, first16, ymax, &have_max, shift);
       if (!have_max) k::vecmax(tmp, other, ymax, s);
       k::spmvt_scatter(A, first16, tmp, sc, ymax, next, out, h.scratch2, s);   // (the same 2-byte indices: one copy serves both products)
       if (h.comm.active()) h.comm.allreduce(out, (uint64_t)len, 1, s);
     } else if (right_side) {
-      spmv_launch(A, v, tmp, s, nullptr, first16, nullptr, nullptr, shift);
-      spmv_launch(At, tmp, out, s, &h.scratch2, second16);   // (centred: A^T y is A_c^T y, 1^T y = 0)
+      spmv_launch(A, v, tmp, s, sw, nullptr, first16, nullptr, nullptr, shift);
+      spmv_launch(At, tmp, out, s, sw, &h.scratch2, second16);   // (centred: A^T y is A_c^T y, 1^T y = 0)
       if (h.comm.active()) h.comm.allreduce(out, (uint64_t)len, 1, s);
     } else {
-      spmv_launch(At, v, tmp, s, nullptr, first16, nullptr, nullptr, shift, mu);                            // t = A^T v - mu (1^T v)
-      spmv_launch(A, tmp, out, s, &h.scratch2, second16, nullptr, nullptr, centred ? dots + 1 : nullptr);   // A t - (g^T v) 1
+      spmv_launch(At, v, tmp, s, sw, nullptr, first16, nullptr, nullptr, shift, mu);                            // t = A^T v - mu (1^T v)
+      spmv_launch(A, tmp, out, s, sw, &h.scratch2, second16, nullptr, nullptr, centred ? dots + 1 : nullptr);   // A t - (g^T v) 1
     }
   };
 
@@ -751,7 +772,7 @@ void lanczos_fit(sapca_handle_s& h, bool centred) {
     for (int i = 0; i < k; ++i) {
       hipLaunchKernelGGL((load_column_kernel<T>), dim3(grid1(m)), dim3(256), 0, s, Ut, m, i, ldk, w);
       if (centred) hipLaunchKernelGGL(dot_kernel, dim3(1), dim3(256), 0, s, w, (const double*)nullptr, m, dots + 2);
-      spmv_launch(At, w, tmp, s, nullptr, nullptr, nullptr, nullptr, centred ? dots + 2 : nullptr, mu);
+      spmv_launch(At, w, tmp, s, sw, nullptr, nullptr, nullptr, nullptr, centred ? dots + 2 : nullptr, mu);
       hipLaunchKernelGGL(column_scale_f64_kernel, dim3(grid1(n_used)), dim3(256), 0, s, tmp, n_used,
                          h.sing[i] > 0 ? 1.0 / h.sing[i] : 0.0);
       hipLaunchKernelGGL((store_column_kernel<T>), dim3(grid1(n_used)), dim3(256), 0, s, tmp, n_used, i, ldk, VtT);

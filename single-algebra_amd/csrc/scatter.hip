@@ -159,6 +159,10 @@ colrange_bounds_kernel(const int64_t* __restrict__ ptr, const int32_t* __restric
 
 // Column statistics of columns [c0, c0 + nc) (pass p of `passes`): per workgroup fixed-point sums of a and a^2 and entry
 // counts in LDS.  A row's entries inside the range are the run [bounds[r][p], bounds[r][p + 1]) of the row.
+// Rows whose columns do NOT ascend (include/sapca.h: wrong numbers, not stray accesses): the searches above still end inside
+// the row, but with more than one pass a run can then hold a column of another pass's range, and c would index LDS below ss
+// or past the three arrays (sq + c reaches 8 (nc + c) bytes of the 20 nc there are).  Such an entry is skipped.  With one
+// pass c is the column itself, which is < cols = nc for every array the library accepts.
 template <typename T>
 __global__ void __launch_bounds__(SC_THREADS)
 colstats_scatter_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx, const T* __restrict__ val, int64_t rows, int c0,
@@ -181,7 +185,9 @@ colstats_scatter_kernel(const int64_t* __restrict__ ptr, const int32_t* __restri
     const int64_t hi = p + 1 < passes ? e0 + (int64_t)bounds[r * (passes - 1) + p] : ptr[r + 1];
     for (int64_t e = lo + lane; e < hi; e += WAVE) {
       const int c = idx[e] - c0;
-      const double v = (double)val[e];
+      double v = (double)val[e];
+      asm volatile("" : "+v"(v));   // (the value's load stays beside the column's: sunk behind the check it waits a second memory latency)
+      if ((unsigned)c >= (unsigned)nc) continue;
       atomicAdd(reinterpret_cast<unsigned long long*>(ss + c), (unsigned long long)__double2ll_rn(v * s1));
       atomicAdd(reinterpret_cast<unsigned long long*>(sq + c), (unsigned long long)__double2ll_rn(v * v * s2));
       atomicAdd(cn + c, 1u);

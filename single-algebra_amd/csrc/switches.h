@@ -18,7 +18,8 @@
 //   spmm_tiled.hip  SAPCA_SWEEP_STAGED
 //   spmm_dq.hip  SAPCA_NO_DQ, SAPCA_NO_DQ_F64      prep.hip  SAPCA_TRANSPOSE_GATHER
 //   dense.hip    SAPCA_CHOL_GENERAL, SAPCA_EIG_DEVICE
-//   lanczos.hip  SAPCA_SPMV_NO_LDS, SAPCA_SPMV_NO_SLICE_GRID, SAPCA_SPMV_IDX32, SAPCA_LANCZOS_CHECK
+//   lanczos.hip  SAPCA_SPMV_NO_LDS, SAPCA_SPMV_NO_SLICE_GRID, SAPCA_SPMV_IDX32 (SpmvSwitches: read once per fit, so one process can
+//                walk the routes), SAPCA_LANCZOS_CHECK
 //   tsne.hip     SAPCA_TSNE_SPLIT (0 | 1: the repulsion's j chunks walked by one workgroup per i block | one workgroup each)
 //   api.cpp      SAPCA_UPLOAD_STATS_OFF, SAPCA_UP_CHUNK (entries per chunk of the host upload, >= 1; read on every upload)
 //   comm.cpp     SAPCA_COMM_FORCE_RCCL (a one-rank RCCL communicator: how a one-GPU box tests the binding), SAPCA_COMM_NO_SPLIT,
