@@ -1021,7 +1021,7 @@ void rotate_into_components(H& h, int ld, const double* Mdev, const double** sig
   k::flip_transpose(VtT, n_used, ldk, k, comps, h.scratch2, h.stream, sign_out);
 }
 
-// GramDevice: the eigenproblem stays on the device (one workgroup, parallel Jacobi: dense.hip).  The singular values (and the
+// GramDevice: the eigenproblem stays on the device (one workgroup, parallel Jacobi: sym_eig.hip).  The singular values (and the
 // solver's status) cross in page-locked memory behind everything else; finish_fit() reads them after the fit's last wait.
 template <typename T>
 void small_svd_gram_device(H& h, const RandomizedPlan& p, FitPanels<T>& f) {

@@ -268,11 +268,12 @@ void spmm_tiled_piece(const TiledOp& op, int piece, int npieces, int wgs, int64_
 void spmm_tiled(const TiledOp& op, const double* X, int ldx, double* Y, int ldy, int ncols, const double* cvec, DevBuf& scratch,
                 hipStream_t s, PanelSource<double>* keep = nullptr);
 
-// ---- dense.hip -------------------------------------------------------------------------
+// ---- the dense panel units (dense_common.h: what they share) ---------------------------
 // widest panel (n_components + n_oversamples, padded) the dense kernels take: up to 128 columns in one launch, beyond that in
 // blocks of 64 / 128 columns (correct, not tuned)
 constexpr int kMaxPanelWidth = 1024;
 
+// ---- gram.hip ----
 // G = P^T P (ld x ld, f64, full symmetric) for a rows x ld panel with ld % 16 == 0 (ld <= 128) or ld % 64 == 0 (ld <= 1024).
 template <typename T>
 void materialize(T* P, int64_t rows, int ld, const PanelSource<T>& src, hipStream_t s);
@@ -280,26 +281,31 @@ void materialize(T* P, int64_t rows, int ld, const PanelSource<T>& src, hipStrea
 template <typename T>
 void gram(T* P, int64_t rows, int ld, double* G, DevBuf& scratch, hipStream_t s, const PanelSource<T>* src = nullptr, const T* w = nullptr,
           double* wsum = nullptr);
+// ---- chol.hip ----
 // Upper Cholesky G = R^T R on the leading l x l block, Rinv = R^{-1}; both ld x ld, zero padded.
 // *info += number of pivots that had to be regularised.
 // wsum / vec32 / vec64 (nullable): vec[j] = sum_i Rinv[i][j] wsum[i] -- the column sums of P R^-1 from those of P
 void chol_inv(const double* G, int l, int ld, double* R, double* Rinv, int* info, hipStream_t s, const double* wsum = nullptr,
               float* vec32 = nullptr, double* vec64 = nullptr);
 
+// ---- sym_eig.hip ----
 // Eigen-decomposition of the symmetric l x l matrix G (row stride ld) on the device, one workgroup (parallel Jacobi in LDS,
 // l <= 112): M (ld x ldk, zero padded) = leading k eigenvectors in columns, each divided by sigma_j = sqrt(lambda_j), in
 // descending order; sigma[0..l) = all of them; status[0] = 0 / 1 (not converged) | 2 (non-finite), status[1] = sweeps.
 bool sym_eig_device_ok(int l);
 void sym_eig_device(const double* G, int l, int ld, int k, int ldk, double* M, double* sigma, int* status, hipStream_t s);
+// ---- panel_gemm.hip ----
 // out[rows x ldo] = P[rows x ld] * M[ld x ldo]  (M f64, row-major, ldo % 16 == 0); out may alias P
 // when ldo == ld.
 // out_stride (0: ldo) is the row stride of `out`, out_cols (0: ldo) the number of leading columns written.
 template <typename T>
 void panel_gemm(const T* P, int64_t rows, int ld, const double* M, int ldo, T* out, hipStream_t s, bool upper = false, int out_stride = 0,
                 int out_cols = 0);
+// ---- gram.hip (the column sums) ----
 // out[j] = sum_r w[r] P[r][j]  (w null => ones), j < ld, f64 accumulation.
 template <typename T>
 void weighted_colsum(const T* P, int64_t rows, int ld, const T* w, T* out, DevBuf& scratch, hipStream_t s);
+// ---- panel_ops.hip ----
 // Z[r][j] -= mu[r] * svec[j]
 template <typename T>
 void rank1_subtract(T* Z, int64_t rows, int ld, const T* mu, const T* svec, hipStream_t s);

@@ -17,7 +17,7 @@
 //                SAPCA_ROWSORT_ALWAYS, SAPCA_FILL_DIRECT, SAPCA_AT_BUCKETS, SAPCA_AT_SORT, SAPCA_RUNS_SEG_LDS_MAX, SAPCA_NO_DQ, SAPCA_DEBUG
 //   spmm_tiled.hip  SAPCA_SWEEP_STAGED
 //   spmm_dq.hip  SAPCA_NO_DQ, SAPCA_NO_DQ_F64      prep.hip  SAPCA_TRANSPOSE_GATHER
-//   dense.hip    SAPCA_CHOL_GENERAL, SAPCA_EIG_DEVICE
+//   chol.hip     SAPCA_CHOL_GENERAL              sym_eig.hip  SAPCA_EIG_DEVICE
 //   lanczos.hip  SAPCA_SPMV_NO_LDS, SAPCA_SPMV_NO_SLICE_GRID, SAPCA_SPMV_IDX32 (SpmvSwitches: read once per fit, so one process can
 //                walk the routes), SAPCA_LANCZOS_CHECK
 //   tsne.hip     SAPCA_TSNE_SPLIT (0 | 1: the repulsion's j chunks walked by one workgroup per i block | one workgroup each)

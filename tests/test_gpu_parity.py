@@ -237,9 +237,12 @@ def test_normalizer_qr_orthonormal_same_span(session, dtype, tol):
     assert np.array_equal(session.normalize_panel(P, PIN.NONE), P)
 
 
-@pytest.mark.parametrize("l", [1, 7, 16, 17, 33, 48, 60, 64, 90])
+@pytest.mark.parametrize("l", [1, 7, 16, 17, 33, 48, 60, 64, 90, 100, 113, 128])
 def test_normalizer_every_block_count_of_the_cholesky(session, l):
-    """l <= 64 runs the blocked one-workgroup Cholesky (1-4 blocks of 16 columns, padded), wider panels the general one"""
+    """Every Cholesky route the device takes, and the Gram route that feeds it (the panel is padded to ld = l rounded up to 16):
+    l <= 64: the blocked one-workgroup kernel, 1-4 blocks of 16 columns (ld = 64: the fused 64-column Gram, else the plain one);
+    l = 90, 100 (ld = 96, 112): the general kernel (plain Gram: six tiles in one wave, seven split over the four waves);
+    l = 113, 128 (ld = 128): the 128-column kernel on two 64 x 64 halves, the second one partly / fully filled (fused Gram)."""
     P = synth.gaussian_panel(4000, l, 11).numpy().astype(np.float64)
     P *= np.logspace(0, 3, l)[None, :]                          # graded column scales
     Q = session.normalize_panel(P, PIN.QR)

@@ -1,8 +1,8 @@
-// Phase timing of the blocked Cholesky + inverse (dense.hip) for l = 60: shader-clock stamps at the
+// Phase timing of the blocked Cholesky + inverse (chol.hip) for l = 60: shader-clock stamps at the
 // phase boundaries, and the kernel's duration from HIP events.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DSAPCA_CHOL_TIMING -I single-algebra_amd/csrc -I include \
 //         tools/ubench/chol_phases.hip -o /tmp/chol_phases -ldl
-#include "../../single-algebra_amd/csrc/dense.hip"
+#include "../../single-algebra_amd/csrc/chol.hip"
 #include <cstdio>
 #include <random>
 #include <vector>
