@@ -74,7 +74,9 @@ extern "C" {
                                                   sapca_tsne_device_*, sapca_tsne_*
                                  additive, ABI 4: sapca_kmeans_options_default, sapca_kmeans_seed_device_*,
                                                   sapca_kmeans_assign_device_*, sapca_kmeans_update_device_*,
-                                                  sapca_kmeans_device_*, sapca_kmeans_*                               */
+                                                  sapca_kmeans_device_*, sapca_kmeans_*
+                                 additive, ABI 4: sapca_umap_options_default, sapca_umap_find_ab, sapca_umap_graph_device_*,
+                                                  sapca_umap_embed_device_*, sapca_umap_device_*, sapca_umap_*          */
 
 typedef struct sapca_handle_s* sapca_handle;
 
@@ -886,6 +888,112 @@ sapca_status sapca_kmeans_f32(sapca_handle h, uint64_t m, uint64_t d, const floa
                               int32_t* labels, double* inertia, uint64_t* n_iter);
 sapca_status sapca_kmeans_f64(sapca_handle h, uint64_t m, uint64_t d, const double* x, const sapca_kmeans_options* opts, double* centroids,
                               int32_t* labels, double* inertia, uint64_t* n_iter);
+
+/* ---- UMAP of device-resident score rows (sapca_umap_*) ----
+ * The third consumer of the neighbour search, beside t-SNE and k-means.  The reference has no UMAP and umap-learn is not
+ * available to this project: an opt-in superset.  PARITY STATUS: UNPINNED by any package; the algorithm is umap-learn's
+ * (fuzzy_simplicial_set, find_ab_params, optimize_layout_euclidean) with the deviations listed below, stated here in full and
+ * pinned by a numpy restatement (tests/umap_ref.py).  x is a row-major DEVICE panel, m x d, row stride ldx >= d, searched in
+ * place.  n_neighbors follows umap-learn and counts the point itself: K = n_neighbors - 1 other rows are searched.
+ *   1. K Euclidean nearest neighbours of every row, itself excluded (sapca_knn_device_*).
+ *   2. Smooth distances, per row i, all f64 whatever T is.  A slot whose index is outside [0, m) (the search's -1) contributes
+ *      nothing anywhere.  rho_i = the smallest distance > 0 among the row's valid slots, 0 when there is none
+ *      (local_connectivity = 1).  target = log2(n_neighbors).  From lo = 0, hi = +inf, mid = 1, at most 64 steps:
+ *      psum = sum_k (d_k - rho > 0 ? exp(-(d_k - rho) / mid) : 1); stop when |psum - target| < 1e-5; psum > target: hi = mid,
+ *      mid = (lo + hi) / 2; otherwise lo = mid and mid is doubled while hi is infinite, else mid = (lo + hi) / 2.
+ *      sigma_i = mid, then floored: with rho_i > 0 to 1e-3 (sum_k d_k) / n_neighbors, otherwise to 1e-3 (the sum over all valid
+ *      slots of the panel) / (m n_neighbors) -- umap-learn's means, which count the point's own zero; both sums f64 in an
+ *      order fixed by (m, K).  Membership a_ik = 1 where d_k - rho_i <= 0, else exp(-(d_k - rho_i) / sigma_i), this exp
+ *      correctly rounded.
+ *   3. Fuzzy union (set_op_mix_ratio = 1): G_ij = (a_ij + a_ji) - a_ij a_ji in f64, a missing direction counting 0 (the value
+ *      is then exactly a), rounded once to T.  The expression is symmetric in its two terms: G_ij == G_ji bit for bit.  A
+ *      canonical CSR: int64 offsets, int32 columns ascending without repeats.  (A list that names one row twice is outside
+ *      the contract of the search; its repeats fold left to right.)
+ *   4. Curve: a and b as given (both > 0), or, both 0, fitted as umap-learn's find_ab_params does: x_t = 3 spread t / 299 for
+ *      t = 0 .. 299, y_t = 1 for x_t < min_dist, else exp(-(x_t - min_dist) / spread); least squares of 1 / (1 + a x^(2b)) by
+ *      Gauss-Newton / Levenberg-Marquardt in f64 from (1, 1) until the step is below 1e-12 relative (sapca_umap_find_ab).
+ *   5. Layout: optimize_layout_euclidean made synchronous and deterministic.  w_max = the largest stored value.  A directed
+ *      stored entry e = (i -> j, w_e) with w_e < w_max / n_epochs is left out of the layout (not of the graph).
+ *      eps_e = w_max / w_e (f64, from the stored T values), next_e = eps_e, epsn_e = eps_e / negative_sample_rate,
+ *      nextn_e = epsn_e.  Epoch n = 0 .. n_epochs - 1, alpha = learning_rate (1 - n / n_epochs): every vertex i reads the
+ *      previous epoch's Y only and only y_i is written by it (two buffers, no floating-point atomic).  For each of its
+ *      entries with next_e <= n: attraction, delta = y_i - y_j, s = |delta|^2, c = s > 0 ? -2 a b s^(b-1) / (a s^b + 1) : 0,
+ *      add clip(c delta, -4, 4) componentwise, next_e += eps_e; repulsion, q = floor((n - nextn_e) / epsn_e), for
+ *      p = 0 .. q - 1: k = floor(hash_u01(seed, 32, (n nnz + e) 64 + p) m) with e the entry's position in the stored graph,
+ *      delta = y_i - y_k, s = |delta|^2, c = s > 0 ? 2 repulsion_strength b / ((0.001 + s)(a s^b + 1)) : 0, add
+ *      clip(c delta, -4, 4); nextn_e += q epsn_e (negative_sample_rate = 0: no repulsion).  Then y_i <- y_i + alpha (sum):
+ *      everything in f64 from the stored T values, rounded once per epoch to T, the sum added in an order fixed by the graph
+ *      alone; a vertex whose sum is exactly 0 keeps its bits.  The graph is symmetric and both directions are stored with the
+ *      same weight, so head-only moves act on both ends of an edge in the same epochs.  q <= 2 negative_sample_rate (from
+ *      eps >= 1); the rate is limited to 31, so p < 64.  A sample k == i gives s = 0 and no force.
+ *      Start: SAPCA_UMAP_INIT_PANEL (default) y[:, c] = 10 (x[:, c] - min_c) / (max_c - min_c) for the first output_dim
+ *      columns of x, a constant column giving 0 (needs d >= output_dim); SAPCA_UMAP_INIT_RANDOM
+ *      10 hash_u01(seed, 31, i output_dim + c); SAPCA_UMAP_INIT_GIVEN the caller's panel as it is.
+ * Deviations from umap-learn: synchronous instead of sequential in-place updates; this library's counter generator instead of
+ * tau_rand; no spectral initialisation; set_op_mix_ratio = 1 and local_connectivity = 1 only; Euclidean only; no transform of
+ * new points.
+ * Deterministic: the same bytes from call to call.  Integer atomics count and hand out positions in stage 3 and take the
+ * maximum of bit patterns for w_max; the rows are then sorted by column and a pair combined symmetrically, so no order reaches
+ * a value; every floating-point sum that crosses lanes is added in an order fixed by the shape or the graph, never by the device.
+ * Outputs are complete when the call returns.  Every call runs on the handle's stream in buffers of its own: a fitted model,
+ * a cached preparation, the upload's statistics, the selection, the canonical, the t-SNE and the k-means buffers are
+ * untouched; on a handle that belongs to a communicator the call is local to the rank and issues no collective.  The epoch
+ * loop enqueues kernels only and swaps the two buffers; nothing is read back.  No index outside the arrays is touched: a
+ * neighbour slot or a column of G outside [0, m) is skipped where it is read, a sample is below m, the emitted positions are
+ * counted before they are written, and the offsets of a caller's G are trusted as in every *_csr_device_* call.  Non-finite
+ * input values give an unspecified embedding.
+ * SAPCA_ERR_ARG, checked on the host before anything is enqueued (the handle stays usable), each with a message that names
+ * the offending number: a wrong struct_size; output_dim outside 1 .. 3; an unknown init; n_neighbors outside 2 .. 129;
+ * n_neighbors > m when m > 0; negative_sample_rate > 31; K outside 1 .. 128 or n_neighbors < 2 in the graph call; a non-finite
+ * or negative learning_rate / repulsion_strength (0 is valid); exactly one of a, b zero, or either negative or non-finite;
+ * the refusals of sapca_umap_find_ab; INIT_PANEL with d < output_dim, or passed to the embed stage; the d / stride limits of
+ * sapca_knn_device_*; m >= 2^31; a non-square graph; a null pointer with a non-empty shape.  m == 0 is valid and writes
+ * nothing.                                                                                                                */
+typedef enum sapca_umap_init { SAPCA_UMAP_INIT_PANEL = 0, SAPCA_UMAP_INIT_RANDOM = 1, SAPCA_UMAP_INIT_GIVEN = 2 } sapca_umap_init;
+typedef struct sapca_umap_options {
+  uint32_t struct_size;            /* sizeof(sapca_umap_options): 80                                   */
+  uint32_t random_seed;            /* default 42                                                       */
+  uint32_t output_dim;             /* default 2; 1 .. 3                                                */
+  uint32_t init;                   /* sapca_umap_init, default SAPCA_UMAP_INIT_PANEL                   */
+  uint32_t n_neighbors;            /* default 15; 2 .. 129 (counts the point itself)                   */
+  uint32_t negative_sample_rate;   /* default 5; 0 .. 31                                               */
+  uint64_t epochs;                 /* 0 (default): umap-learn's rule, 500 for m <= 10000, else 200     */
+  double min_dist;                 /* default 0.1                                                      */
+  double spread;                   /* default 1.0                                                      */
+  double a;                        /* default 0: fitted from (spread, min_dist) together with b        */
+  double b;                        /* default 0                                                        */
+  double learning_rate;            /* default 1.0                                                      */
+  double repulsion_strength;       /* default 1.0                                                      */
+} sapca_umap_options;
+void sapca_umap_options_default(sapca_umap_options* opts);
+/* Stage 4 alone: pure host code, no handle.  SAPCA_ERR_ARG for non-finite arguments, spread <= 0, min_dist < 0 or
+ * min_dist >= 3 spread; SAPCA_ERR_SVD if the fit does not converge in 200 steps.                                           */
+sapca_status sapca_umap_find_ab(double spread, double min_dist, double* a, double* b);
+/* Stages 2-3 on neighbour lists laid out as sapca_knn_device_* writes them (m x K, DEVICE; 1 <= K <= SAPCA_KNN_MAX_NEIGHBORS).
+ * The graph comes back in handle-owned DEVICE arrays like the t-SNE affinities': valid until the next graph call
+ * (sapca_umap_device_* and sapca_umap_* make one) or destroy, and accepted by every *_csr_device_* entry point.  d_sigma and
+ * d_rho (m f64 each, DEVICE, may be NULL) receive sigma_i and rho_i.                                                        */
+sapca_status sapca_umap_graph_device_f32(sapca_handle h, uint64_t m, const int32_t* d_indices, const float* d_dist, uint32_t K,
+                                         uint32_t n_neighbors, uint64_t* nnz_out, const int64_t** d_row_offsets,
+                                         const int32_t** d_col_indices, float** d_values, double* d_sigma, double* d_rho);
+sapca_status sapca_umap_graph_device_f64(sapca_handle h, uint64_t m, const int32_t* d_indices, const double* d_dist, uint32_t K,
+                                         uint32_t n_neighbors, uint64_t* nnz_out, const int64_t** d_row_offsets,
+                                         const int32_t** d_col_indices, double** d_values, double* d_sigma, double* d_rho);
+/* Stage 5 on a given symmetric graph: d_y (m x output_dim packed, DEVICE) is read for SAPCA_UMAP_INIT_GIVEN and receives the
+ * embedding.  SAPCA_UMAP_INIT_PANEL is refused here (there is no panel); n_neighbors is not read.                           */
+sapca_status sapca_umap_embed_device_f32(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                         const float* values, const sapca_umap_options* opts, float* d_y);
+sapca_status sapca_umap_embed_device_f64(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                         const double* values, const sapca_umap_options* opts, double* d_y);
+/* Stages 1-5 on a resident m x d panel with row stride ldx: exactly sapca_knn_device_* (EUCLIDEAN, EXCLUDE_SELF,
+ * n_neighbors - 1), sapca_umap_graph_device_*, then the layout.                                                              */
+sapca_status sapca_umap_device_f32(sapca_handle h, uint64_t m, const float* d_x, uint64_t ldx, uint64_t d,
+                                   const sapca_umap_options* opts, float* d_y);
+sapca_status sapca_umap_device_f64(sapca_handle h, uint64_t m, const double* d_x, uint64_t ldx, uint64_t d,
+                                   const sapca_umap_options* opts, double* d_y);
+/* The same with HOST arrays in and out (x: m x d row-major; y: m x output_dim, read for SAPCA_UMAP_INIT_GIVEN).             */
+sapca_status sapca_umap_f32(sapca_handle h, uint64_t m, uint64_t d, const float* x, const sapca_umap_options* opts, float* y);
+sapca_status sapca_umap_f64(sapca_handle h, uint64_t m, uint64_t d, const double* x, const sapca_umap_options* opts, double* y);
 
 /* Measurement support: the rate (GB/s, read + write counted) of a 16-byte-per-lane streaming copy of `bytes`
  * bytes on the handle's device, best of `reps` -- the HBM rate a kernel of this library can attain, reported by

@@ -879,6 +879,24 @@ sapca_status sapca_get_column_scale(sapca_handle h, int32_t* mode, double* out, 
                                 double* kl) {                                                                             \
     return guarded(h, [&] { resident::tsne_host<T>(*h, m, d, x, opts, y, kl); });                                        \
   }                                                                                                                      \
+  sapca_status sapca_umap_graph_device_##SUF(sapca_handle h, uint64_t m, const int32_t* d_indices, const T* d_dist, uint32_t K, \
+                                             uint32_t n_neighbors, uint64_t* nnz_out, const int64_t** dp, const int32_t** di, \
+                                             T** dv, double* d_sigma, double* d_rho) {                                     \
+    return guarded(h, [&] {                                                                                              \
+      resident::umap_graph<T>(*h, m, d_indices, d_dist, K, n_neighbors, nnz_out, dp, di, dv, d_sigma, d_rho);            \
+    });                                                                                                                  \
+  }                                                                                                                      \
+  sapca_status sapca_umap_embed_device_##SUF(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* p, const int32_t* i,  \
+                                             const T* v, const sapca_umap_options* opts, T* d_y) {                        \
+    return guarded(h, [&] { resident::umap_embed<T>(*h, unchecked_view(m, m, nnz, p, i, v), opts, d_y); });              \
+  }                                                                                                                      \
+  sapca_status sapca_umap_device_##SUF(sapca_handle h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d,                 \
+                                       const sapca_umap_options* opts, T* d_y) {                                          \
+    return guarded(h, [&] { resident::umap_device<T>(*h, m, d_x, ldx, d, opts, d_y); });                                 \
+  }                                                                                                                      \
+  sapca_status sapca_umap_##SUF(sapca_handle h, uint64_t m, uint64_t d, const T* x, const sapca_umap_options* opts, T* y) { \
+    return guarded(h, [&] { resident::umap_host<T>(*h, m, d, x, opts, y); });                                            \
+  }                                                                                                                      \
   sapca_status sapca_kmeans_seed_device_##SUF(sapca_handle h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d,           \
                                               uint32_t n_clusters, uint32_t random_seed, T* d_centroids, int32_t* d_rows) { \
     return guarded(h, [&] { resident::kmeans_seed<T>(*h, m, d_x, ldx, d, n_clusters, random_seed, d_centroids, d_rows); }); \
@@ -943,6 +961,34 @@ void sapca_kmeans_options_default(sapca_kmeans_options* o) {
   o->init = SAPCA_KMEANS_PLUSPLUS;
   o->max_iter = 300;
   o->tol = 1e-4;
+}
+
+void sapca_umap_options_default(sapca_umap_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  o->struct_size = (uint32_t)sizeof(sapca_umap_options);
+  o->random_seed = 42;
+  o->output_dim = 2;
+  o->init = SAPCA_UMAP_INIT_PANEL;
+  o->n_neighbors = 15;
+  o->negative_sample_rate = 5;
+  o->epochs = 0;
+  o->min_dist = 0.1;
+  o->spread = 1.0;
+  o->learning_rate = 1.0;
+  o->repulsion_strength = 1.0;
+}
+
+// (no handle: a refusal has no message to leave, only its status)
+sapca_status sapca_umap_find_ab(double spread, double min_dist, double* a, double* b) {
+  try {
+    resident::umap_find_ab(spread, min_dist, a, b);
+    return SAPCA_OK;
+  } catch (const Error& e) {
+    return e.code;
+  } catch (const std::exception&) {
+    return SAPCA_ERR_ARG;
+  }
 }
 
 void sapca_tsne_options_default(sapca_tsne_options* o) {

@@ -178,6 +178,16 @@ struct sapca_handle_s {
     sapca::DevBuf bias, xb, amb, lab0, lab1, cnt, tab, scan, order, partial, shiftpart, ctl, scal, rowd, sum_part, colpart, cols;
     sapca::DevBuf rows, seed_dist, seed_bsum, x, cen, labels;
   } kmeans;
+  // sapca_umap_*: the memberships and the emitted entries (raw_*), the row sort's work space and output (as in Tsne), the fuzzy
+  // union handed back (one of raw_ptr / out_ptr, one of raw_idx / sort_idx, out_val), the row sums and their total, the
+  // layout's schedule, its second embedding buffer, and the arrays of the host and one-call routes.  Nothing else lives in these.
+  struct Umap {
+    sapca::DevBuf p, raw_ptr, nvalid, cursor, raw_idx, raw_val, scan, ctr, rows, long_off, keys, sort_idx, sort_val, out_ptr, out_val;
+    sapca::DevBuf rowsum, sum_part, scal, next, nextn, y2, minmax, knn_idx, knn_dist, x, y;
+    bool owns(const void* q) const {
+      return raw_ptr.contains(q) || out_ptr.contains(q) || raw_idx.contains(q) || sort_idx.contains(q) || out_val.contains(q);
+    }
+  } umap;
   sapca::DevBuf at_ptr, at_idx, at_val;                          // A^T
   sapca::DevBuf ca_ptr, ca_idx, ca_val, cat_ptr, cat_idx, cat_val;  // mask-compacted A, A^T
   sapca::DevBuf drop_stats, drop_tmp;                              // their sums (sum | sumsq, full width) and the sort's work space

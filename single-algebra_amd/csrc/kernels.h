@@ -428,6 +428,38 @@ void tsne_center(T* y, int64_t m, int D, double* colpart, double* mean, bool sum
 template <typename T>
 void tsne_init_state(T* y_or_null, T* v, T* gain, int64_t m, int D, uint32_t seed, hipStream_t s);
 
+// ---- umap.hip: UMAP on dense row panels (sapca_umap_*); include/sapca.h states the algorithm -------------------------------
+// rowsum[i] = the sum of row i's distances over the slots whose index is inside [0, m) (f64, one order).  One wave per row, K <= 128.
+template <typename T>
+void umap_row_sums(const int32_t* idx, const T* dist, int64_t m, int K, double* rowsum, hipStream_t s);
+// a[i * K + slot] = the membership of the slot (0 where its index is outside [0, m)), sigma[i], rho[i] (both nullable);
+// *total = the sum of every valid distance of the panel (the floor of sigma where rho is 0)
+template <typename T>
+void umap_smooth(const int32_t* idx, const T* dist, int64_t m, int K, int n_neighbors, const double* total, double* a, double* sigma,
+                 double* rho, hipStream_t s);
+// (idx, val) at offsets ptr, every row sorted -> (out_idx, out_val) at new_ptr (which may be ptr): a run of equal columns becomes
+// one entry, folded by (a + b) - a b in f64; every value rounded once to T
+template <typename T>
+void umap_union_fill(const int64_t* ptr, const int32_t* idx, const double* val, int64_t m, const int64_t* new_ptr, int32_t* out_idx,
+                     T* out_val, hipStream_t s);
+// *wmax = the largest positive value (0: none); next[e] = *wmax / val[e], nextn[e] = next[e] / rate
+template <typename T>
+void umap_schedule(const T* val, int64_t nnz, int rate, double* wmax, double* next, double* nextn, hipStream_t s);
+// y (m x D packed) = 10 (x[:, c] - min_c) / (max_c - min_c), 0 for a constant column; minmax: 2 D doubles of work space
+template <typename T>
+void umap_init_panel(const T* x, int64_t ldx, int64_t m, int D, double* minmax, T* y, hipStream_t s);
+// y[i * D + c] = T(10 hash_u01(seed, 31, i D + c))
+template <typename T>
+void umap_init_random(T* y, int64_t m, int D, uint32_t seed, hipStream_t s);
+struct UmapEpoch {
+  uint64_t epoch = 0, seed = 0;
+  double n_epochs = 1, alpha = 0, a = 1, b = 1, gamma = 1, rate = 0;
+};
+// one epoch of the layout: y_out from y_in (distinct, m x D packed), the schedule advanced in place.  One launch.
+template <typename T>
+void umap_epoch(const CsrView<T>& G, const T* y_in, T* y_out, int D, const UmapEpoch& p, const double* wmax, double* next, double* nextn,
+                hipStream_t s);
+
 // ---- kmeans.hip: k-means on dense row panels (sapca_kmeans_*); include/sapca.h states the algorithm ------------------------
 // The control block of a run (device, unsigned 64-bit words).  Every kernel below that takes `skip` returns at once when
 // *skip != 0 (null: never): the loop's kernels watch kKmDone, the closing assignment watches kKmStrict.

@@ -90,5 +90,18 @@ template <typename T>
 void kmeans_host(H& h, uint64_t m, uint64_t d, const T* x, const sapca_kmeans_options* opts, T* centroids, int32_t* labels, double* inertia,
                  uint64_t* n_iter);
 
+// sapca_umap_* (umap.cpp): the curve fit (host only), the fuzzy union of neighbour lists, the layout, and the whole chain on a
+// device panel or on host arrays
+void umap_find_ab(double spread, double min_dist, double* a, double* b);
+template <typename T>
+void umap_graph(H& h, uint64_t m, const int32_t* d_indices, const T* d_dist, uint32_t K, uint32_t n_neighbors, uint64_t* nnz_out,
+                const int64_t** d_ptr, const int32_t** d_idx, T** d_val, double* d_sigma, double* d_rho);
+template <typename T>
+void umap_embed(H& h, const CsrView<T>& G, const sapca_umap_options* opts, T* d_y);
+template <typename T>
+void umap_device(H& h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d, const sapca_umap_options* opts, T* d_y);
+template <typename T>
+void umap_host(H& h, uint64_t m, uint64_t d, const T* x, const sapca_umap_options* opts, T* y);
+
 }  // namespace resident
 }  // namespace sapca

@@ -167,6 +167,65 @@ inline double tsne(sapca_handle h, uint64_t m, uint64_t d, const T* host_x, cons
   return kl;
 }
 
+// UMAP of device-resident rows (sapca_umap_*; include/sapca.h states the algorithm).  UmapOptions() holds the library's
+// defaults (umap-learn's).  Every pointer but the options is a DEVICE pointer unless the name says host.
+struct UmapOptions : sapca_umap_options {
+  UmapOptions() { sapca_umap_options_default(this); }
+};
+// the fuzzy union a call left in the handle's UMAP buffers (valid until the next graph call)
+template <typename T>
+struct UmapGraph {
+  uint64_t m = 0, nnz = 0;
+  const int64_t* row_offsets = nullptr;
+  const int32_t* col_indices = nullptr;
+  T* values = nullptr;
+};
+template <typename T> struct UmapAbi;
+template <> struct UmapAbi<float> {
+  static constexpr auto graph = &sapca_umap_graph_device_f32;
+  static constexpr auto embed = &sapca_umap_embed_device_f32;
+  static constexpr auto device = &sapca_umap_device_f32;
+  static constexpr auto host = &sapca_umap_f32;
+};
+template <> struct UmapAbi<double> {
+  static constexpr auto graph = &sapca_umap_graph_device_f64;
+  static constexpr auto embed = &sapca_umap_embed_device_f64;
+  static constexpr auto device = &sapca_umap_device_f64;
+  static constexpr auto host = &sapca_umap_f64;
+};
+inline void umap_check(sapca_handle h, sapca_status st) {
+  if (st != SAPCA_OK) throw Error(st, sapca_last_error(h));
+}
+// (a, b) of the curve fitted to (spread, min_dist): host code, no handle
+inline void umap_find_ab(double spread, double min_dist, double* a, double* b) {
+  const sapca_status st = sapca_umap_find_ab(spread, min_dist, a, b);
+  if (st != SAPCA_OK) throw Error(st, "sapca_umap_find_ab: refused (spread, min_dist), or the fit did not converge");
+}
+// stages 2-3 on neighbour lists as knn_device writes them; d_sigma, d_rho (m doubles each) may be null
+template <typename T>
+inline UmapGraph<T> umap_graph_device(sapca_handle h, uint64_t m, const int32_t* d_indices, const T* d_dist, uint32_t K,
+                                      uint32_t n_neighbors, double* d_sigma = nullptr, double* d_rho = nullptr) {
+  UmapGraph<T> g;
+  g.m = m;
+  umap_check(h, UmapAbi<T>::graph(h, m, d_indices, d_dist, K, n_neighbors, &g.nnz, &g.row_offsets, &g.col_indices, &g.values, d_sigma, d_rho));
+  return g;
+}
+// the layout alone (opts.init: SAPCA_UMAP_INIT_RANDOM, or SAPCA_UMAP_INIT_GIVEN with d_y holding the start)
+template <typename T>
+inline void umap_embed_device(sapca_handle h, const UmapGraph<T>& G, const sapca_umap_options& opts, T* d_y) {
+  umap_check(h, UmapAbi<T>::embed(h, G.m, G.nnz, G.row_offsets, G.col_indices, G.values, &opts, d_y));
+}
+// neighbours, graph and layout of an m x d panel (row stride ldx) in one call; d_y: m x output_dim
+template <typename T>
+inline void umap_device(sapca_handle h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d, const sapca_umap_options& opts, T* d_y) {
+  umap_check(h, UmapAbi<T>::device(h, m, d_x, ldx, d, &opts, d_y));
+}
+// the same with host arrays
+template <typename T>
+inline void umap(sapca_handle h, uint64_t m, uint64_t d, const T* host_x, const sapca_umap_options& opts, T* host_y) {
+  umap_check(h, UmapAbi<T>::host(h, m, d, host_x, &opts, host_y));
+}
+
 // K-means of device-resident rows (sapca_kmeans_*; include/sapca.h states the algorithm).  KmeansOptions() holds the library's
 // defaults.  Every pointer is a DEVICE pointer unless the name says host.
 struct KmeansOptions : sapca_kmeans_options {

@@ -625,6 +625,98 @@ pub mod kmeans {
     run!(run_f64, f64, sapca_kmeans_f64);
 }
 
+/// UMAP of dense rows (`sapca_umap_f32` / `_f64`): umap-learn's fuzzy simplicial set and a synchronous, deterministic
+/// restatement of its layout (include/sapca.h states the algorithm and the deviations).  The reference has no UMAP: this is
+/// the crate's own, shaped like `tsne`.
+pub mod umap {
+    use super::{check, ffi};
+    use anyhow::{anyhow, Result};
+    use ndarray::{Array2, ArrayD, ArrayViewD};
+    use sapca_sys::sapca_umap_options as RawOptions;
+
+    #[derive(Clone, Copy, Debug)]
+    pub struct UmapConfig {
+        pub output_dim: u8,
+        pub n_neighbors: u32,
+        pub min_dist: f64,
+        pub spread: f64,
+        /// 0: umap-learn's rule (500 for at most 10000 rows, else 200)
+        pub n_epochs: usize,
+        pub negative_sample_rate: u32,
+        pub learning_rate: f64,
+        pub repulsion_strength: f64,
+        /// false: the first `output_dim` columns of the panel scaled to 0 .. 10; true: uniform under `random_seed`
+        pub random_init: bool,
+        pub random_seed: u32,
+    }
+    impl Default for UmapConfig {
+        /// umap-learn's defaults: 2 dimensions, 15 neighbours, min_dist 0.1, spread 1, 5 negative samples
+        fn default() -> Self {
+            Self { output_dim: 2, n_neighbors: 15, min_dist: 0.1, spread: 1.0, n_epochs: 0, negative_sample_rate: 5, learning_rate: 1.0,
+                   repulsion_strength: 1.0, random_init: false, random_seed: 42 }
+        }
+    }
+
+    /// (a, b) of the curve 1 / (1 + a x^(2b)) fitted to (spread, min_dist): host code, no device
+    pub fn find_ab_params(spread: f64, min_dist: f64) -> Result<(f64, f64)> {
+        let (mut a, mut b) = (0f64, 0f64);
+        let st = unsafe { ffi::sapca_umap_find_ab(spread, min_dist, &mut a, &mut b) };
+        if st != ffi::SAPCA_OK { return Err(anyhow!("sapca_umap_find_ab({}, {}) failed with status {}", spread, min_dist, st)); }
+        Ok((a, b))
+    }
+
+    fn options(config: &UmapConfig) -> RawOptions {
+        let mut o: RawOptions = unsafe { std::mem::zeroed() };
+        unsafe { ffi::sapca_umap_options_default(&mut o) };
+        o.output_dim = config.output_dim as u32;
+        o.n_neighbors = config.n_neighbors;
+        o.min_dist = config.min_dist;
+        o.spread = config.spread;
+        o.epochs = config.n_epochs as u64;
+        o.negative_sample_rate = config.negative_sample_rate;
+        o.learning_rate = config.learning_rate;
+        o.repulsion_strength = config.repulsion_strength;
+        o.init = if config.random_init { ffi::SAPCA_UMAP_INIT_RANDOM as u32 } else { ffi::SAPCA_UMAP_INIT_PANEL as u32 };
+        o.random_seed = config.random_seed;
+        o
+    }
+
+    fn with_handle<R>(f: impl FnOnce(ffi::sapca_handle) -> Result<R>) -> Result<R> {
+        let mut o: ffi::sapca_options = unsafe { std::mem::zeroed() };
+        unsafe { ffi::sapca_options_default(&mut o) };
+        let mut h: ffi::sapca_handle = std::ptr::null_mut();
+        if unsafe { ffi::sapca_create(&o, &mut h) } != ffi::SAPCA_OK {
+            return Err(anyhow!("sapca_create failed (no usable GPU?)"));
+        }
+        let r = f(h);
+        unsafe { ffi::sapca_destroy(h) };
+        r
+    }
+
+    fn shape_of(shape: &[usize]) -> Result<(usize, usize)> {
+        if shape.len() != 2 { return Err(anyhow!("UMAP wants a two-dimensional array, got {} axes", shape.len())); }
+        Ok((shape[0], shape[1]))
+    }
+
+    pub fn run_f32(x: ArrayViewD<f32>, config: UmapConfig) -> Result<ArrayD<f32>> {
+        let (n_obs, n_dim) = shape_of(x.shape())?;
+        let x = x.as_standard_layout();
+        let o = options(&config);
+        let mut y = vec![0f32; n_obs * config.output_dim as usize];
+        with_handle(|h| check(h, unsafe { ffi::sapca_umap_f32(h, n_obs as u64, n_dim as u64, x.as_ptr(), &o, y.as_mut_ptr()) }))?;
+        Ok(Array2::from_shape_vec((n_obs, config.output_dim as usize), y)?.into_dyn())
+    }
+
+    pub fn run_f64(x: ArrayViewD<f64>, config: UmapConfig) -> Result<ArrayD<f64>> {
+        let (n_obs, n_dim) = shape_of(x.shape())?;
+        let x = x.as_standard_layout();
+        let o = options(&config);
+        let mut y = vec![0f64; n_obs * config.output_dim as usize];
+        with_handle(|h| check(h, unsafe { ffi::sapca_umap_f64(h, n_obs as u64, n_dim as u64, x.as_ptr(), &o, y.as_mut_ptr()) }))?;
+        Ok(Array2::from_shape_vec((n_obs, config.output_dim as usize), y)?.into_dyn())
+    }
+}
+
 /// The reference's module tree (src/dimred/pca/mod.rs:36-42; README.md:51-53 imports
 /// `dimred::pca::{SparsePCABuilder, SVDMethod}` and `dimred::pca::sparse::PowerIterationNormalizer`).
 pub mod dimred {

@@ -59,6 +59,16 @@ class KmeansOptions(C.Structure):
     ]
 
 
+class UmapOptions(C.Structure):
+    """sapca_umap_options"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("random_seed", C.c_uint32), ("output_dim", C.c_uint32), ("init", C.c_uint32),
+        ("n_neighbors", C.c_uint32), ("negative_sample_rate", C.c_uint32), ("epochs", C.c_uint64),
+        ("min_dist", C.c_double), ("spread", C.c_double), ("a", C.c_double), ("b", C.c_double),
+        ("learning_rate", C.c_double), ("repulsion_strength", C.c_double),
+    ]
+
+
 # sapca_csr_report and its flags (sapca_check_csr_device_*, sapca_canonicalize_csr_device_*)
 CSR_BAD_OFFSETS, CSR_COL_RANGE, CSR_UNSORTED, CSR_DUPLICATES, CSR_NONFINITE = 1, 2, 4, 8, 16
 CSR_FLAG_NAMES = {CSR_BAD_OFFSETS: "BAD_OFFSETS", CSR_COL_RANGE: "COL_RANGE", CSR_UNSORTED: "UNSORTED",
@@ -75,6 +85,9 @@ KNN_MAX_NEIGHBORS = 128
 # sapca_kmeans_*: the seeding rules, the most clusters
 KMEANS_PLUSPLUS, KMEANS_GIVEN = 0, 1
 KMEANS_MAX_CLUSTERS = 1024
+# sapca_umap_*: how the layout starts
+UMAP_INIT_PANEL, UMAP_INIT_RANDOM, UMAP_INIT_GIVEN = 0, 1, 2
+UMAP_INITS = {"panel": UMAP_INIT_PANEL, "random": UMAP_INIT_RANDOM}
 # covariate columns + the intercept that center = 1 adds (sapca_set_covariates)
 MAX_DESIGN_COLUMNS = 16
 # sapca_column_scaling (sapca_set_column_scaling)
@@ -109,6 +122,7 @@ _TYPED = [
     "sapca_select_submatrix_csr_device", "sapca_knn_device",
     "sapca_tsne_affinities_device", "sapca_tsne_gradient_device", "sapca_tsne_embed_device", "sapca_tsne_device", "sapca_tsne",
     "sapca_kmeans_seed_device", "sapca_kmeans_assign_device", "sapca_kmeans_update_device", "sapca_kmeans_device", "sapca_kmeans",
+    "sapca_umap_graph_device", "sapca_umap_embed_device", "sapca_umap_device", "sapca_umap",
     "sapca_multi_fit_csr", "sapca_multi_transform_csr", "sapca_multi_fit_transform_csr",
     "sapca_multi_upload_csr", "sapca_multi_transform_resident", "sapca_multi_fit_transform_resident",
 ]
@@ -123,6 +137,7 @@ _PLAIN = [
     "sapca_covariate_basis", "sapca_set_covariates", "sapca_get_covariate_rank",
     "sapca_set_column_scaling", "sapca_get_column_scale",
     "sapca_tsne_options_default", "sapca_kmeans_options_default",
+    "sapca_umap_options_default", "sapca_umap_find_ab",
 ]
 EXPORTED_SYMBOLS = _PLAIN + [f"{n}_{s}" for n in _TYPED for s in ("f32", "f64")]
 
@@ -250,7 +265,39 @@ def _open(path):
             getattr(lib, f"sapca_kmeans_{suf}").argtypes = [
                 C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(KmeansOptions), C.c_void_p, C.c_void_p,
                 C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    if hasattr(lib, "sapca_umap_options_default"):   # (absent from an older build loaded for an A/B run)
+        lib.sapca_umap_options_default.argtypes = [C.POINTER(UmapOptions)]
+        lib.sapca_umap_options_default.restype = None
+        lib.sapca_umap_find_ab.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        csr = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]   # h, m, nnz, offsets, columns, values
+        for suf in ("f32", "f64"):
+            getattr(lib, f"sapca_umap_graph_device_{suf}").argtypes = [
+                C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64),
+                C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
+            getattr(lib, f"sapca_umap_embed_device_{suf}").argtypes = csr + [C.POINTER(UmapOptions), C.c_void_p]
+            getattr(lib, f"sapca_umap_device_{suf}").argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64,
+                                                                 C.POINTER(UmapOptions), C.c_void_p]
+            getattr(lib, f"sapca_umap_{suf}").argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(UmapOptions),
+                                                          C.c_void_p]
     return lib
+
+
+def default_umap_options() -> UmapOptions:
+    o = UmapOptions()
+    load().sapca_umap_options_default(C.byref(o))
+    return o
+
+
+def find_ab_params(spread=1.0, min_dist=0.1):
+    """sapca_umap_find_ab: (a, b) of the curve 1 / (1 + a x^(2b)) fitted to (spread, min_dist) as umap-learn's find_ab_params
+    does.  Pure host code, no device.  Bad arguments raise SapcaError (ERR_ARG), a fit that does not converge ERR_SVD."""
+    a, b = C.c_double(), C.c_double()
+    st = load().sapca_umap_find_ab(C.c_double(float(spread)), C.c_double(float(min_dist)), C.byref(a), C.byref(b))
+    if st != OK:
+        raise SapcaError(st, f"sapca_umap_find_ab(spread={spread}, min_dist={min_dist}): "
+                         + ("the fit did not converge in 200 steps" if st == 4 else
+                            "spread must be finite and positive, min_dist finite, not negative and below 3 spread"))
+    return a.value, b.value
 
 
 def default_kmeans_options() -> KmeansOptions:

@@ -310,6 +310,117 @@ class Session:
             C.c_void_p(Y.data_ptr() if m else None), C.byref(kl)))
         return Y, kl.value
 
+    # ---- UMAP (sapca_umap_*): the fuzzy union of neighbour lists, the layout, the whole chain ----
+    def _umap_options(self, n_neighbors, min_dist, spread, n_epochs, output_dim, init, negative_sample_rate, learning_rate,
+                      repulsion_strength, a, b, seed):
+        """(options, the initial embedding or None): init is "panel", "random" or an array / tensor to start from"""
+        o = L.default_umap_options()
+        o.random_seed = int(self._seed if seed is None else seed)
+        o.n_neighbors, o.output_dim, o.negative_sample_rate = int(n_neighbors), int(output_dim), int(negative_sample_rate)
+        o.min_dist, o.spread, o.epochs = float(min_dist), float(spread), int(n_epochs or 0)
+        o.learning_rate, o.repulsion_strength = float(learning_rate), float(repulsion_strength)
+        if (a is None) != (b is None):
+            raise ValueError(f"a = {a!r}, b = {b!r}: give both, or neither to have them fitted from (spread, min_dist)")
+        o.a, o.b = (0.0, 0.0) if a is None else (float(a), float(b))
+        given = None
+        if isinstance(init, str):
+            if init.lower() not in L.UMAP_INITS:
+                raise ValueError(f"unknown init {init!r}: one of {sorted(L.UMAP_INITS)} or an initial embedding")
+            o.init = L.UMAP_INITS[init.lower()]
+        else:
+            o.init, given = L.UMAP_INIT_GIVEN, init
+        return o, given
+
+    def umap_graph(self, indices, dist, n_neighbors):
+        """sapca_umap_graph_device_*: (G, sigma, rho) from neighbour lists as knn() returns them (m x K device tensors, int32
+        indices and f32 / f64 distances; n_neighbors counts the point itself, usually K + 1).  G is the fuzzy union as a
+        canonical ResidentCsr in the Session's UMAP buffers (valid until the next graph call on the Session), sigma and rho
+        the m smooth-distance scales and offsets (f64 device tensors)."""
+        import torch
+        m, K, ld, dt = _knn_panel("dist", dist)
+        if not (isinstance(indices, torch.Tensor) and indices.dtype == torch.int32 and tuple(indices.shape) == (m, K)
+                and indices.is_contiguous() and dist.is_contiguous()):
+            raise ValueError("indices must be a contiguous int32 tensor of the shape of dist, dist contiguous")
+        if not (indices.is_cuda and dist.is_cuda):
+            raise ValueError("indices and dist must live on the device")
+        sigma = torch.empty((m,), dtype=torch.float64, device=dist.device)
+        rho = torch.empty((m,), dtype=torch.float64, device=dist.device)
+        suf = "f32" if dt == torch.float32 else "f64"
+        nnz = C.c_uint64()
+        dp, di, dv = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_umap_graph_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_void_p(indices.data_ptr() if m else None), C.c_void_p(dist.data_ptr() if m else None),
+            C.c_uint32(K), C.c_uint32(int(n_neighbors)), C.byref(nnz), C.byref(dp), C.byref(di), C.byref(dv),
+            C.c_void_p(sigma.data_ptr() if m else None), C.c_void_p(rho.data_ptr() if m else None)))
+        G = ResidentCsr(self, (m, m), nnz.value, np.float32 if suf == "f32" else np.float64, dp.value or 0, di.value or 0, dv.value or 0)
+        return G, sigma, rho
+
+    def umap_embed(self, G, n_epochs=None, output_dim=2, init="random", negative_sample_rate=5, learning_rate=1.0,
+                   repulsion_strength=1.0, min_dist=0.1, spread=1.0, a=None, b=None, seed=None):
+        """sapca_umap_embed_device_*: Y for the symmetric graph G (a ResidentCsr): the layout alone.  init: "random", or an
+        m x output_dim device tensor to start from (copied); "panel" needs the panel and is refused here."""
+        import torch
+        m = G.shape[0]
+        o, given = self._umap_options(2, min_dist, spread, n_epochs, output_dim, init, negative_sample_rate, learning_rate,
+                                      repulsion_strength, a, b, seed)
+        D = int(output_dim)
+        dt = torch.float32 if G.dtype == np.float32 else torch.float64
+        if given is not None:
+            if not (isinstance(given, torch.Tensor) and given.is_cuda and given.dtype == dt and tuple(given.shape) == (m, D)):
+                raise ValueError(f"init must be a device tensor of shape {(m, D)} and dtype {dt}")
+            Y = given.contiguous().clone()
+        else:
+            Y = torch.empty((m, D), dtype=dt, device=self._device())
+        suf = "f32" if dt == torch.float32 else "f64"
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_umap_embed_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_uint64(G.nnz), C.c_void_p(G.d_ptr), C.c_void_p(G.d_idx), C.c_void_p(G.d_val), C.byref(o),
+            C.c_void_p(Y.data_ptr() if m else None)))
+        return Y
+
+    def umap(self, X, n_neighbors=15, min_dist=0.1, spread=1.0, n_epochs=None, output_dim=2, init="panel", negative_sample_rate=5,
+             learning_rate=1.0, repulsion_strength=1.0, a=None, b=None, seed=None):
+        """sapca_umap_device_* / sapca_umap_*: Y, the UMAP embedding of the rows of X.  X: an m x d torch device tensor of
+        float32 / float64 with contiguous rows (a column slice of the scores is searched in place; Y is a device tensor), or a
+        numpy array (the host route; Y is a numpy array).  init: "panel" (the first output_dim columns of X scaled to 0 .. 10),
+        "random" (under `seed`, the Session's by default), or the initial embedding in the same kind of array.  n_epochs None:
+        500 for at most 10000 rows, else 200.  a, b None: fitted from (spread, min_dist).  The same bytes from call to call."""
+        o, given = self._umap_options(n_neighbors, min_dist, spread, n_epochs, output_dim, init, negative_sample_rate, learning_rate,
+                                      repulsion_strength, a, b, seed)
+        D = int(output_dim)
+        if isinstance(X, np.ndarray):
+            if X.ndim != 2 or X.dtype not in _SUF:
+                raise ValueError(f"X must be a two-dimensional float32 / float64 array, got {X.dtype} {X.shape}")
+            X = np.ascontiguousarray(X)
+            m, d = X.shape
+            Y = np.zeros((m, D), dtype=X.dtype)
+            if given is not None:
+                given = np.asarray(given)
+                if given.shape != (m, D):
+                    raise ValueError(f"init must have shape {(m, D)}, got {given.shape}")
+                Y[...] = given
+            suf, ct = _SUF[X.dtype]
+            L.check(self._h, getattr(L.load(), f"sapca_umap_{suf}")(
+                self._h, C.c_uint64(m), C.c_uint64(d), X.ctypes.data_as(C.c_void_p), C.byref(o), Y.ctypes.data_as(C.c_void_p)))
+            return Y
+        import torch
+        m, d, ld, dt = _knn_panel("X", X)
+        if not X.is_cuda:
+            raise ValueError(f"X must live on the device (a CUDA tensor) or be a numpy array, got a tensor on {X.device}")
+        if given is not None:
+            if not (isinstance(given, torch.Tensor) and given.is_cuda and given.dtype == dt and tuple(given.shape) == (m, D)):
+                raise ValueError(f"init must be a device tensor of shape {(m, D)} and dtype {dt}")
+            Y = given.contiguous().clone()
+        else:
+            Y = torch.empty((m, D), dtype=dt, device=X.device)
+        suf = "f32" if dt == torch.float32 else "f64"
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_umap_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_void_p(X.data_ptr() if m else None), C.c_uint64(ld), C.c_uint64(d), C.byref(o),
+            C.c_void_p(Y.data_ptr() if m else None)))
+        return Y
+
     # ---- k-means (sapca_kmeans_*): seeding, one assignment, one update, the whole run ----
     @staticmethod
     def _kmeans_shape(name, X, n_clusters, at_most_rows):

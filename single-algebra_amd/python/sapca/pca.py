@@ -574,6 +574,41 @@ class TSNE:
         return self
 
 
+class UMAP:
+    """UMAP of dense rows on the GPU (sapca_umap_*): umap-learn's fuzzy simplicial set and a synchronous, deterministic
+    restatement of its layout (include/sapca.h states the algorithm and the deviations), as an estimator.
+
+        emb = sapca.UMAP(n_neighbors=15, min_dist=0.1).fit_transform(scores)   # a torch device tensor, or a numpy array
+
+    `scores` is usually what SparsePCA.fit_transform left on the device; it is searched in place.  init: "panel" (the first
+    output_dim columns of X, scaled to 0 .. 10), "random", or an m x output_dim array to start from.  n_epochs None:
+    umap-learn's rule (500 for at most 10000 rows, else 200).  a, b None: fitted from (spread, min_dist).  After the call
+    `embedding_` holds the result."""
+
+    def __init__(self, n_neighbors=15, min_dist=0.1, spread=1.0, n_epochs=None, output_dim=2, init="panel", negative_sample_rate=5,
+                 learning_rate=1.0, repulsion_strength=1.0, a=None, b=None, random_seed=42):
+        self.n_neighbors, self.min_dist, self.spread, self.n_epochs = int(n_neighbors), float(min_dist), float(spread), n_epochs
+        self.output_dim, self.init, self.negative_sample_rate = int(output_dim), init, int(negative_sample_rate)
+        self.learning_rate, self.repulsion_strength = float(learning_rate), float(repulsion_strength)
+        self.a, self.b, self.random_seed = a, b, int(random_seed)
+        self.embedding_ = None
+        self._session = None
+
+    def fit_transform(self, X):
+        from .ops import Session
+        if self._session is None:
+            self._session = Session(seed=self.random_seed)
+        self.embedding_ = self._session.umap(
+            X, n_neighbors=self.n_neighbors, min_dist=self.min_dist, spread=self.spread, n_epochs=self.n_epochs,
+            output_dim=self.output_dim, init=self.init, negative_sample_rate=self.negative_sample_rate,
+            learning_rate=self.learning_rate, repulsion_strength=self.repulsion_strength, a=self.a, b=self.b, seed=self.random_seed)
+        return self.embedding_
+
+    def fit(self, X):
+        self.fit_transform(X)
+        return self
+
+
 class KMeans:
     """K-means clustering of dense rows on the GPU (sapca_kmeans_*): Lloyd's iteration under scikit-learn's stopping rule with
     k-means++ seeding, deterministic under `seed`; a cluster that loses all its rows keeps its centroid.
