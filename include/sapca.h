@@ -76,7 +76,10 @@ extern "C" {
                                                   sapca_kmeans_assign_device_*, sapca_kmeans_update_device_*,
                                                   sapca_kmeans_device_*, sapca_kmeans_*
                                  additive, ABI 4: sapca_umap_options_default, sapca_umap_find_ab, sapca_umap_graph_device_*,
-                                                  sapca_umap_embed_device_*, sapca_umap_device_*, sapca_umap_*          */
+                                                  sapca_umap_embed_device_*, sapca_umap_device_*, sapca_umap_*
+                                 additive, ABI 4: sapca_louvain_options_default, sapca_louvain_modularity_device_*,
+                                                  sapca_louvain_sweep_device_*, sapca_louvain_aggregate_device_*,
+                                                  sapca_louvain_device_*, sapca_louvain_*                               */
 
 typedef struct sapca_handle_s* sapca_handle;
 
@@ -994,6 +997,101 @@ sapca_status sapca_umap_device_f64(sapca_handle h, uint64_t m, const double* d_x
 /* The same with HOST arrays in and out (x: m x d row-major; y: m x output_dim, read for SAPCA_UMAP_INIT_GIVEN).             */
 sapca_status sapca_umap_f32(sapca_handle h, uint64_t m, uint64_t d, const float* x, const sapca_umap_options* opts, float* y);
 sapca_status sapca_umap_f64(sapca_handle h, uint64_t m, uint64_t d, const double* x, const sapca_umap_options* opts, double* y);
+
+/* ---- Louvain clustering of a resident graph (sapca_louvain_*): an opt-in superset, the reference has no graph clustering ----
+ * The step scanpy runs after `neighbors`: communities of the symmetric graph sapca_umap_graph_device_* leaves in the handle (its
+ * `connectivities`), without the graph leaving the device.  Sequential Louvain cannot be restated on a GPU bit for bit and a
+ * naive synchronous sweep oscillates, so the local moving is restated as hashed half-active sweeps with anchored targets;
+ * tests/louvain_ref.py says the same in numpy and is held to networkx's louvain_communities / modularity.
+ * Input: an m x m CSR, int64 offsets, int32 columns, values of type T, symmetric and canonical with finite weights >= 0.  A
+ * stored diagonal entry is A_ii.  Symmetry is trusted, as the offsets are.  All arithmetic is f64 from the stored T values,
+ * products and sums as written, no contraction.
+ * Per level (graph A with n vertices; level 0 is the input): k_i = sum_j A_ij, S = sum_i k_i, tot_C = sum_{c_i = C} k_i,
+ *   Q(c) = (sum_i s_i) / S - gamma sum_C (tot_C / S)^2,  s_i = sum_{j: c_j = c_i} A_ij (diagonal included).
+ * Orders of the sums: a row's k_i and s_i by 64 lanes (lane l adds the entries l, l + 64, .. in stored order) that meet in a
+ * butterfly; tot_C over C's members in ascending vertex order; the sums over all vertices / communities (S, sum s_i,
+ * sum (tot_C / S)^2) in an order fixed by n; a weight w_iD over the row's entries in stored order.  No floating-point atomic.
+ * If S == 0: every vertex is its own community, Q = 0, n_levels = 0.
+ * Start: c_i = i, Q = Q(c), misses = 0.  Sweep t = 0, 1, ..:
+ *   u_i = hash_u01(seed, 41, ((level 4096 + t) << 32) + i); vertex i is active iff u_i < 0.5; community C is anchored iff some
+ *   inactive vertex has c_i = C.  Each active i, with C = c_i, computes from the assignment at the start of the sweep only:
+ *   r_i = (gamma k_i) / S; w_iD = sum_{j != i, c_j = D} A_ij; g_C = w_iC - r_i (tot_C - k_i); for every anchored D != C that holds
+ *   at least one entry j != i of the row, g_D = w_iD - r_i tot_D.  i moves to the D of largest g_D if g_D > g_C strictly, ties
+ *   among D going to the lowest label; otherwise it stays.  Inactive vertices stay: no community that is joined in a sweep can
+ *   empty in that sweep.
+ *   Keep or undo: no vertex moved: a miss.  Otherwise Q' = Q(c'); Q' > Q + tol: c = c', Q = Q', misses = 0; else a miss and c
+ *   is unchanged.  The level ends at 4 consecutive misses or at t = max_sweeps.
+ * Between levels: a level that kept no sweep ends the run.  Otherwise communities are renumbered 0 .. n' - 1 in ascending order
+ * of label, the labels composed with the earlier levels', and the next graph is A'_CD = sum_{i in C, j in D} A_ij (C == D
+ * included; f64; canonical CSR), added first within each row i over its entries in stored order, then over the members i of C
+ * in ascending vertex order.  The run also ends at n' == 1 or after max_levels levels.
+ * Outputs: labels (m int32 in [0, n_communities)), n_communities, the last kept Q (the start's Q where nothing was kept) and
+ * n_levels, the levels that kept a sweep.
+ * Deterministic: the same bytes from call to call.  Within a level the loop enqueues kernels only; keep / undo is a word of a
+ * device control block that says which of two label generations is current, a device flag turns the sweeps enqueued behind
+ * the level's end into no-ops, and the host peeks at it every 8 sweeps, so nothing depends on when it looks.  Between levels the
+ * host reads back counts (rows per length class, n', the entries of the coarse graph) to size buffers and launches.  No kernel
+ * waits for another workgroup.  Integer atomics count moved vertices and hand out list slots whose order reaches no value.
+ * No address outside the arrays is touched: a column or a label outside [0, m) is skipped where it is read; such a vertex is
+ * inactive, anchors nothing and its label is copied through (the aggregation leaves it out).  Non-finite or negative weights
+ * or an asymmetric graph give unspecified labels inside their range; the call still terminates.
+ * All work is in buffers of the handle's own, distinct from the upload's, the selection's, the canonical form's, t-SNE's,
+ * k-means' and the UMAP graph's, which stay valid and untouched.  On a handle that belongs to a communicator the calls are
+ * local and issue no collective.
+ * SAPCA_ERR_ARG, checked on the host before anything is enqueued (the handle stays usable), each with a message that names the
+ * offending number: a wrong struct_size; resolution or tol negative or non-finite; max_sweeps outside 1 .. 4096; max_levels
+ * above 64; level >= 2^20 or sweep >= 4096 in the sweep call; m >= 2^31; a null pointer with a non-empty shape.  (The entry
+ * points take one dimension: a non-square graph cannot be passed.)  m == 0 is valid and writes nothing.                      */
+typedef struct sapca_louvain_options {
+  uint32_t struct_size;   /* sizeof(sapca_louvain_options): 32                */
+  uint32_t random_seed;   /* default 42                                       */
+  uint32_t max_levels;    /* default 0: 32; at most 64                        */
+  uint32_t max_sweeps;    /* default 256; 1 .. 4096                           */
+  double resolution;      /* gamma, default 1.0                               */
+  double tol;             /* default 1e-7 (networkx's threshold)              */
+} sapca_louvain_options;
+void sapca_louvain_options_default(sapca_louvain_options* opts);
+/* *modularity = Q(d_labels) at the given resolution (d_labels: m int32, DEVICE): on its own it scores any labels, k-means' for
+ * instance, on the graph.                                                                                                   */
+sapca_status sapca_louvain_modularity_device_f32(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets,
+                                                 const int32_t* col_indices, const float* values, const int32_t* d_labels,
+                                                 double resolution, double* modularity);
+sapca_status sapca_louvain_modularity_device_f64(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets,
+                                                 const int32_t* col_indices, const double* values, const int32_t* d_labels,
+                                                 double resolution, double* modularity);
+/* One sweep (no keep / undo) from d_labels_in into d_labels_out (m int32 each, DEVICE, distinct); *n_moved = the vertices that
+ * moved.                                                                                                                    */
+sapca_status sapca_louvain_sweep_device_f32(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets,
+                                            const int32_t* col_indices, const float* values, const int32_t* d_labels_in, uint32_t seed,
+                                            uint32_t level, uint32_t sweep, double resolution, int32_t* d_labels_out, uint64_t* n_moved);
+sapca_status sapca_louvain_sweep_device_f64(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets,
+                                            const int32_t* col_indices, const double* values, const int32_t* d_labels_in, uint32_t seed,
+                                            uint32_t level, uint32_t sweep, double resolution, int32_t* d_labels_out, uint64_t* n_moved);
+/* The coarse graph of d_labels: *n_out communities, *nnz_out entries, in handle-owned DEVICE arrays with f64 values in both
+ * variants (it feeds the _f64 stage calls), valid until the next Louvain call.  d_renumbered (m int32, DEVICE, may be NULL)
+ * receives every vertex's renumbered label.                                                                                 */
+sapca_status sapca_louvain_aggregate_device_f32(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets,
+                                                const int32_t* col_indices, const float* values, const int32_t* d_labels, uint64_t* n_out,
+                                                uint64_t* nnz_out, const int64_t** d_row_offsets, const int32_t** d_col_indices,
+                                                double** d_values, int32_t* d_renumbered);
+sapca_status sapca_louvain_aggregate_device_f64(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets,
+                                                const int32_t* col_indices, const double* values, const int32_t* d_labels, uint64_t* n_out,
+                                                uint64_t* nnz_out, const int64_t** d_row_offsets, const int32_t** d_col_indices,
+                                                double** d_values, int32_t* d_renumbered);
+/* The whole run on a resident graph: d_labels (m int32, DEVICE) out; n_communities, modularity, n_levels may be NULL.       */
+sapca_status sapca_louvain_device_f32(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                      const float* values, const sapca_louvain_options* opts, int32_t* d_labels, uint64_t* n_communities,
+                                      double* modularity, uint32_t* n_levels);
+sapca_status sapca_louvain_device_f64(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                      const double* values, const sapca_louvain_options* opts, int32_t* d_labels, uint64_t* n_communities,
+                                      double* modularity, uint32_t* n_levels);
+/* The same with a HOST CSR in (int64 offsets, int32 columns, as on the device) and HOST labels out.                         */
+sapca_status sapca_louvain_f32(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                               const float* values, const sapca_louvain_options* opts, int32_t* labels, uint64_t* n_communities,
+                               double* modularity, uint32_t* n_levels);
+sapca_status sapca_louvain_f64(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                               const double* values, const sapca_louvain_options* opts, int32_t* labels, uint64_t* n_communities,
+                               double* modularity, uint32_t* n_levels);
 
 /* Measurement support: the rate (GB/s, read + write counted) of a 16-byte-per-lane streaming copy of `bytes`
  * bytes on the handle's device, best of `reps` -- the HBM rate a kernel of this library can attain, reported by

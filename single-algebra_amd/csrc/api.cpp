@@ -897,6 +897,37 @@ sapca_status sapca_get_column_scale(sapca_handle h, int32_t* mode, double* out, 
   sapca_status sapca_umap_##SUF(sapca_handle h, uint64_t m, uint64_t d, const T* x, const sapca_umap_options* opts, T* y) { \
     return guarded(h, [&] { resident::umap_host<T>(*h, m, d, x, opts, y); });                                            \
   }                                                                                                                      \
+  sapca_status sapca_louvain_modularity_device_##SUF(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* p, const int32_t* i, \
+                                                     const T* v, const int32_t* d_labels, double resolution, double* modularity) { \
+    return guarded(h, [&] { resident::louvain_modularity<T>(*h, unchecked_view(m, m, nnz, p, i, v), d_labels, resolution, modularity); }); \
+  }                                                                                                                      \
+  sapca_status sapca_louvain_sweep_device_##SUF(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* p, const int32_t* i, \
+                                                const T* v, const int32_t* d_labels_in, uint32_t seed, uint32_t level,     \
+                                                uint32_t sweep, double resolution, int32_t* d_labels_out, uint64_t* n_moved) { \
+    return guarded(h, [&] {                                                                                              \
+      resident::louvain_sweep<T>(*h, unchecked_view(m, m, nnz, p, i, v), d_labels_in, seed, level, sweep, resolution, d_labels_out, \
+                                 n_moved);                                                                               \
+    });                                                                                                                  \
+  }                                                                                                                      \
+  sapca_status sapca_louvain_aggregate_device_##SUF(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* p, const int32_t* i, \
+                                                    const T* v, const int32_t* d_labels, uint64_t* n_out, uint64_t* nnz_out, \
+                                                    const int64_t** dp, const int32_t** di, double** dv, int32_t* d_renumbered) { \
+    return guarded(h, [&] {                                                                                              \
+      resident::louvain_aggregate<T>(*h, unchecked_view(m, m, nnz, p, i, v), d_labels, n_out, nnz_out, dp, di, dv, d_renumbered); \
+    });                                                                                                                  \
+  }                                                                                                                      \
+  sapca_status sapca_louvain_device_##SUF(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* p, const int32_t* i,      \
+                                          const T* v, const sapca_louvain_options* opts, int32_t* d_labels,                \
+                                          uint64_t* n_communities, double* modularity, uint32_t* n_levels) {               \
+    return guarded(h, [&] {                                                                                              \
+      resident::louvain_device<T>(*h, unchecked_view(m, m, nnz, p, i, v), opts, d_labels, n_communities, modularity, n_levels); \
+    });                                                                                                                  \
+  }                                                                                                                      \
+  sapca_status sapca_louvain_##SUF(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, \
+                                   const sapca_louvain_options* opts, int32_t* labels, uint64_t* n_communities,           \
+                                   double* modularity, uint32_t* n_levels) {                                              \
+    return guarded(h, [&] { resident::louvain_host<T>(*h, m, nnz, p, i, v, opts, labels, n_communities, modularity, n_levels); }); \
+  }                                                                                                                      \
   sapca_status sapca_kmeans_seed_device_##SUF(sapca_handle h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d,           \
                                               uint32_t n_clusters, uint32_t random_seed, T* d_centroids, int32_t* d_rows) { \
     return guarded(h, [&] { resident::kmeans_seed<T>(*h, m, d_x, ldx, d, n_clusters, random_seed, d_centroids, d_rows); }); \
@@ -961,6 +992,17 @@ void sapca_kmeans_options_default(sapca_kmeans_options* o) {
   o->init = SAPCA_KMEANS_PLUSPLUS;
   o->max_iter = 300;
   o->tol = 1e-4;
+}
+
+void sapca_louvain_options_default(sapca_louvain_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  o->struct_size = (uint32_t)sizeof(sapca_louvain_options);
+  o->random_seed = 42;
+  o->max_levels = 0;
+  o->max_sweeps = 256;
+  o->resolution = 1.0;
+  o->tol = 1e-7;
 }
 
 void sapca_umap_options_default(sapca_umap_options* o) {

@@ -188,6 +188,20 @@ struct sapca_handle_s {
       return raw_ptr.contains(q) || out_ptr.contains(q) || raw_idx.contains(q) || sort_idx.contains(q) || out_val.contains(q);
     }
   } umap;
+  // sapca_louvain_*: the row lists per length class and the long rows' keys (of the level's graph, and `2` of the coarse rows
+  // before their merge), the vertex sort's keys, k, s and (tot / S)^2 per vertex, the two generations of labels and totals, the
+  // anchor bytes, the control block, the renumbering and the aggregation's counts, places and unmerged coarse rows, the two
+  // coarse graphs that alternate from level to level (the aggregate call's result is set 0), the composed labels of the host
+  // route and its graph.  Nothing else lives in these.
+  struct Louvain {
+    sapca::DevBuf lists, long_off, ctr, keys, skeys, k, srow, sq, sum_part, tot0, tot1, lab0, lab1, anchored, ctl, scan;
+    sapca::DevBuf flag, renum, cnt, rawcnt, pos, raw_ptr, raw_idx, raw_val, lists2, long_off2, keys2, cnt2;
+    sapca::DevBuf agg_ptr[2], agg_idx[2], agg_val[2], in_ptr, in_idx, in_val, labels;
+    bool owns(const void* q) const {
+      return agg_ptr[0].contains(q) || agg_idx[0].contains(q) || agg_val[0].contains(q) || agg_ptr[1].contains(q) ||
+             agg_idx[1].contains(q) || agg_val[1].contains(q);
+    }
+  } louvain;
   sapca::DevBuf at_ptr, at_idx, at_val;                          // A^T
   sapca::DevBuf ca_ptr, ca_idx, ca_val, cat_ptr, cat_idx, cat_val;  // mask-compacted A, A^T
   sapca::DevBuf drop_stats, drop_tmp;                              // their sums (sum | sumsq, full width) and the sort's work space

@@ -515,6 +515,69 @@ void kmeans_fold_columns(const double* partial, int slices, int d, int64_t m, do
 // a strict run's labels are those of its last iteration: out = (ctl[kKmIter] - 1) & 1 ? lab1 : lab0 when ctl[kKmStrict]
 void kmeans_take_labels(const unsigned long long* ctl, const int32_t* lab0, const int32_t* lab1, int32_t* out, int64_t m, hipStream_t s);
 
+// ---- louvain.hip: Louvain clustering of a symmetric CSR graph (sapca_louvain_*); include/sapca.h states the algorithm ------
+// The control block of a level (device).  A kernel that takes a LouvainState returns at once when ctl->done is set (and, where
+// it works on the candidate assignment, when ctl->moved is 0); ctl null: never.  `cur` says which of the two label / total
+// generations holds the kept assignment; flip = 1 addresses the other, the candidate.
+struct LouvainCtl {
+  unsigned long long done, cur, sweeps, misses, kept, moved;
+  double Q, S, sum_s, sum_sq, tol, gamma;
+};
+struct LouvainState {
+  LouvainCtl* ctl = nullptr;
+  int32_t* lab[2] = {nullptr, nullptr};   // (lab[0] null with ctl null: every vertex its own community, the coarse rows' merge)
+  double* tot[2] = {nullptr, nullptr};
+};
+// rows per length class: <= kLvWaveCap entries (a wave, keys in 512 bytes of LDS), <= kLvLdsCap (a workgroup, keys in LDS),
+// longer (a workgroup, keys in global scratch: ctr[kLvLongKeys] of them in all, row j of the class at long_off[j])
+constexpr int kLvWaveCap = 64, kLvLdsCap = 4096;
+enum { kLvListWave = 0, kLvListLds = 1, kLvListLong = 2, kLvLongKeys = 3, kLvCtrWords = 4 };
+struct LouvainLists {
+  const uint32_t* rows = nullptr;   // 3 n words: class c at rows + c n, in no particular order
+  const unsigned long long* long_off = nullptr;
+  int64_t n = 0, counts[3] = {0, 0, 0};
+  unsigned long long* keys = nullptr;
+};
+void louvain_list_rows(const int64_t* ptr, int64_t n, uint32_t* rows, unsigned long long* long_off, unsigned long long* ctr, hipStream_t s);
+void louvain_iota(int32_t* lab, int64_t n, hipStream_t s);
+// internal false: out[i] = k_i, the sum of row i over its columns inside [0, n).  true: s_i under the labels (st, flip): the
+// entries whose column carries the row's label, 0 for a row whose label is outside [0, n).  One wave per row: lane l adds the
+// entries l, l + 64, .. in order and the lanes meet in a fixed butterfly.
+template <typename TV>
+void louvain_row_sums(const CsrView<TV>& A, const LouvainState& st, int flip, bool internal, double* out, hipStream_t s);
+// anchored[C] = 1 where an inactive vertex carries label C (cleared here); active: hash_u01(seed, 41, ((level 4096 + sweep) << 32) + i) < 0.5
+void louvain_anchor(const LouvainState& st, int64_t n, uint64_t seed, uint64_t level, uint64_t sweep, uint8_t* anchored, hipStream_t s);
+// one local-moving sweep from the kept assignment into the candidate generation; ctl->moved += the vertices that moved
+template <typename TV>
+void louvain_sweep(const CsrView<TV>& A, const LouvainLists& L, const LouvainState& st, const double* k, const uint8_t* anchored,
+                   uint64_t seed, uint64_t level, uint64_t sweep, hipStream_t s);
+int64_t louvain_sort_len(int64_t n);   // keys the vertex sort needs
+// the vertices sorted by (label, vertex) into keys (label << 32 | vertex, a label outside [0, n) left out), tot[C] = the sum of
+// k over C's members in ascending vertex order (0 for an empty C), sq[C] = (tot[C] / *S)^2 (sq, S nullable)
+void louvain_totals(const LouvainState& st, int flip, bool need_moved, int64_t n, const double* k, unsigned long long* keys, const double* S,
+                    double* sq, hipStream_t s);
+// the end of a sweep: keep or undo, misses, done (init: Q = Q of the generation just summed, nothing else)
+void louvain_decide(const LouvainState& st, bool init, hipStream_t s);
+// aggregation: flag[C] = 1 for every label in use (flag: n + 1 words, cleared here; its exclusive scan renumbers)
+void louvain_flag(const int32_t* labels, int64_t n, int64_t* flag, hipStream_t s);
+// renum[C] = int32 of the scan; renumbered[i] (nullable) = renum[labels[i]], a label outside [0, n) copied through
+void louvain_renumber(const int32_t* labels, int64_t n, const int64_t* scan, int32_t* renum, int32_t* renumbered, hipStream_t s);
+// cnt[i] = the distinct labels among the entries of row i (diagonal included; 0 for a row whose own label is out of range)
+template <typename TV>
+void louvain_group_count(const CsrView<TV>& A, const LouvainLists& L, const int32_t* labels, int64_t* cnt, hipStream_t s);
+// pos[vertex] = its place p in the sorted keys, rawcnt[p] = cnt[vertex] (0 behind the last vertex; n + 1 words)
+void louvain_positions(const unsigned long long* keys, int64_t n, const int64_t* cnt, int32_t* pos, int64_t* rawcnt, hipStream_t s);
+// rawptr[renum[C]] = rawoff[first member of C], rawptr[n'] = rawoff[n] (n' = scan[n], on the device)
+void louvain_coarse_offsets(const unsigned long long* keys, int64_t n, const int64_t* rawoff, const int32_t* renum, const int64_t* scan,
+                            int64_t* rawptr, hipStream_t s);
+// row i's entries grouped by label, each group's f64 sum added in stored order, written at out_off[pos ? pos[i] : i] in
+// ascending label order as (renum ? renum[label] : label, sum)
+template <typename TV>
+void louvain_group_emit(const CsrView<TV>& A, const LouvainLists& L, const int32_t* labels, const int32_t* renum, const int64_t* out_off,
+                        const int32_t* pos, int32_t* out_idx, double* out_val, hipStream_t s);
+// final[v] = renum[labels[first ? v : final[v]]]
+void louvain_compose(int32_t* final_labels, int64_t m, const int32_t* labels, const int32_t* renum, bool first, hipStream_t s);
+
 // ---- rng.hip ---------------------------------------------------------------------------
 // Omega[r][j] ~ N(0,1) for j < l (zero for l <= j < ld), a pure function of (seed, r*l+j).
 template <typename T>

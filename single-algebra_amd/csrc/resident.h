@@ -103,5 +103,23 @@ void umap_device(H& h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d, const
 template <typename T>
 void umap_host(H& h, uint64_t m, uint64_t d, const T* x, const sapca_umap_options* opts, T* y);
 
+
+// sapca_louvain_* (louvain.cpp): the modularity of given labels, one sweep, one aggregation, and the whole run on a resident
+// graph or on host arrays
+template <typename T>
+void louvain_modularity(H& h, const CsrView<T>& G, const int32_t* d_labels, double resolution, double* modularity);
+template <typename T>
+void louvain_sweep(H& h, const CsrView<T>& G, const int32_t* d_labels_in, uint32_t seed, uint32_t level, uint32_t sweep, double resolution,
+                   int32_t* d_labels_out, uint64_t* n_moved);
+template <typename T>
+void louvain_aggregate(H& h, const CsrView<T>& G, const int32_t* d_labels, uint64_t* n_out, uint64_t* nnz_out, const int64_t** d_ptr,
+                       const int32_t** d_idx, double** d_val, int32_t* d_renumbered);
+template <typename T>
+void louvain_device(H& h, const CsrView<T>& G, const sapca_louvain_options* opts, int32_t* d_labels, uint64_t* n_communities,
+                    double* modularity, uint32_t* n_levels);
+template <typename T>
+void louvain_host(H& h, uint64_t m, uint64_t nnz, const int64_t* ptr, const int32_t* idx, const T* val, const sapca_louvain_options* opts,
+                  int32_t* labels, uint64_t* n_communities, double* modularity, uint32_t* n_levels);
+
 }  // namespace resident
 }  // namespace sapca

@@ -226,6 +226,82 @@ inline void umap(sapca_handle h, uint64_t m, uint64_t d, const T* host_x, const 
   umap_check(h, UmapAbi<T>::host(h, m, d, host_x, &opts, host_y));
 }
 
+// Louvain clustering of a device-resident symmetric graph (sapca_louvain_*; include/sapca.h states the algorithm).
+// LouvainOptions() holds the library's defaults.  Every pointer but the options is a DEVICE pointer unless the name says host.
+struct LouvainOptions : sapca_louvain_options {
+  LouvainOptions() { sapca_louvain_options_default(this); }
+};
+struct LouvainResult {
+  uint64_t n_communities = 0;
+  double modularity = 0.0;
+  uint32_t n_levels = 0;
+};
+struct LouvainCoarse {   // handle-owned, f64 values, valid until the next Louvain call
+  uint64_t n = 0, nnz = 0;
+  const int64_t* row_offsets = nullptr;
+  const int32_t* col_indices = nullptr;
+  double* values = nullptr;
+};
+template <typename T> struct LouvainAbi;
+template <> struct LouvainAbi<float> {
+  static constexpr auto modularity = &sapca_louvain_modularity_device_f32;
+  static constexpr auto sweep = &sapca_louvain_sweep_device_f32;
+  static constexpr auto aggregate = &sapca_louvain_aggregate_device_f32;
+  static constexpr auto device = &sapca_louvain_device_f32;
+  static constexpr auto host = &sapca_louvain_f32;
+};
+template <> struct LouvainAbi<double> {
+  static constexpr auto modularity = &sapca_louvain_modularity_device_f64;
+  static constexpr auto sweep = &sapca_louvain_sweep_device_f64;
+  static constexpr auto aggregate = &sapca_louvain_aggregate_device_f64;
+  static constexpr auto device = &sapca_louvain_device_f64;
+  static constexpr auto host = &sapca_louvain_f64;
+};
+inline void louvain_check(sapca_handle h, sapca_status st) {
+  if (st != SAPCA_OK) throw Error(st, sapca_last_error(h));
+}
+template <typename T>
+inline double louvain_modularity_device(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                        const T* values, const int32_t* d_labels, double resolution = 1.0) {
+  double q = 0.0;
+  louvain_check(h, LouvainAbi<T>::modularity(h, m, nnz, row_offsets, col_indices, values, d_labels, resolution, &q));
+  return q;
+}
+template <typename T>
+inline uint64_t louvain_sweep_device(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                     const T* values, const int32_t* d_labels_in, uint32_t seed, uint32_t level, uint32_t sweep,
+                                     double resolution, int32_t* d_labels_out) {
+  uint64_t moved = 0;
+  louvain_check(h, LouvainAbi<T>::sweep(h, m, nnz, row_offsets, col_indices, values, d_labels_in, seed, level, sweep, resolution,
+                                        d_labels_out, &moved));
+  return moved;
+}
+template <typename T>
+inline LouvainCoarse louvain_aggregate_device(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets,
+                                              const int32_t* col_indices, const T* values, const int32_t* d_labels,
+                                              int32_t* d_renumbered = nullptr) {
+  LouvainCoarse c;
+  louvain_check(h, LouvainAbi<T>::aggregate(h, m, nnz, row_offsets, col_indices, values, d_labels, &c.n, &c.nnz, &c.row_offsets,
+                                            &c.col_indices, &c.values, d_renumbered));
+  return c;
+}
+template <typename T>
+inline LouvainResult louvain_device(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                    const T* values, const sapca_louvain_options& opts, int32_t* d_labels) {
+  LouvainResult r;
+  louvain_check(h, LouvainAbi<T>::device(h, m, nnz, row_offsets, col_indices, values, &opts, d_labels, &r.n_communities, &r.modularity,
+                                         &r.n_levels));
+  return r;
+}
+template <typename T>
+inline LouvainResult louvain(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* host_row_offsets, const int32_t* host_col_indices,
+                             const T* host_values, const sapca_louvain_options& opts, int32_t* host_labels) {
+  LouvainResult r;
+  louvain_check(h, LouvainAbi<T>::host(h, m, nnz, host_row_offsets, host_col_indices, host_values, &opts, host_labels, &r.n_communities,
+                                       &r.modularity, &r.n_levels));
+  return r;
+}
+
 // K-means of device-resident rows (sapca_kmeans_*; include/sapca.h states the algorithm).  KmeansOptions() holds the library's
 // defaults.  Every pointer is a DEVICE pointer unless the name says host.
 struct KmeansOptions : sapca_kmeans_options {

@@ -717,6 +717,92 @@ pub mod umap {
     }
 }
 
+/// Louvain communities of a symmetric graph on the GPU (sapca_louvain_*; include/sapca.h states the algorithm): an opt-in
+/// superset, the reference has no graph clustering.  The graph is a host CSR with i64 offsets and i32 columns.
+pub mod louvain {
+    use super::{check, ffi};
+    use anyhow::{anyhow, Result};
+    use sapca_sys::sapca_louvain_options as RawOptions;
+
+    #[derive(Clone, Copy, Debug)]
+    pub struct LouvainConfig {
+        pub resolution: f64,
+        pub tol: f64,
+        pub max_sweeps: u32,
+        /// 0: 32
+        pub max_levels: u32,
+        pub random_seed: u32,
+    }
+    impl Default for LouvainConfig {
+        fn default() -> Self {
+            Self { resolution: 1.0, tol: 1e-7, max_sweeps: 256, max_levels: 0, random_seed: 42 }
+        }
+    }
+
+    #[derive(Clone, Debug)]
+    pub struct LouvainResult {
+        pub labels: Vec<i32>,
+        pub n_communities: usize,
+        pub modularity: f64,
+        pub n_levels: u32,
+    }
+
+    fn options(config: &LouvainConfig) -> RawOptions {
+        let mut o: RawOptions = unsafe { std::mem::zeroed() };
+        unsafe { ffi::sapca_louvain_options_default(&mut o) };
+        o.resolution = config.resolution;
+        o.tol = config.tol;
+        o.max_sweeps = config.max_sweeps;
+        o.max_levels = config.max_levels;
+        o.random_seed = config.random_seed;
+        o
+    }
+
+    fn with_handle<R>(f: impl FnOnce(ffi::sapca_handle) -> Result<R>) -> Result<R> {
+        let mut o: ffi::sapca_options = unsafe { std::mem::zeroed() };
+        unsafe { ffi::sapca_options_default(&mut o) };
+        let mut h: ffi::sapca_handle = std::ptr::null_mut();
+        if unsafe { ffi::sapca_create(&o, &mut h) } != ffi::SAPCA_OK {
+            return Err(anyhow!("sapca_create failed (no usable GPU?)"));
+        }
+        let r = f(h);
+        unsafe { ffi::sapca_destroy(h) };
+        r
+    }
+
+    fn shape_of(row_offsets: &[i64], col_indices: &[i32], n_values: usize) -> Result<(usize, usize)> {
+        if row_offsets.is_empty() { return Err(anyhow!("Louvain wants m + 1 row offsets, got none")); }
+        if col_indices.len() != n_values {
+            return Err(anyhow!("Louvain wants as many column indices as values, got {} and {}", col_indices.len(), n_values));
+        }
+        Ok((row_offsets.len() - 1, n_values))
+    }
+
+    pub fn run_f32(row_offsets: &[i64], col_indices: &[i32], values: &[f32], config: LouvainConfig) -> Result<LouvainResult> {
+        let (m, nnz) = shape_of(row_offsets, col_indices, values.len())?;
+        let o = options(&config);
+        let mut labels = vec![0i32; m];
+        let (mut n, mut q, mut levels) = (0u64, 0f64, 0u32);
+        with_handle(|h| check(h, unsafe {
+            ffi::sapca_louvain_f32(h, m as u64, nnz as u64, row_offsets.as_ptr(), col_indices.as_ptr(), values.as_ptr(), &o,
+                                   labels.as_mut_ptr(), &mut n, &mut q, &mut levels)
+        }))?;
+        Ok(LouvainResult { labels, n_communities: n as usize, modularity: q, n_levels: levels })
+    }
+
+    pub fn run_f64(row_offsets: &[i64], col_indices: &[i32], values: &[f64], config: LouvainConfig) -> Result<LouvainResult> {
+        let (m, nnz) = shape_of(row_offsets, col_indices, values.len())?;
+        let o = options(&config);
+        let mut labels = vec![0i32; m];
+        let (mut n, mut q, mut levels) = (0u64, 0f64, 0u32);
+        with_handle(|h| check(h, unsafe {
+            ffi::sapca_louvain_f64(h, m as u64, nnz as u64, row_offsets.as_ptr(), col_indices.as_ptr(), values.as_ptr(), &o,
+                                   labels.as_mut_ptr(), &mut n, &mut q, &mut levels)
+        }))?;
+        Ok(LouvainResult { labels, n_communities: n as usize, modularity: q, n_levels: levels })
+    }
+}
+
 /// The reference's module tree (src/dimred/pca/mod.rs:36-42; README.md:51-53 imports
 /// `dimred::pca::{SparsePCABuilder, SVDMethod}` and `dimred::pca::sparse::PowerIterationNormalizer`).
 pub mod dimred {

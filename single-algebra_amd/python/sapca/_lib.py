@@ -59,6 +59,14 @@ class KmeansOptions(C.Structure):
     ]
 
 
+class LouvainOptions(C.Structure):
+    """sapca_louvain_options"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("random_seed", C.c_uint32), ("max_levels", C.c_uint32), ("max_sweeps", C.c_uint32),
+        ("resolution", C.c_double), ("tol", C.c_double),
+    ]
+
+
 class UmapOptions(C.Structure):
     """sapca_umap_options"""
     _fields_ = [
@@ -123,6 +131,8 @@ _TYPED = [
     "sapca_tsne_affinities_device", "sapca_tsne_gradient_device", "sapca_tsne_embed_device", "sapca_tsne_device", "sapca_tsne",
     "sapca_kmeans_seed_device", "sapca_kmeans_assign_device", "sapca_kmeans_update_device", "sapca_kmeans_device", "sapca_kmeans",
     "sapca_umap_graph_device", "sapca_umap_embed_device", "sapca_umap_device", "sapca_umap",
+    "sapca_louvain_modularity_device", "sapca_louvain_sweep_device", "sapca_louvain_aggregate_device", "sapca_louvain_device",
+    "sapca_louvain",
     "sapca_multi_fit_csr", "sapca_multi_transform_csr", "sapca_multi_fit_transform_csr",
     "sapca_multi_upload_csr", "sapca_multi_transform_resident", "sapca_multi_fit_transform_resident",
 ]
@@ -137,7 +147,7 @@ _PLAIN = [
     "sapca_covariate_basis", "sapca_set_covariates", "sapca_get_covariate_rank",
     "sapca_set_column_scaling", "sapca_get_column_scale",
     "sapca_tsne_options_default", "sapca_kmeans_options_default",
-    "sapca_umap_options_default", "sapca_umap_find_ab",
+    "sapca_umap_options_default", "sapca_umap_find_ab", "sapca_louvain_options_default",
 ]
 EXPORTED_SYMBOLS = _PLAIN + [f"{n}_{s}" for n in _TYPED for s in ("f32", "f64")]
 
@@ -279,7 +289,27 @@ def _open(path):
                                                                  C.POINTER(UmapOptions), C.c_void_p]
             getattr(lib, f"sapca_umap_{suf}").argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(UmapOptions),
                                                           C.c_void_p]
+    if hasattr(lib, "sapca_louvain_options_default"):   # (absent from an older build loaded for an A/B run)
+        lib.sapca_louvain_options_default.argtypes = [C.POINTER(LouvainOptions)]
+        lib.sapca_louvain_options_default.restype = None
+        csr = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]   # h, m, nnz, offsets, columns, values
+        for suf in ("f32", "f64"):
+            getattr(lib, f"sapca_louvain_modularity_device_{suf}").argtypes = csr + [C.c_void_p, C.c_double, C.POINTER(C.c_double)]
+            getattr(lib, f"sapca_louvain_sweep_device_{suf}").argtypes = csr + [
+                C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_void_p, C.POINTER(C.c_uint64)]
+            getattr(lib, f"sapca_louvain_aggregate_device_{suf}").argtypes = csr + [
+                C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                C.POINTER(C.c_void_p), C.c_void_p]
+            for name in (f"sapca_louvain_device_{suf}", f"sapca_louvain_{suf}"):
+                getattr(lib, name).argtypes = csr + [C.POINTER(LouvainOptions), C.c_void_p, C.POINTER(C.c_uint64),
+                                                     C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     return lib
+
+
+def default_louvain_options() -> LouvainOptions:
+    o = LouvainOptions()
+    load().sapca_louvain_options_default(C.byref(o))
+    return o
 
 
 def default_umap_options() -> UmapOptions:

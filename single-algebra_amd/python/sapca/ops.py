@@ -560,6 +560,123 @@ class Session:
             C.c_void_p(cen.data_ptr()), C.c_void_p(labels.data_ptr() if m else None), C.byref(inertia), C.byref(n_iter)))
         return labels, cen, inertia.value, n_iter.value
 
+    # ---- Louvain (sapca_louvain_*): the modularity of labels, one sweep, one aggregation, the whole run ----
+    @staticmethod
+    def _louvain_graph(G):
+        if not isinstance(G, ResidentCsr) or G.shape[0] != G.shape[1]:
+            raise ValueError("the graph must be a square ResidentCsr (what umap_graph returns)")
+        return G.shape[0], _SUF[G.dtype][0]
+
+    @staticmethod
+    def _louvain_labels(labels, m):
+        import torch
+        if isinstance(labels, np.ndarray):
+            labels = torch.as_tensor(np.ascontiguousarray(labels, dtype=np.int32), device="cuda")
+        if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int32 and tuple(labels.shape) == (m,)
+                and labels.is_contiguous()):
+            raise ValueError(f"labels must be {m} contiguous int32 values (a device tensor or a numpy array)")
+        return labels
+
+    @staticmethod
+    def _louvain_gamma(resolution):
+        if not (float(resolution) >= 0.0 and np.isfinite(float(resolution))):
+            raise ValueError(f"resolution must be finite and not negative, got {resolution}")
+        return float(resolution)
+
+    def modularity(self, G, labels, resolution=1.0):
+        """sapca_louvain_modularity_device_*: Q of `labels` (m int32: a device tensor, or a numpy array that is uploaded) on the
+        symmetric graph G (a ResidentCsr), at the given resolution: scores any labels, k-means' for instance."""
+        import torch
+        m, suf = self._louvain_graph(G)
+        gamma = self._louvain_gamma(resolution)
+        labels = self._louvain_labels(labels, m)
+        q = C.c_double()
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_louvain_modularity_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_uint64(G.nnz), C.c_void_p(G.d_ptr), C.c_void_p(G.d_idx), C.c_void_p(G.d_val),
+            C.c_void_p(labels.data_ptr() if m else None), C.c_double(gamma), C.byref(q)))
+        return q.value
+
+    def louvain_sweep(self, G, labels, seed=None, level=0, sweep=0, resolution=1.0):
+        """sapca_louvain_sweep_device_*: (labels', n_moved) -- one hashed half-active sweep from `labels`, no keep / undo."""
+        import torch
+        m, suf = self._louvain_graph(G)
+        gamma = self._louvain_gamma(resolution)
+        labels = self._louvain_labels(labels, m)
+        out = torch.empty_like(labels)
+        moved = C.c_uint64()
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_louvain_sweep_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_uint64(G.nnz), C.c_void_p(G.d_ptr), C.c_void_p(G.d_idx), C.c_void_p(G.d_val),
+            C.c_void_p(labels.data_ptr() if m else None), C.c_uint32(int(self._seed if seed is None else seed)), C.c_uint32(int(level)),
+            C.c_uint32(int(sweep)), C.c_double(gamma), C.c_void_p(out.data_ptr() if m else None), C.byref(moved)))
+        return out, moved.value
+
+    def louvain_aggregate(self, G, labels):
+        """sapca_louvain_aggregate_device_*: (coarse graph, renumbered labels) -- the communities of `labels` as vertices, f64
+        values whatever G's; a ResidentCsr in the Session's Louvain buffers, valid until the next Louvain call."""
+        import torch
+        m, suf = self._louvain_graph(G)
+        labels = self._louvain_labels(labels, m)
+        ren = torch.empty_like(labels)
+        n_out, nnz = C.c_uint64(), C.c_uint64()
+        dp, di, dv = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_louvain_aggregate_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_uint64(G.nnz), C.c_void_p(G.d_ptr), C.c_void_p(G.d_idx), C.c_void_p(G.d_val),
+            C.c_void_p(labels.data_ptr() if m else None), C.byref(n_out), C.byref(nnz), C.byref(dp), C.byref(di), C.byref(dv),
+            C.c_void_p(ren.data_ptr() if m else None)))
+        return ResidentCsr(self, (n_out.value, n_out.value), nnz.value, np.float64, dp.value or 0, di.value or 0, dv.value or 0), ren
+
+    def _louvain_options(self, resolution, tol, max_sweeps, max_levels, seed):
+        o = L.default_louvain_options()
+        o.random_seed = int(self._seed if seed is None else seed)
+        o.resolution = self._louvain_gamma(resolution)
+        if not (float(tol) >= 0.0 and np.isfinite(float(tol))):
+            raise ValueError(f"tol must be finite and not negative, got {tol}")
+        if not 1 <= int(max_sweeps) <= 4096:
+            raise ValueError(f"max_sweeps = {max_sweeps} is outside 1 .. 4096")
+        if max_levels is not None and not 1 <= int(max_levels) <= 64:
+            raise ValueError(f"max_levels = {max_levels} is outside 1 .. 64")
+        o.tol, o.max_sweeps, o.max_levels = float(tol), int(max_sweeps), 0 if max_levels is None else int(max_levels)
+        return o
+
+    def louvain(self, G_or_X, resolution=1.0, tol=1e-7, max_sweeps=256, max_levels=None, seed=None, n_neighbors=15):
+        """sapca_louvain_device_*: (labels, n_communities, modularity, n_levels) -- Louvain communities (include/sapca.h states
+        the algorithm) of a symmetric graph.  A ResidentCsr is clustered as it is; an m x d device panel goes through knn
+        (Euclidean, self excluded, n_neighbors - 1), umap_graph and then the run.  labels: m int32 on the device.  The same bytes
+        from call to call."""
+        import torch
+        o = self._louvain_options(resolution, tol, max_sweeps, max_levels, seed)
+        G = G_or_X
+        if not isinstance(G, ResidentCsr):
+            idx, dist = self.knn(G_or_X, n_neighbors=int(n_neighbors) - 1, metric="euclidean", exclude_self=True)
+            G = self.umap_graph(idx, dist, int(n_neighbors))[0]
+        m, suf = self._louvain_graph(G)
+        labels = torch.empty((m,), dtype=torch.int32, device=self._device())
+        ncomm, q, levels = C.c_uint64(), C.c_double(), C.c_uint32()
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_louvain_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_uint64(G.nnz), C.c_void_p(G.d_ptr), C.c_void_p(G.d_idx), C.c_void_p(G.d_val), C.byref(o),
+            C.c_void_p(labels.data_ptr() if m else None), C.byref(ncomm), C.byref(q), C.byref(levels)))
+        return labels, ncomm.value, q.value, levels.value
+
+    def louvain_host(self, indptr, indices, data, resolution=1.0, tol=1e-7, max_sweeps=256, max_levels=None, seed=None):
+        """sapca_louvain_*: the same with a host CSR in (scipy's three arrays) and host labels out."""
+        o = self._louvain_options(resolution, tol, max_sweeps, max_levels, seed)
+        data = np.ascontiguousarray(data)
+        if data.dtype not in _SUF:
+            raise ValueError(f"data must be float32 / float64, got {data.dtype}")
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        m = len(indptr) - 1
+        labels = np.zeros((m,), dtype=np.int32)
+        ncomm, q, levels = C.c_uint64(), C.c_double(), C.c_uint32()
+        L.check(self._h, getattr(L.load(), f"sapca_louvain_{_SUF[data.dtype][0]}")(
+            self._h, C.c_uint64(m), C.c_uint64(len(data)), indptr.ctypes.data_as(C.c_void_p), indices.ctypes.data_as(C.c_void_p),
+            data.ctypes.data_as(C.c_void_p), C.byref(o), labels.ctypes.data_as(C.c_void_p), C.byref(ncomm), C.byref(q), C.byref(levels)))
+        return labels, ncomm.value, q.value, levels.value
+
 
 ROW, COLUMN = 0, 1   # Direction of the reference's Normalize / statistics traits (src/utils.rs)
 

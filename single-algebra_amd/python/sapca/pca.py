@@ -651,3 +651,37 @@ class KMeans:
         cen = torch.as_tensor(self.cluster_centers_, device=Xd.device).to(Xd.dtype)
         labels = ops.kmeans_assign(Xd, cen)[0]
         return labels.cpu().numpy() if host else labels
+
+
+class Louvain:
+    """Louvain communities of the neighbour graph on the GPU (sapca_louvain_*): what scanpy runs after `neighbors`, restated as
+    deterministic synchronous sweeps (include/sapca.h).
+
+        lv = sapca.Louvain(resolution=1.0)
+        labels = lv.fit_predict(scores)          # an m x d device tensor: knn -> fuzzy union -> communities; or a ResidentCsr graph
+        lv.labels_, lv.modularity_, lv.n_communities_, lv.n_levels_
+
+    The number of clusters is found, not given; `resolution` above 1 gives more and smaller communities."""
+
+    def __init__(self, resolution=1.0, tol=1e-7, max_sweeps=256, max_levels=None, n_neighbors=15, seed=42):
+        self.resolution, self.tol, self.max_sweeps, self.max_levels = float(resolution), float(tol), int(max_sweeps), max_levels
+        self.n_neighbors, self.seed = int(n_neighbors), int(seed)
+        self.labels_ = self.modularity_ = self.n_communities_ = self.n_levels_ = None
+        self._session = None
+
+    def _ops(self):
+        from .ops import Session
+        if self._session is None:
+            self._session = Session(seed=self.seed)
+        return self._session
+
+    def fit(self, G_or_X):
+        from .ops import ResidentCsr
+        ops = G_or_X._s if isinstance(G_or_X, ResidentCsr) else self._ops()   # (a resident graph is clustered by the Session that owns it)
+        self.labels_, self.n_communities_, self.modularity_, self.n_levels_ = ops.louvain(
+            G_or_X, resolution=self.resolution, tol=self.tol, max_sweeps=self.max_sweeps, max_levels=self.max_levels, seed=self.seed,
+            n_neighbors=self.n_neighbors)
+        return self
+
+    def fit_predict(self, G_or_X):
+        return self.fit(G_or_X).labels_
