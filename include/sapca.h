@@ -79,7 +79,8 @@ extern "C" {
                                                   sapca_umap_embed_device_*, sapca_umap_device_*, sapca_umap_*
                                  additive, ABI 4: sapca_louvain_options_default, sapca_louvain_modularity_device_*,
                                                   sapca_louvain_sweep_device_*, sapca_louvain_aggregate_device_*,
-                                                  sapca_louvain_device_*, sapca_louvain_*                               */
+                                                  sapca_louvain_device_*, sapca_louvain_*
+                                 additive, ABI 4: sapca_rank_sums_csr_device_*, sapca_rank_groups_csr_device_*         */
 
 typedef struct sapca_handle_s* sapca_handle;
 
@@ -1092,6 +1093,76 @@ sapca_status sapca_louvain_f32(sapca_handle h, uint64_t m, uint64_t nnz, const i
 sapca_status sapca_louvain_f64(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
                                const double* values, const sapca_louvain_options* opts, int32_t* labels, uint64_t* n_communities,
                                double* modularity, uint32_t* n_levels);
+
+/* ---- Rank groups: marker columns of a labelled resident CSR (sapca_rank_*): an opt-in superset, the reference has no counterpart ----
+ * The step scanpy runs after clustering (rank_genes_groups with method "wilcoxon" or "t-test"): which columns (genes) set each
+ * group of rows (cells) apart from the rest, with the labels and the matrix staying on the device.  tests/rank_groups_ref.py
+ * says the same in numpy and is held to scipy's rankdata, mannwhitneyu and ttest_ind.
+ * Input: a device-resident CSR A (m x n) from any *_csr_device_* source (uploaded, selected or canonical; a row holds a column
+ * at most once), d_labels (m int32, DEVICE, as the k-means and Louvain device calls write them) and n_groups = K.  A row whose
+ * label is outside [0, K) is excluded altogether: it is in no group and in no "rest", and is skipped where it is read, so a
+ * subset is analysed without a selection.  M = the included rows, n_g = those of group g, r_g = M - n_g; group g is always
+ * compared with the rest.
+ * Ranks, per column j, over the M included rows: the stored entries with value == 0 (+0.0 or -0.0) and the implicit zeros form
+ * one block of Z equal values; a = the stored values < 0 of included rows; values are ranked ascending from 1 and ties get
+ * their average rank.  f32 subnormals are distinct values and are not flushed; -inf and +inf sort at the ends.  A NaN makes its
+ * column's results unspecified; no address outside the arrays is touched.
+ * Exact outputs (integers; no floating-point atomic, no order reaches a value):
+ *   rank_sum2[g][j] = 2 * (sum of the ranks of group g's rows), int64 below M (M + 1): every non-zero entry of g adds the first
+ *                     plus the last 1-based position of its tie run in the full order, the zeros add
+ *                     (n_g - c_gj) ((a + 1) + (a + Z));
+ *   nonzero[g][j]   = c_gj, the stored non-zero entries of group g in column j;
+ *   group_rows[g]   = n_g;
+ *   tie_sum[j]      = sum over the tie runs of t^3 - t, the zero block included, in f64: every term and the sum are integers
+ *                     below 2^53 whenever M <= 208,063, so the value is exact there; beyond it is rounded, in an order fixed by
+ *                     the column's content.
+ * Wilcoxon z (scanpy's formula), R_g = rank_sum2 / 2:
+ *   z = (R_g - n_g (M + 1) / 2) / sqrt(n_g r_g (M + 1) / 12 * T),  T = 1 - tie_sum / (M^3 - M) with tie_correct = 1, T = 1 with
+ *   tie_correct = 0 (scanpy's default);  p = erfc(|z| / sqrt(2));  z = 0 and p = 1 where n_g = 0, r_g = 0 or the denominator is 0.
+ * Welch t, with s and q the sum and the sum of squares of the group's stored entries (implicit zeros count in the denominators):
+ *   mean_g = s_g / n_g;  var_g = max(0, (q_g - s_g^2 / n_g) / (n_g - 1)), 0 when n_g < 2;  the rest takes s_tot - s_g and
+ *   q_tot - q_g over r_g rows, the totals being the sums over g = 0 .. K - 1 in that order, in f64;
+ *   t = (mean_g - mean_r) / sqrt(var_g / n_g + var_r / r_g);  df = the Welch-Satterthwaite value
+ *   (var_g / n_g + var_r / r_g)^2 / ((var_g / n_g)^2 / (n_g - 1) + (var_r / r_g)^2 / (r_g - 1));
+ *   t = 0 and df = 0 where n_g = 0, r_g = 0 or the denominator is 0;  df = 0 where n_g < 2 or r_g < 2.
+ *   No p-value for t is returned (it needs the incomplete beta function; the Python layer adds one through scipy).
+ * How: group sizes with integer atomics; the matrix is transposed; per column the stored non-zero entries of included rows are
+ * kept as (order-preserving unsigned key, label), sorted by key -- in a wave's LDS, in a workgroup's LDS, or for the longest
+ * columns by a segmented radix sort in global scratch -- tie runs are found from the sorted keys, and every entry adds first +
+ * last position to its group's 64-bit counter in LDS.  The moments come from the labelled statistics of
+ * sapca_batch_stats_csr_device_* (s, and q = m2 + s^2 / c over the c stored entries), SAPCA_RANK_MAX_GROUPS codes at most.
+ * The host finishes the formulas in f64 on K x n values.
+ * Outputs are HOST arrays, code-major K x n like sapca_batch_stats_csr_device_* (group_rows: K; tie_sum: n); any may be NULL,
+ * and only what a non-NULL output needs is computed: no rank pass runs when neither z_score nor z_pvalue is asked for, no
+ * moment pass when none of mean, var, t_score, t_df is.  m == 0 or n == 0 is valid.
+ * SAPCA_ERR_ARG, checked on the host before anything is enqueued (the handle stays usable), each with a message that names the
+ * offending number: n_groups == 0 or above SAPCA_RANK_MAX_GROUPS; m >= 2^31; tie_correct outside {0, 1}; a null d_labels with
+ * m > 0; and the view checks of the other resident operations (a null CSR array, n >= 2^31).
+ * Like sapca_batch_stats_csr_device_* with grouped_axis 0 the call transposes into the buffers prepare() uses: a cached
+ * preparation is dropped.  A fitted model, the selection, the canonical form and the k-means, UMAP and Louvain buffers are
+ * untouched.  On a handle that belongs to a communicator the call is local to the rank's shard and issues no collective.
+ * Deterministic: the same bytes from call to call.                                                                         */
+#define SAPCA_RANK_MAX_GROUPS 1024
+/* The stage-level operator with the exact quantities: group_rows (K), rank_sum2 (K x n), nonzero (K x n), tie_sum (n).      */
+sapca_status sapca_rank_sums_csr_device_f32(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* row_offsets,
+                                            const int32_t* col_indices, const float* values, const int32_t* d_labels,
+                                            uint32_t n_groups, uint64_t* group_rows, int64_t* rank_sum2, uint64_t* nonzero,
+                                            double* tie_sum);
+sapca_status sapca_rank_sums_csr_device_f64(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* row_offsets,
+                                            const int32_t* col_indices, const double* values, const int32_t* d_labels,
+                                            uint32_t n_groups, uint64_t* group_rows, int64_t* rank_sum2, uint64_t* nonzero,
+                                            double* tie_sum);
+/* The scores of every group against the rest: group_rows (K); mean, var, nonzero, t_score, t_df, z_score, z_pvalue (K x n).  */
+sapca_status sapca_rank_groups_csr_device_f32(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* row_offsets,
+                                              const int32_t* col_indices, const float* values, const int32_t* d_labels,
+                                              uint32_t n_groups, int32_t tie_correct, uint64_t* group_rows, double* mean,
+                                              double* var, uint64_t* nonzero, double* t_score, double* t_df, double* z_score,
+                                              double* z_pvalue);
+sapca_status sapca_rank_groups_csr_device_f64(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* row_offsets,
+                                              const int32_t* col_indices, const double* values, const int32_t* d_labels,
+                                              uint32_t n_groups, int32_t tie_correct, uint64_t* group_rows, double* mean,
+                                              double* var, uint64_t* nonzero, double* t_score, double* t_df, double* z_score,
+                                              double* z_pvalue);
 
 /* Measurement support: the rate (GB/s, read + write counted) of a 16-byte-per-lane streaming copy of `bytes`
  * bytes on the handle's device, best of `reps` -- the HBM rate a kernel of this library can attain, reported by

@@ -818,6 +818,23 @@ sapca_status sapca_get_column_scale(sapca_handle h, int32_t* mode, double* out, 
       resident::batch_stats<T>(*h, unchecked_view(m, n, nnz, p, i, v), grouped_axis, codes, codes_len, n_batches, mean, var, count); \
     });                                                                                                                  \
   }                                                                                                                      \
+  sapca_status sapca_rank_sums_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p,   \
+                                                const int32_t* i, const T* v, const int32_t* d_labels, uint32_t n_groups,  \
+                                                uint64_t* group_rows, int64_t* rank_sum2, uint64_t* nonzero, double* tie_sum) { \
+    return guarded(h, [&] {                                                                                              \
+      resident::rank_sums<T>(*h, unchecked_view(m, n, nnz, p, i, v), d_labels, n_groups, group_rows, rank_sum2, nonzero, tie_sum); \
+    });                                                                                                                  \
+  }                                                                                                                      \
+  sapca_status sapca_rank_groups_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, \
+                                                  const int32_t* i, const T* v, const int32_t* d_labels, uint32_t n_groups, \
+                                                  int32_t tie_correct, uint64_t* group_rows, double* mean, double* var,    \
+                                                  uint64_t* nonzero, double* t_score, double* t_df, double* z_score,       \
+                                                  double* z_pvalue) {                                                      \
+    return guarded(h, [&] {                                                                                              \
+      resident::rank_groups<T>(*h, unchecked_view(m, n, nnz, p, i, v), d_labels, n_groups, tie_correct, group_rows, mean, var, \
+                               nonzero, t_score, t_df, z_score, z_pvalue);                                               \
+    });                                                                                                                  \
+  }                                                                                                                      \
   sapca_status sapca_masked_stats_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, \
                                                    const int32_t* i, const T* v, int32_t direction, const uint8_t* mask,    \
                                                    uint64_t mask_len, double* sum, double* sum_squared, uint64_t* count,    \

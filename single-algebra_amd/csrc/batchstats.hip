@@ -5,6 +5,7 @@
 // Both kernels give one wave to a row of the operand R and keep everything the row needs in that wave's own LDS, so
 // no workgroup barrier and no global atomic is involved; lanes of a wave meet only in LDS, ordered by wave fences.
 #include "kernels.h"
+#include "value_keys.h"
 
 namespace sapca {
 namespace k {
@@ -81,27 +82,7 @@ __global__ void __launch_bounds__(WAVE * WAVES) batch_row_stats_kernel(const int
 }
 
 // ---- top-n row sums --------------------------------------------------------------------------------------------------
-// The order-preserving unsigned image of a value: larger value <=> larger key (-0 just below +0; NaN unspecified).
-template <typename T> struct Keys;
-template <> struct Keys<float> {
-  using K = uint32_t;
-  static constexpr int BITS = 32;
-  __device__ static K key(float x) {
-    const uint32_t u = __float_as_uint(x);
-    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-  }
-  __device__ static float value(K k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
-};
-template <> struct Keys<double> {
-  using K = uint64_t;
-  static constexpr int BITS = 64;
-  __device__ static K key(double x) {
-    const uint64_t u = (uint64_t)__double_as_longlong(x);
-    return u ^ ((u >> 63) ? ~0ull : 0x8000000000000000ull);
-  }
-  __device__ static double value(K k) { return __longlong_as_double((long long)(k ^ ((k >> 63) ? 0x8000000000000000ull : ~0ull))); }
-};
-
+// (the keys the select runs on: Keys<T> of value_keys.h, the order-preserving unsigned image of a value)
 constexpr int DIGIT = 8, BINS = 1 << DIGIT;   // radix digits: 4 passes (f32) / 8 (f64), a 1 KiB histogram per wave
 constexpr int TILE = 16;                        // values per lane held in registers: rows up to 1,024 entries are read once
 // (row_top_n_kernel: 87 / 106 VGPRs in f32 / f64, no scratch, 4 KiB of LDS per workgroup: 5 / 4 waves per SIMD)

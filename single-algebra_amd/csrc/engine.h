@@ -202,6 +202,12 @@ struct sapca_handle_s {
              agg_idx[1].contains(q) || agg_val[1].contains(q);
     }
   } louvain;
+  // sapca_rank_sums_csr_device_* / sapca_rank_groups_csr_device_*: the group sizes, the rank pass's results (rank sums | tie sums |
+  // counts), the long columns' list and segment offsets, and their key scratch (keys, labels, counts, the sort's work space).
+  // Nothing else lives in these; the transposition and the moments use at_* and batch_out as sapca_batch_stats_csr_device_* does.
+  struct Rank {
+    sapca::DevBuf group, out, list, scratch;
+  } rank;
   sapca::DevBuf at_ptr, at_idx, at_val;                          // A^T
   sapca::DevBuf ca_ptr, ca_idx, ca_val, cat_ptr, cat_idx, cat_val;  // mask-compacted A, A^T
   sapca::DevBuf drop_stats, drop_tmp;                              // their sums (sum | sumsq, full width) and the sort's work space

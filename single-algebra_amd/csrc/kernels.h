@@ -100,6 +100,24 @@ void batch_row_stats(const CsrView<T>& R, const int32_t* codes, int lo, int nb, 
 template <typename T>
 void row_top_n(const CsrView<T>& A, const uint64_t* ns, int n_ns, double* out, hipStream_t s);
 
+// ---- rankgroups.hip: the rank pass of sapca_rank_sums_csr_device_* / sapca_rank_groups_csr_device_* (classes: rankgroups.h) ----
+// group[b] = the labels equal to b, b < nk (device, zeroed here; labels outside [0, nk) are skipped)
+void rank_group_sizes(const int32_t* labels, int64_t m, int nk, unsigned long long* group, hipStream_t s);
+// cnt[b * At.rows + j] = the stored non-zero entries of row j of At whose row of A carries label b (no sort: the counts alone)
+template <typename T>
+void rank_count_nonzero(const CsrView<T>& At, const int32_t* labels, int nk, uint32_t* cnt, hipStream_t s);
+// Per row j of At (a column of A) of stored length <= kRankLdsMax: rs[b * At.rows + j] = twice the rank sum of group b among the
+// M included rows (M = sum of group[]), cnt[..] as above, tie[j] = sum over tie runs of t^3 - t, the zero block included.
+template <typename T>
+void rank_sums_lds(const CsrView<T>& At, const int32_t* labels, int nk, const unsigned long long* group, int64_t M, long long* rs,
+                   uint32_t* cnt, double* tie, hipStream_t s);
+// The same for the nseg longer rows cols_list[0 .. nseg) (device), row cols_list[i] at seg[i] .. seg[i + 1] (device, nseg + 1,
+// seg[0] = 0, seg[nseg] = total) of the key scratch: build, segmented radix sort, walk.  `scratch` grows to what `total` needs.
+template <typename T>
+void rank_sums_long(const CsrView<T>& At, const int32_t* labels, int nk, const unsigned long long* group, int64_t M,
+                    const int32_t* cols_list, const uint32_t* seg, int nseg, uint32_t total, DevBuf& scratch, long long* rs, uint32_t* cnt,
+                    double* tie, hipStream_t s);
+
 // ---- maskedstats.hip: masked and stored-entry statistics (MatrixSum / MatrixNonZero / MatrixVariance *_masked, *_chunk) ----
 // Per row r of A, over its stored entries e whose column's bit (col_bits[c / 32] >> c % 32) & 1 is set (all of them when
 // col_bits is null): cnt[r] = their count, sum[r] / sumsq[r] = their sum / sum of squares, m2[r] = sum (x - sum / cnt)^2

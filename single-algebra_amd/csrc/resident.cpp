@@ -12,12 +12,6 @@ void check_direction(int32_t direction) {
   SAPCA_CHECK(direction == 0 || direction == 1, SAPCA_ERR_ARG, "direction must be 0 (ROW) or 1 (COLUMN)");
 }
 
-// dst <- the dst.size() elements at `d`, queued on the stream: the caller synchronises once behind its last one
-template <typename U>
-void fetch(std::vector<U>& dst, const U* d, hipStream_t s) {
-  SAPCA_HIP(hipMemcpyAsync(dst.data(), d, dst.size() * sizeof(U), hipMemcpyDeviceToHost, s));
-}
-
 }  // namespace
 
 template <typename T>
@@ -103,22 +97,8 @@ void batch_stats(H& h, const CsrView<T>& A, int32_t grouped_axis, const int32_t*
   int32_t* d_codes = h.batch_in.as<int32_t>(std::max<uint64_t>(codes_len, 1));
   if (codes_len) SAPCA_HIP(hipMemcpyAsync(d_codes, codes, codes_len * sizeof(int32_t), hipMemcpyHostToDevice, s));
   const CsrView<T> R = grouped_axis == 0 ? transpose_into_at(h, A) : A;
-  const int per = k::batch_codes_per_launch();
-  const int nb_max = (int)std::min<uint32_t>(n_batches, (uint32_t)per);
-  double* d_sum = h.batch_out.as<double>((size_t)nb_max * len * 5 / 2 + 1);   // sum, m2 (f64) and count (u32) per slot
-  double* d_m2 = d_sum + (size_t)nb_max * len;
-  uint32_t* d_cnt = reinterpret_cast<uint32_t*>(d_m2 + (size_t)nb_max * len);
-  std::vector<double> hs, hm;
-  std::vector<uint32_t> hc;
-  for (uint32_t lo = 0; lo < n_batches; lo += (uint32_t)per) {
-    const int nb = (int)std::min<uint32_t>(n_batches - lo, (uint32_t)per);
-    const size_t cells = (size_t)nb * len;
-    k::batch_row_stats(R, d_codes, (int)lo, nb, d_sum, d_m2, d_cnt, s);
-    hs.resize(cells); hm.resize(cells); hc.resize(cells);
-    fetch(hs, d_sum, s);
-    fetch(hm, d_m2, s);
-    fetch(hc, d_cnt, s);
-    SAPCA_HIP(hipStreamSynchronize(s));
+  for_each_code_slice(h, R, d_codes, n_batches, [&](uint32_t lo, int nb, const std::vector<double>& hs, const std::vector<double>& hm,
+                                                    const std::vector<uint32_t>& hc) {
     for (int b = 0; b < nb; ++b) {
       const uint64_t g = group[lo + b];
       const size_t base = ((size_t)lo + b) * len;
@@ -129,7 +109,7 @@ void batch_stats(H& h, const CsrView<T>& A, int32_t grouped_axis, const int32_t*
         if (count) count[base + r] = hc[c];
       }
     }
-  }
+  });
 }
 
 // MatrixNonZero / MatrixSum / MatrixVariance *_masked (csr.rs:153-252, 418-556, 815-914) and the stored-entry variance of

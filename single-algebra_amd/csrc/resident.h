@@ -25,6 +25,40 @@ namespace resident {
 
 using H = sapca_handle_s;
 
+// dst <- the dst.size() elements at `d`, queued on the stream: the caller synchronises once behind its last one
+template <typename U>
+void fetch(std::vector<U>& dst, const U* d, hipStream_t s) {
+  if (dst.empty()) return;
+  SAPCA_HIP(hipMemcpyAsync(dst.data(), d, dst.size() * sizeof(U), hipMemcpyDeviceToHost, s));
+}
+
+// The code-slice loop of the labelled statistics (batch_stats, rank_groups): k::batch_row_stats on the rows of R for
+// batch_codes_per_launch() codes at a time (d_codes: device, one per column of R; a code outside the slice is skipped), into
+// h.batch_out.  f(lo, nb, sum, m2, cnt) sees each slice once its results are on the host: [nb][R.rows], code-major.
+template <typename T, typename F>
+void for_each_code_slice(H& h, const CsrView<T>& R, const int32_t* d_codes, uint32_t n_codes, F&& f) {
+  hipStream_t s = h.stream;
+  const uint64_t len = (uint64_t)R.rows;
+  const int per = k::batch_codes_per_launch();
+  const int nb_max = (int)std::min<uint32_t>(n_codes, (uint32_t)per);
+  double* d_sum = h.batch_out.as<double>((size_t)nb_max * len * 5 / 2 + 1);   // sum, m2 (f64) and count (u32) per slot
+  double* d_m2 = d_sum + (size_t)nb_max * len;
+  uint32_t* d_cnt = reinterpret_cast<uint32_t*>(d_m2 + (size_t)nb_max * len);
+  std::vector<double> hs, hm;
+  std::vector<uint32_t> hc;
+  for (uint32_t lo = 0; lo < n_codes; lo += (uint32_t)per) {
+    const int nb = (int)std::min<uint32_t>(n_codes - lo, (uint32_t)per);
+    const size_t cells = (size_t)nb * len;
+    k::batch_row_stats(R, d_codes, (int)lo, nb, d_sum, d_m2, d_cnt, s);
+    hs.resize(cells); hm.resize(cells); hc.resize(cells);
+    fetch(hs, d_sum, s);
+    fetch(hm, d_m2, s);
+    fetch(hc, d_cnt, s);
+    SAPCA_HIP(hipStreamSynchronize(s));
+    f(lo, nb, hs, hm, hc);
+  }
+}
+
 template <typename T>
 void normalize(H& h, const CsrView<T>& A, T* v, const double* sums, uint64_t sums_len, double target, int32_t direction);
 template <typename T>
@@ -38,6 +72,14 @@ void batch_stats(H& h, const CsrView<T>& A, int32_t grouped_axis, const int32_t*
 template <typename T>
 void masked_stats(H& h, const CsrView<T>& A, int32_t direction, const uint8_t* mask, uint64_t mask_len, double* sum, double* sumsq,
                   uint64_t* count, double* var);
+// sapca_rank_sums_csr_device_* / sapca_rank_groups_csr_device_* (rankgroups.cpp): the exact quantities of the rank pass, and the
+// Wilcoxon / Welch scores of every group against the rest; d_labels: device, one per row; every output: host, may be null
+template <typename T>
+void rank_sums(H& h, const CsrView<T>& A, const int32_t* d_labels, uint32_t n_groups, uint64_t* group_rows, int64_t* rank_sum2,
+               uint64_t* nonzero, double* tie_sum);
+template <typename T>
+void rank_groups(H& h, const CsrView<T>& A, const int32_t* d_labels, uint32_t n_groups, int32_t tie_correct, uint64_t* group_rows,
+                 double* mean, double* var, uint64_t* nonzero, double* t_score, double* t_df, double* z_score, double* z_pvalue);
 // MatrixNTop::sum_row_n_top (csr.rs:1347-1376) for several n in one pass over the rows: out[i * m + r]
 template <typename T>
 void top_n(H& h, const CsrView<T>& A, const uint64_t* ns, uint32_t n_ns, double* out);

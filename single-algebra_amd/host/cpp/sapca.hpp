@@ -73,6 +73,8 @@ template <typename T> struct ResidentAbi;
     static sapca_status batch_stats(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, int32_t ax, const int32_t* c, uint64_t cl, uint32_t nb, double* mean, double* var, uint64_t* cnt) { return sapca_batch_stats_csr_device_##SUF(h, m, n, nnz, p, i, v, ax, c, cl, nb, mean, var, cnt); } \
     static sapca_status masked_stats(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, int32_t d, const uint8_t* mk, uint64_t ml, double* s, double* q, uint64_t* c, double* var) { return sapca_masked_stats_csr_device_##SUF(h, m, n, nnz, p, i, v, d, mk, ml, s, q, c, var); } \
     static sapca_status n_top(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, const uint64_t* ns, uint32_t k, double* out) { return sapca_sum_row_n_top_csr_device_##SUF(h, m, n, nnz, p, i, v, ns, k, out); } \
+    static sapca_status rank_sums(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, const int32_t* lab, uint32_t k, uint64_t* rows, int64_t* rs2, uint64_t* nz, double* tie) { return sapca_rank_sums_csr_device_##SUF(h, m, n, nnz, p, i, v, lab, k, rows, rs2, nz, tie); } \
+    static sapca_status rank_groups(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, const int32_t* lab, uint32_t k, int32_t tc, uint64_t* rows, double* mean, double* var, uint64_t* nz, double* t, double* df, double* z, double* pz) { return sapca_rank_groups_csr_device_##SUF(h, m, n, nnz, p, i, v, lab, k, tc, rows, mean, var, nz, t, df, z, pz); } \
     static sapca_status check(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, sapca_csr_report* rep) { return sapca_check_csr_device_##SUF(h, m, n, nnz, p, i, v, rep); } \
     static sapca_status canonicalize(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, uint64_t* nnz_out, const int64_t** op, const int32_t** oi, T** ov, sapca_csr_report* rep) { return sapca_canonicalize_csr_device_##SUF(h, m, n, nnz, p, i, v, nnz_out, op, oi, ov, rep); } \
     static sapca_status select_rows(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, const uint64_t* rows, uint64_t nr, uint64_t* nnz_out, const int64_t** op, const int32_t** oi, T** ov) { return sapca_select_rows_csr_device_##SUF(h, m, n, nnz, p, i, v, rows, nr, nnz_out, op, oi, ov); } \
@@ -400,6 +402,39 @@ class ResidentCsr {
     std::vector<double> out(m_);
     check(ResidentAbi<T>::n_top(h_, m_, n_, nnz_, ptr_, idx_, val_, &n, 1, out.data()));
     return out;
+  }
+  // Rank groups (sapca_rank_sums_csr_device_* / sapca_rank_groups_csr_device_*; no reference counterpart): every group of rows
+  // against the rest, per column.  d_labels: m int32 on the DEVICE (k-means' or Louvain's), a label outside [0, n_groups)
+  // excludes its row.  Every array is code-major n_groups x n; what `want_*` leaves out is not computed and stays empty.
+  struct RankSums {
+    std::vector<uint64_t> group_rows, nonzero;
+    std::vector<int64_t> rank_sum2;   // twice the rank sums
+    std::vector<double> tie_sum;      // per column
+  };
+  RankSums rank_sums(const int32_t* d_labels, uint32_t n_groups) const {
+    RankSums r;
+    const size_t cells = (size_t)n_groups * n_;
+    r.group_rows.resize(n_groups); r.nonzero.resize(cells); r.rank_sum2.resize(cells); r.tie_sum.resize(n_);
+    check(ResidentAbi<T>::rank_sums(h_, m_, n_, nnz_, ptr_, idx_, val_, d_labels, n_groups, r.group_rows.data(), r.rank_sum2.data(),
+                                    r.nonzero.data(), r.tie_sum.data()));
+    return r;
+  }
+  struct RankGroups {
+    std::vector<uint64_t> group_rows, nonzero;
+    std::vector<double> mean, var, t_score, t_df, z_score, z_pvalue;
+  };
+  RankGroups rank_groups(const int32_t* d_labels, uint32_t n_groups, bool want_wilcoxon = true, bool want_t = false,
+                         bool tie_correct = false) const {
+    RankGroups r;
+    const size_t cells = (size_t)n_groups * n_;
+    r.group_rows.resize(n_groups); r.nonzero.resize(cells);
+    if (want_wilcoxon) { r.z_score.resize(cells); r.z_pvalue.resize(cells); }
+    if (want_t) { r.mean.resize(cells); r.var.resize(cells); r.t_score.resize(cells); r.t_df.resize(cells); }
+    const auto ptr = [](std::vector<double>& v) { return v.empty() ? nullptr : v.data(); };
+    check(ResidentAbi<T>::rank_groups(h_, m_, n_, nnz_, ptr_, idx_, val_, d_labels, n_groups, tie_correct ? 1 : 0, r.group_rows.data(),
+                                      ptr(r.mean), ptr(r.var), r.nonzero.data(), ptr(r.t_score), ptr(r.t_df), ptr(r.z_score),
+                                      ptr(r.z_pvalue)));
+    return r;
   }
   // *_masked (csr.rs:153-252, 418-556, 815-914): col = per column over the rows with mask[row] (mask.size() >= m),
   // row = per row over the columns with mask[col] (mask.size() >= n); f64 sums, stored-entry variance without correction

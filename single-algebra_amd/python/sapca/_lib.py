@@ -90,6 +90,7 @@ KNN_EUCLIDEAN, KNN_COSINE, KNN_PEARSON = 0, 1, 2
 KNN_METRICS = {"euclidean": KNN_EUCLIDEAN, "cosine": KNN_COSINE, "pearson": KNN_PEARSON}
 KNN_EXCLUDE_SELF = 1
 KNN_MAX_NEIGHBORS = 128
+RANK_MAX_GROUPS = 1024   # SAPCA_RANK_MAX_GROUPS
 # sapca_kmeans_*: the seeding rules, the most clusters
 KMEANS_PLUSPLUS, KMEANS_GIVEN = 0, 1
 KMEANS_MAX_CLUSTERS = 1024
@@ -132,7 +133,7 @@ _TYPED = [
     "sapca_kmeans_seed_device", "sapca_kmeans_assign_device", "sapca_kmeans_update_device", "sapca_kmeans_device", "sapca_kmeans",
     "sapca_umap_graph_device", "sapca_umap_embed_device", "sapca_umap_device", "sapca_umap",
     "sapca_louvain_modularity_device", "sapca_louvain_sweep_device", "sapca_louvain_aggregate_device", "sapca_louvain_device",
-    "sapca_louvain",
+    "sapca_louvain", "sapca_rank_sums_csr_device", "sapca_rank_groups_csr_device",
     "sapca_multi_fit_csr", "sapca_multi_transform_csr", "sapca_multi_fit_transform_csr",
     "sapca_multi_upload_csr", "sapca_multi_transform_resident", "sapca_multi_fit_transform_resident",
 ]
@@ -303,6 +304,13 @@ def _open(path):
             for name in (f"sapca_louvain_device_{suf}", f"sapca_louvain_{suf}"):
                 getattr(lib, name).argtypes = csr + [C.POINTER(LouvainOptions), C.c_void_p, C.POINTER(C.c_uint64),
                                                      C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
+    if hasattr(lib, "sapca_rank_sums_csr_device_f32"):   # (absent from an older build loaded for an A/B run)
+        mat = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]   # h, m, n, nnz, offsets, columns, values
+        u64p, f64p = C.POINTER(C.c_uint64), C.POINTER(C.c_double)
+        for suf in ("f32", "f64"):
+            getattr(lib, f"sapca_rank_sums_csr_device_{suf}").argtypes = mat + [C.c_void_p, C.c_uint32, u64p, C.POINTER(C.c_int64), u64p, f64p]
+            getattr(lib, f"sapca_rank_groups_csr_device_{suf}").argtypes = mat + [C.c_void_p, C.c_uint32, C.c_int32, u64p, f64p, f64p, u64p,
+                                                                                  f64p, f64p, f64p, f64p]
     return lib
 
 

@@ -783,6 +783,33 @@ def _new_report():
     return r
 
 
+class RankGroupsResult:
+    """What ResidentCsr.rank_groups returns, every array K x n (group x column): `scores` and `pvals` (arrays, or with method
+    "both" dicts keyed "wilcoxon" / "t-test"), `means`, `vars`, `pct_nonzero` (stored non-zero entries / rows of the group, 0
+    for an empty group), `group_rows` (K) and `names`: per group the column indices by descending score, ties to the lower
+    index, cut to n_top (with "both": by the Wilcoxon score)."""
+
+    def __init__(self, method, scores, pvals, means, vars_, nonzero, group_rows, n_top):
+        self.method, self.scores, self.pvals, self.means, self.vars = method, scores, pvals, means, vars_
+        self.nonzero, self.group_rows = nonzero, group_rows
+        rows = group_rows.astype(np.float64)[:, None]
+        self.pct_nonzero = np.divide(nonzero.astype(np.float64), rows, out=np.zeros(nonzero.shape), where=rows > 0)
+        by = scores["wilcoxon"] if isinstance(scores, dict) else scores
+        order = np.argsort(-by, axis=1, kind="stable")   # (stable: equal scores keep ascending column order)
+        self.names = order if n_top is None else order[:, :int(n_top)]
+
+    def logfoldchanges(self, base=2):
+        """scanpy's convention on log1p data: log_base((expm1(mean_group) + 1e-9) / (expm1(mean_rest) + 1e-9)), the rest's
+        mean from the groups' means and sizes (host arithmetic; nan where a side has no rows)."""
+        rows = self.group_rows.astype(np.float64)[:, None]
+        total = (self.means * rows).sum(axis=0, keepdims=True)
+        rest = rows.sum() - rows
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean_rest = (total - self.means * rows) / rest
+            mean_group = np.where(rows > 0, self.means, np.nan)
+            return np.log((np.expm1(mean_group) + 1e-9) / (np.expm1(mean_rest) + 1e-9)) / np.log(float(base))
+
+
 class ResidentCsr:
     """A CSR matrix uploaded once into buffers owned by a Session (sapca_upload_csr_*): normalize -> log1p ->
     statistics -> PCA on it without crossing PCIe again.  `as_device_csr()` gives the
@@ -880,6 +907,90 @@ class ResidentCsr:
         """BatchMatrixMean::mean_batch_col (csr.rs:1299-1343): batches label the rows; {label: per-column sum / number of
         rows with that label}"""
         return self._grouped(batches, 0, "mean", "Number of batch identifiers ({}) must match number of rows ({})")
+
+    # ---- rank groups (sapca_rank_sums_csr_device_* / sapca_rank_groups_csr_device_*): marker columns of labelled rows ----
+    def _rank_labels(self, labels, n_groups):
+        """(device int32 labels, K): `labels` a numpy array (copied up), a torch device tensor or an estimator with device
+        labels_ (KMeans, Louvain), used in place; n_groups None: 1 + the largest label."""
+        import torch
+        m = self.shape[0]
+
+        def check_groups(k):
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+                raise ValueError(f"n_groups must be an integer, got {k!r}")
+            if not 1 <= int(k) <= L.RANK_MAX_GROUPS:
+                raise ValueError(f"n_groups = {int(k)} is outside 1 .. {L.RANK_MAX_GROUPS}")
+            return int(k)
+
+        if n_groups is not None:
+            n_groups = check_groups(n_groups)
+        labels = getattr(labels, "labels_", labels)
+        if labels is None:
+            raise ValueError("labels: the estimator has not been fitted")
+        if isinstance(labels, np.ndarray) or not isinstance(labels, torch.Tensor):
+            a = np.asarray(labels)
+            if a.ndim != 1 or a.size != m or a.dtype.kind not in "iu":
+                raise ValueError(f"labels must be {m} integers, got shape {a.shape} of dtype {a.dtype}")
+            if a.size and (a.max() > 2 ** 31 - 1 or a.min() < -2 ** 31):
+                raise ValueError("labels must fit int32")
+            labels = torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=self._s._device())
+        if not (labels.is_cuda and labels.dtype == torch.int32 and tuple(labels.shape) == (m,) and labels.is_contiguous()):
+            raise ValueError(f"labels must be {m} contiguous int32 values (a device tensor or a numpy array)")
+        if n_groups is None:
+            n_groups = check_groups(max(int(labels.max().item()) + 1, 1) if m else 1)
+        return labels, n_groups
+
+    def rank_sums(self, labels, n_groups=None):
+        """sapca_rank_sums_csr_device_*: the exact quantities of the rank pass, every group of rows against the rest, per
+        column: {"group_rows": K u64, "rank_sum2": K x n i64 (twice the rank sums), "nonzero": K x n u64, "tie_sum": n f64}.
+        Rows whose label is outside [0, n_groups) are excluded."""
+        import torch
+        labels, K = self._rank_labels(labels, n_groups)
+        suf, _ = _SUF[self.dtype]
+        m, n = self.shape
+        out = {"group_rows": np.zeros(K, dtype=np.uint64), "rank_sum2": np.zeros((K, n), dtype=np.int64),
+               "nonzero": np.zeros((K, n), dtype=np.uint64), "tie_sum": np.zeros(n)}
+        torch.cuda.current_stream().synchronize()
+        L.check(self._s._h, getattr(L.load(), f"sapca_rank_sums_csr_device_{suf}")(
+            *self._args(), C.c_void_p(labels.data_ptr() if m else None), C.c_uint32(K), _p(out["group_rows"], C.c_uint64),
+            _p(out["rank_sum2"], C.c_int64), _p(out["nonzero"], C.c_uint64), _p(out["tie_sum"], C.c_double)))
+        return out
+
+    def rank_groups(self, labels, n_groups=None, method="wilcoxon", tie_correct=False, n_top=None):
+        """sapca_rank_groups_csr_device_*: scanpy's rank_genes_groups of every group against the rest, method "wilcoxon"
+        (scores: z, pvals: erfc(|z| / sqrt 2)), "t-test" (scores: Welch's t, pvals through scipy.stats.t.sf where scipy
+        imports, else None) or "both" (scores / pvals become {"wilcoxon": .., "t-test": ..}).  Returns a RankGroupsResult."""
+        import torch
+        if method not in ("wilcoxon", "t-test", "both"):
+            raise ValueError(f'method must be "wilcoxon", "t-test" or "both", got {method!r}')
+        if n_top is not None and (isinstance(n_top, bool) or not isinstance(n_top, (int, np.integer)) or n_top < 0):
+            raise ValueError(f"n_top must be a non-negative integer or None, got {n_top!r}")
+        labels, K = self._rank_labels(labels, n_groups)
+        suf, _ = _SUF[self.dtype]
+        m, n = self.shape
+        wil, tt = method != "t-test", method != "wilcoxon"
+        a = {k: np.zeros((K, n)) for k in ("mean", "var") + (("t", "df") if tt else ()) + (("z", "pz") if wil else ())}
+        rows, nz = np.zeros(K, dtype=np.uint64), np.zeros((K, n), dtype=np.uint64)
+        f = lambda k: _p(a[k], C.c_double) if k in a else None   # noqa: E731
+        torch.cuda.current_stream().synchronize()
+        L.check(self._s._h, getattr(L.load(), f"sapca_rank_groups_csr_device_{suf}")(
+            *self._args(), C.c_void_p(labels.data_ptr() if m else None), C.c_uint32(K), C.c_int32(1 if tie_correct else 0),
+            _p(rows, C.c_uint64), f("mean"), f("var"), _p(nz, C.c_uint64), f("t"), f("df"), f("z"), f("pz")))
+        scores, pvals = {}, {}
+        if wil:
+            scores["wilcoxon"], pvals["wilcoxon"] = a["z"], a["pz"]
+        if tt:
+            scores["t-test"] = a["t"]
+            try:
+                from scipy import stats
+                with np.errstate(invalid="ignore"):
+                    pt = 2.0 * stats.t.sf(np.abs(a["t"]), np.where(a["df"] > 0, a["df"], 1.0))
+                pvals["t-test"] = np.where(a["df"] > 0, pt, 1.0)
+            except ImportError:
+                pvals["t-test"] = None
+        if method != "both":
+            scores, pvals = scores[method], pvals[method]
+        return RankGroupsResult(method, scores, pvals, a["mean"], a["var"], nz, rows, n_top)
 
     def sum_row_n_top(self, n):
         """MatrixNTop::sum_row_n_top (csr.rs:1347-1376): per row, the sum of the n largest stored values (all of them when
