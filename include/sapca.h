@@ -80,7 +80,8 @@ extern "C" {
                                  additive, ABI 4: sapca_louvain_options_default, sapca_louvain_modularity_device_*,
                                                   sapca_louvain_sweep_device_*, sapca_louvain_aggregate_device_*,
                                                   sapca_louvain_device_*, sapca_louvain_*
-                                 additive, ABI 4: sapca_rank_sums_csr_device_*, sapca_rank_groups_csr_device_*         */
+                                 additive, ABI 4: sapca_rank_sums_csr_device_*, sapca_rank_groups_csr_device_*
+                                 additive, ABI 4: sapca_normalize_panel_ex_*, sapca_rotate_panel_*                     */
 
 typedef struct sapca_handle_s* sapca_handle;
 
@@ -381,6 +382,27 @@ sapca_status sapca_project_out_panel_f64(sapca_handle h, uint64_t rows, uint64_t
  * is rounded once to T, each product once (csrc/colscale.hip).                                                           */
 sapca_status sapca_scale_panel_rows_f32(sapca_handle h, uint64_t rows, uint64_t l, float* panel, const double* scale);
 sapca_status sapca_scale_panel_rows_f64(sapca_handle h, uint64_t rows, uint64_t l, double* panel, const double* scale);
+/* The normaliser as a fit calls it, for inspection: the panel arrives as the sum of `nsplit` row-major rows x l slabs (slab s
+ * at slabs + s * rows * l; one slab is staged in the panel buffer itself, several in a buffer of their own -- the two shapes
+ * the A^T sweeps leave behind) minus the centring term mu sv^T (mu: rows, sv: l; both NULL or both given).  passes: 0 = what
+ * the normaliser implies (QR two, LU one), else 1 or 2 CholeskyQR passes.  panel_out (rows x l) receives the normalised panel
+ * (SAPCA_NORM_NONE: the summed, centred panel), vec_out (l, nullable) sum_r w[r] panel_out[r][:] (w: rows, NULL = ones) as the
+ * Gram's read pass and R^-1 give it, r1 / r2 (l x l f64 row-major, nullable) the upper factors of the first / second pass
+ * (zeros for a pass that did not run), *regularised (nullable) the number of pivots the factorisations floored.           */
+sapca_status sapca_normalize_panel_ex_f32(sapca_handle h, int32_t normalizer, int32_t passes, uint64_t rows, uint64_t l,
+                                          uint32_t nsplit, const float* slabs, const float* mu, const float* sv, const float* w,
+                                          float* panel_out, float* vec_out, double* r1, double* r2, int32_t* regularised);
+sapca_status sapca_normalize_panel_ex_f64(sapca_handle h, int32_t normalizer, int32_t passes, uint64_t rows, uint64_t l,
+                                          uint32_t nsplit, const double* slabs, const double* mu, const double* sv, const double* w,
+                                          double* panel_out, double* vec_out, double* r1, double* r2, int32_t* regularised);
+/* The rotation a randomized fit ends in, for inspection: components (k x n row-major) = svd_flip((panel factor)^T) for an
+ * n x l row-major panel and an l x k f64 row-major factor, 1 <= k <= l <= 1024, n >= 1.  Row c is column c of the product
+ * times signs[c] (k doubles, nullable): -1 where the entry of largest magnitude in that column (the first row on ties) is
+ * negative, else +1 (a column without a largest entry -- all nan -- keeps +1).  Drops the handle's fitted model.           */
+sapca_status sapca_rotate_panel_f32(sapca_handle h, uint64_t n, uint64_t l, uint64_t k, const float* panel, const double* factor,
+                                    float* components, double* signs);
+sapca_status sapca_rotate_panel_f64(sapca_handle h, uint64_t n, uint64_t l, uint64_t k, const double* panel, const double* factor,
+                                    double* components, double* signs);
 /* The built-in Omega generator (rows x l standard normal from (seed)), for inspection.        */
 sapca_status sapca_generate_omega_f32(sapca_handle h, uint64_t rows, uint64_t l, float* out);
 sapca_status sapca_generate_omega_f64(sapca_handle h, uint64_t rows, uint64_t l, double* out);

@@ -471,6 +471,101 @@ sapca_status normalize_host(sapca_handle h, int32_t normalizer, uint64_t rows, u
   });
 }
 
+// Engine::normalize with its extras filled in, on host buffers: the panel arrives as the slabs a sweep leaves behind (one slab:
+// staged IN the panel buffer, as sweep_at_one_piece leaves it; several: in a buffer of their own, as spmm_tiled leaves them),
+// with the centring term mu sv^T still to be subtracted; the Gram's read pass does both and gathers sum_r w[r] P[r][:].
+template <typename T>
+sapca_status normalize_ex_host(sapca_handle h, int32_t normalizer, int32_t passes, uint64_t rows, uint64_t l, uint32_t nsplit, const T* slabs,
+                               const T* mu, const T* sv, const T* w, T* panel_out, T* vec_out, double* r1, double* r2,
+                               int32_t* regularised) {
+  return guarded(h, [&] {
+    SAPCA_CHECK(l >= 1 && l <= (uint64_t)sapca::k::kMaxPanelWidth && rows >= 1 && slabs && panel_out, SAPCA_ERR_ARG,
+                "normalize_ex: panel width must be in [1, 1024]");
+    SAPCA_CHECK(normalizer >= 0 && normalizer <= 2, SAPCA_ERR_ARG, "unknown normalizer");
+    SAPCA_CHECK(passes >= 0 && passes <= 2, SAPCA_ERR_ARG, "normalize_ex: passes must be 0 (the normaliser's own), 1 or 2");
+    SAPCA_CHECK(nsplit >= 1 && nsplit <= 4096, SAPCA_ERR_ARG, "normalize_ex: nsplit must be in [1, 4096]");
+    SAPCA_CHECK((mu == nullptr) == (sv == nullptr), SAPCA_ERR_ARG, "normalize_ex: mu and sv go together");
+    hipStream_t s = h->stream;
+    const int ld = (int)sapca::round_up((int64_t)l, l > 128 ? 64 : 16);
+    const sapca::SmallLayout lay(h->small, ld);
+    const size_t ldld = (size_t)ld * ld;
+    T* stage = h->scratch.as<T>((uint64_t)nsplit * rows * l);
+    T* P = h->panel_x.as<T>((rows + 1) * ld);
+    T* rowvec = h->split_scratch2.as<T>(2 * rows);   // mu | w
+    sapca::k::PanelSource<T> src;
+    SAPCA_HIP(hipMemcpyAsync(stage, slabs, (uint64_t)nsplit * rows * l * sizeof(T), hipMemcpyHostToDevice, s));
+    if (nsplit == 1) {
+      sapca::k::add_padding(stage, (int64_t)rows, (int)l, P, ld, s);
+      src.parts = P;
+      src.nsplit = 1;
+    } else {
+      T* S = h->split_scratch.as<T>((uint64_t)nsplit * rows * ld);
+      sapca::k::add_padding(stage, (int64_t)(nsplit * rows), (int)l, S, ld, s);
+      src.parts = S;
+      src.nsplit = (int)nsplit;
+      src.slab_stride = (int64_t)rows * ld;
+    }
+    std::vector<T> sv_pad((size_t)ld, (T)0);
+    if (mu) {
+      std::copy(sv, sv + l, sv_pad.begin());
+      SAPCA_HIP(hipMemcpyAsync(rowvec, mu, rows * sizeof(T), hipMemcpyHostToDevice, s));
+      SAPCA_HIP(hipMemcpyAsync(lay.s<T>(), sv_pad.data(), (size_t)ld * sizeof(T), hipMemcpyHostToDevice, s));
+      src.mu = rowvec;
+      src.sv = lay.s<T>();
+    }
+    if (w) SAPCA_HIP(hipMemcpyAsync(rowvec + rows, w, rows * sizeof(T), hipMemcpyHostToDevice, s));
+    SAPCA_HIP(hipMemsetAsync(lay.info(), 0, sizeof(int), s));
+    SAPCA_HIP(hipMemsetAsync(lay.r1(), 0, 2 * ldld * sizeof(double), s));   // (r1 | r2: a pass that does not run leaves zeros)
+    sapca::NormalizeExtras<T> x;
+    x.R1 = r1 ? lay.r1() : nullptr;
+    x.R2 = r2 ? lay.r2() : nullptr;
+    x.passes = passes;
+    x.src = &src;
+    x.w = w ? rowvec + rows : nullptr;
+    x.vec_out = vec_out ? lay.c<T>() : nullptr;
+    Engine<T>::normalize(*h, P, (int64_t)rows, (int)l, ld, normalizer, false, x);
+    sapca::k::strip_padding(P, (int64_t)rows, ld, (int)l, stage, s);
+    std::vector<double> rr(r1 || r2 ? 2 * ldld : 0);
+    int info = 0;
+    if (vec_out) SAPCA_HIP(hipMemcpyAsync(vec_out, lay.c<T>(), l * sizeof(T), hipMemcpyDeviceToHost, s));
+    if (!rr.empty()) SAPCA_HIP(hipMemcpyAsync(rr.data(), lay.r1(), rr.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    SAPCA_HIP(hipMemcpyAsync(&info, lay.info(), sizeof(int), hipMemcpyDeviceToHost, s));
+    download_out(h, stage, panel_out, (size_t)(rows * l));   // (waits for the stream: sv_pad, rr and info are still alive)
+    for (int which = 0; which < 2; ++which) {
+      double* out = which ? r2 : r1;
+      if (!out) continue;
+      for (uint64_t i = 0; i < l; ++i) std::copy(&rr[which * ldld + i * ld], &rr[which * ldld + i * ld] + l, out + i * l);
+    }
+    if (regularised) *regularised = info;
+  });
+}
+
+// components = svd_flip((panel factor)^T): the rotation a fit ends in (Engine::rotate_into_components) on host buffers
+template <typename T>
+sapca_status rotate_host(sapca_handle h, uint64_t n, uint64_t l, uint64_t k, const T* panel, const double* factor, T* components,
+                         double* signs) {
+  return guarded(h, [&] {
+    SAPCA_CHECK(k >= 1 && k <= l && l <= (uint64_t)sapca::k::kMaxPanelWidth && n >= 1, SAPCA_ERR_ARG,
+                "rotate_panel: needs 1 <= k <= l <= 1024 and n >= 1");
+    SAPCA_CHECK(panel && factor && components, SAPCA_ERR_ARG, "rotate_panel: null pointer");
+    hipStream_t s = h->stream;
+    const int ld = (int)sapca::round_up((int64_t)l, l > 128 ? 64 : 16), ldk = (int)sapca::round_up((int64_t)k, 16);
+    const sapca::SmallLayout lay(h->small, ld);
+    h->fitted = false;   // (components_dev is the fitted model's)
+    std::vector<double> M((size_t)ld * ldk, 0.0);
+    for (uint64_t i = 0; i < l; ++i) std::copy(factor + i * k, factor + (i + 1) * k, M.begin() + i * ldk);
+    T* stage = h->scratch.as<T>(n * l);
+    T* X = h->panel_x.as<T>(n * ld);
+    SAPCA_HIP(hipMemcpyAsync(stage, panel, n * l * sizeof(T), hipMemcpyHostToDevice, s));
+    SAPCA_HIP(hipMemcpyAsync(lay.m(), M.data(), M.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    sapca::k::add_padding(stage, (int64_t)n, (int)l, X, ld, s);
+    const double* d_sign = nullptr;
+    Engine<T>::rotate_into_components(*h, X, (int64_t)n, ld, (int)k, lay.m(), &d_sign);
+    if (signs) SAPCA_HIP(hipMemcpyAsync(signs, d_sign, k * sizeof(double), hipMemcpyDeviceToHost, s));
+    download_out(h, h->components_dev.ptr<T>(), components, (size_t)(k * n));   // (waits for the stream: M is still alive)
+  });
+}
+
 // panel <- panel - Q (Q^T panel): the two kernels of the covariate route on host buffers
 template <typename T>
 sapca_status project_out_host(sapca_handle h, uint64_t rows, uint64_t l, T* panel, uint32_t r, const T* q) {
@@ -994,6 +1089,15 @@ sapca_status sapca_get_column_scale(sapca_handle h, int32_t* mode, double* out, 
   }                                                                                                                      \
   sapca_status sapca_scale_panel_rows_##SUF(sapca_handle h, uint64_t rows, uint64_t l, T* panel, const double* scale) {  \
     return scale_rows_host<T>(h, rows, l, panel, scale);                                                                 \
+  }                                                                                                                      \
+  sapca_status sapca_normalize_panel_ex_##SUF(sapca_handle h, int32_t normalizer, int32_t passes, uint64_t rows, uint64_t l, \
+                                              uint32_t nsplit, const T* slabs, const T* mu, const T* sv, const T* w,       \
+                                              T* panel_out, T* vec_out, double* r1, double* r2, int32_t* regularised) {    \
+    return normalize_ex_host<T>(h, normalizer, passes, rows, l, nsplit, slabs, mu, sv, w, panel_out, vec_out, r1, r2, regularised); \
+  }                                                                                                                      \
+  sapca_status sapca_rotate_panel_##SUF(sapca_handle h, uint64_t n, uint64_t l, uint64_t k, const T* panel, const double* factor, \
+                                        T* components, double* signs) {                                                    \
+    return rotate_host<T>(h, n, l, k, panel, factor, components, signs);                                                 \
   }
 
 SAPCA_DEFINE_TYPED(f32, float)

@@ -1009,17 +1009,21 @@ void power_iterations(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
   sweep_at(h, p, f, true);
 }
 
-// vt = (B^T M)^T with the sign convention of svd_flip (R13): the components, from the un-rotated panel X = B^T (panel_x,
-// n_used x ld) and the small factor M (ld x ldk) of whichever small SVD produced it.  sign_out: the device address of the k flip signs.
+}  // namespace
+
+// vt = (B^T M)^T with the sign convention of svd_flip (R13): the components, from an un-rotated panel X = B^T (n x ld) and
+// the small factor M (ld x ldk, ldk = round_up(k, 16)) of whichever small SVD produced it.  A fit passes panel_x and its
+// n_used rows; sapca_rotate_panel_* a caller's panel.  sign_out: the device address of the k flip signs.
 template <typename T>
-void rotate_into_components(H& h, int ld, const double* Mdev, const double** sign_out = nullptr) {
-  const int k = (int)h.opt.n_components, ldk = (int)round_up(k, 16);
-  const int64_t n_used = h.a_used.cols;
-  T* VtT = h.panel_w.as<T>((size_t)std::max<int64_t>(n_used, 1) * ldk);
-  k::panel_gemm(h.panel_x.ptr<T>(), n_used, ld, Mdev, ldk, VtT, h.stream);
-  T* comps = h.components_dev.as<T>((size_t)k * std::max<int64_t>(n_used, 1));
-  k::flip_transpose(VtT, n_used, ldk, k, comps, h.scratch2, h.stream, sign_out);
+void Engine<T>::rotate_into_components(H& h, const T* X, int64_t n, int ld, int k, const double* Mdev, const double** sign_out) {
+  const int ldk = (int)round_up(k, 16);
+  T* VtT = h.panel_w.as<T>((size_t)std::max<int64_t>(n, 1) * ldk);
+  k::panel_gemm(X, n, ld, Mdev, ldk, VtT, h.stream);
+  T* comps = h.components_dev.as<T>((size_t)k * std::max<int64_t>(n, 1));
+  k::flip_transpose(VtT, n, ldk, k, comps, h.scratch2, h.stream, sign_out);
 }
+
+namespace {
 
 // GramDevice: the eigenproblem stays on the device (one workgroup, parallel Jacobi: sym_eig.hip).  The singular values (and the
 // solver's status) cross in page-locked memory behind everything else; finish_fit() reads them after the fit's last wait.
@@ -1036,7 +1040,7 @@ void small_svd_gram_device(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
   SAPCA_HIP(hipMemcpyAsync(host, d_sigma, (size_t)p.l * sizeof(double), hipMemcpyDeviceToHost, s));
   SAPCA_HIP(hipMemcpyAsync(host_i, d_status, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
   SAPCA_HIP(hipMemcpyAsync(host_i + 2, f.lay.info(), sizeof(int), hipMemcpyDeviceToHost, s));
-  rotate_into_components<T>(h, p.ld, f.lay.m());
+  Engine<T>::rotate_into_components(h, f.X, p.n_used, p.ld, p.k, f.lay.m());
   h.held_tail.sing_l = p.l;
 }
 
@@ -1095,7 +1099,7 @@ void small_svd_qr_jacobi(H& h, const RandomizedPlan& p, FitPanels<T>& f) {
     for (int i = 0; i < l; ++i)
       for (int j = 0; j < p.k; ++j) M[(size_t)i * p.ldk + j] = Ur[(size_t)i * l + j];
     SAPCA_HIP(hipMemcpyAsync(f.lay.m(), M.data(), M.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    rotate_into_components<T>(h, ld, f.lay.m());
+    Engine<T>::rotate_into_components(h, f.X, p.n_used, ld, p.k, f.lay.m());
     SAPCA_HIP(hipStreamSynchronize(s));   // M goes out of scope
     h.sing.assign(sv.begin(), sv.begin() + p.k);
   }
@@ -1168,7 +1172,7 @@ void Engine<T>::finish_small_svd(H& h, const double** sign_out) {
       for (int i = 0; i < l; ++i) M[(size_t)i * ldk + j] = Vt[(size_t)j * l + i] * inv;
     }
     SAPCA_HIP(hipMemcpyAsync(lay.m(), M, (size_t)ld * ldk * sizeof(double), hipMemcpyHostToDevice, s));
-    rotate_into_components<T>(h, ld, lay.m(), sign_out);
+    rotate_into_components(h, h.panel_x.ptr<T>(), h.a_used.cols, ld, k, lay.m(), sign_out);
     h.sing.assign(sv.begin(), sv.begin() + k);
     h.chol_regularised = info_host;
   } catch (...) {

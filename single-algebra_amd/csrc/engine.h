@@ -315,6 +315,8 @@ struct Engine {
   static int64_t piece_vote(H& h, int ld);     // this rank's vote: the first output row of its second piece, 0 = one piece
   // normaliser on a rows x ld panel
   static void normalize(H& h, T* P, int64_t rows, int l, int ld, int normalizer, bool sharded, const NormalizeExtras<T>& x);
+  // components (k x n, in components_dev) = svd_flip((X M)^T) of an n x ld panel X and the ld x round_up(k, 16) factor M
+  static void rotate_into_components(H& h, const T* X, int64_t n, int ld, int k, const double* Mdev, const double** sign_out = nullptr);
   static CsrView<T> view(const H::RawCsr& r) {
     CsrView<T> v;
     v.rows = r.rows; v.cols = r.cols; v.nnz = r.nnz;

@@ -48,7 +48,8 @@ flip_sign_kernel(const T* __restrict__ VtT, int64_t n, int ld, double* __restric
     }
     __syncthreads();
   }
-  if (threadIdx.x == 0) sign[r] = (n > 0 && (double)VtT[best_i[0] * ld + r] < 0) ? -1.0 : 1.0;
+  // (best_a[0] < 0: no |v| compared greater than -1 -- a column of nan, or n = 0 -- and best_i[0] is no row: sign +1)
+  if (threadIdx.x == 0) sign[r] = (n > 0 && best_a[0] >= 0.0 && (double)VtT[best_i[0] * ld + r] < 0) ? -1.0 : 1.0;
 }
 
 // The same in two coalesced stages for the usual leading dimensions (256 % ld == 0): a block scans a run of rows with a thread

@@ -6,6 +6,26 @@
 
 namespace sapca {
 
+// The solvers below square their input (column norms, f * f + g * g) and hold differences of eigenvalues that are orders
+// below the norm: within 1e+-100 of the ends of the format those overflow or fall among the denormals (rotations from a
+// denormal r are not orthogonal: 2e-12 off at n = 128, |A| = 1e-300).  Such a matrix is solved at a power-of-two multiple
+// of itself -- exact both ways -- and every other matrix exactly as before: the factor is 1 and nothing is multiplied.
+namespace {
+struct RangeScale {
+  double to = 1.0, back = 1.0;
+  RangeScale(const double* a, size_t na, const double* b = nullptr, size_t nb = 0) {
+    double amax = 0;
+    for (size_t i = 0; i < na; ++i) amax = std::max(amax, std::fabs(a[i]));
+    for (size_t i = 0; i < nb; ++i) amax = std::max(amax, std::fabs(b[i]));
+    if (!(amax > 0) || !std::isfinite(amax) || (amax >= 1e-100 && amax <= 1e100)) return;
+    const int ex = std::ilogb(amax);
+    to = std::ldexp(1.0, -ex);
+    back = std::ldexp(1.0, ex);
+  }
+  bool on() const { return to != 1.0; }
+};
+}  // namespace
+
 // One-sided Jacobi on the columns of W = A (column-major for stride-1 rotations): A V = W, W -> U diag(s).
 // The squared column norms are carried along and refreshed once per sweep, so a pair costs one dot
 // product and one rotation.  Cloned for AVX2+FMA (resolved at load time): this runs on the host between
@@ -53,6 +73,8 @@ void jacobi_svd(const std::vector<double>& A, int l, std::vector<double>& U, std
   std::vector<double> W((size_t)l * l), nrm((size_t)std::max(l, 1));
   for (int i = 0; i < l; ++i)
     for (int j = 0; j < l; ++j) W[(size_t)j * l + i] = A[(size_t)i * l + j];
+  const RangeScale rs(W.data(), W.size());
+  if (rs.on()) for (double& x : W) x *= rs.to;
   jacobi_rotate_sweeps(W.data(), nrm.data(), l);
   std::vector<double> norm(l);
   for (int j = 0; j < l; ++j) {
@@ -67,7 +89,7 @@ void jacobi_svd(const std::vector<double>& A, int l, std::vector<double>& U, std
   s.assign(l, 0.0);
   for (int c = 0; c < l; ++c) {
     const int j = order[c];
-    s[c] = norm[j];
+    s[c] = rs.on() ? norm[j] * rs.back : norm[j];
     if (norm[j] > 0)
       for (int i = 0; i < l; ++i) U[(size_t)i * l + c] = W[(size_t)j * l + i] / norm[j];
   }
@@ -217,6 +239,8 @@ bool sym_eigh_desc(const std::vector<double>& A, int n, std::vector<double>& w, 
   Vt.assign((size_t)n * n, 0.0);
   if (n <= 0) return true;
   std::vector<double> a(A.begin(), A.begin() + (size_t)n * n), d((size_t)n), e((size_t)n), zt((size_t)n * n);
+  const RangeScale rs(a.data(), a.size());
+  if (rs.on()) for (double& x : a) x *= rs.to;
   for (int j = 0; j < n; ++j)
     for (int k = j + 1; k < n; ++k) a[(size_t)j * n + k] = a[(size_t)k * n + j];   // the lower triangle is the matrix
   std::vector<double> work((size_t)2 * n);
@@ -228,7 +252,7 @@ bool sym_eigh_desc(const std::vector<double>& A, int n, std::vector<double>& w, 
   std::iota(order.begin(), order.end(), 0);
   std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return d[x] > d[y]; });
   for (int c = 0; c < n; ++c) {
-    w[c] = d[order[c]];
+    w[c] = rs.on() ? d[order[c]] * rs.back : d[order[c]];
     std::copy(zt.begin() + (size_t)order[c] * n, zt.begin() + (size_t)(order[c] + 1) * n, Vt.begin() + (size_t)c * n);
   }
   return true;
@@ -243,6 +267,10 @@ bool tridiag_eigh(std::vector<double>& d, std::vector<double>& e, int n, std::ve
   Z.assign((size_t)zr * n, 0.0);
   for (int i = k0; i < n; ++i) Z[(size_t)(i - k0) * n + i] = 1.0;
   if (n == 0) return true;
+  const RangeScale rs(d.data(), (size_t)n, e.data() + 1, (size_t)n - 1);   // (e[0] is unused)
+  if (rs.on()) {
+    for (int i = 0; i < n; ++i) { d[i] *= rs.to; e[i] *= rs.to; }
+  }
   for (int i = 1; i < n; ++i) e[i - 1] = e[i];
   e[n - 1] = 0.0;
   for (int l = 0; l < n; ++l) {
@@ -294,7 +322,7 @@ bool tridiag_eigh(std::vector<double>& d, std::vector<double>& e, int n, std::ve
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return d[a] < d[b]; });
   std::vector<double> d2(n), Z2((size_t)zr * n);
   for (int c = 0; c < n; ++c) {
-    d2[c] = d[order[c]];
+    d2[c] = rs.on() ? d[order[c]] * rs.back : d[order[c]];
     for (int k = 0; k < zr; ++k) Z2[(size_t)k * n + c] = Z[(size_t)k * n + order[c]];
   }
   d.swap(d2);

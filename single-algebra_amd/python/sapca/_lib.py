@@ -125,6 +125,7 @@ _TYPED = [
     "sapca_get_explained_variance_ratio", "sapca_get_cumulative_explained_variance_ratio",
     "sapca_get_feature_importances", "sapca_colstats_csr", "sapca_spmm_csr", "sapca_spmmt_csr",
     "sapca_normalize_panel", "sapca_generate_omega", "sapca_project_out_panel", "sapca_scale_panel_rows",
+    "sapca_normalize_panel_ex", "sapca_rotate_panel",
     "sapca_upload_csr", "sapca_normalize_csr_device", "sapca_log1p_csr_device", "sapca_stats_csr_device",
     "sapca_batch_stats_csr_device", "sapca_sum_row_n_top_csr_device", "sapca_masked_stats_csr_device",
     "sapca_select_rows_csr_device", "sapca_check_csr_device", "sapca_canonicalize_csr_device",
@@ -235,6 +236,13 @@ def _open(path):
         for suf, ct in (("f32", C.c_float), ("f64", C.c_double)):
             getattr(lib, f"sapca_scale_panel_rows_{suf}").argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(ct),
                                                                       C.POINTER(C.c_double)]
+    if hasattr(lib, "sapca_rotate_panel_f32"):   # (absent from an older build loaded for an A/B run)
+        for suf, ct in (("f32", C.c_float), ("f64", C.c_double)):
+            pt, pd = C.POINTER(ct), C.POINTER(C.c_double)
+            getattr(lib, f"sapca_normalize_panel_ex_{suf}").argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64,
+                                                                        C.c_uint32, pt, pt, pt, pt, pt, pt, pd, pd,
+                                                                        C.POINTER(C.c_int32)]
+            getattr(lib, f"sapca_rotate_panel_{suf}").argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, pt, pd, pt, pd]
     for suf, ct in (("f32", C.c_float), ("f64", C.c_double)):
         fn = getattr(lib, f"sapca_select_submatrix_csr_device_{suf}", None)   # (absent from an older build loaded for an A/B run)
         if fn is not None:

@@ -131,6 +131,55 @@ class Session:
             self._h, C.c_uint64(P.shape[0]), C.c_uint64(P.shape[1]), _p(P, ct), _p(d, C.c_double)))
         return P
 
+    def normalize_panel_ex(self, slabs, normalizer, passes=0, mu=None, sv=None, w=None, want_vec=True, want_r=True):
+        """sapca_normalize_panel_ex_*: Engine::normalize with its extras on a panel still lying in the nsplit x rows x l slabs
+        of a sweep (a rows x l array is one slab), minus mu sv^T.  Returns a dict: panel (rows x l), vec (l: sum_r w[r]
+        panel[r, :], w None = ones; None without want_vec), r1 / r2 (l x l f64 upper factors of the CholeskyQR passes, zeros
+        for a pass that did not run; None without want_r), regularised (pivots floored)."""
+        S = np.array(slabs, order="C", copy=True)
+        if S.ndim == 2:
+            S = S[None]
+        if S.ndim != 3:
+            raise ValueError(f"slabs {S.shape} must be nsplit x rows x l (or rows x l)")
+        nsplit, rows, l = S.shape
+        suf, ct = _SUF[S.dtype]
+        if (mu is None) != (sv is None):
+            raise ValueError("mu and sv go together")
+        vecs = {}
+        for name, v, n in (("mu", mu, rows), ("sv", sv, l), ("w", w, rows)):
+            if v is not None:
+                v = np.ascontiguousarray(v, dtype=S.dtype)
+                if v.shape != (n,):
+                    raise ValueError(f"{name} {v.shape} must hold {n} values")
+            vecs[name] = v
+        ptr = lambda a, t=ct: None if a is None else _p(a, t)   # noqa: E731
+        panel = np.zeros((rows, l), dtype=S.dtype)
+        vec = np.zeros(l, dtype=S.dtype) if want_vec else None
+        r1 = np.zeros((l, l)) if want_r else None
+        r2 = np.zeros((l, l)) if want_r else None
+        reg = C.c_int32(-1)
+        L.check(self._h, getattr(L.load(), f"sapca_normalize_panel_ex_{suf}")(
+            self._h, C.c_int32(int(normalizer)), C.c_int32(int(passes)), C.c_uint64(rows), C.c_uint64(l), C.c_uint32(nsplit),
+            _p(S, ct), ptr(vecs["mu"]), ptr(vecs["sv"]), ptr(vecs["w"]), _p(panel, ct), ptr(vec), ptr(r1, C.c_double),
+            ptr(r2, C.c_double), C.byref(reg)))
+        return {"panel": panel, "vec": vec, "r1": r1, "r2": r2, "regularised": int(reg.value)}
+
+    def rotate_panel(self, P, M):
+        """sapca_rotate_panel_*: (components, signs) = svd_flip((P M)^T) for an n x l panel P and an l x k factor M (taken as
+        f64) -- components k x n in P's dtype, signs k doubles -- by the panel product and the sign kernels a fit ends in."""
+        P = np.ascontiguousarray(P)
+        M = np.ascontiguousarray(M, dtype=np.float64)
+        if P.ndim != 2 or M.ndim != 2 or M.shape[0] != P.shape[1]:
+            raise ValueError(f"panel {P.shape} and factor {M.shape} must be n x l and l x k")
+        suf, ct = _SUF[P.dtype]
+        n, l = P.shape
+        k = M.shape[1]
+        comps = np.zeros((k, n), dtype=P.dtype)
+        signs = np.zeros(k)
+        L.check(self._h, getattr(L.load(), f"sapca_rotate_panel_{suf}")(
+            self._h, C.c_uint64(n), C.c_uint64(l), C.c_uint64(k), _p(P, ct), _p(M, C.c_double), _p(comps, ct), _p(signs, C.c_double)))
+        return comps, signs
+
     def generate_omega(self, rows, l, dtype=np.float64):
         out = np.zeros((rows, l), dtype=dtype)
         suf, ct = _SUF[np.dtype(dtype)]
