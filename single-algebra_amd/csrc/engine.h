@@ -7,6 +7,7 @@
 #include "comm.h"
 #include "common.h"
 #include "kernels.h"
+#include "rowsort.h"
 
 struct sapca_handle_s {
   sapca_options opt{};
@@ -148,10 +149,10 @@ struct sapca_handle_s {
     bool owns(const void* q) const { return ptr.contains(q) || idx.contains(q) || val.contains(q); }   // the result's arrays, not the work space
   } selection;
   // the canonical form of sapca_canonicalize_csr_device_*: a third CSR beside the upload's and the selection's (idx2 / val2
-  // hold it when duplicates merged: the fill's output), and the work space of the check and the sort: the counter block,
-  // per row {defect bits, distinct columns, three row lists} and the long rows' key offsets, their keys, the scan's
+  // hold it when duplicates merged: the fill's output), and the work space of the check and the row sort (rowsort.h)
   struct Canonical {
-    sapca::DevBuf ptr, idx, val, idx2, val2, ctr, rows, long_off, keys, scan;
+    sapca::DevBuf ptr, idx, val, idx2, val2;
+    sapca::resident::RowSort sort;
     bool owns(const void* q) const {
       return ptr.contains(q) || idx.contains(q) || val.contains(q) || idx2.contains(q) || val2.contains(q);
     }
@@ -161,15 +162,21 @@ struct sapca_handle_s {
   struct Knn {
     sapca::DevBuf unit_q, unit_c, bias, part_sc, part_ix, merged;
   } knn;
-  // sapca_tsne_*: the conditional affinities and the emitted entries (raw_*), the row sort's work space and output (as in
-  // Canonical), the symmetric P handed back (one of raw_ptr / out_ptr, one of raw_idx / sort_idx, out_val), the optimiser's
-  // state and sums, and the panels of the host and one-call routes.  Nothing else lives in these.
-  struct Tsne {
-    sapca::DevBuf p, raw_ptr, nvalid, cursor, raw_idx, raw_val, scan, ctr, rows, long_off, keys, sort_idx, sort_val, out_ptr, out_val;
-    sapca::DevBuf part, rep, sum_part, scal, klrow, grad, v, gain, colpart, knn_idx, knn_dist, x, y;
+  // a symmetric graph built from neighbour lists (tsne.cpp, neighbour_graph): the per-slot weights (p) and the emitted entries
+  // (raw_*), the row sort's copies, work space and merged offsets, and the graph handed back: one of raw_ptr / out_ptr, one of
+  // raw_idx / sort_idx, out_val
+  struct NeighbourGraph {
+    sapca::DevBuf p, raw_ptr, nvalid, cursor, raw_idx, raw_val, sort_idx, sort_val, out_ptr, out_val;
+    sapca::resident::RowSort sort;
     bool owns(const void* q) const {
       return raw_ptr.contains(q) || out_ptr.contains(q) || raw_idx.contains(q) || sort_idx.contains(q) || out_val.contains(q);
     }
+  };
+  // sapca_tsne_*: the symmetric P and what built it, the optimiser's state and sums, and the panels of the host and one-call
+  // routes.  Nothing else lives in these.
+  struct Tsne {
+    NeighbourGraph graph;
+    sapca::DevBuf part, rep, sum_part, scal, klrow, grad, v, gain, colpart, knn_idx, knn_dist, x, y;
   } tsne;
   // sapca_kmeans_*: the norms of the centroids and the rows, the list of ambiguous rows, the two label generations of the loop, the
   // counting sort's counts, offsets, scan space and row order, the slices' sums, the control block and the scalars, the seeding's
@@ -178,15 +185,12 @@ struct sapca_handle_s {
     sapca::DevBuf bias, xb, amb, lab0, lab1, cnt, tab, scan, order, partial, shiftpart, ctl, scal, rowd, sum_part, colpart, cols;
     sapca::DevBuf rows, seed_dist, seed_bsum, x, cen, labels;
   } kmeans;
-  // sapca_umap_*: the memberships and the emitted entries (raw_*), the row sort's work space and output (as in Tsne), the fuzzy
-  // union handed back (one of raw_ptr / out_ptr, one of raw_idx / sort_idx, out_val), the row sums and their total, the
-  // layout's schedule, its second embedding buffer, and the arrays of the host and one-call routes.  Nothing else lives in these.
+  // sapca_umap_*: the fuzzy union and what built it (a graph of its own: a t-SNE call never disturbs it), the row sums and their
+  // total, the layout's schedule, its second embedding buffer, and the arrays of the host and one-call routes.  Nothing else
+  // lives in these.
   struct Umap {
-    sapca::DevBuf p, raw_ptr, nvalid, cursor, raw_idx, raw_val, scan, ctr, rows, long_off, keys, sort_idx, sort_val, out_ptr, out_val;
+    NeighbourGraph graph;
     sapca::DevBuf rowsum, sum_part, scal, next, nextn, y2, minmax, knn_idx, knn_dist, x, y;
-    bool owns(const void* q) const {
-      return raw_ptr.contains(q) || out_ptr.contains(q) || raw_idx.contains(q) || sort_idx.contains(q) || out_val.contains(q);
-    }
   } umap;
   // sapca_louvain_*: the row lists per length class and the long rows' keys (of the level's graph, and `2` of the coarse rows
   // before their merge), the vertex sort's keys, k, s and (tot / S)^2 per vertex, the two generations of labels and totals, the

@@ -2,8 +2,6 @@
 // argument checks, buffer layouts, launches.  Everything that can be refused is refused before anything is enqueued or a
 // buffer is touched.  All work space lives in h.kmeans: a fitted model, a cached preparation, the upload's statistics, the
 // selection, the canonical and the t-SNE buffers are not touched.
-#include <cmath>
-
 #include "resident.h"
 
 namespace sapca {
@@ -13,8 +11,6 @@ namespace {
 
 namespace KK = sapca::k;
 
-std::string num(uint64_t v) { return std::to_string(v); }
-
 // n_clusters (at_most_rows: seeding and the whole run pick n_clusters distinct rows)
 void check_clusters(uint64_t k, uint64_t m, bool at_most_rows, const std::string& w) {
   SAPCA_CHECK(k != 0, SAPCA_ERR_ARG, w + ": n_clusters is 0");
@@ -23,34 +19,22 @@ void check_clusters(uint64_t k, uint64_t m, bool at_most_rows, const std::string
   SAPCA_CHECK(!at_most_rows || m == 0 || k <= m, SAPCA_ERR_ARG, w + ": n_clusters = " + num(k) + " exceeds the m = " + num(m) + " rows");
 }
 
-// the limits of the neighbour search on a panel's width and row stride, and the row count
-void check_panel(uint64_t m, uint64_t d, uint64_t ldx, const std::string& w) {
-  SAPCA_CHECK(d != 0, SAPCA_ERR_ARG, w + ": d is 0");
-  SAPCA_CHECK(d <= 1024, SAPCA_ERR_ARG, w + ": d = " + num(d) + " exceeds 1024 columns");
-  SAPCA_CHECK(ldx >= d, SAPCA_ERR_ARG, w + ": ldx = " + num(ldx) + " is less than d = " + num(d));
-  SAPCA_CHECK(ldx < (1ull << 28), SAPCA_ERR_ARG, w + ": a row stride of " + num(ldx) + " elements; 2^28 or more are not supported");
-  SAPCA_CHECK(m < (1ull << 31), SAPCA_ERR_ARG, w + ": m = " + num(m) + " rows; 2^31 or more are not supported");
-}
-
 void check_stage(uint64_t m, uint64_t d, uint64_t ldx, uint64_t k, bool at_most_rows, const char* who) {
   check_clusters(k, m, at_most_rows, who);
-  check_panel(m, d, ldx, who);
+  check_panel(d, ldx, "ldx", who);
+  check_rows(m, who);
 }
 
 // a whole run: the options, then the shape, in the order the header lists them
 void check_run(const sapca_kmeans_options* o, uint64_t m, uint64_t d, uint64_t ldx, const char* who) {
   const std::string w(who);
-  SAPCA_CHECK(o != nullptr, SAPCA_ERR_ARG, w + ": null options");
-  SAPCA_CHECK(o->struct_size == sizeof(sapca_kmeans_options), SAPCA_ERR_ARG,
-              w + ": options->struct_size is " + num(o->struct_size) + ", this library's sapca_kmeans_options has " +
-                  num(sizeof(sapca_kmeans_options)) + " bytes");
+  check_options_header(o, "sapca_kmeans_options", w);
   check_clusters(o->n_clusters, m, true, w);
   SAPCA_CHECK(o->init == SAPCA_KMEANS_PLUSPLUS || o->init == SAPCA_KMEANS_GIVEN, SAPCA_ERR_ARG,
               w + ": unknown init " + num(o->init) + " (0 PLUSPLUS, 1 GIVEN)");
-  char tol[40];
-  std::snprintf(tol, sizeof(tol), "%g", o->tol);
-  SAPCA_CHECK(std::isfinite(o->tol) && o->tol >= 0.0, SAPCA_ERR_ARG, w + ": tol = " + tol + " must be finite and not negative");
-  check_panel(m, d, ldx, w);
+  check_constant(o->tol, "tol", w);
+  check_panel(d, ldx, "ldx", w);
+  check_rows(m, w);
 }
 
 // the scalars of a call in h.kmeans.scal (f64): the inertia | tol_abs
@@ -239,17 +223,11 @@ void kmeans_host(H& h, uint64_t m, uint64_t d, const T* x, const sapca_kmeans_op
   }
   SAPCA_CHECK(x != nullptr && centroids != nullptr && labels != nullptr, SAPCA_ERR_ARG, std::string(who) + ": a NULL array with m = " + num(m));
   H::Kmeans& w = h.kmeans;
-  hipStream_t s = h.stream;
-  const size_t nc = (size_t)opts->n_clusters * d;
-  T* dx = w.x.as<T>((size_t)m * d);
-  T* dc = w.cen.as<T>(nc);
   int32_t* dl = w.labels.as<int32_t>(m);
-  SAPCA_HIP(hipMemcpyAsync(dx, x, (size_t)m * d * sizeof(T), hipMemcpyHostToDevice, s));
-  if (opts->init == SAPCA_KMEANS_GIVEN) SAPCA_HIP(hipMemcpyAsync(dc, centroids, nc * sizeof(T), hipMemcpyHostToDevice, s));
-  kmeans_device<T>(h, m, dx, d, d, opts, dc, dl, inertia, n_iter);
-  SAPCA_HIP(hipMemcpyAsync(centroids, dc, nc * sizeof(T), hipMemcpyDeviceToHost, s));
-  SAPCA_HIP(hipMemcpyAsync(labels, dl, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  SAPCA_HIP(hipStreamSynchronize(s));
+  host_route<T>(h, w.x, x, (size_t)m * d, w.cen, centroids, (size_t)opts->n_clusters * d, opts->init == SAPCA_KMEANS_GIVEN,
+                [&](const T* dx, T* dc) { kmeans_device<T>(h, m, dx, d, d, opts, dc, dl, inertia, n_iter); });
+  SAPCA_HIP(hipMemcpyAsync(labels, dl, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, h.stream));
+  SAPCA_HIP(hipStreamSynchronize(h.stream));
 }
 
 #define SAPCA_INSTANTIATE_KMEANS(T)                                                                                                 \

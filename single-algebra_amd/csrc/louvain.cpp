@@ -2,8 +2,6 @@
 // checks, buffer layouts, launches.  Everything that can be refused is refused before anything is enqueued or a buffer is
 // touched.  All work space lives in h.louvain: a fitted model, a cached preparation, the upload's statistics, the selection, the
 // canonical, the t-SNE, the k-means and the UMAP buffers are not touched.
-#include <cmath>
-
 #include "resident.h"
 
 namespace sapca {
@@ -13,20 +11,9 @@ namespace {
 
 namespace KK = sapca::k;
 
-std::string num(uint64_t v) { return std::to_string(v); }
-std::string numd(double v) {
-  char buf[40];
-  std::snprintf(buf, sizeof(buf), "%g", v);
-  return buf;
-}
-
-void check_constant(double v, const char* name, const std::string& w) {
-  SAPCA_CHECK(std::isfinite(v) && v >= 0.0, SAPCA_ERR_ARG, w + ": " + name + " = " + numd(v) + " must be finite and not negative");
-}
-
 template <typename T>
 void check_graph(const CsrView<T>& G, const std::string& w) {
-  SAPCA_CHECK((uint64_t)G.rows < (1ull << 31), SAPCA_ERR_ARG, w + ": m = " + num((uint64_t)G.rows) + " rows; 2^31 or more are not supported");
+  check_rows((uint64_t)G.rows, w);
   SAPCA_CHECK(G.rows == G.cols, SAPCA_ERR_ARG, w + ": the graph must be square");
   SAPCA_CHECK(G.rows == 0 || G.ptr != nullptr, SAPCA_ERR_ARG, w + ": NULL row offsets with m = " + num((uint64_t)G.rows));
   SAPCA_CHECK(G.nnz == 0 || (G.idx != nullptr && G.val != nullptr), SAPCA_ERR_ARG,
@@ -34,10 +21,7 @@ void check_graph(const CsrView<T>& G, const std::string& w) {
 }
 
 void check_options(const sapca_louvain_options* o, const std::string& w) {
-  SAPCA_CHECK(o != nullptr, SAPCA_ERR_ARG, w + ": null options");
-  SAPCA_CHECK(o->struct_size == sizeof(sapca_louvain_options), SAPCA_ERR_ARG,
-              w + ": options->struct_size is " + num(o->struct_size) + ", this library's sapca_louvain_options has " +
-                  num(sizeof(sapca_louvain_options)) + " bytes");
+  check_options_header(o, "sapca_louvain_options", w);
   check_constant(o->resolution, "resolution", w);
   check_constant(o->tol, "tol", w);
   SAPCA_CHECK(o->max_sweeps >= 1 && o->max_sweeps <= 4096, SAPCA_ERR_ARG, w + ": max_sweeps = " + num(o->max_sweeps) + " is outside 1 .. 4096");

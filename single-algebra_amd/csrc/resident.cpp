@@ -377,52 +377,34 @@ void select_submatrix(H& h, const CsrView<T>& A, const uint64_t* rows, uint64_t 
 // ---- the gate in front of the device entry points (canon.hip) ----------------------------------------------------------
 namespace {
 
-// The check of a device CSR: the offsets first (one synchronisation: nothing reads an entry before they are known to be
-// sound), then one pass over the entries; with_lists: the rows that need sorting are listed behind it for canonicalize.
-// ctr_host receives the counter block; the per-row words stay in h.canonical.rows.
+// The survey of an untrusted device CSR (rowsort.h) as a report; with_lists: the rows that need sorting are listed behind the
+// check for canonicalize.  The counter block stays in h.canonical.sort.counters.
 template <typename T>
-void run_check(H& h, const CsrView<T>& A, sapca_csr_report* rep, unsigned long long* ctr_host, bool with_lists) {
+sapca_csr_report run_check(H& h, const CsrView<T>& A, bool with_lists) {
   namespace K = sapca::k;
-  hipStream_t s = h.stream;
-  const int64_t m = A.rows;
-  unsigned long long* ctr = h.canonical.ctr.as<unsigned long long>(K::kCtrSlots);
-  // per row: defect bits, and for canonicalize behind them distinct columns | three lists (uint32 each)
-  uint32_t* rows = h.canonical.rows.as<uint32_t>((size_t)std::max<int64_t>(with_lists ? 5 * m : m, 1));
-  unsigned long long* long_off = with_lists ? h.canonical.long_off.as<unsigned long long>((size_t)std::max<int64_t>(m, 1)) : nullptr;
-  K::canon_check_offsets(A.ptr, m, A.nnz, ctr, s);
-  SAPCA_HIP(hipMemcpyAsync(ctr_host, ctr, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  SAPCA_HIP(hipStreamSynchronize(s));
+  const bool sound = h.canonical.sort.survey(A, with_lists, true, h.stream);
+  const unsigned long long* c = h.canonical.sort.counters;
   const uint64_t none = UINT64_MAX;
   sapca_csr_report r{};
   r.struct_size = (uint32_t)sizeof(sapca_csr_report);
-  r.first_bad_offset_row = ctr_host[K::kCtrFirstBadOffset];
+  r.first_bad_offset_row = c[K::kCtrFirstBadOffset];
   r.first_out_of_range_row = r.first_unsorted_row = r.first_duplicate_row = r.first_nonfinite_row = none;
-  if (r.first_bad_offset_row != none) {
+  if (!sound) {
     r.flags = SAPCA_CSR_BAD_OFFSETS;
-  } else {
-    K::canon_check_entries(A, rows, ctr, s);
-    if (with_lists) K::canon_list_rows(A.ptr, rows, m, rows + 2 * m, long_off, ctr, s);
-    SAPCA_HIP(hipMemcpyAsync(ctr_host, ctr, K::kCtrSlots * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    SAPCA_HIP(hipStreamSynchronize(s));
-    r.cols_out_of_range = ctr_host[K::kCtrColsOutOfRange];
-    r.first_out_of_range_row = ctr_host[K::kCtrFirstOutOfRange];
-    r.unsorted_rows = ctr_host[K::kCtrUnsortedRows];
-    r.first_unsorted_row = ctr_host[K::kCtrFirstUnsorted];
-    r.duplicate_entries = ctr_host[K::kCtrDuplicates];
-    r.first_duplicate_row = ctr_host[K::kCtrFirstDuplicate];
-    r.nonfinite_values = ctr_host[K::kCtrNonfinite];
-    r.first_nonfinite_row = ctr_host[K::kCtrFirstNonfinite];
-    r.stored_zeros = ctr_host[K::kCtrStoredZeros];
-    r.flags = (r.cols_out_of_range ? SAPCA_CSR_COL_RANGE : 0u) | (r.unsorted_rows ? SAPCA_CSR_UNSORTED : 0u) |
-              (r.duplicate_entries ? SAPCA_CSR_DUPLICATES : 0u) | (r.nonfinite_values ? SAPCA_CSR_NONFINITE : 0u);
+    return r;
   }
-  *rep = r;
-}
-
-void check_report_arg(const sapca_csr_report* report, const char* who) {
-  SAPCA_CHECK(report->struct_size == sizeof(sapca_csr_report), SAPCA_ERR_ARG,
-              std::string(who) + ": report->struct_size is " + std::to_string(report->struct_size) + ", this library's sapca_csr_report has " +
-                  std::to_string(sizeof(sapca_csr_report)) + " bytes");
+  r.cols_out_of_range = c[K::kCtrColsOutOfRange];
+  r.first_out_of_range_row = c[K::kCtrFirstOutOfRange];
+  r.unsorted_rows = c[K::kCtrUnsortedRows];
+  r.first_unsorted_row = c[K::kCtrFirstUnsorted];
+  r.duplicate_entries = c[K::kCtrDuplicates];
+  r.first_duplicate_row = c[K::kCtrFirstDuplicate];
+  r.nonfinite_values = c[K::kCtrNonfinite];
+  r.first_nonfinite_row = c[K::kCtrFirstNonfinite];
+  r.stored_zeros = c[K::kCtrStoredZeros];
+  r.flags = (r.cols_out_of_range ? SAPCA_CSR_COL_RANGE : 0u) | (r.unsorted_rows ? SAPCA_CSR_UNSORTED : 0u) |
+            (r.duplicate_entries ? SAPCA_CSR_DUPLICATES : 0u) | (r.nonfinite_values ? SAPCA_CSR_NONFINITE : 0u);
+  return r;
 }
 
 // dst <- src, `bytes` of device memory on the stream: the 16-byte streaming copy where both ends allow it, the tail (and an
@@ -443,12 +425,9 @@ void device_copy(const void* src, void* dst, size_t bytes, hipStream_t s) {
 template <typename T>
 void check(H& h, const CsrView<T>& A, sapca_csr_report* report) {
   SAPCA_CHECK(report != nullptr, SAPCA_ERR_ARG, "check_csr: null report");
-  check_report_arg(report, "check_csr");
+  check_struct_size(report, "report", "sapca_csr_report", "check_csr");
   check_view(A);
-  unsigned long long ctr_host[k::kCtrSlots] = {};
-  sapca_csr_report r;
-  run_check(h, A, &r, ctr_host, false);
-  *report = r;
+  *report = run_check(h, A, false);
 }
 
 // Rows sorted by column, equal columns summed (canon.hip).  Everything that can be refused is refused before a canonical
@@ -458,15 +437,13 @@ void canonicalize(H& h, const CsrView<T>& A, uint64_t* nnz_out, const int64_t** 
                   sapca_csr_report* report) {
   namespace K = sapca::k;
   SAPCA_CHECK(nnz_out && d_ptr && d_idx && d_val, SAPCA_ERR_ARG, "canonicalize: null output pointer");
-  if (report) check_report_arg(report, "canonicalize");
+  if (report) check_struct_size(report, "report", "sapca_csr_report", "canonicalize");
   check_view(A);
   const uint64_t m = (uint64_t)A.rows, n = (uint64_t)A.cols, nnz = (uint64_t)A.nnz;
   H::Canonical& can = h.canonical;
   SAPCA_CHECK(!can.owns(A.ptr) && !can.owns(A.idx) && !can.owns(A.val), SAPCA_ERR_ARG,
               "canonicalize: the source is this handle's own canonical result, which the call overwrites (it is canonical already)");
-  unsigned long long ctr_host[K::kCtrSlots] = {};
-  sapca_csr_report r;
-  run_check(h, A, &r, ctr_host, true);
+  sapca_csr_report r = run_check(h, A, true);
   if (r.flags & SAPCA_CSR_BAD_OFFSETS)
     throw Error(SAPCA_ERR_ARG, "canonicalize: the row offsets are broken at row " + std::to_string(r.first_bad_offset_row) +
                                    " (ptr[0] != 0, a decreasing offset, or ptr[m] != nnz): this cannot be repaired");
@@ -490,19 +467,11 @@ void canonicalize(H& h, const CsrView<T>& A, uint64_t* nnz_out, const int64_t** 
   T* o_val = can.val.as<T>(nnz);
   device_copy(A.idx, o_idx, nnz * sizeof(int32_t), s);
   device_copy(A.val, o_val, nnz * sizeof(T), s);
-  uint32_t* row_bits = can.rows.ptr<uint32_t>();
-  const int64_t counts[3] = {(int64_t)ctr_host[K::kCtrListWave], (int64_t)ctr_host[K::kCtrListLds], (int64_t)ctr_host[K::kCtrListLong]};
-  unsigned long long* keys = counts[2] ? can.keys.as<unsigned long long>(ctr_host[K::kCtrLongEntries]) : nullptr;
-  unsigned long long* ctr = can.ctr.ptr<unsigned long long>();
-  K::canon_sort_rows(A, row_bits + 2 * rows, can.long_off.ptr<unsigned long long>(), counts, keys, o_idx, o_val, row_bits + rows, ctr, s);
-  unsigned long long merged = 0;
-  SAPCA_HIP(hipMemcpyAsync(&merged, ctr + K::kCtrMerged, sizeof(merged), hipMemcpyDeviceToHost, s));
-  SAPCA_HIP(hipStreamSynchronize(s));
+  const uint64_t merged = can.sort.sort(A, o_idx, o_val, s);
   if (merged == 0) {   // the rows did not move: the offsets are the input's
     device_copy(A.ptr, o_ptr, (m + 1) * sizeof(int64_t), s);
   } else {
-    K::canon_new_lengths(A.ptr, row_bits, row_bits + rows, rows, o_ptr, s);
-    K::exclusive_scan_i64(o_ptr, rows + 1, can.scan, 0, s);
+    can.sort.merged_offsets(A.ptr, rows, o_ptr, s);
     int32_t* f_idx = can.idx2.as<int32_t>(nnz - merged + 1);
     T* f_val = can.val2.as<T>(nnz - merged + 1);
     K::canon_merge_fill(A.ptr, o_idx, o_val, rows, o_ptr, f_idx, f_val, s);
@@ -540,7 +509,6 @@ SAPCA_INSTANTIATE_RESIDENT(double)
 template <typename T>
 void knn(H& h, uint64_t mq, const T* dq, uint64_t ldq, uint64_t mc, const T* dc, uint64_t ldc, uint64_t d, int32_t metric,
          uint32_t n_neighbors, uint32_t flags, int32_t* d_indices, T* d_values) {
-  const auto num = [](uint64_t v) { return std::to_string(v); };
   SAPCA_CHECK(metric == SAPCA_KNN_EUCLIDEAN || metric == SAPCA_KNN_COSINE || metric == SAPCA_KNN_PEARSON, SAPCA_ERR_ARG,
               "knn: unknown metric " + std::to_string(metric) + " (0 EUCLIDEAN, 1 COSINE, 2 PEARSON)");
   SAPCA_CHECK((flags & ~(uint32_t)SAPCA_KNN_EXCLUDE_SELF) == 0, SAPCA_ERR_ARG,
@@ -549,12 +517,10 @@ void knn(H& h, uint64_t mq, const T* dq, uint64_t ldq, uint64_t mc, const T* dc,
   SAPCA_CHECK(n_neighbors != 0, SAPCA_ERR_ARG, "knn: n_neighbors is 0");
   SAPCA_CHECK(n_neighbors <= SAPCA_KNN_MAX_NEIGHBORS, SAPCA_ERR_ARG,
               "knn: n_neighbors = " + num(n_neighbors) + " exceeds SAPCA_KNN_MAX_NEIGHBORS = " + num(SAPCA_KNN_MAX_NEIGHBORS));
-  SAPCA_CHECK(d != 0, SAPCA_ERR_ARG, "knn: d is 0");
-  SAPCA_CHECK(d <= 1024, SAPCA_ERR_ARG, "knn: d = " + num(d) + " exceeds 1024 columns");
-  SAPCA_CHECK(ldq >= d, SAPCA_ERR_ARG, "knn: ldq = " + num(ldq) + " is less than d = " + num(d));
-  SAPCA_CHECK(ldc >= d, SAPCA_ERR_ARG, "knn: ldc = " + num(ldc) + " is less than d = " + num(d));
-  SAPCA_CHECK(ldq < (1ull << 28) && ldc < (1ull << 28), SAPCA_ERR_ARG,
-              "knn: a row stride of " + num(ldq < (1ull << 28) ? ldc : ldq) + " elements; 2^28 or more are not supported");
+  check_panel_width(d, "knn");
+  check_stride_covers(d, ldq, "ldq", "knn");
+  check_stride_covers(d, ldc, "ldc", "knn");
+  check_stride_limit(ldq < (1ull << 28) ? ldc : ldq, "knn");   // (the first of the two that is too long)
   SAPCA_CHECK(mc < (1ull << 31), SAPCA_ERR_ARG, "knn: mc = " + num(mc) + " corpus rows; 2^31 or more are not supported");
   SAPCA_CHECK(mq < (1ull << 31), SAPCA_ERR_ARG, "knn: mq = " + num(mq) + " query rows; 2^31 or more are not supported");
   if ((uint64_t)n_neighbors + (exclude_self ? 1 : 0) > mc)
@@ -567,9 +533,7 @@ void knn(H& h, uint64_t mq, const T* dq, uint64_t ldq, uint64_t mc, const T* dc,
 
   hipStream_t s = h.stream;
   const int nn = (int)n_neighbors, dd = (int)d;
-  int n_cus = 0;
-  SAPCA_HIP(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, h.device));
-  const k::KnnPlan plan = k::knn_plan<T>((int64_t)mq, (int64_t)mc, nn, n_cus);
+  const k::KnnPlan plan = k::knn_plan<T>((int64_t)mq, (int64_t)mc, nn, cu_count(h));
   H::Knn& w = h.knn;
   // prepare: what the ranking s(i, j) = alpha <a_i, b_j> + bias_j runs on
   const T *sq = dq, *sc = dc, *bias = nullptr;

@@ -2,6 +2,9 @@
 // statistics, row selection, check / canonicalise.  Host side only: buffer layouts, launches, the finishing arithmetic.
 // They throw sapca::Error; api.cpp turns that into a status.
 #pragma once
+#include <functional>
+
+#include "checks.h"
 #include "engine.h"
 
 namespace sapca {
@@ -100,6 +103,22 @@ void canonicalize(H& h, const CsrView<T>& A, uint64_t* nnz_out, const int64_t** 
 template <typename T>
 void knn(H& h, uint64_t mq, const T* d_queries, uint64_t ldq, uint64_t mc, const T* d_corpus, uint64_t ldc, uint64_t d, int32_t metric,
          uint32_t n_neighbors, uint32_t flags, int32_t* d_indices, T* d_values);
+
+// The front half of the two neighbour-graph builders (tsne.cpp; count / emit are tsne.hip's): the checks on m, K and the lists,
+// g's buffers, `weights(p)` (enqueues the m x K per-slot weights), the emitted rows, and the row sort with its merged offsets.
+// What it leaves for the caller's finish: the emitted rows, then the rows to read (sorted: g.sort_*, the raw arrays are free to
+// take the result; else the raw ones), the offsets and the entry count of the graph (merged != 0: g.out_ptr).  m == 0 gives
+// the empty graph, complete.
+struct RawGraph {
+  CsrView<double> raw;
+  const int64_t* ptr = nullptr;
+  const int32_t* idx = nullptr;
+  const double* val = nullptr;
+  uint64_t nnz = 0, merged = 0;
+  bool sorted = false;
+};
+RawGraph neighbour_graph(H& h, H::NeighbourGraph& g, const std::string& who, uint64_t m, uint32_t K, const int32_t* d_indices,
+                         bool dist_given, const std::function<void(double*)>& weights);
 
 // sapca_tsne_* (tsne.cpp): the affinity graph of neighbour lists, one gradient evaluation, the optimiser, and the whole chain
 // on a device panel or on host arrays

@@ -1,9 +1,7 @@
-// Host staging of sapca_umap_* (the kernels are umap.hip's, the neighbour search knn.hip's, count / emit tsne.hip's, the row sort
-// canon.hip's): argument checks, the curve fit, buffer layouts, launches.  Everything that can be refused is refused before
+// Host staging of sapca_umap_* (the kernels are umap.hip's, the neighbour search knn.hip's, the graph's front half tsne.cpp's
+// neighbour_graph): argument checks, the curve fit, buffer layouts, launches.  Everything that can be refused is refused before
 // anything is enqueued or a buffer is touched.  All work space lives in h.umap: a fitted model, a cached preparation, the
 // upload's statistics, the selection, the canonical, the t-SNE and the k-means buffers are not touched.
-#include <cmath>
-
 #include "resident.h"
 
 namespace sapca {
@@ -11,28 +9,10 @@ namespace resident {
 
 namespace {
 
-std::string num(uint64_t v) { return std::to_string(v); }
-std::string numd(double v) {
-  char buf[40];
-  std::snprintf(buf, sizeof(buf), "%g", v);
-  return buf;
-}
-
-void check_rows(uint64_t m, const std::string& w) {
-  SAPCA_CHECK(m < (1ull << 31), SAPCA_ERR_ARG, w + ": m = " + num(m) + " rows; 2^31 or more are not supported");
-}
-
-void check_constant(double v, const char* name, const std::string& w) {
-  SAPCA_CHECK(std::isfinite(v) && v >= 0.0, SAPCA_ERR_ARG, w + ": " + name + " = " + numd(v) + " must be finite and not negative");
-}
-
 // everything about the options that needs no shape; the curve (a, b) comes back fitted where both are 0
 void check_options(const sapca_umap_options* o, const char* who, double* a, double* b) {
   const std::string w(who);
-  SAPCA_CHECK(o != nullptr, SAPCA_ERR_ARG, w + ": null options");
-  SAPCA_CHECK(o->struct_size == sizeof(sapca_umap_options), SAPCA_ERR_ARG,
-              w + ": options->struct_size is " + num(o->struct_size) + ", this library's sapca_umap_options has " +
-                  num(sizeof(sapca_umap_options)) + " bytes");
+  check_options_header(o, "sapca_umap_options", w);
   SAPCA_CHECK(o->output_dim >= 1 && o->output_dim <= 3, SAPCA_ERR_ARG, w + ": output_dim = " + num(o->output_dim) + " is outside 1 .. 3");
   SAPCA_CHECK(o->init <= SAPCA_UMAP_INIT_GIVEN, SAPCA_ERR_ARG, w + ": init = " + num(o->init) + " is not a sapca_umap_init");
   SAPCA_CHECK(o->n_neighbors >= 2 && o->n_neighbors <= SAPCA_KNN_MAX_NEIGHBORS + 1, SAPCA_ERR_ARG,
@@ -56,14 +36,6 @@ void check_options(const sapca_umap_options* o, const char* who, double* a, doub
 void check_neighbours_fit(uint32_t n_neighbors, uint64_t m, const std::string& w) {
   SAPCA_CHECK(m == 0 || n_neighbors <= m, SAPCA_ERR_ARG,
               w + ": n_neighbors = " + num(n_neighbors) + " exceeds the m = " + num(m) + " rows");
-}
-
-// the limits of the neighbour search on a panel's width and row stride (knn<T> checks them again, after)
-void check_panel(uint64_t d, uint64_t ld, const std::string& w) {
-  SAPCA_CHECK(d != 0, SAPCA_ERR_ARG, w + ": d is 0");
-  SAPCA_CHECK(d <= 1024, SAPCA_ERR_ARG, w + ": d = " + num(d) + " exceeds 1024 columns");
-  SAPCA_CHECK(ld >= d, SAPCA_ERR_ARG, w + ": ldx = " + num(ld) + " is less than d = " + num(d));
-  SAPCA_CHECK(ld < (1ull << 28), SAPCA_ERR_ARG, w + ": a row stride of " + num(ld) + " elements; 2^28 or more are not supported");
 }
 
 void check_init_panel(const sapca_umap_options* o, uint64_t d, const std::string& w) {
@@ -201,90 +173,28 @@ void umap_graph(H& h, uint64_t m, const int32_t* d_indices, const T* d_dist, uin
   const std::string who("umap_graph");
   SAPCA_CHECK(nnz_out && d_ptr && d_idx && d_val, SAPCA_ERR_ARG, who + ": null output pointer");
   SAPCA_CHECK(n_neighbors >= 2, SAPCA_ERR_ARG, who + ": n_neighbors = " + num(n_neighbors) + " must be at least 2");
-  check_rows(m, who);
-  SAPCA_CHECK(K >= 1 && K <= SAPCA_KNN_MAX_NEIGHBORS, SAPCA_ERR_ARG,
-              who + ": K = " + num(K) + " neighbours per row is outside 1 .. " + num(SAPCA_KNN_MAX_NEIGHBORS));
-  SAPCA_CHECK(m == 0 || (d_indices && d_dist), SAPCA_ERR_ARG, who + ": a NULL neighbour list with m = " + num(m));
   H::Umap& w = h.umap;
+  H::NeighbourGraph& g = w.graph;
   hipStream_t s = h.stream;
-  h.drop_preparation_of(w);
   const int64_t rows = (int64_t)m;
-  const size_t cap = std::max<size_t>((size_t)2 * m * K, 1);
-  double* p = w.p.as<double>(std::max<size_t>((size_t)m * K, 1));
-  int64_t* raw_ptr = w.raw_ptr.as<int64_t>(m + 1);
-  int32_t* nvalid = w.nvalid.as<int32_t>(std::max<size_t>(m, 1));
-  int32_t* cursor = w.cursor.as<int32_t>(std::max<size_t>(m, 1));
-  int32_t* raw_idx = w.raw_idx.as<int32_t>(cap);
-  double* raw_val = w.raw_val.as<double>(cap);
-  int32_t* s_idx = w.sort_idx.as<int32_t>(cap);
-  if (m == 0) {   // valid: an empty graph
-    SAPCA_HIP(hipMemsetAsync(raw_ptr, 0, sizeof(int64_t), s));
-    SAPCA_HIP(hipStreamSynchronize(s));
-    *nnz_out = 0;
-    *d_ptr = raw_ptr;
-    *d_idx = raw_idx;
-    *d_val = w.out_val.as<T>(1);
-    return;
+  const RawGraph r = neighbour_graph(h, g, who, m, K, d_indices, d_dist != nullptr, [&](double* p) {   // the memberships
+    double* scal = w.scal.as<double>(kScalCount);
+    double* rowsum = w.rowsum.as<double>((size_t)m);
+    double* sum_part = w.sum_part.as<double>(KK::tsne_sum_parts(rows) + 1);
+    KK::umap_row_sums<T>(d_indices, d_dist, rows, (int)K, rowsum, s);
+    KK::tsne_sum(rowsum, rows, sum_part, scal + kScalTotal, s);
+    KK::umap_smooth<T>(d_indices, d_dist, rows, (int)K, (int)n_neighbors, scal + kScalTotal, p, d_sigma, d_rho, s);
+  });
+  // the two directions of a pair combined by the fill, into whichever index array the rows are not read from (sorted: the raw
+  // arrays have been gathered from)
+  int32_t* o_idx = r.sorted || m == 0 ? g.raw_idx.ptr<int32_t>() : g.sort_idx.ptr<int32_t>();
+  T* out_val = g.out_val.as<T>(std::max<size_t>((size_t)r.raw.nnz, 1));
+  if (m) {
+    KK::umap_union_fill<T>(r.raw.ptr, r.idx, r.val, rows, r.ptr, o_idx, out_val, s);
+    SAPCA_HIP(hipStreamSynchronize(s));   // complete when the call returns
   }
-  double* scal = w.scal.as<double>(kScalCount);
-  double* rowsum = w.rowsum.as<double>((size_t)m);
-  double* sum_part = w.sum_part.as<double>(KK::tsne_sum_parts(rows) + 1);
-  KK::umap_row_sums<T>(d_indices, d_dist, rows, (int)K, rowsum, s);
-  KK::tsne_sum(rowsum, rows, sum_part, scal + kScalTotal, s);
-  KK::umap_smooth<T>(d_indices, d_dist, rows, (int)K, (int)n_neighbors, scal + kScalTotal, p, d_sigma, d_rho, s);
-  KK::tsne_count(d_indices, rows, (int)K, raw_ptr, nvalid, s);
-  KK::exclusive_scan_i64(raw_ptr, rows + 1, w.scan, 0, s);
-  int64_t nnz_raw = 0;
-  SAPCA_HIP(hipMemcpyAsync(&nnz_raw, raw_ptr + rows, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  SAPCA_HIP(hipStreamSynchronize(s));
-  KK::tsne_emit(d_indices, p, rows, (int)K, raw_ptr, nvalid, cursor, raw_idx, raw_val, s);
-
-  // rows by ascending column (the sequence of resident::canonicalize, in buffers of this call's own), then the two directions
-  // of a pair combined by the fill
-  CsrView<double> A;
-  A.rows = rows; A.cols = rows; A.nnz = nnz_raw; A.ptr = raw_ptr; A.idx = raw_idx; A.val = raw_val;
-  unsigned long long ctr_host[KK::kCtrSlots] = {};
-  unsigned long long* ctr = w.ctr.as<unsigned long long>(KK::kCtrSlots);
-  uint32_t* row_bits = w.rows.as<uint32_t>((size_t)std::max<int64_t>(5 * rows, 1));
-  unsigned long long* long_off = w.long_off.as<unsigned long long>((size_t)std::max<int64_t>(rows, 1));
-  if (nnz_raw > 0) {   // (no valid slot at all: an empty graph, nothing to sort)
-    KK::canon_check_offsets(A.ptr, rows, A.nnz, ctr, s);
-    KK::canon_check_entries(A, row_bits, ctr, s);
-    KK::canon_list_rows(A.ptr, row_bits, rows, row_bits + 2 * rows, long_off, ctr, s);
-    SAPCA_HIP(hipMemcpyAsync(ctr_host, ctr, KK::kCtrSlots * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    SAPCA_HIP(hipStreamSynchronize(s));
-  }
-  const int64_t* o_ptr = raw_ptr;
-  const int32_t* in_idx = raw_idx;
-  const double* in_val = raw_val;
-  int32_t* o_idx = s_idx;
-  uint64_t nnz = (uint64_t)nnz_raw;
-  if (nnz_raw > 0 && (ctr_host[KK::kCtrUnsortedRows] || ctr_host[KK::kCtrDuplicates])) {
-    double* s_val = w.sort_val.as<double>(cap);
-    SAPCA_HIP(hipMemcpyAsync(s_idx, raw_idx, (size_t)nnz_raw * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    SAPCA_HIP(hipMemcpyAsync(s_val, raw_val, (size_t)nnz_raw * sizeof(double), hipMemcpyDeviceToDevice, s));
-    const int64_t counts[3] = {(int64_t)ctr_host[KK::kCtrListWave], (int64_t)ctr_host[KK::kCtrListLds], (int64_t)ctr_host[KK::kCtrListLong]};
-    unsigned long long* keys = counts[2] ? w.keys.as<unsigned long long>(ctr_host[KK::kCtrLongEntries]) : nullptr;
-    KK::canon_sort_rows(A, row_bits + 2 * rows, long_off, counts, keys, s_idx, s_val, row_bits + rows, ctr, s);
-    unsigned long long merged = 0;
-    SAPCA_HIP(hipMemcpyAsync(&merged, ctr + KK::kCtrMerged, sizeof(merged), hipMemcpyDeviceToHost, s));
-    SAPCA_HIP(hipStreamSynchronize(s));
-    in_idx = s_idx;
-    in_val = s_val;
-    o_idx = raw_idx;   // (the raw arrays have been gathered from: they take the filled rows)
-    if (merged) {
-      int64_t* n_ptr = w.out_ptr.as<int64_t>(m + 1);
-      KK::canon_new_lengths(A.ptr, row_bits, row_bits + rows, rows, n_ptr, s);
-      KK::exclusive_scan_i64(n_ptr, rows + 1, w.scan, 0, s);
-      o_ptr = n_ptr;
-      nnz -= merged;
-    }
-  }
-  T* out_val = w.out_val.as<T>(std::max<size_t>((size_t)nnz_raw, 1));
-  KK::umap_union_fill<T>(raw_ptr, in_idx, in_val, rows, o_ptr, o_idx, out_val, s);
-  SAPCA_HIP(hipStreamSynchronize(s));   // complete when the call returns
-  *nnz_out = nnz;
-  *d_ptr = o_ptr;
+  *nnz_out = r.nnz;
+  *d_ptr = r.ptr;
   *d_idx = o_idx;
   *d_val = out_val;
 }
@@ -311,7 +221,7 @@ void umap_device(H& h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d, const
   check_options(opts, who.c_str(), &a, &b);
   check_rows(m, who);
   check_neighbours_fit(opts->n_neighbors, m, who);
-  check_panel(d, ldx, who);
+  check_panel(d, ldx, "ldx", who);   // (knn<T> checks them again, after)
   check_init_panel(opts, d, who);
   if (m == 0) return;
   SAPCA_CHECK(d_x != nullptr && d_y != nullptr, SAPCA_ERR_ARG, who + ": a NULL panel with m = " + num(m));
@@ -338,20 +248,13 @@ void umap_host(H& h, uint64_t m, uint64_t d, const T* x, const sapca_umap_option
   check_options(opts, who.c_str(), &a, &b);
   check_rows(m, who);
   check_neighbours_fit(opts->n_neighbors, m, who);
-  check_panel(d, d, who);
+  check_panel(d, d, "ldx", who);
   check_init_panel(opts, d, who);
   if (m == 0) return;
   SAPCA_CHECK(x != nullptr && y != nullptr, SAPCA_ERR_ARG, who + ": a NULL array with m = " + num(m));
-  H::Umap& w = h.umap;
-  hipStream_t s = h.stream;
-  const size_t ny = (size_t)m * opts->output_dim;
-  T* dx = w.x.as<T>((size_t)m * d);
-  T* dy = w.y.as<T>(ny);
-  SAPCA_HIP(hipMemcpyAsync(dx, x, (size_t)m * d * sizeof(T), hipMemcpyHostToDevice, s));
-  if (opts->init == SAPCA_UMAP_INIT_GIVEN) SAPCA_HIP(hipMemcpyAsync(dy, y, ny * sizeof(T), hipMemcpyHostToDevice, s));
-  umap_device<T>(h, m, dx, d, d, opts, dy);
-  SAPCA_HIP(hipMemcpyAsync(y, dy, ny * sizeof(T), hipMemcpyDeviceToHost, s));
-  SAPCA_HIP(hipStreamSynchronize(s));
+  host_route<T>(h, h.umap.x, x, (size_t)m * d, h.umap.y, y, (size_t)m * opts->output_dim, opts->init == SAPCA_UMAP_INIT_GIVEN,
+                [&](const T* dx, T* dy) { umap_device<T>(h, m, dx, d, d, opts, dy); });
+  SAPCA_HIP(hipStreamSynchronize(h.stream));
 }
 
 #define SAPCA_INSTANTIATE_UMAP(T)                                                                                                   \

@@ -129,6 +129,54 @@ def test_unfilled_slots_contribute_nothing(sess, gold, dt):
     assert np.isfinite(got.data).all() and np.isfinite(beta.cpu().numpy()).all()
 
 
+def _bytes_of(P, beta):
+    got = _host_csr(P)
+    return got.indptr.tobytes(), got.indices.tobytes(), got.data.tobytes(), beta.cpu().numpy().tobytes()
+
+
+@pytest.mark.parametrize("dt", DTYPES, **IDS)
+def test_affinities_through_every_length_class_of_the_row_sort(sess, dt):
+    """hand-made lists: one raw row beyond canon_lds_cap() that merges mutual pairs, one between 65 entries and the cap"""
+    idx, dist = TR.hub_lists()
+    m, K = idx.shape
+    counts, merged = TR.sort_classes(idx)
+    print(f"rows that need the sort per length class {counts}, merged entries {merged}")
+    assert all(c > 0 for c in counts) and merged > 0                           # from the lists alone, before the GPU runs
+    assert np.isin(idx[0], np.nonzero((idx == 0).any(axis=1))[0]).all()        # the long row lists rows that list it back
+    dist_t = dist.astype(dt)
+    P, beta = sess.tsne_affinities(_dev(idx), _dev(dist_t), 2.0)
+    got = _check_affinities(P, beta.cpu().numpy(), idx, dist_t, 2.0, dt)
+    assert got.nnz == 2 * m * K - merged and np.diff(got.indptr)[0] == m - 1
+    assert _bytes_of(*sess.tsne_affinities(_dev(idx), _dev(dist_t), 2.0)) == _bytes_of(P, beta)
+
+
+@pytest.mark.parametrize("dt", DTYPES, **IDS)
+def test_affinities_of_a_directed_ring_merge_nothing(sess, dt):
+    """K = 1, no mutual pair: every row is sorted, none merges, and the offsets stay the raw ones"""
+    m = 65
+    idx = ((np.arange(m) + 1) % m).astype(np.int32)[:, None]
+    dist_t = np.random.default_rng(65).uniform(0.5, 1.5, size=(m, 1)).astype(np.float32).astype(dt)
+    assert TR.sort_classes(idx) == ([m - 2, 0, 0], 0)                          # (rows 0 and m - 1 are ascending as emitted)
+    P, beta = sess.tsne_affinities(_dev(idx), _dev(dist_t), 1.0)
+    got = _check_affinities(P, beta.cpu().numpy(), idx, dist_t, 1.0, dt)
+    assert got.nnz == 2 * m
+    np.testing.assert_array_equal(got.indptr, 2 * np.arange(m + 1))
+    assert _bytes_of(*sess.tsne_affinities(_dev(idx), _dev(dist_t), 1.0)) == _bytes_of(P, beta)
+
+
+@pytest.mark.parametrize("dt", DTYPES, **IDS)
+def test_affinities_without_a_valid_slot_are_an_empty_graph(sess, dt):
+    m, K = 8, 3
+    idx = np.full((m, K), -1, dtype=np.int32)
+    dist_t = np.full((m, K), np.nan, dtype=dt)
+    P, beta = sess.tsne_affinities(_dev(idx), _dev(dist_t), 2.0)
+    got = _host_csr(P)
+    assert got.shape == (m, m) and got.nnz == 0 and (got.indptr == 0).all() and got.data.dtype == np.dtype(dt)
+    assert np.isfinite(beta.cpu().numpy()).all()
+    assert P.check().canonical
+    assert _bytes_of(*sess.tsne_affinities(_dev(idx), _dev(dist_t), 2.0)) == _bytes_of(P, beta)
+
+
 # ------------------------------------------------------------------ 2. gradient
 _GRAD = {}
 

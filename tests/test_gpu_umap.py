@@ -154,6 +154,39 @@ def test_degenerate_rows_and_unfilled_slots(sess, gold, dt):
     assert (got[3].data[np.isin(got[3].indices, idx[3])] >= 1 - 2.0 ** -53).all()   # (1 + b) - b: 1 up to one rounding
 
 
+@pytest.mark.parametrize("dt", DTYPES, **IDS)
+def test_graph_through_every_length_class_of_the_row_sort(sess, dt):
+    """hand-made lists: one raw row beyond canon_lds_cap() that merges mutual pairs, one between 65 entries and the cap"""
+    idx, dist = UR.hub_lists()
+    m, K = idx.shape
+    counts, merged = UR.sort_classes(idx)
+    print(f"rows that need the sort per length class {counts}, merged entries {merged}")
+    assert all(c > 0 for c in counts) and merged > 0                           # from the lists alone, before the GPU runs
+    assert np.isin(idx[0], np.nonzero((idx == 0).any(axis=1))[0]).all()        # the long row lists rows that list it back
+    got = _check_graph(sess, idx, dist.astype(dt), K + 1, dt)[0]
+    assert got.nnz == 2 * m * K - merged and np.diff(got.indptr)[0] == m - 1
+
+
+@pytest.mark.parametrize("dt", DTYPES, **IDS)
+def test_graph_of_a_directed_ring_merges_nothing(sess, dt):
+    """K = 1, no mutual pair: every row is sorted, none merges, and the offsets stay the raw ones"""
+    m = 65
+    idx = ((np.arange(m) + 1) % m).astype(np.int32)[:, None]
+    dist = np.random.default_rng(65).uniform(0.5, 1.5, size=(m, 1)).astype(np.float32)
+    assert UR.sort_classes(idx) == ([m - 2, 0, 0], 0)                          # (rows 0 and m - 1 are ascending as emitted)
+    got = _check_graph(sess, idx, dist.astype(dt), 2, dt)[0]
+    assert got.nnz == 2 * m
+    np.testing.assert_array_equal(got.indptr, 2 * np.arange(m + 1))
+
+
+@pytest.mark.parametrize("dt", DTYPES, **IDS)
+def test_graph_without_a_valid_slot_is_empty(sess, dt):
+    m, K = 8, 3
+    got, sigma, rho, _ = _check_graph(sess, np.full((m, K), -1, dtype=np.int32), np.full((m, K), np.nan, dtype=dt), K + 1, dt)
+    assert got.shape == (m, m) and got.nnz == 0 and (got.indptr == 0).all()
+    assert np.isfinite(sigma).all() and np.isfinite(rho).all()
+
+
 # ------------------------------------------------------------------ 3. the trajectory
 @pytest.mark.parametrize("dt", DTYPES, **IDS)
 @pytest.mark.parametrize("D,rate", [(2, 5), (1, 5), (3, 5), (2, 0), (2, 31)], ids=["D2", "D1", "D3", "rate0", "rate31"])

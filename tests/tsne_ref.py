@@ -134,6 +134,37 @@ def initial_embedding(m, D, seed):
     return 1e-4 * synth.gaussian_panel(m, D, seed).numpy().astype(np.float64)
 
 
+def hub_lists(m=4200, hub=300, seed=5):
+    """(indices, dist), K = 3, that take the row sort of stage 3 through every length class: every row lists row 0, rows
+    2 .. hub + 1 list row 1, the other slots are a ring over rows 2 .. m - 1; rows 0 and 1 list 1, 2, 3 and 0, 2, 3, so that
+    the hub rows hold mutual pairs.  No row lists itself or a row twice; the distances are f32-representable."""
+    i = np.arange(m)
+    ring = lambda s: 2 + (i - 2 + s) % (m - 2)   # noqa: E731
+    idx = np.stack([np.zeros(m, dtype=np.int64), np.where((i >= 2) & (i < 2 + hub), 1, ring(1)), ring(2)], axis=1)
+    idx[0], idx[1] = (1, 2, 3), (0, 2, 3)
+    dist = np.random.default_rng(seed).uniform(0.5, 1.5, size=(m, 3)).astype(np.float32)
+    return idx.astype(np.int32), dist
+
+
+def sort_classes(indices, wave=64, lds=4096):
+    """(rows per length class, merged entries) of the raw rows stage 3 emits (a row's own valid slots in slot order, then an
+    entry per row that lists it, in any order), counting a row only where it needs the sort in whatever order the second part
+    arrives: its own part is not strictly ascending, or a row that lists it does not lie above its last own entry."""
+    indices = np.asarray(indices)
+    m, K = indices.shape
+    ok = (indices >= 0) & (indices < m)
+    listed_by = sp.csr_matrix((np.ones(int(ok.sum())), (indices[ok], np.repeat(np.arange(m), K).reshape(m, K)[ok])), shape=(m, m))
+    counts = [0, 0, 0]
+    for r in range(m):
+        own = indices[r][ok[r]]
+        inc = listed_by.indices[listed_by.indptr[r]:listed_by.indptr[r + 1]]
+        if (np.diff(own) <= 0).any() or (own.size and inc.size and inc.min() <= own[-1]):
+            n = own.size + inc.size
+            counts[0 if n <= wave else 1 if n <= lds else 2] += 1
+    pairs = listed_by + listed_by.T
+    return counts, 2 * int(ok.sum()) - pairs.nnz
+
+
 def clusters(m, d, seed, centres=3, spread=8.0):
     """(X, labels): `centres` separated Gaussian clusters in d dimensions"""
     rng = np.random.default_rng(seed)

@@ -7,7 +7,7 @@ Dense m x m intermediates in the union: for the few hundred rows the tests use, 
 import numpy as np
 import scipy.sparse as sp
 
-from tsne_ref import clusters, exp_exact   # noqa: F401  (the same synthetic clusters, the correctly rounded exp)
+from tsne_ref import clusters, exp_exact, hub_lists, sort_classes   # noqa: F401  (the same synthetic clusters and hand-made lists, the correctly rounded exp)
 
 MASK64 = (1 << 64) - 1
 
