@@ -1186,6 +1186,116 @@ sapca_status sapca_rank_groups_csr_device_f64(sapca_handle h, uint64_t m, uint64
                                               double* var, uint64_t* nonzero, double* t_score, double* t_df, double* z_score,
                                               double* z_pvalue);
 
+/* ---- Variable genes: feature selection on the resident CSR (sapca_hvg_*, sapca_loess_f64): an opt-in superset, the reference
+ *      has no counterpart ----
+ * scanpy's pp.highly_variable_genes between log1p and the fit, flavours "seurat_v3" (on counts) and "seurat" (on log1p data,
+ * scanpy's default).  "cell_ranger", "seurat_v3_paper" and "pearson_residuals" are NOT provided.  The result's highly_variable
+ * bytes feed sapca_set_mask and the col_mask of sapca_select_submatrix_csr_device_* unchanged.  tests/hvg_ref.py says
+ * everything below in numpy.
+ * Rows: d_batch (m int32, DEVICE, the convention of sapca_rank_groups_csr_device_*) labels the rows; NULL means one batch of
+ * all rows.  A row whose label is outside [0, n_batches) is excluded altogether: its values are not read.
+ *
+ * 1. Transformed column moments, sapca_hvg_moments_csr_device_*: for every column j, over the stored entries x of the included
+ *    rows (d_batch[r] == batch, every row when d_batch is NULL),
+ *      sum[j] = sum f_j(x), sum_squared[j] = sum f_j(x)^2, in f64 whatever the matrix's type, with
+ *      SAPCA_HVG_CLIP:  f_j(x) = min((double)x, clip[j])  (clip: HOST, n f64; scanpy clips in f64 after astype(float64)),
+ *      SAPCA_HVG_EXPM1: f_j(x) = expm1((double)x);
+ *      n_clipped[j] = the included stored entries with x > clip[j] (0 for EXPM1), exact.
+ *    How: the matrix is transposed (stable: a column's entries in ascending row order); one wave per column sums every 64th
+ *    entry per lane in stored order and folds the 64 partial sums by a fixed butterfly.  No floating-point atomic, no order
+ *    reaches a value: the same bytes from call to call.  A sum of L terms is within (L / 64 + 7) ulp of the sum of their
+ *    magnitudes of the exact sum.  A NaN or inf propagates as in an f64 sum.
+ *    Every call of this stage transposes the matrix anew (about the cost of the plain column statistics; the pass itself is a
+ *    small fraction of it): nothing is kept between calls.  A loop over K batches through this entry point pays K
+ *    transpositions; the chain below transposes once for all its passes, so batched use belongs there.
+ * 2. Local quadratic regression, sapca_loess_f64(h, n, x, y, span, fitted): HOST f64 arrays, the arithmetic on the device in
+ *    f64.  It is the "direct" surface of Cleveland's loess with degree 2, tricube weights and the gaussian family.
+ *    STATED DEVIATION: skmisc's default (surface="interpolate"), which scanpy calls, evaluates the fit at the vertices of a
+ *    k-d tree and interpolates between them; this call fits at every point.  How far the two surfaces lie apart on real data
+ *    has not been measured, so equality with scanpy's seurat_v3 is not claimed.  The fit at x_i:
+ *      q = min(n, max(3, floor(span n + 1e-5)));  h = the q-th smallest |x_j - x_i|, j = i counted;
+ *      w_j = (1 - (|x_j - x_i| / h)^3)^3 where |x_j - x_i| < h, else 0;  t_j = (x_j - x_i) / h;
+ *      the weighted least squares of y on {1, t, t^2} (normal equations of the sums of w t^k, k = 0 .. 4, and w y t^k,
+ *      k = 0 .. 2); fitted[i] = the intercept.  The degree follows the number of distinct x among the points with w > 0:
+ *      three or more: quadratic; two: linear on {1, t}; one, or h == 0: the plain mean of y over ALL points with x_j == x_i.
+ *    Non-finite x or y give unspecified values.  n == 0 is valid.
+ * 3. The chain, sapca_hvg_csr_device_*.  N_b = the rows of batch b; per batch, from sums s and ss over its rows,
+ *      mean = s / N_b,  var = (ss / N_b - mean^2) N_b / (N_b - 1)   (scanpy's ddof-1 variance).
+ *    s and ss come from the moment kernel of 1. (untransformed), not from the exact accumulators of the masked statistics:
+ *    exact on whole counts below 2^53, a plain f64 sum with the error bound of 1. otherwise.
+ *    SAPCA_HVG_SEURAT_V3, per batch: loess of log10(var) on log10(mean) over the columns with var > 0, est = 0 elsewhere;
+ *      reg_std = sqrt(10^est);  clip = reg_std sqrt(N_b) + mean;  s, ss = the CLIP moments;
+ *      norm_var = (N_b mean^2 + ss - 2 s mean) / ((N_b - 1) reg_std^2).
+ *      The loess and these n-sized steps run on the device; clip never visits the host.  Across batches (host arithmetic):
+ *      the batch's rank of a column = its position in a stable descending sort of norm_var (ties, and NaN last, by column
+ *      index); ranks >= n_top become NaN; rank = the median of the non-NaN ranks over the batches (NaN if none);
+ *      n_batches_hv = how many there are; variances_norm = the mean of norm_var over the batches; means and variances are
+ *      taken over all included rows; highly_variable = the first n_top columns of a stable sort by (rank ascending, NaN last;
+ *      n_batches_hv descending; column index).  dispersions and dispersions_norm are written as NaN.
+ *    SAPCA_HVG_SEURAT, per batch, host f64 arithmetic on n values behind the EXPM1 moments: mean == 0 becomes 1e-12;
+ *      disp = var / mean, 0 becomes NaN; disp = ln(disp); mean = log1p(mean); n_bins equal-width bins of mean as
+ *      pandas.cut(mean, bins = n_bins) makes them (edges min + i (max - min) / n_bins, the last one max, the lowest lowered by
+ *      0.1 % of the range; right-closed; min == max: the range is widened by 0.1 % of |min| on both sides, by 0.001 when it
+ *      is 0); per bin the mean and the ddof-1 standard deviation (two passes) of the non-NaN disp; a bin with fewer than two
+ *      of them takes std = its mean and mean = 0;  dispersions_norm = (disp - bin mean) / bin std (IEEE: a bin whose std is 0
+ *      gives +-inf or NaN).  Selection with n_top: cutoff = the n_top-th largest non-NaN dispersions_norm (the smallest when
+ *      there are fewer; nothing is selected when there is none), selected where nan_to_num(dispersions_norm) >= cutoff
+ *      (numpy's nan_to_num: NaN 0, +-inf +-DBL_MAX).  With n_top == 0: min_mean < mean < max_mean and
+ *      min_disp < d < max_disp with d = dispersions_norm, NaN taken as 0.  With batches: means, dispersions and
+ *      dispersions_norm are the means over the batches of the non-NaN values (NaN if none), n_batches_hv counts the batches
+ *      that selected the column; with n_top the selection is the first n_top of a stable sort by (n_batches_hv descending,
+ *      averaged dispersions_norm descending with NaN last, column index), else the four cutoffs on the averaged values.
+ *      variances = the per-batch var of expm1(x) averaged likewise; variances_norm and rank are written as NaN; without
+ *      batches n_batches_hv equals highly_variable.
+ * Outputs of the chain are HOST arrays of length n, any may be NULL.  m == 0 writes zeros (NaN where the flavour writes NaN or
+ * ranks) and selects nothing; n == 0 writes nothing.
+ * SAPCA_ERR_ARG, raised on the host before the first pass over the matrix (the handle stays usable), each with a message that
+ * names the offending number: an unknown flavor or transform; SAPCA_HVG_SEURAT_V3 with n_top == 0; n_top > n; span outside
+ * (0, 1]; n_bins == 0; n_batches == 0, or above SAPCA_HVG_MAX_BATCHES with non-NULL labels; a batch with fewer than 2 included
+ * rows (found from integer counts made on the device); m >= 2^31; a NULL clip for CLIP; a negative batch with labels; a wrong
+ * struct_size; and the view checks of the other resident operations.
+ * Handle state: like sapca_rank_groups_csr_device_* the matrix calls transpose into the buffers prepare() uses, so a cached
+ * preparation is dropped.  A fitted model, a set mask, the selection, the canonical form and the k-means, UMAP, Louvain and
+ * rank buffers are untouched; the work arrays are the handle's own.  sapca_loess_f64 touches none of this.  On a handle that
+ * belongs to a communicator the calls are local to the rank's shard and issue no collective.                                */
+#define SAPCA_HVG_MAX_BATCHES 1024
+#define SAPCA_HVG_CLIP 0
+#define SAPCA_HVG_EXPM1 1
+#define SAPCA_HVG_SEURAT_V3 0
+#define SAPCA_HVG_SEURAT 1
+typedef struct sapca_hvg_options {
+  uint32_t struct_size;   /* sizeof(sapca_hvg_options): 64                          */
+  int32_t flavor;         /* SAPCA_HVG_SEURAT_V3 (default) or SAPCA_HVG_SEURAT       */
+  uint64_t n_top;         /* default 2000; 0: the four cutoffs (SEURAT only)         */
+  double span;            /* loess span, default 0.3; (0, 1]                         */
+  uint32_t n_bins;        /* default 20                                             */
+  uint32_t reserved;      /* 0                                                      */
+  double min_mean;        /* default 0.0125                                         */
+  double max_mean;        /* default 3                                              */
+  double min_disp;        /* default 0.5                                            */
+  double max_disp;        /* default +inf                                           */
+} sapca_hvg_options;
+void sapca_hvg_options_default(sapca_hvg_options* opts);
+sapca_status sapca_hvg_moments_csr_device_f32(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* row_offsets,
+                                              const int32_t* col_indices, const float* values, const int32_t* d_batch, int32_t batch,
+                                              int32_t transform, const double* clip, double* sum, double* sum_squared,
+                                              uint64_t* n_clipped);
+sapca_status sapca_hvg_moments_csr_device_f64(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* row_offsets,
+                                              const int32_t* col_indices, const double* values, const int32_t* d_batch, int32_t batch,
+                                              int32_t transform, const double* clip, double* sum, double* sum_squared,
+                                              uint64_t* n_clipped);
+sapca_status sapca_loess_f64(sapca_handle h, uint64_t n, const double* x, const double* y, double span, double* fitted);
+sapca_status sapca_hvg_csr_device_f32(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* row_offsets,
+                                      const int32_t* col_indices, const float* values, const int32_t* d_batch, uint32_t n_batches,
+                                      const sapca_hvg_options* opts, double* means, double* variances, double* variances_norm,
+                                      double* dispersions, double* dispersions_norm, double* rank, uint32_t* n_batches_hv,
+                                      uint8_t* highly_variable);
+sapca_status sapca_hvg_csr_device_f64(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* row_offsets,
+                                      const int32_t* col_indices, const double* values, const int32_t* d_batch, uint32_t n_batches,
+                                      const sapca_hvg_options* opts, double* means, double* variances, double* variances_norm,
+                                      double* dispersions, double* dispersions_norm, double* rank, uint32_t* n_batches_hv,
+                                      uint8_t* highly_variable);
+
 /* Measurement support: the rate (GB/s, read + write counted) of a 16-byte-per-lane streaming copy of `bytes`
  * bytes on the handle's device, best of `reps` -- the HBM rate a kernel of this library can attain, reported by
  * bench.py beside the data-sheet peak.  Allocates and frees its two buffers.                       */

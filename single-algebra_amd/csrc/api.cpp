@@ -930,6 +930,24 @@ sapca_status sapca_get_column_scale(sapca_handle h, int32_t* mode, double* out, 
                                nonzero, t_score, t_df, z_score, z_pvalue);                                               \
     });                                                                                                                  \
   }                                                                                                                      \
+  sapca_status sapca_hvg_moments_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, \
+                                                  const int32_t* i, const T* v, const int32_t* d_batch, int32_t batch,     \
+                                                  int32_t transform, const double* clip, double* sum, double* sum_squared, \
+                                                  uint64_t* n_clipped) {                                                   \
+    return guarded(h, [&] {                                                                                              \
+      resident::hvg_moments<T>(*h, unchecked_view(m, n, nnz, p, i, v), d_batch, batch, transform, clip, sum, sum_squared, n_clipped); \
+    });                                                                                                                  \
+  }                                                                                                                      \
+  sapca_status sapca_hvg_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p,         \
+                                          const int32_t* i, const T* v, const int32_t* d_batch, uint32_t n_batches,        \
+                                          const sapca_hvg_options* opts, double* means, double* variances,                 \
+                                          double* variances_norm, double* dispersions, double* dispersions_norm,           \
+                                          double* rank, uint32_t* n_batches_hv, uint8_t* highly_variable) {                \
+    return guarded(h, [&] {                                                                                              \
+      resident::hvg<T>(*h, unchecked_view(m, n, nnz, p, i, v), d_batch, n_batches, opts, means, variances, variances_norm, \
+                       dispersions, dispersions_norm, rank, n_batches_hv, highly_variable);                               \
+    });                                                                                                                  \
+  }                                                                                                                      \
   sapca_status sapca_masked_stats_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, \
                                                    const int32_t* i, const T* v, int32_t direction, const uint8_t* mask,    \
                                                    uint64_t mask_len, double* sum, double* sum_squared, uint64_t* count,    \
@@ -1113,6 +1131,24 @@ void sapca_kmeans_options_default(sapca_kmeans_options* o) {
   o->init = SAPCA_KMEANS_PLUSPLUS;
   o->max_iter = 300;
   o->tol = 1e-4;
+}
+
+void sapca_hvg_options_default(sapca_hvg_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  o->struct_size = (uint32_t)sizeof(sapca_hvg_options);
+  o->flavor = SAPCA_HVG_SEURAT_V3;
+  o->n_top = 2000;
+  o->span = 0.3;
+  o->n_bins = 20;
+  o->min_mean = 0.0125;
+  o->max_mean = 3.0;
+  o->min_disp = 0.5;
+  o->max_disp = HUGE_VAL;
+}
+
+sapca_status sapca_loess_f64(sapca_handle h, uint64_t n, const double* x, const double* y, double span, double* fitted) {
+  return guarded(h, [&] { resident::loess(*h, n, x, y, span, fitted); });
 }
 
 void sapca_louvain_options_default(sapca_louvain_options* o) {

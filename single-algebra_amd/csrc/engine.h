@@ -212,6 +212,11 @@ struct sapca_handle_s {
   struct Rank {
     sapca::DevBuf group, out, list, scratch;
   } rank;
+  // sapca_hvg_*_csr_device_* / sapca_loess_f64: the batch sizes, the n-sized f64 work arrays of a call with the sort's index
+  // arrays and a counter behind them, and the sort's work space.  Nothing else lives in these; the transposition uses at_*.
+  struct Hvg {
+    sapca::DevBuf group, vec, sort;
+  } hvg;
   sapca::DevBuf at_ptr, at_idx, at_val;                          // A^T
   sapca::DevBuf ca_ptr, ca_idx, ca_val, cat_ptr, cat_idx, cat_val;  // mask-compacted A, A^T
   sapca::DevBuf drop_stats, drop_tmp;                              // their sums (sum | sumsq, full width) and the sort's work space

@@ -118,6 +118,29 @@ void rank_sums_long(const CsrView<T>& At, const int32_t* labels, int nk, const u
                     const int32_t* cols_list, const uint32_t* seg, int nseg, uint32_t total, DevBuf& scratch, long long* rs, uint32_t* cnt,
                     double* tie, hipStream_t s);
 
+// ---- hvg.hip: variable genes (sapca_hvg_moments_csr_device_*, sapca_loess_f64, sapca_hvg_csr_device_*) ----
+constexpr int kHvgPlain = -1;   // the untransformed moments of the chain's first pass (beside SAPCA_HVG_CLIP / SAPCA_HVG_EXPM1)
+// Per row j of At (a column of A), over its stored entries whose row of A is included: sum[j] / sumsq[j] of f(x) in f64 and
+// n_clipped[j] (may be null) = the entries with x > d_clip[j] (CLIP only; d_clip: device, At.rows).  labels null: every row;
+// batch >= 0: the rows with labels[r] == batch; batch < 0: the rows with a label in [0, nk).  A column's entries are summed
+// in stored order by a fixed lane assignment and butterfly: deterministic, no atomic.
+template <typename T>
+void hvg_moments(const CsrView<T>& At, const int32_t* labels, int32_t batch, int nk, int transform, const double* d_clip, double* sum,
+                 double* sumsq, uint32_t* n_clipped, hipStream_t s);
+// Local quadratic regression (the header's definition) of y on x over the nv smallest of the n abscissae x (the others must be
+// +inf), window q <= nv: fit[j] is written for those nv points and left alone for the rest.  xs, ys (f64, n), iota, perm (u32, n):
+// work arrays; sort_tmp grows to what the sort needs.
+void hvg_loess(const double* x, const double* y, int64_t n, int64_t nv, int64_t q, double* xs, double* ys, uint32_t* iota, uint32_t* perm,
+               double* fit, DevBuf& sort_tmp, hipStream_t s);
+// The n-sized steps of the seurat_v3 chain, N the batch's rows: mean and ddof-1 variance from s / ss with the loess
+// coordinates (lx = +inf where var <= 0) and *n_valid = the columns with var > 0; reg_std and clip from the estimate;
+// norm_var from the clipped moments.
+void hvg_mean_var(const double* s_, const double* ss, double N, int64_t n, double* mean, double* var, double* lx, double* ly,
+                  uint32_t* n_valid, hipStream_t s);
+void hvg_clip(const double* est, const double* mean, double N, int64_t n, double* reg_std, double* clip, hipStream_t s);
+void hvg_norm_var(const double* s_, const double* ss, const double* mean, const double* reg_std, double N, int64_t n, double* norm_var,
+                  hipStream_t s);
+
 // ---- maskedstats.hip: masked and stored-entry statistics (MatrixSum / MatrixNonZero / MatrixVariance *_masked, *_chunk) ----
 // Per row r of A, over its stored entries e whose column's bit (col_bits[c / 32] >> c % 32) & 1 is set (all of them when
 // col_bits is null): cnt[r] = their count, sum[r] / sumsq[r] = their sum / sum of squares, m2[r] = sum (x - sum / cnt)^2

@@ -83,6 +83,17 @@ void rank_sums(H& h, const CsrView<T>& A, const int32_t* d_labels, uint32_t n_gr
 template <typename T>
 void rank_groups(H& h, const CsrView<T>& A, const int32_t* d_labels, uint32_t n_groups, int32_t tie_correct, uint64_t* group_rows,
                  double* mean, double* var, uint64_t* nonzero, double* t_score, double* t_df, double* z_score, double* z_pvalue);
+// sapca_hvg_moments_csr_device_* / sapca_loess_f64 / sapca_hvg_csr_device_* (hvg.cpp): the transformed column moments of one
+// batch, the local quadratic regression of host arrays, and the seurat_v3 / seurat selection; d_batch: device, one per row or
+// null; clip and every output: host, outputs may be null
+template <typename T>
+void hvg_moments(H& h, const CsrView<T>& A, const int32_t* d_batch, int32_t batch, int32_t transform, const double* clip, double* sum,
+                 double* sumsq, uint64_t* n_clipped);
+void loess(H& h, uint64_t n, const double* x, const double* y, double span, double* fitted);
+template <typename T>
+void hvg(H& h, const CsrView<T>& A, const int32_t* d_batch, uint32_t n_batches, const sapca_hvg_options* opts, double* means,
+         double* variances, double* variances_norm, double* dispersions, double* dispersions_norm, double* rank, uint32_t* n_batches_hv,
+         uint8_t* highly_variable);
 // MatrixNTop::sum_row_n_top (csr.rs:1347-1376) for several n in one pass over the rows: out[i * m + r]
 template <typename T>
 void top_n(H& h, const CsrView<T>& A, const uint64_t* ns, uint32_t n_ns, double* out);

@@ -75,6 +75,8 @@ template <typename T> struct ResidentAbi;
     static sapca_status n_top(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, const uint64_t* ns, uint32_t k, double* out) { return sapca_sum_row_n_top_csr_device_##SUF(h, m, n, nnz, p, i, v, ns, k, out); } \
     static sapca_status rank_sums(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, const int32_t* lab, uint32_t k, uint64_t* rows, int64_t* rs2, uint64_t* nz, double* tie) { return sapca_rank_sums_csr_device_##SUF(h, m, n, nnz, p, i, v, lab, k, rows, rs2, nz, tie); } \
     static sapca_status rank_groups(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, const int32_t* lab, uint32_t k, int32_t tc, uint64_t* rows, double* mean, double* var, uint64_t* nz, double* t, double* df, double* z, double* pz) { return sapca_rank_groups_csr_device_##SUF(h, m, n, nnz, p, i, v, lab, k, tc, rows, mean, var, nz, t, df, z, pz); } \
+    static sapca_status hvg_moments(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, const int32_t* bt, int32_t b, int32_t tr, const double* clip, double* s, double* q, uint64_t* nc) { return sapca_hvg_moments_csr_device_##SUF(h, m, n, nnz, p, i, v, bt, b, tr, clip, s, q, nc); } \
+    static sapca_status hvg(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, const int32_t* bt, uint32_t nb, const sapca_hvg_options* o, double* mean, double* var, double* vn, double* d, double* dn, double* rk, uint32_t* nhv, uint8_t* hv) { return sapca_hvg_csr_device_##SUF(h, m, n, nnz, p, i, v, bt, nb, o, mean, var, vn, d, dn, rk, nhv, hv); } \
     static sapca_status check(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, sapca_csr_report* rep) { return sapca_check_csr_device_##SUF(h, m, n, nnz, p, i, v, rep); } \
     static sapca_status canonicalize(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, uint64_t* nnz_out, const int64_t** op, const int32_t** oi, T** ov, sapca_csr_report* rep) { return sapca_canonicalize_csr_device_##SUF(h, m, n, nnz, p, i, v, nnz_out, op, oi, ov, rep); } \
     static sapca_status select_rows(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, const uint64_t* rows, uint64_t nr, uint64_t* nnz_out, const int64_t** op, const int32_t** oi, T** ov) { return sapca_select_rows_csr_device_##SUF(h, m, n, nnz, p, i, v, rows, nr, nnz_out, op, oi, ov); } \
@@ -434,6 +436,37 @@ class ResidentCsr {
     check(ResidentAbi<T>::rank_groups(h_, m_, n_, nnz_, ptr_, idx_, val_, d_labels, n_groups, tie_correct ? 1 : 0, r.group_rows.data(),
                                       ptr(r.mean), ptr(r.var), r.nonzero.data(), ptr(r.t_score), ptr(r.t_df), ptr(r.z_score),
                                       ptr(r.z_pvalue)));
+    return r;
+  }
+  // Variable genes (sapca_hvg_moments_csr_device_* / sapca_hvg_csr_device_*; no reference counterpart): scanpy's
+  // highly_variable_genes, flavours seurat_v3 and seurat.  d_batch: m int32 on the DEVICE or null (one batch of all rows); a
+  // label outside [0, n_batches) excludes its row.  highly_variable feeds sapca_set_mask and select(col_mask) unchanged.
+  struct HvgMoments {
+    std::vector<double> sum, sum_squared;
+    std::vector<uint64_t> n_clipped;
+  };
+  HvgMoments hvg_moments(int32_t transform, const double* clip = nullptr, const int32_t* d_batch = nullptr, int32_t batch = 0) const {
+    HvgMoments r;
+    r.sum.resize(n_); r.sum_squared.resize(n_); r.n_clipped.resize(n_);
+    check(ResidentAbi<T>::hvg_moments(h_, m_, n_, nnz_, ptr_, idx_, val_, d_batch, batch, transform, clip, r.sum.data(), r.sum_squared.data(),
+                                      r.n_clipped.data()));
+    return r;
+  }
+  struct HvgOptions : sapca_hvg_options {
+    HvgOptions() { sapca_hvg_options_default(this); }
+  };
+  struct Hvg {
+    std::vector<double> means, variances, variances_norm, dispersions, dispersions_norm, rank;
+    std::vector<uint32_t> n_batches_hv;
+    std::vector<uint8_t> highly_variable;
+  };
+  Hvg highly_variable(const sapca_hvg_options& opts, const int32_t* d_batch = nullptr, uint32_t n_batches = 1) const {
+    Hvg r;
+    for (auto* v : {&r.means, &r.variances, &r.variances_norm, &r.dispersions, &r.dispersions_norm, &r.rank}) v->resize(n_);
+    r.n_batches_hv.resize(n_); r.highly_variable.resize(n_);
+    check(ResidentAbi<T>::hvg(h_, m_, n_, nnz_, ptr_, idx_, val_, d_batch, n_batches, &opts, r.means.data(), r.variances.data(),
+                              r.variances_norm.data(), r.dispersions.data(), r.dispersions_norm.data(), r.rank.data(),
+                              r.n_batches_hv.data(), r.highly_variable.data()));
     return r;
   }
   // *_masked (csr.rs:153-252, 418-556, 815-914): col = per column over the rows with mask[row] (mask.size() >= m),

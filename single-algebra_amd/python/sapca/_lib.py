@@ -67,6 +67,15 @@ class LouvainOptions(C.Structure):
     ]
 
 
+class HvgOptions(C.Structure):
+    """sapca_hvg_options"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flavor", C.c_int32), ("n_top", C.c_uint64), ("span", C.c_double),
+        ("n_bins", C.c_uint32), ("reserved", C.c_uint32),
+        ("min_mean", C.c_double), ("max_mean", C.c_double), ("min_disp", C.c_double), ("max_disp", C.c_double),
+    ]
+
+
 class UmapOptions(C.Structure):
     """sapca_umap_options"""
     _fields_ = [
@@ -91,6 +100,12 @@ KNN_METRICS = {"euclidean": KNN_EUCLIDEAN, "cosine": KNN_COSINE, "pearson": KNN_
 KNN_EXCLUDE_SELF = 1
 KNN_MAX_NEIGHBORS = 128
 RANK_MAX_GROUPS = 1024   # SAPCA_RANK_MAX_GROUPS
+# sapca_hvg_*: the most batches, the transforms of the moments, the flavours
+HVG_MAX_BATCHES = 1024
+HVG_CLIP, HVG_EXPM1 = 0, 1
+HVG_TRANSFORMS = {"clip": HVG_CLIP, "expm1": HVG_EXPM1}
+HVG_SEURAT_V3, HVG_SEURAT = 0, 1
+HVG_FLAVORS = {"seurat_v3": HVG_SEURAT_V3, "seurat": HVG_SEURAT}
 # sapca_kmeans_*: the seeding rules, the most clusters
 KMEANS_PLUSPLUS, KMEANS_GIVEN = 0, 1
 KMEANS_MAX_CLUSTERS = 1024
@@ -135,6 +150,7 @@ _TYPED = [
     "sapca_umap_graph_device", "sapca_umap_embed_device", "sapca_umap_device", "sapca_umap",
     "sapca_louvain_modularity_device", "sapca_louvain_sweep_device", "sapca_louvain_aggregate_device", "sapca_louvain_device",
     "sapca_louvain", "sapca_rank_sums_csr_device", "sapca_rank_groups_csr_device",
+    "sapca_hvg_moments_csr_device", "sapca_hvg_csr_device",
     "sapca_multi_fit_csr", "sapca_multi_transform_csr", "sapca_multi_fit_transform_csr",
     "sapca_multi_upload_csr", "sapca_multi_transform_resident", "sapca_multi_fit_transform_resident",
 ]
@@ -150,6 +166,7 @@ _PLAIN = [
     "sapca_set_column_scaling", "sapca_get_column_scale",
     "sapca_tsne_options_default", "sapca_kmeans_options_default",
     "sapca_umap_options_default", "sapca_umap_find_ab", "sapca_louvain_options_default",
+    "sapca_hvg_options_default", "sapca_loess_f64",
 ]
 EXPORTED_SYMBOLS = _PLAIN + [f"{n}_{s}" for n in _TYPED for s in ("f32", "f64")]
 
@@ -319,7 +336,23 @@ def _open(path):
             getattr(lib, f"sapca_rank_sums_csr_device_{suf}").argtypes = mat + [C.c_void_p, C.c_uint32, u64p, C.POINTER(C.c_int64), u64p, f64p]
             getattr(lib, f"sapca_rank_groups_csr_device_{suf}").argtypes = mat + [C.c_void_p, C.c_uint32, C.c_int32, u64p, f64p, f64p, u64p,
                                                                                   f64p, f64p, f64p, f64p]
+    if hasattr(lib, "sapca_hvg_options_default"):   # (absent from an older build loaded for an A/B run)
+        lib.sapca_hvg_options_default.argtypes = [C.POINTER(HvgOptions)]
+        lib.sapca_hvg_options_default.restype = None
+        mat = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]   # h, m, n, nnz, offsets, columns, values
+        u64p, f64p = C.POINTER(C.c_uint64), C.POINTER(C.c_double)
+        lib.sapca_loess_f64.argtypes = [C.c_void_p, C.c_uint64, f64p, f64p, C.c_double, f64p]
+        for suf in ("f32", "f64"):
+            getattr(lib, f"sapca_hvg_moments_csr_device_{suf}").argtypes = mat + [C.c_void_p, C.c_int32, C.c_int32, f64p, f64p, f64p, u64p]
+            getattr(lib, f"sapca_hvg_csr_device_{suf}").argtypes = mat + [C.c_void_p, C.c_uint32, C.POINTER(HvgOptions), f64p, f64p, f64p,
+                                                                          f64p, f64p, f64p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
     return lib
+
+
+def default_hvg_options() -> HvgOptions:
+    o = HvgOptions()
+    load().sapca_hvg_options_default(C.byref(o))
+    return o
 
 
 def default_louvain_options() -> LouvainOptions:

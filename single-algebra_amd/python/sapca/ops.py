@@ -726,6 +726,20 @@ class Session:
             data.ctypes.data_as(C.c_void_p), C.byref(o), labels.ctypes.data_as(C.c_void_p), C.byref(ncomm), C.byref(q), C.byref(levels)))
         return labels, ncomm.value, q.value, levels.value
 
+    # ---- local regression (sapca_loess_f64) ----
+    def loess(self, x, y, span=0.3):
+        """sapca_loess_f64: the local quadratic regression of y on x (host f64 arrays) fitted at every x_i on the device: the
+        "direct" surface of Cleveland's loess, degree 2, tricube weights (include/sapca.h, "Variable genes").  Returns the
+        fitted values, one per point."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if x.ndim != 1 or x.shape != y.shape:
+            raise ValueError(f"x and y must be one-dimensional and alike, got shapes {x.shape} and {y.shape}")
+        out = np.zeros(x.size)
+        L.check(self._h, L.load().sapca_loess_f64(self._h, C.c_uint64(x.size), _p(x, C.c_double), _p(y, C.c_double),
+                                                  C.c_double(float(span)), _p(out, C.c_double)))
+        return out
+
 
 ROW, COLUMN = 0, 1   # Direction of the reference's Normalize / statistics traits (src/utils.rs)
 
@@ -857,6 +871,22 @@ class RankGroupsResult:
             mean_rest = (total - self.means * rows) / rest
             mean_group = np.where(rows > 0, self.means, np.nan)
             return np.log((np.expm1(mean_group) + 1e-9) / (np.expm1(mean_rest) + 1e-9)) / np.log(float(base))
+
+
+class HvgResult:
+    """What ResidentCsr.highly_variable returns, every array of length n (one per column): `means`, `variances`,
+    `variances_norm` (seurat_v3), `dispersions`, `dispersions_norm` (seurat), `rank` (f64, NaN where the column is not
+    ranked), `n_batches_hv` (u32) and `highly_variable` (bool, the library's u8 bytes viewed: the mask of a masked estimator
+    and select(cols=...) take it as it is)."""
+
+    def __init__(self, flavor, arrays):
+        self.flavor = flavor
+        for k, v in arrays.items():
+            setattr(self, k, v)
+
+    @property
+    def n_selected(self):
+        return int(self.highly_variable.sum())
 
 
 class ResidentCsr:
@@ -1040,6 +1070,66 @@ class ResidentCsr:
         if method != "both":
             scores, pvals = scores[method], pvals[method]
         return RankGroupsResult(method, scores, pvals, a["mean"], a["var"], nz, rows, n_top)
+
+    # ---- variable genes (sapca_hvg_moments_csr_device_* / sapca_hvg_csr_device_*): feature selection between log1p and the fit ----
+    def hvg_moments(self, transform, clip=None, batch=None, code=0):
+        """sapca_hvg_moments_csr_device_*: per column, the sum and the sum of squares (f64) of the transformed stored entries
+        of the included rows, and how many were clipped: {"sum", "sum_squared", "n_clipped"}.  transform "clip"
+        (min(x, clip[j]); clip: n f64) or "expm1"; batch: labels per row (numpy or device int32) of which the rows with
+        label == code are included, None: every row."""
+        import torch
+        if transform not in L.HVG_TRANSFORMS and not isinstance(transform, (int, np.integer)):
+            raise ValueError(f'transform must be "clip" or "expm1", got {transform!r}')
+        tr = L.HVG_TRANSFORMS.get(transform, transform)
+        m, n = self.shape
+        labels = None
+        if batch is not None:
+            labels, _ = self._rank_labels(batch, 1)
+        if clip is not None:
+            clip = np.ascontiguousarray(clip, dtype=np.float64)
+            if clip.shape != (n,):
+                raise ValueError(f"clip must hold {n} values, got shape {clip.shape}")
+        suf, _ = _SUF[self.dtype]
+        out = {"sum": np.zeros(n), "sum_squared": np.zeros(n), "n_clipped": np.zeros(n, dtype=np.uint64)}
+        torch.cuda.current_stream().synchronize()
+        L.check(self._s._h, getattr(L.load(), f"sapca_hvg_moments_csr_device_{suf}")(
+            *self._args(), C.c_void_p(labels.data_ptr() if labels is not None and m else None), C.c_int32(int(code)),
+            C.c_int32(int(tr)), _p(clip, C.c_double) if clip is not None else None, _p(out["sum"], C.c_double),
+            _p(out["sum_squared"], C.c_double), _p(out["n_clipped"], C.c_uint64)))
+        return out
+
+    def highly_variable(self, n_top=2000, flavor="seurat_v3", batch=None, n_batches=None, span=0.3, n_bins=20, min_mean=0.0125,
+                        max_mean=3.0, min_disp=0.5, max_disp=float("inf")):
+        """sapca_hvg_csr_device_*: scanpy's pp.highly_variable_genes, flavor "seurat_v3" (on counts) or "seurat" (on log1p
+        data; n_top None or 0: the four cutoffs).  batch: labels per row (numpy or device int32; a label outside
+        [0, n_batches) excludes its row), None: one batch of all rows.  The loess of seurat_v3 is the direct surface, not
+        skmisc's interpolated one (include/sapca.h).  Returns an HvgResult."""
+        import torch
+        if flavor not in L.HVG_FLAVORS and not isinstance(flavor, (int, np.integer)):
+            raise ValueError(f'flavor must be "seurat_v3" or "seurat", got {flavor!r}')
+        m, n = self.shape
+        labels, K = None, 1
+        if batch is not None:
+            labels, K = self._rank_labels(batch, n_batches)
+        elif n_batches is not None:
+            K = int(n_batches)
+        o = L.default_hvg_options()
+        o.flavor = int(L.HVG_FLAVORS.get(flavor, flavor))
+        o.n_top = int(n_top or 0)
+        o.span, o.n_bins = float(span), int(n_bins)
+        o.min_mean, o.max_mean, o.min_disp, o.max_disp = float(min_mean), float(max_mean), float(min_disp), float(max_disp)
+        a = {k: np.zeros(n) for k in ("means", "variances", "variances_norm", "dispersions", "dispersions_norm", "rank")}
+        a["n_batches_hv"] = np.zeros(n, dtype=np.uint32)
+        a["highly_variable"] = np.zeros(n, dtype=np.uint8)
+        suf, _ = _SUF[self.dtype]
+        torch.cuda.current_stream().synchronize()
+        L.check(self._s._h, getattr(L.load(), f"sapca_hvg_csr_device_{suf}")(
+            *self._args(), C.c_void_p(labels.data_ptr() if labels is not None and m else None), C.c_uint32(K), C.byref(o),
+            _p(a["means"], C.c_double), _p(a["variances"], C.c_double), _p(a["variances_norm"], C.c_double),
+            _p(a["dispersions"], C.c_double), _p(a["dispersions_norm"], C.c_double), _p(a["rank"], C.c_double),
+            _p(a["n_batches_hv"], C.c_uint32), _p(a["highly_variable"], C.c_uint8)))
+        a["highly_variable"] = a["highly_variable"].view(np.bool_)   # (0 / 1 bytes)
+        return HvgResult(flavor, a)
 
     def sum_row_n_top(self, n):
         """MatrixNTop::sum_row_n_top (csr.rs:1347-1376): per row, the sum of the n largest stored values (all of them when
