@@ -81,7 +81,11 @@ extern "C" {
                                                   sapca_louvain_sweep_device_*, sapca_louvain_aggregate_device_*,
                                                   sapca_louvain_device_*, sapca_louvain_*
                                  additive, ABI 4: sapca_rank_sums_csr_device_*, sapca_rank_groups_csr_device_*
-                                 additive, ABI 4: sapca_normalize_panel_ex_*, sapca_rotate_panel_*                     */
+                                 additive, ABI 4: sapca_normalize_panel_ex_*, sapca_rotate_panel_*
+                                 additive, ABI 4: sapca_graph_components_device, sapca_spectral_options_default,
+                                                  sapca_spectral_scale_device_*, sapca_spectral_apply_device_*,
+                                                  sapca_spectral_device_*, sapca_spectral_*,
+                                                  sapca_umap_spectral_init_device_*                                    */
 
 typedef struct sapca_handle_s* sapca_handle;
 
@@ -956,7 +960,8 @@ sapca_status sapca_kmeans_f64(sapca_handle h, uint64_t m, uint64_t d, const doub
  *      columns of x, a constant column giving 0 (needs d >= output_dim); SAPCA_UMAP_INIT_RANDOM
  *      10 hash_u01(seed, 31, i output_dim + c); SAPCA_UMAP_INIT_GIVEN the caller's panel as it is.
  * Deviations from umap-learn: synchronous instead of sequential in-place updates; this library's counter generator instead of
- * tau_rand; no spectral initialisation; set_op_mix_ratio = 1 and local_connectivity = 1 only; Euclidean only; no transform of
+ * tau_rand; no spectral initialisation (a start can be computed by sapca_umap_spectral_init_device_*, below, and given as
+ * SAPCA_UMAP_INIT_GIVEN); set_op_mix_ratio = 1 and local_connectivity = 1 only; Euclidean only; no transform of
  * new points.
  * Deterministic: the same bytes from call to call.  Integer atomics count and hand out positions in stage 3 and take the
  * maximum of bit patterns for w_max; the rows are then sorted by column and a pair combined symmetrically, so no order reaches
@@ -1115,6 +1120,117 @@ sapca_status sapca_louvain_f32(sapca_handle h, uint64_t m, uint64_t nnz, const i
 sapca_status sapca_louvain_f64(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
                                const double* values, const sapca_louvain_options* opts, int32_t* labels, uint64_t* n_communities,
                                double* modularity, uint32_t* n_levels);
+
+/* ---- Spectral embedding and diffusion maps of a resident graph (sapca_spectral_*, sapca_graph_components_device): an opt-in
+ * superset, the reference has no counterpart ----
+ * The leading eigenpairs of S = diag(s) W diag(s) for a symmetric graph W with weights >= 0 (the graph
+ * sapca_umap_graph_device_* leaves in the handle, or any m x m CSR with int64 offsets, int32 columns and values of type T):
+ * what umap-learn's spectral_layout / scikit-learn's spectral_embedding (NORMALIZED) and scanpy's tl.diffmap (DIFFMAP) compute.
+ * tests/spectral_ref.py says the same in numpy and is held to scipy's laplacian, eigsh and connected_components and to
+ * scikit-learn's spectral_embedding.  Symmetry is trusted, as the offsets are.  All arithmetic is f64 from the stored T values.
+ *   1. Components (sapca_graph_components_device): structure only, every stored entry is an edge, values are not read.
+ *      parent_i = i; a round hooks, for every stored (i, j), the larger of the two roots onto the smaller with an integer
+ *      atomicMin, then shortens every chain to its root (pointer jumping); rounds repeat until one changes nothing (the host
+ *      peeks at a device word between rounds).  parent never exceeds its index, so the fixed point is the smallest vertex of
+ *      the component whatever the order: deterministic.  d_labels[i] = the number of roots below parent_i (a prefix count):
+ *      components numbered in ascending order of their smallest vertex, as scipy's connected_components(directed=False) does.
+ *   2. Scale (sapca_spectral_scale_device_*): a row's sums by a lane group of g lanes (g from the mean row length: the smallest
+ *      of 8, 16, 32, 64 that is not below it), lane l adds the entries l, l + g, .. in stored order, alternating between two
+ *      partial sums that are added at the end, and the lanes meet in a butterfly: an order fixed by the row's length and g.
+ *      SAPCA_SPECTRAL_NORMALIZED: d_i = sum_j W_ij, s_i = 1 / sqrt(d_i): S = D^-1/2 W D^-1/2 = I - L_sym.
+ *      SAPCA_SPECTRAL_DIFFMAP: q_i = sum_j W_ij, z_i = sum_j W_ij / (q_i q_j), s_i = 1 / (q_i sqrt(z_i)): S is scanpy's
+ *      density-normalised symmetric transition matrix (compute_transitions(density_normalize=True)).
+ *      A row whose sum (d_i; q_i or z_i) is not finite and positive has s_i = 0: the vertex drops out of the operator.
+ *   3. Operator (sapca_spectral_apply_device_*): Wt_ij = W_ij (s_i s_j) as one f64 copy (the product s_i s_j commutes, so Wt is
+ *      symmetric bit for bit), y_i = sum_j Wt_ij x_j by the lane groups of stage 2 with fma in place of the addition.  The
+ *      eigen-solve builds the copy once, the stage call per call.  The step of the eigen-solve multiplies the same copy with
+ *      the wave-per-row product of the Lanczos SVD (64 lanes to a row, four partial sums a lane, a 64-lane butterfly; for
+ *      4096 <= m <= 19200 the same with x staged in LDS): measured on a 200 000-row neighbour graph it is the faster of the
+ *      two, and its order is as fixed.  That product does not look at its columns, so the solve hands it a copy of the
+ *      columns in which one outside [0, m) is replaced by the row's own number, with the value 0: such an entry adds 0 x_i.
+ *   4. Locked pairs.  With t_i = 1 / s_i (= sqrt(d_i)) for NORMALIZED and t_i = 1 / (s_i q_i) (= sqrt(z_i)) for DIFFMAP, and
+ *      t_i = 0 where s_i = 0: every component C with a vertex of t_i > 0 has the eigenvalue 1 with the eigenvector
+ *      u_C = t 1_C / |t 1_C|.  (1 / s is that vector for NORMALIZED only: S (q sqrt(z)) = 1 / sqrt(z).)  t and the norm (summed
+ *      in ascending vertex order) are computed on the host from one read-back of s, q and the labels.  The locked pairs come
+ *      first, in label order.  With at least n_eigen of them the first n_eigen are the result and n_steps = 0.
+ *   5. Otherwise a single-vector Lanczos iteration on S in the orthogonal complement of the c locked vectors: start vector
+ *      gaussian_panel (m x 1) under random_seed; every new vector (the start included) goes through classical Gram-Schmidt
+ *      twice against the locked vectors and the whole Lanczos basis, with the fixed-order kernels of the Lanczos SVD; alpha_j
+ *      and beta_j are those of the Lanczos part.  From step n_eigen - c on the host reads alpha and beta back (every step up
+ *      to 64, then every 2nd, 4th, 8th as the Lanczos SVD does) and runs implicit QL with the bottom row: the run stops when
+ *      the n_eigen - c largest (algebraic) Ritz values all have |beta_j s_ji| <= tol, or when the Krylov space is exhausted
+ *      (beta_j <= 1e-13 times the largest |Ritz value|, or j = m - c).  max_steps without that: SAPCA_ERR_SVD, "spectral:
+ *      Lanczos did not converge k of n pairs in j steps".  A Krylov space exhausted in fewer than n_eigen - c steps (beta_j <=
+ *      1e-13 (max_i |alpha_i| + 2 |beta_i|), looked at every step until then: a graph without weights, or components so small
+ *      that the start vector spans less) holds fewer pairs than were asked for: SAPCA_ERR_SVD, "spectral: the Krylov space is
+ *      exhausted after j steps, k pairs were to be iterated", no padded pairs.
+ *   6. Output: eigenvalues descending (the locked 1.0s, then the Ritz values); eigenvectors m x n_eigen row-major.  Ritz
+ *      vectors are combined on the device in f64, their sign fixed so that the entry of largest magnitude (lowest index on a
+ *      tie) is positive, and rounded once to T; the locked vectors are positive already.  n_components counts every
+ *      component, isolated vertices included.
+ * Deviations: scanpy's eigsh(which="LM") would also admit values near -1; the largest algebraic ones are taken here.
+ * Spectral start for UMAP (sapca_umap_spectral_init_device_*): from eigenvectors E (m x n_eigen, row stride ld, NORMALIZED),
+ *   y[i][c] = 10 E[i][1 + c] / max|E[:, 1 .. output_dim]| + 1e-4 (2 hash_u01(seed, 51, i output_dim + c) - 1)
+ * in f64 with every product, quotient and sum rounded as written, then rounded to T: umap-learn's expansion to +-10 with
+ * uniform instead of Gaussian tie-breaking noise.  Pass it to the layout as SAPCA_UMAP_INIT_GIVEN; the layout itself still has
+ * no spectral initialisation of its own.  On a disconnected graph the columns are component indicators; umap-learn's
+ * per-component meta-layout is not built.  A maximum of 0 gives the noise alone.
+ * Deterministic: the same bytes from call to call; no floating-point atomic.  Outputs are complete when the call returns.
+ * All work is in buffers of the handle's own: the UMAP graph, Louvain's buffers, the upload, a fitted model and a cached
+ * preparation stay valid and untouched; on a handle that belongs to a communicator the calls are local and issue no
+ * collective.  A column outside [0, m) is skipped where it is read.  Negative or non-finite weights or an asymmetric graph
+ * give unspecified numbers; the call still terminates at max_steps.  The Lanczos basis takes (c + max_steps + 1) m doubles;
+ * one that cannot be allocated is SAPCA_ERR_NOMEM.
+ * SAPCA_ERR_ARG, checked on the host before anything is enqueued (the handle stays usable), each with a message that names the
+ * offending number: a wrong struct_size; an unknown kind; n_eigen outside 1 .. 64 or above m; max_steps above 4096; tol
+ * negative or non-finite; m >= 2^31; output_dim outside 1 .. 3 or n_eigen <= output_dim or ld < n_eigen in the start; a null
+ * pointer with a non-empty shape.  m == 0 is valid and writes nothing.                                                       */
+typedef enum sapca_spectral_kind { SAPCA_SPECTRAL_NORMALIZED = 0, SAPCA_SPECTRAL_DIFFMAP = 1 } sapca_spectral_kind;
+typedef struct sapca_spectral_options {
+  uint32_t struct_size;   /* sizeof(sapca_spectral_options): 32               */
+  uint32_t random_seed;   /* default 42                                       */
+  uint32_t kind;          /* sapca_spectral_kind, default NORMALIZED          */
+  uint32_t n_eigen;       /* default 16; 1 .. 64 and <= m                     */
+  uint32_t max_steps;     /* default 0: min(m, 1000); at most 4096            */
+  uint32_t reserved;
+  double tol;             /* default 1e-8                                     */
+} sapca_spectral_options;
+void sapca_spectral_options_default(sapca_spectral_options* opts);
+/* Stage 1: d_labels (m int32, DEVICE) out; n_components may be NULL.                                                         */
+sapca_status sapca_graph_components_device(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets,
+                                           const int32_t* col_indices, int32_t* d_labels, uint64_t* n_components);
+/* Stage 2: d_scale (m f64, DEVICE) receives s.                                                                               */
+sapca_status sapca_spectral_scale_device_f32(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets,
+                                             const int32_t* col_indices, const float* values, uint32_t kind, double* d_scale);
+sapca_status sapca_spectral_scale_device_f64(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets,
+                                             const int32_t* col_indices, const double* values, uint32_t kind, double* d_scale);
+/* Stage 3: d_y = S d_x (m f64 each, DEVICE, distinct).                                                                       */
+sapca_status sapca_spectral_apply_device_f32(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets,
+                                             const int32_t* col_indices, const float* values, uint32_t kind, const double* d_x,
+                                             double* d_y);
+sapca_status sapca_spectral_apply_device_f64(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets,
+                                             const int32_t* col_indices, const double* values, uint32_t kind, const double* d_x,
+                                             double* d_y);
+/* The whole solve on a resident graph: evals (n_eigen f64, HOST), d_evecs (m x n_eigen row-major, DEVICE); n_components and
+ * n_steps may be NULL.                                                                                                       */
+sapca_status sapca_spectral_device_f32(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                       const float* values, const sapca_spectral_options* opts, double* evals, float* d_evecs,
+                                       uint64_t* n_components, uint32_t* n_steps);
+sapca_status sapca_spectral_device_f64(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                       const double* values, const sapca_spectral_options* opts, double* evals, double* d_evecs,
+                                       uint64_t* n_components, uint32_t* n_steps);
+/* The same with a HOST CSR in (int64 offsets, int32 columns, as on the device) and HOST eigenvectors out.                    */
+sapca_status sapca_spectral_f32(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                const float* values, const sapca_spectral_options* opts, double* evals, float* evecs,
+                                uint64_t* n_components, uint32_t* n_steps);
+sapca_status sapca_spectral_f64(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                const double* values, const sapca_spectral_options* opts, double* evals, double* evecs,
+                                uint64_t* n_components, uint32_t* n_steps);
+/* The spectral start: d_evecs (m rows of stride ld, DEVICE) in, d_y (m x output_dim packed, DEVICE) out.                     */
+sapca_status sapca_umap_spectral_init_device_f32(sapca_handle h, uint64_t m, uint32_t output_dim, const float* d_evecs, uint64_t ld,
+                                                 uint32_t n_eigen, uint32_t seed, float* d_y);
+sapca_status sapca_umap_spectral_init_device_f64(sapca_handle h, uint64_t m, uint32_t output_dim, const double* d_evecs, uint64_t ld,
+                                                 uint32_t n_eigen, uint32_t seed, double* d_y);
 
 /* ---- Rank groups: marker columns of a labelled resident CSR (sapca_rank_*): an opt-in superset, the reference has no counterpart ----
  * The step scanpy runs after clustering (rank_genes_groups with method "wilcoxon" or "t-test"): which columns (genes) set each

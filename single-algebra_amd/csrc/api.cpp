@@ -1058,6 +1058,30 @@ sapca_status sapca_get_column_scale(sapca_handle h, int32_t* mode, double* out, 
                                    double* modularity, uint32_t* n_levels) {                                              \
     return guarded(h, [&] { resident::louvain_host<T>(*h, m, nnz, p, i, v, opts, labels, n_communities, modularity, n_levels); }); \
   }                                                                                                                      \
+  sapca_status sapca_spectral_scale_device_##SUF(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* p, const int32_t* i, \
+                                                 const T* v, uint32_t kind, double* d_scale) {                              \
+    return guarded(h, [&] { resident::spectral_scale<T>(*h, unchecked_view(m, m, nnz, p, i, v), kind, d_scale); });      \
+  }                                                                                                                      \
+  sapca_status sapca_spectral_apply_device_##SUF(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* p, const int32_t* i, \
+                                                 const T* v, uint32_t kind, const double* d_x, double* d_y) {               \
+    return guarded(h, [&] { resident::spectral_apply<T>(*h, unchecked_view(m, m, nnz, p, i, v), kind, d_x, d_y); });     \
+  }                                                                                                                      \
+  sapca_status sapca_spectral_device_##SUF(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* p, const int32_t* i,    \
+                                           const T* v, const sapca_spectral_options* opts, double* evals, T* d_evecs,      \
+                                           uint64_t* n_components, uint32_t* n_steps) {                                    \
+    return guarded(h, [&] {                                                                                              \
+      resident::spectral_device<T>(*h, unchecked_view(m, m, nnz, p, i, v), opts, evals, d_evecs, n_components, n_steps); \
+    });                                                                                                                  \
+  }                                                                                                                      \
+  sapca_status sapca_spectral_##SUF(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* p, const int32_t* i, const T* v, \
+                                    const sapca_spectral_options* opts, double* evals, T* evecs, uint64_t* n_components,   \
+                                    uint32_t* n_steps) {                                                                   \
+    return guarded(h, [&] { resident::spectral_host<T>(*h, m, nnz, p, i, v, opts, evals, evecs, n_components, n_steps); }); \
+  }                                                                                                                      \
+  sapca_status sapca_umap_spectral_init_device_##SUF(sapca_handle h, uint64_t m, uint32_t output_dim, const T* d_evecs,    \
+                                                     uint64_t ld, uint32_t n_eigen, uint32_t seed, T* d_y) {               \
+    return guarded(h, [&] { resident::umap_spectral_init<T>(*h, m, output_dim, d_evecs, ld, n_eigen, seed, d_y); });     \
+  }                                                                                                                      \
   sapca_status sapca_kmeans_seed_device_##SUF(sapca_handle h, uint64_t m, const T* d_x, uint64_t ldx, uint64_t d,           \
                                               uint32_t n_clusters, uint32_t random_seed, T* d_centroids, int32_t* d_rows) { \
     return guarded(h, [&] { resident::kmeans_seed<T>(*h, m, d_x, ldx, d, n_clusters, random_seed, d_centroids, d_rows); }); \
@@ -1160,6 +1184,22 @@ void sapca_louvain_options_default(sapca_louvain_options* o) {
   o->max_sweeps = 256;
   o->resolution = 1.0;
   o->tol = 1e-7;
+}
+
+void sapca_spectral_options_default(sapca_spectral_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  o->struct_size = (uint32_t)sizeof(sapca_spectral_options);
+  o->random_seed = 42;
+  o->kind = SAPCA_SPECTRAL_NORMALIZED;
+  o->n_eigen = 16;
+  o->max_steps = 0;
+  o->tol = 1e-8;
+}
+
+sapca_status sapca_graph_components_device(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets,
+                                           const int32_t* col_indices, int32_t* d_labels, uint64_t* n_components) {
+  return guarded(h, [&] { resident::graph_components(*h, m, nnz, row_offsets, col_indices, d_labels, n_components); });
 }
 
 void sapca_umap_options_default(sapca_umap_options* o) {

@@ -206,6 +206,16 @@ struct sapca_handle_s {
              agg_idx[1].contains(q) || agg_val[1].contains(q);
     }
   } louvain;
+  // sapca_graph_components_device / sapca_spectral_* / sapca_umap_spectral_init_device_*: the parents, the changed word, the root
+  // flags and their scan space; the scale (q | t | s), the scaled f64 copy of the values and the solve's safe copy of the columns; the
+  // labels of a solve, the locked table (t | 1 / norm | lock_of), the Lanczos basis with the locked vectors in front, w, h1 | h2 |
+  // alpha | beta | partial sums, the Ritz matrix and vectors, the signs; the graph and eigenvectors of the host route; the
+  // start's maximum.  Nothing else lives in these.
+  struct Spectral {
+    sapca::DevBuf parent, changed, flag, scan, scale, wt, safe_idx, labels, lock_tab, basis, w, small, ritz_s, ritz_v, signs;
+    sapca::DevBuf in_ptr, in_idx, in_val, evecs, mx;
+    sapca::PinnedBuf host;
+  } spectral;
   // sapca_rank_sums_csr_device_* / sapca_rank_groups_csr_device_*: the group sizes, the rank pass's results (rank sums | tie sums |
   // counts), the long columns' list and segment offsets, and their key scratch (keys, labels, counts, the sort's work space).
   // Nothing else lives in these; the transposition and the moments use at_* and batch_out as sapca_batch_stats_csr_device_* does.

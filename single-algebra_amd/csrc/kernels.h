@@ -619,6 +619,41 @@ void louvain_group_emit(const CsrView<TV>& A, const LouvainLists& L, const int32
 // final[v] = renum[labels[first ? v : final[v]]]
 void louvain_compose(int32_t* final_labels, int64_t m, const int32_t* labels, const int32_t* renum, bool first, hipStream_t s);
 
+// ---- spectral.hip: components, scale and operator of a symmetric graph (sapca_spectral_*); include/sapca.h states the algorithm ----
+// parent[i] = i, *changed = 0
+void components_init(int32_t* parent, int64_t m, unsigned long long* changed, hipStream_t s);
+// one round: every stored (i, j) with j inside [0, m) hooks the larger root onto the smaller (atomicMin) and sets *changed,
+// then every chain is shortened to its root
+void components_round(const int64_t* ptr, const int32_t* idx, int64_t m, int32_t* parent, unsigned long long* changed, hipStream_t s);
+// flag[i] = parent[i] == i (flag: m + 1 words, flag[m] = 0; its exclusive scan numbers the roots)
+void components_flag(const int32_t* parent, int64_t m, int64_t* flag, hipStream_t s);
+// labels[i] = scan[parent[i]]
+void components_label(const int32_t* parent, int64_t m, const int64_t* scan, int32_t* labels, hipStream_t s);
+// the lanes a row gets (8, 16, 32 or 64) from the mean row length; forced > 0: that one (debug switch SAPCA_SPECTRAL_GROUP)
+int spectral_group(int64_t m, int64_t nnz, int forced);
+// out[i] = sum_j W_ij / div_j over the columns inside [0, m) (div null: ones), by lane groups of g
+template <typename T>
+void spectral_row_sums(const CsrView<T>& W, const double* div, int g, double* out, hipStream_t s);
+// s[i] = 1 / sqrt(d[i]) (q null) or 1 / (q[i] sqrt(z[i] / q[i])), z = d; 0 where a sum is not finite and positive
+void spectral_scale_finish(const double* d, const double* q, int64_t m, double* s_out, hipStream_t s);
+// wt[e] = W_e (s_i s_j), 0 for a column outside [0, m); safe_idx (nnz int32, nullable) = the columns with one outside [0, m)
+// replaced by the row's own number: what a product that does not look at its columns (k::spmv) may read
+template <typename T>
+void spectral_scaled_copy(const CsrView<T>& W, const double* sc, double* wt, int32_t* safe_idx, hipStream_t s);
+// y = Wt x by lane groups of g (the short-row product)
+void spectral_spmv(const CsrView<double>& Wt, const double* x, double* y, int g, hipStream_t s);
+// U[l][i] = lock_of[labels[i]] == l && t[i] > 0 ? t[i] inv_norm[l] : 0 for l < nlock (U: nlock x m, f64)
+void spectral_locked(const int32_t* labels, const int32_t* lock_of, const double* inv_norm, const double* t, int64_t m, int nlock,
+                     double* U, hipStream_t s);
+// out[i * ldo + col0 + l] = T(sign_l src[l * lds_row + i * lds_col]), l < nvec; fix_sign: sign_l makes the entry of largest
+// magnitude (lowest index on a tie) positive, else + (signs: nvec ints of work space)
+template <typename T>
+void spectral_store(const double* src, int64_t lds_row, int64_t lds_col, int64_t m, int nvec, bool fix_sign, int* signs, T* out,
+                    int64_t ldo, int col0, hipStream_t s);
+// the spectral start of UMAP; mx: one word of work space
+template <typename T>
+void umap_spectral_init(const T* E, int64_t ld, int64_t m, int od, uint32_t seed, unsigned long long* mx, T* y, hipStream_t s);
+
 // ---- rng.hip ---------------------------------------------------------------------------
 // Omega[r][j] ~ N(0,1) for j < l (zero for l <= j < ld), a pure function of (seed, r*l+j).
 template <typename T>

@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "lanczos.h"
+#include "lanczos_step.h"
 #include "small_svd.h"
 
 namespace sapca {
@@ -585,6 +586,46 @@ void spmv(const CsrView<T>& A, const double* x, double* y, hipStream_t s) {
 }
 template void spmv<float>(const CsrView<float>&, const double*, double*, hipStream_t);
 template void spmv<double>(const CsrView<double>&, const double*, double*, hipStream_t);
+
+// lanczos_step.h: the launches of an uncentred step, as lanczos_fit issues them
+void lanczos_gemv_t(const double* V, int64_t len, int nvec, const double* w, double* h, hipStream_t s) {
+  if (nvec <= 0) return;
+  hipLaunchKernelGGL(gemv_t_kernel, dim3(nvec), dim3(GEMV_T_THREADS), 0, s, V, len, nvec, w, h, 0);
+  SAPCA_HIP(hipGetLastError());
+}
+void lanczos_gemv_n_sub(const double* V, int64_t len, int nvec, const double* h, double* w, hipStream_t s) {
+  if (nvec <= 0 || len == 0) return;
+  hipLaunchKernelGGL(gemv_n_sub_kernel, dim3(grid1(len)), dim3(256), 0, s, V, len, nvec, h, w);
+  SAPCA_HIP(hipGetLastError());
+}
+int lanczos_gemv_n_sub_norm(const double* V, int64_t len, int nvec, const double* h1, const double* h2, double* w, double* partial,
+                            int j, double* alpha, hipStream_t s) {
+  static_assert(kLanczosPartialSlots == kPartStride, "one slot per block");
+  const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((len + 255) / 256, kPartStride));
+  hipLaunchKernelGGL(gemv_n_sub_norm_kernel<0>, dim3(nb), dim3(256), 0, s, V, len, nvec, h1, h2, w, partial, j, alpha,
+                     (const double*)nullptr, (const double*)nullptr);
+  SAPCA_HIP(hipGetLastError());
+  return nb;
+}
+int lanczos_norm2(const double* w, int64_t len, double* partial, hipStream_t s) {
+  const int nparts = 256;
+  hipLaunchKernelGGL(norm2_kernel<0>, dim3(nparts), dim3(256), 0, s, w, len, partial, (const double*)nullptr, (const double*)nullptr);
+  SAPCA_HIP(hipGetLastError());
+  return nparts;
+}
+void lanczos_scale(const double* w, int64_t len, const double* partial, int nparts, double* beta_out, double* vnext, hipStream_t s) {
+  hipLaunchKernelGGL(scale_kernel<0>, dim3(grid1(len, 256, 1024)), dim3(256), 0, s, w, len, partial, nparts, beta_out, vnext,
+                     (double*)nullptr);
+  SAPCA_HIP(hipGetLastError());
+}
+template <typename T>
+void lanczos_combine(const double* V, int64_t len, int nvec, const double* S, int k, int ldo, T* out, hipStream_t s) {
+  if (len == 0 || k <= 0) return;
+  hipLaunchKernelGGL((combine_kernel<T>), dim3(grid1(len), k), dim3(256), 0, s, V, len, nvec, S, k, ldo, out);
+  SAPCA_HIP(hipGetLastError());
+}
+template void lanczos_combine<float>(const double*, int64_t, int, const double*, int, int, float*, hipStream_t);
+template void lanczos_combine<double>(const double*, int64_t, int, const double*, int, int, double*, hipStream_t);
 }  // namespace k
 
 template <typename T>

@@ -193,5 +193,22 @@ template <typename T>
 void louvain_host(H& h, uint64_t m, uint64_t nnz, const int64_t* ptr, const int32_t* idx, const T* val, const sapca_louvain_options* opts,
                   int32_t* labels, uint64_t* n_communities, double* modularity, uint32_t* n_levels);
 
+// sapca_graph_components_device / sapca_spectral_* / sapca_umap_spectral_init_device_* (spectral.cpp): the components of a graph's
+// structure, the scale and one application of S = diag(s) W diag(s), the leading eigenpairs on a resident graph or on host
+// arrays, and UMAP's spectral start from eigenvectors
+void graph_components(H& h, uint64_t m, uint64_t nnz, const int64_t* ptr, const int32_t* idx, int32_t* d_labels, uint64_t* n_components);
+template <typename T>
+void spectral_scale(H& h, const CsrView<T>& G, uint32_t kind, double* d_scale);
+template <typename T>
+void spectral_apply(H& h, const CsrView<T>& G, uint32_t kind, const double* d_x, double* d_y);
+template <typename T>
+void spectral_device(H& h, const CsrView<T>& G, const sapca_spectral_options* opts, double* evals, T* d_evecs, uint64_t* n_components,
+                     uint32_t* n_steps);
+template <typename T>
+void spectral_host(H& h, uint64_t m, uint64_t nnz, const int64_t* ptr, const int32_t* idx, const T* val, const sapca_spectral_options* opts,
+                   double* evals, T* evecs, uint64_t* n_components, uint32_t* n_steps);
+template <typename T>
+void umap_spectral_init(H& h, uint64_t m, uint32_t output_dim, const T* d_evecs, uint64_t ld, uint32_t n_eigen, uint32_t seed, T* d_y);
+
 }  // namespace resident
 }  // namespace sapca

@@ -21,6 +21,10 @@
 //   lanczos.hip  SAPCA_SPMV_NO_LDS, SAPCA_SPMV_NO_SLICE_GRID, SAPCA_SPMV_IDX32 (SpmvSwitches: read once per fit, so one process can
 //                walk the routes), SAPCA_LANCZOS_CHECK
 //   tsne.hip     SAPCA_TSNE_SPLIT (0 | 1: the repulsion's j chunks walked by one workgroup per i block | one workgroup each)
+//   spectral.cpp SAPCA_SPECTRAL_GROUP (8 | 16 | 32 | 64: the lanes a row gets in the scale and the short-row product, whatever the
+//                mean row length; read on every call), SAPCA_SPECTRAL_SPMV_ROW (the stage call's product through the wave-per-row
+//                k::spmv: the yardstick of tools/time_spectral.py), SAPCA_SPECTRAL_STEP_SHORT (the solve's step through the short-row
+//                kernel instead of k::spmv), SAPCA_SPECTRAL_APPLY_REPS (the stage call runs its product that often)
 //   api.cpp      SAPCA_UPLOAD_STATS_OFF, SAPCA_UP_CHUNK (entries per chunk of the host upload, >= 1; read on every upload)
 //   comm.cpp     SAPCA_COMM_FORCE_RCCL (a one-rank RCCL communicator: how a one-GPU box tests the binding), SAPCA_COMM_NO_SPLIT,
 //                SAPCA_RCCL_LIBRARY (path of the tests' stand-in for librccl: tests/fake_rccl)

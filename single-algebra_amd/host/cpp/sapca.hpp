@@ -306,6 +306,75 @@ inline LouvainResult louvain(sapca_handle h, uint64_t m, uint64_t nnz, const int
   return r;
 }
 
+// Spectral embedding and diffusion maps of a device-resident symmetric graph (sapca_graph_components_device, sapca_spectral_*,
+// sapca_umap_spectral_init_device_*; include/sapca.h states the algorithm).  SpectralOptions() holds the library's defaults.
+// Every pointer but the options and the eigenvalues is a DEVICE pointer unless the name says host.
+struct SpectralOptions : sapca_spectral_options {
+  SpectralOptions() { sapca_spectral_options_default(this); }
+};
+struct SpectralResult {
+  uint64_t n_components = 0;
+  uint32_t n_steps = 0;
+};
+template <typename T> struct SpectralAbi;
+template <> struct SpectralAbi<float> {
+  static constexpr auto scale = &sapca_spectral_scale_device_f32;
+  static constexpr auto apply = &sapca_spectral_apply_device_f32;
+  static constexpr auto device = &sapca_spectral_device_f32;
+  static constexpr auto host = &sapca_spectral_f32;
+  static constexpr auto umap_start = &sapca_umap_spectral_init_device_f32;
+};
+template <> struct SpectralAbi<double> {
+  static constexpr auto scale = &sapca_spectral_scale_device_f64;
+  static constexpr auto apply = &sapca_spectral_apply_device_f64;
+  static constexpr auto device = &sapca_spectral_device_f64;
+  static constexpr auto host = &sapca_spectral_f64;
+  static constexpr auto umap_start = &sapca_umap_spectral_init_device_f64;
+};
+inline void spectral_check(sapca_handle h, sapca_status st) {
+  if (st != SAPCA_OK) throw Error(st, sapca_last_error(h));
+}
+// the number of components; d_labels: m int32
+inline uint64_t graph_components_device(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                        int32_t* d_labels) {
+  uint64_t n = 0;
+  spectral_check(h, sapca_graph_components_device(h, m, nnz, row_offsets, col_indices, d_labels, &n));
+  return n;
+}
+template <typename T>
+inline void spectral_scale_device(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                  const T* values, sapca_spectral_kind kind, double* d_scale) {
+  spectral_check(h, SpectralAbi<T>::scale(h, m, nnz, row_offsets, col_indices, values, (uint32_t)kind, d_scale));
+}
+template <typename T>
+inline void spectral_apply_device(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                  const T* values, sapca_spectral_kind kind, const double* d_x, double* d_y) {
+  spectral_check(h, SpectralAbi<T>::apply(h, m, nnz, row_offsets, col_indices, values, (uint32_t)kind, d_x, d_y));
+}
+// host_evals: opts.n_eigen doubles on the host; d_evecs: m x opts.n_eigen row-major
+template <typename T>
+inline SpectralResult spectral_device(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* row_offsets, const int32_t* col_indices,
+                                      const T* values, const sapca_spectral_options& opts, double* host_evals, T* d_evecs) {
+  SpectralResult r;
+  spectral_check(h, SpectralAbi<T>::device(h, m, nnz, row_offsets, col_indices, values, &opts, host_evals, d_evecs, &r.n_components,
+                                           &r.n_steps));
+  return r;
+}
+template <typename T>
+inline SpectralResult spectral(sapca_handle h, uint64_t m, uint64_t nnz, const int64_t* host_row_offsets, const int32_t* host_col_indices,
+                               const T* host_values, const sapca_spectral_options& opts, double* host_evals, T* host_evecs) {
+  SpectralResult r;
+  spectral_check(h, SpectralAbi<T>::host(h, m, nnz, host_row_offsets, host_col_indices, host_values, &opts, host_evals, host_evecs,
+                                         &r.n_components, &r.n_steps));
+  return r;
+}
+// UMAP's spectral start from NORMALIZED eigenvectors: d_y (m x output_dim) is what umap_embed_device takes with SAPCA_UMAP_INIT_GIVEN
+template <typename T>
+inline void umap_spectral_init_device(sapca_handle h, uint64_t m, uint32_t output_dim, const T* d_evecs, uint64_t ld, uint32_t n_eigen,
+                                      uint32_t seed, T* d_y) {
+  spectral_check(h, SpectralAbi<T>::umap_start(h, m, output_dim, d_evecs, ld, n_eigen, seed, d_y));
+}
+
 // K-means of device-resident rows (sapca_kmeans_*; include/sapca.h states the algorithm).  KmeansOptions() holds the library's
 // defaults.  Every pointer is a DEVICE pointer unless the name says host.
 struct KmeansOptions : sapca_kmeans_options {

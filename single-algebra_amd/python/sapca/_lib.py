@@ -67,6 +67,19 @@ class LouvainOptions(C.Structure):
     ]
 
 
+class SpectralOptions(C.Structure):
+    """sapca_spectral_options"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("random_seed", C.c_uint32), ("kind", C.c_uint32), ("n_eigen", C.c_uint32),
+        ("max_steps", C.c_uint32), ("reserved", C.c_uint32), ("tol", C.c_double),
+    ]
+
+
+# sapca_spectral_kind
+SPECTRAL_NORMALIZED, SPECTRAL_DIFFMAP = 0, 1
+SPECTRAL_KINDS = {"normalized": SPECTRAL_NORMALIZED, "diffmap": SPECTRAL_DIFFMAP}
+
+
 class HvgOptions(C.Structure):
     """sapca_hvg_options"""
     _fields_ = [
@@ -151,6 +164,8 @@ _TYPED = [
     "sapca_louvain_modularity_device", "sapca_louvain_sweep_device", "sapca_louvain_aggregate_device", "sapca_louvain_device",
     "sapca_louvain", "sapca_rank_sums_csr_device", "sapca_rank_groups_csr_device",
     "sapca_hvg_moments_csr_device", "sapca_hvg_csr_device",
+    "sapca_spectral_scale_device", "sapca_spectral_apply_device", "sapca_spectral_device", "sapca_spectral",
+    "sapca_umap_spectral_init_device",
     "sapca_multi_fit_csr", "sapca_multi_transform_csr", "sapca_multi_fit_transform_csr",
     "sapca_multi_upload_csr", "sapca_multi_transform_resident", "sapca_multi_fit_transform_resident",
 ]
@@ -167,6 +182,7 @@ _PLAIN = [
     "sapca_tsne_options_default", "sapca_kmeans_options_default",
     "sapca_umap_options_default", "sapca_umap_find_ab", "sapca_louvain_options_default",
     "sapca_hvg_options_default", "sapca_loess_f64",
+    "sapca_spectral_options_default", "sapca_graph_components_device",
 ]
 EXPORTED_SYMBOLS = _PLAIN + [f"{n}_{s}" for n in _TYPED for s in ("f32", "f64")]
 
@@ -346,7 +362,27 @@ def _open(path):
             getattr(lib, f"sapca_hvg_moments_csr_device_{suf}").argtypes = mat + [C.c_void_p, C.c_int32, C.c_int32, f64p, f64p, f64p, u64p]
             getattr(lib, f"sapca_hvg_csr_device_{suf}").argtypes = mat + [C.c_void_p, C.c_uint32, C.POINTER(HvgOptions), f64p, f64p, f64p,
                                                                           f64p, f64p, f64p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
+    if hasattr(lib, "sapca_spectral_options_default"):   # (absent from an older build loaded for an A/B run)
+        lib.sapca_spectral_options_default.argtypes = [C.POINTER(SpectralOptions)]
+        lib.sapca_spectral_options_default.restype = None
+        lib.sapca_graph_components_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.POINTER(C.c_uint64)]
+        csr = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]   # h, m, nnz, offsets, columns, values
+        for suf in ("f32", "f64"):
+            getattr(lib, f"sapca_spectral_scale_device_{suf}").argtypes = csr + [C.c_uint32, C.c_void_p]
+            getattr(lib, f"sapca_spectral_apply_device_{suf}").argtypes = csr + [C.c_uint32, C.c_void_p, C.c_void_p]
+            for name in (f"sapca_spectral_device_{suf}", f"sapca_spectral_{suf}"):
+                getattr(lib, name).argtypes = csr + [C.POINTER(SpectralOptions), C.POINTER(C.c_double), C.c_void_p,
+                                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+            getattr(lib, f"sapca_umap_spectral_init_device_{suf}").argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
+                                                                               C.c_uint32, C.c_uint32, C.c_void_p]
     return lib
+
+
+def default_spectral_options() -> SpectralOptions:
+    o = SpectralOptions()
+    load().sapca_spectral_options_default(C.byref(o))
+    return o
 
 
 def default_hvg_options() -> HvgOptions:

@@ -726,6 +726,148 @@ class Session:
             data.ctypes.data_as(C.c_void_p), C.byref(o), labels.ctypes.data_as(C.c_void_p), C.byref(ncomm), C.byref(q), C.byref(levels)))
         return labels, ncomm.value, q.value, levels.value
 
+    # ---- spectral embedding / diffusion maps (sapca_graph_components_device, sapca_spectral_*): components, scale, operator,
+    # the eigen-solve, the diffusion map and UMAP's spectral start ----
+    @staticmethod
+    def _spectral_kind(kind):
+        if not isinstance(kind, str) or kind.lower() not in L.SPECTRAL_KINDS:
+            raise ValueError(f"unknown kind {kind!r}: one of {sorted(L.SPECTRAL_KINDS)}")
+        return L.SPECTRAL_KINDS[kind.lower()]
+
+    def _spectral_options(self, n_eigen, kind, tol, max_steps, seed):
+        o = L.default_spectral_options()
+        o.kind = self._spectral_kind(kind)
+        if not 1 <= int(n_eigen) <= 64:
+            raise ValueError(f"n_eigen = {n_eigen} is outside 1 .. 64")
+        if not (float(tol) >= 0.0 and np.isfinite(float(tol))):
+            raise ValueError(f"tol must be finite and not negative, got {tol}")
+        if max_steps is not None and not 1 <= int(max_steps) <= 4096:
+            raise ValueError(f"max_steps = {max_steps} is outside 1 .. 4096")
+        o.random_seed = int(self._seed if seed is None else seed)
+        o.n_eigen, o.tol, o.max_steps = int(n_eigen), float(tol), 0 if max_steps is None else int(max_steps)
+        return o
+
+    def graph_components(self, G):
+        """sapca_graph_components_device: (labels, n_components) of the structure of the square graph G (a ResidentCsr; every
+        stored entry is an edge).  labels: m int32 on the device, components numbered in ascending order of their smallest
+        vertex, as scipy.sparse.csgraph.connected_components(directed=False) numbers them."""
+        import torch
+        m, _ = self._louvain_graph(G)
+        labels = torch.empty((m,), dtype=torch.int32, device=self._device())
+        n = C.c_uint64()
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, L.load().sapca_graph_components_device(
+            self._h, C.c_uint64(m), C.c_uint64(G.nnz), C.c_void_p(G.d_ptr), C.c_void_p(G.d_idx),
+            C.c_void_p(labels.data_ptr() if m else None), C.byref(n)))
+        return labels, n.value
+
+    def spectral_scale(self, G, kind="normalized"):
+        """sapca_spectral_scale_device_*: s (m f64 on the device) of S = diag(s) G diag(s): "normalized" 1 / sqrt(d), "diffmap"
+        1 / (q sqrt(z)) (include/sapca.h, "Spectral"); 0 for a vertex whose sums are not finite and positive."""
+        import torch
+        code = self._spectral_kind(kind)
+        m, suf = self._louvain_graph(G)
+        sc = torch.empty((m,), dtype=torch.float64, device=self._device())
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_spectral_scale_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_uint64(G.nnz), C.c_void_p(G.d_ptr), C.c_void_p(G.d_idx), C.c_void_p(G.d_val),
+            C.c_uint32(code), C.c_void_p(sc.data_ptr() if m else None)))
+        return sc
+
+    def spectral_apply(self, G, x, kind="normalized"):
+        """sapca_spectral_apply_device_*: y = S x for m f64 values x on the device (the short-row product of a Lanczos step)."""
+        import torch
+        code = self._spectral_kind(kind)
+        m, suf = self._louvain_graph(G)
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float64 and tuple(x.shape) == (m,) and x.is_contiguous()):
+            raise ValueError(f"x must be {m} contiguous float64 values on the device")
+        y = torch.empty_like(x)
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_spectral_apply_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_uint64(G.nnz), C.c_void_p(G.d_ptr), C.c_void_p(G.d_idx), C.c_void_p(G.d_val),
+            C.c_uint32(code), C.c_void_p(x.data_ptr() if m else None), C.c_void_p(y.data_ptr() if m else None)))
+        return y
+
+    def spectral(self, G, n_eigen=16, kind="normalized", tol=1e-8, max_steps=None, seed=None):
+        """sapca_spectral_device_*: (evals, evecs, n_components, n_steps) -- the n_eigen leading eigenpairs of S = diag(s) G diag(s)
+        for the symmetric graph G (a ResidentCsr).  evals: n_eigen f64 (numpy, descending); evecs: m x n_eigen on the device in
+        G's dtype, one exact pair (eigenvalue 1.0) per connected component first, the sign of every other vector fixed by its
+        entry of largest magnitude.  max_steps None: min(m, 1000).  The same bytes from call to call."""
+        import torch
+        o = self._spectral_options(n_eigen, kind, tol, max_steps, seed)
+        m, suf = self._louvain_graph(G)
+        if m and o.n_eigen > m:
+            raise ValueError(f"n_eigen = {n_eigen} exceeds m = {m}")
+        dt = torch.float32 if suf == "f32" else torch.float64
+        evecs = torch.empty((m, o.n_eigen), dtype=dt, device=self._device())
+        evals = np.zeros((o.n_eigen,), dtype=np.float64)
+        ncomp, steps = C.c_uint64(), C.c_uint32()
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_spectral_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_uint64(G.nnz), C.c_void_p(G.d_ptr), C.c_void_p(G.d_idx), C.c_void_p(G.d_val), C.byref(o),
+            _p(evals, C.c_double), C.c_void_p(evecs.data_ptr() if m else None), C.byref(ncomp), C.byref(steps)))
+        return evals, evecs, ncomp.value, steps.value
+
+    def spectral_host(self, indptr, indices, data, n_eigen=16, kind="normalized", tol=1e-8, max_steps=None, seed=None):
+        """sapca_spectral_*: the same with a host CSR in (scipy's three arrays) and host eigenvectors out."""
+        o = self._spectral_options(n_eigen, kind, tol, max_steps, seed)
+        data = np.ascontiguousarray(data)
+        if data.dtype not in _SUF:
+            raise ValueError(f"data must be float32 / float64, got {data.dtype}")
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        m = len(indptr) - 1
+        if m and o.n_eigen > m:
+            raise ValueError(f"n_eigen = {n_eigen} exceeds m = {m}")
+        evecs = np.zeros((m, o.n_eigen), dtype=data.dtype)
+        evals = np.zeros((o.n_eigen,), dtype=np.float64)
+        ncomp, steps = C.c_uint64(), C.c_uint32()
+        L.check(self._h, getattr(L.load(), f"sapca_spectral_{_SUF[data.dtype][0]}")(
+            self._h, C.c_uint64(m), C.c_uint64(len(data)), indptr.ctypes.data_as(C.c_void_p), indices.ctypes.data_as(C.c_void_p),
+            data.ctypes.data_as(C.c_void_p), C.byref(o), _p(evals, C.c_double), evecs.ctypes.data_as(C.c_void_p), C.byref(ncomp),
+            C.byref(steps)))
+        return evals, evecs, ncomp.value, steps.value
+
+    def diffmap(self, G_or_X, n_comps=15, n_neighbors=15, tol=1e-8, max_steps=None, seed=None):
+        """(X_diffmap, evals) -- scanpy's tl.diffmap: the n_comps leading eigenpairs of the density-normalised symmetric transition
+        matrix (spectral(kind="diffmap")) of a symmetric graph.  A ResidentCsr is taken as it is; an m x d device panel goes
+        through knn (Euclidean, self excluded, n_neighbors - 1) and umap_graph first, as louvain does.  The largest algebraic
+        eigenvalues are taken (scanpy's which="LM" would also admit values near -1)."""
+        if not 1 <= int(n_comps) <= 64:
+            raise ValueError(f"n_comps = {n_comps} is outside 1 .. 64")
+        G = G_or_X
+        if not isinstance(G, ResidentCsr):
+            idx, dist = self.knn(G_or_X, n_neighbors=int(n_neighbors) - 1, metric="euclidean", exclude_self=True)
+            G = self.umap_graph(idx, dist, int(n_neighbors))[0]
+        evals, evecs, _, _ = self.spectral(G, n_eigen=int(n_comps), kind="diffmap", tol=tol, max_steps=max_steps, seed=seed)
+        return evecs, evals
+
+    def umap_spectral_init(self, G, output_dim=2, seed=None, tol=1e-8, max_steps=None):
+        """sapca_umap_spectral_init_device_*: umap-learn's spectral start for the symmetric graph G, an m x output_dim device
+        tensor to pass to umap_embed / umap as init=: eigenvectors 1 .. output_dim of spectral(kind="normalized") expanded to
+        +-10 plus 1e-4 uniform noise under `seed`.  On a disconnected graph the leading eigenvectors are component indicators
+        and umap-learn's per-component meta-layout is not built: a warning says so."""
+        import warnings
+
+        import torch
+        D = int(output_dim)
+        if not 1 <= D <= 3:
+            raise ValueError(f"output_dim = {output_dim} is outside 1 .. 3")
+        m, suf = self._louvain_graph(G)
+        if m <= D:
+            raise ValueError(f"the spectral start needs more than output_dim = {D} vertices, got m = {m}")
+        seed = int(self._seed if seed is None else seed)
+        _, evecs, ncomp, _ = self.spectral(G, n_eigen=D + 1, kind="normalized", tol=tol, max_steps=max_steps, seed=seed)
+        if ncomp > 1:
+            warnings.warn(f"umap_spectral_init: the graph has {ncomp} connected components; the start separates components only "
+                          "(umap-learn's per-component meta-layout is not built)", RuntimeWarning, stacklevel=2)
+        Y = torch.empty((m, D), dtype=evecs.dtype, device=evecs.device)
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_umap_spectral_init_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_uint32(D), C.c_void_p(evecs.data_ptr()), C.c_uint64(D + 1), C.c_uint32(D + 1),
+            C.c_uint32(seed), C.c_void_p(Y.data_ptr())))
+        return Y
+
     # ---- local regression (sapca_loess_f64) ----
     def loess(self, x, y, span=0.3):
         """sapca_loess_f64: the local quadratic regression of y on x (host f64 arrays) fitted at every x_i on the device: the

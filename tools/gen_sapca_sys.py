@@ -22,7 +22,7 @@ SCALARS = {
     "sapca_options": "sapca_options", "sapca_timings": "sapca_timings", "sapca_csr_report": "sapca_csr_report",
     "sapca_tsne_options": "sapca_tsne_options", "sapca_kmeans_options": "sapca_kmeans_options",
     "sapca_umap_options": "sapca_umap_options", "sapca_louvain_options": "sapca_louvain_options",
-    "sapca_hvg_options": "sapca_hvg_options",
+    "sapca_hvg_options": "sapca_hvg_options", "sapca_spectral_options": "sapca_spectral_options",
     "sapca_allreduce_fn": "sapca_allreduce_fn",
 }
 
@@ -137,7 +137,7 @@ def render(header_text):
     for name, value in re.findall(r"^#define\s+(SAPCA_CSR_\w+)\s+(\d+)u\b", header_text, flags=re.M):
         w("pub const %s: u32 = %s;" % (name, value))
     for struct in ("sapca_options", "sapca_timings", "sapca_csr_report", "sapca_tsne_options", "sapca_kmeans_options",
-                   "sapca_umap_options", "sapca_louvain_options", "sapca_hvg_options"):
+                   "sapca_umap_options", "sapca_louvain_options", "sapca_hvg_options", "sapca_spectral_options"):
         w("")
         w("#[repr(C)]")
         w("#[derive(Clone, Copy)]")
