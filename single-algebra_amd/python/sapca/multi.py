@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .pca import _SUF, _np_ptr, as_u64
+from ._lib import _SUF, _p, as_u64
 
 
 class MultiDevice:
@@ -35,7 +35,7 @@ class MultiDevice:
         self._mask = mask
         if mask is not None and mask.size:
             m8 = mask.astype(np.uint8)
-            self._check(lib.sapca_multi_set_mask(self._mh, _np_ptr(m8, C.c_uint8), C.c_size_t(m8.size)))
+            self._check(lib.sapca_multi_set_mask(self._mh, _p(m8, C.c_uint8), C.c_size_t(m8.size)))
         self._members = []
         for i in range(len(self.devices)):
             m = copy.copy(estimator)          # same class and configuration, bound to the member's handle, owning nothing
@@ -87,11 +87,11 @@ class MultiDevice:
         if self._mask is not None and self._mask.size != n:
             raise L.SapcaError(L.ERR_MASK_LEN, "The mask vector length and the number of features (columns) have to be the same!")
         ro, ci, va = as_u64(x.indptr), as_u64(x.indices), np.ascontiguousarray(x.data)
-        args = [self._mh, C.c_uint64(m), C.c_uint64(n), C.c_uint64(va.size), _np_ptr(ro, C.c_uint64), _np_ptr(ci, C.c_uint64), _np_ptr(va, ct)]
+        args = [self._mh, C.c_uint64(m), C.c_uint64(n), C.c_uint64(va.size), _p(ro, C.c_uint64), _p(ci, C.c_uint64), _p(va, ct)]
         out = None
         if want_out:
             out = np.empty((m, self.n_components), dtype=dt)
-            args.append(_np_ptr(out, ct))
+            args.append(_p(out, ct))
         self._check(getattr(L.load(), f"sapca_multi_{op}_csr_{suf}")(*args))
         for mem in self._members:
             mem._dtype64 = dt == np.float64
@@ -111,7 +111,7 @@ class MultiDevice:
             raise L.SapcaError(L.ERR_MASK_LEN, "The mask vector length and the number of features (columns) have to be the same!")
         ro, ci, va = as_u64(x.indptr), as_u64(x.indices), np.ascontiguousarray(x.data)
         self._check(getattr(L.load(), f"sapca_multi_upload_csr_{suf}")(
-            self._mh, C.c_uint64(m), C.c_uint64(n), C.c_uint64(va.size), _np_ptr(ro, C.c_uint64), _np_ptr(ci, C.c_uint64), _np_ptr(va, ct)))
+            self._mh, C.c_uint64(m), C.c_uint64(n), C.c_uint64(va.size), _p(ro, C.c_uint64), _p(ci, C.c_uint64), _p(va, ct)))
         self._resident = (m, dt)
         return self
 
@@ -126,7 +126,7 @@ class MultiDevice:
             self._check(lib.sapca_multi_fit_resident(self._mh))
         else:
             out = np.empty((m, self.n_components), dtype=dt)
-            self._check(getattr(lib, f"sapca_multi_{op}_resident_{suf}")(self._mh, _np_ptr(out, ct)))
+            self._check(getattr(lib, f"sapca_multi_{op}_resident_{suf}")(self._mh, _p(out, ct)))
         for mem in self._members:
             mem._dtype64 = dt == np.float64
         return out

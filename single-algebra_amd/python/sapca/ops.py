@@ -8,14 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from ._lib import as_u64
-
-_SUF = {np.dtype(np.float32): ("f32", C.c_float), np.dtype(np.float64): ("f64", C.c_double)}
-
-
-def _p(a, ct):
-    return a.ctypes.data_as(C.POINTER(ct))
-
+from ._lib import _SUF, _p, as_u64
 
 def _knn_panel(name, t):
     """(rows, d, row stride, torch dtype) of a panel for Session.knn: a two-dimensional tensor of float32 / float64 whose

@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib as L
-from ._lib import as_u64
+from ._lib import _SUF, _p, as_u64
 
 
 class PowerIterationNormalizer(enum.IntEnum):
@@ -76,13 +76,6 @@ class DeviceCsr:
         return self.shape[1]
 
 
-_SUF = {np.dtype(np.float32): ("f32", C.c_float), np.dtype(np.float64): ("f64", C.c_double)}
-
-
-def _np_ptr(a, ct):
-    return a.ctypes.data_as(C.POINTER(ct))
-
-
 class _Estimator:
     """State and marshalling shared by SparsePCA and MaskedSparsePCA."""
 
@@ -128,7 +121,7 @@ class _Estimator:
             raise L.SapcaError(st, (lib.sapca_last_error(None) or b"").decode())
         if self._mask is not None and self._mask.size:
             m8 = self._mask.astype(np.uint8)
-            L.check(self._h, lib.sapca_set_mask(self._h, _np_ptr(m8, C.c_uint8), C.c_size_t(m8.size)))
+            L.check(self._h, lib.sapca_set_mask(self._h, _p(m8, C.c_uint8), C.c_size_t(m8.size)))
 
     def __del__(self):
         try:
@@ -150,7 +143,7 @@ class _Estimator:
     def set_omega(self, omega):
         """Inject the Gaussian test matrix of the next randomized fit (parity tests)."""
         om = np.ascontiguousarray(omega, dtype=np.float64)
-        L.check(self._h, L.load().sapca_set_omega_f64(self._h, _np_ptr(om, C.c_double),
+        L.check(self._h, L.load().sapca_set_omega_f64(self._h, _p(om, C.c_double),
                                                       C.c_size_t(om.shape[0]), C.c_size_t(om.shape[1])))
         return self
 
@@ -186,7 +179,7 @@ class _Estimator:
                 i, j = np.argwhere(~np.isfinite(d))[0]
                 raise ValueError(f"covariates: non-finite value at row {i}, column {j}")
         self._covariates = d if d.size else None
-        L.check(self._h, L.load().sapca_set_covariates(self._h, _np_ptr(d, C.c_double) if d.size else None,
+        L.check(self._h, L.load().sapca_set_covariates(self._h, _p(d, C.c_double) if d.size else None,
                                                        C.c_uint64(d.shape[0] if d.size else 0), C.c_uint64(d.shape[1] if d.size else 0)))
         return self
 
@@ -223,7 +216,7 @@ class _Estimator:
             j = int(np.argmax(bad))
             raise ValueError(f"column scaling: weight {w[j]:g} at column {j}")
         self._scale_weights = w
-        L.check(self._h, lib.sapca_set_column_scaling(self._h, C.c_int32(L.SCALE_WEIGHTS), _np_ptr(w, C.c_double) if w.size else None,
+        L.check(self._h, lib.sapca_set_column_scaling(self._h, C.c_int32(L.SCALE_WEIGHTS), _p(w, C.c_double) if w.size else None,
                                                       C.c_uint64(w.size)))
         return self
 
@@ -237,7 +230,7 @@ class _Estimator:
             return None
         _, nu, _ = self._dims()
         out = np.empty(nu, dtype=np.float64)
-        L.check(self._h, L.load().sapca_get_column_scale(self._h, C.byref(mode), _np_ptr(out, C.c_double), C.c_size_t(out.size)))
+        L.check(self._h, L.load().sapca_get_column_scale(self._h, C.byref(mode), _p(out, C.c_double), C.c_size_t(out.size)))
         return out
 
     def _scale_check(self, n):
@@ -294,12 +287,12 @@ class _Estimator:
         ro = as_u64(x.indptr)     # nalgebra_sparse usize layout
         ci = as_u64(x.indices)
         va = np.ascontiguousarray(x.data)
-        args = [self._h, C.c_uint64(m), C.c_uint64(n), C.c_uint64(va.size), _np_ptr(ro, C.c_uint64),
-                _np_ptr(ci, C.c_uint64), _np_ptr(va, ct)]
+        args = [self._h, C.c_uint64(m), C.c_uint64(n), C.c_uint64(va.size), _p(ro, C.c_uint64),
+                _p(ci, C.c_uint64), _p(va, ct)]
         out = None
         if want_out:
             out = np.empty((m, self.n_components), dtype=dt)
-            args.append(_np_ptr(out, ct))
+            args.append(_p(out, ct))
         L.check(self._h, getattr(lib, f"sapca_{op}_csr_{suf}")(*args))
         return out
 
@@ -325,7 +318,7 @@ class _Estimator:
         suf, ct = _SUF[dtype]
         shape = shape_fn(k, nu, nc)
         out = np.empty(shape, dtype=dtype)
-        L.check(self._h, getattr(L.load(), f"sapca_get_{name}_{suf}")(self._h, _np_ptr(out, ct), C.c_size_t(out.size)))
+        L.check(self._h, getattr(L.load(), f"sapca_get_{name}_{suf}")(self._h, _p(out, ct), C.c_size_t(out.size)))
         return out
 
     def _fitted_dtype(self):
@@ -363,7 +356,7 @@ class _Estimator:
         cols = np.zeros(max(n, 1), dtype=np.uint64)
         o2m = np.zeros(max(n, 1), dtype=np.int64)
         L.check(self._h, L.load().sapca_get_mask_index_maps(
-            self._h, _np_ptr(cols, C.c_uint64), C.c_size_t(cols.size), _np_ptr(o2m, C.c_int64), C.c_size_t(o2m.size)))
+            self._h, _p(cols, C.c_uint64), C.c_size_t(cols.size), _p(o2m, C.c_int64), C.c_size_t(o2m.size)))
         n_used = int(self._mask.sum()) if self._mask is not None else 0
         return cols[:n_used], o2m[:n]
 

@@ -84,17 +84,98 @@ def test_cpp_mirror_compiles(tmp_path):
     assert r.returncode == 0, r.stderr
 
 
+def _header_text():
+    """include/sapca.h without its comments"""
+    return re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "sapca.h")).read(), flags=re.S)
+
+
+def _header_arguments():
+    """(name -> the text between its parentheses) of every function include/sapca.h declares: an independent, cruder
+    parse than the generators' (comments stripped, `name(args);`)."""
+    return {name: args.strip() for name, args in re.findall(r"\b(sapca_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header_text())
+            if name != "sapca_allreduce_fn"}
+
+
 def _header_functions():
-    """(name -> argument count) of every function include/sapca.h declares: an independent, cruder parse than the
-    generator's (comments stripped, `name(args);` with the commas counted)."""
-    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "sapca.h")).read(), flags=re.S)
-    out = {}
-    for name, args in re.findall(r"\b(sapca_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
-        if name == "sapca_allreduce_fn":
-            continue
-        args = args.strip()
-        out[name] = 0 if args in ("", "void") else args.count(",") + 1
-    return out
+    """(name -> argument count), with the commas counted"""
+    return {name: 0 if args in ("", "void") else args.count(",") + 1 for name, args in _header_arguments().items()}
+
+
+STRUCT_CLASSES = (("sapca_options", "Options"), ("sapca_timings", "Timings"), ("sapca_csr_report", "CsrReport"),
+                  ("sapca_tsne_options", "TsneOptions"), ("sapca_kmeans_options", "KmeansOptions"),
+                  ("sapca_umap_options", "UmapOptions"), ("sapca_louvain_options", "LouvainOptions"),
+                  ("sapca_hvg_options", "HvgOptions"), ("sapca_spectral_options", "SpectralOptions"))
+
+
+def test_python_abi_table_is_what_its_generator_writes():
+    """sapca/_abi.py, from which sapca/_lib.py builds every structure, constant and signature, is generated from the
+    header (tools/gen_sapca_abi.py): the committed file is what the generator writes today."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_sapca_abi.py"), "--check"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def test_every_declared_function_is_typed_as_the_header_has_it():
+    """After load() every function of the header carries argtypes: as many as the header has arguments, and each
+    argument passed by value (no `*`, no `[n]`) with a ctypes type of its C size."""
+    lib = L.load()
+    c_size = {"uint64_t": 8, "size_t": 8, "double": 8, "sapca_handle": 8, "sapca_multi": 8, "sapca_allreduce_fn": 8,
+              "int32_t": 4, "uint32_t": 4}
+    counts, arguments = _header_functions(), _header_arguments()
+    assert set(L.EXPORTED_SYMBOLS) == set(counts) and len(L.EXPORTED_SYMBOLS) == len(counts)
+    typed = by_value = 0
+    for name, n in counts.items():
+        argtypes = getattr(lib, name).argtypes
+        assert argtypes is not None and len(argtypes) == n, f"{name}: header has {n} arguments, argtypes {argtypes}"
+        typed += 1
+        for i, arg in enumerate(arguments[name].split(",") if n else ()):
+            if "*" in arg or "[" in arg:
+                assert C.sizeof(argtypes[i]) == C.sizeof(C.c_void_p), f"{name} argument {i} ({arg.strip()})"
+                continue
+            ctype = re.match(r"\s*(?:const\s+)?(\w+)\s+\w+\s*$", arg).group(1)
+            assert C.sizeof(argtypes[i]) == c_size[ctype], f"{name} argument {i} ({arg.strip()}): {argtypes[i]}"
+            assert not issubclass(argtypes[i], C._Pointer), f"{name} argument {i} ({arg.strip()}): {argtypes[i]}"
+            by_value += 1
+    assert typed == len(counts) >= 186 and by_value >= typed
+
+
+def test_struct_defaults_write_the_python_class_size():
+    """each sapca_*_options_default writes the struct_size of its ctypes class (host-only calls)"""
+    lib = L.load()
+    defaults = [name for name in _header_functions() if name.endswith("_options_default")]
+    assert len(defaults) == 7
+    classes = dict(STRUCT_CLASSES)
+    for name in defaults:
+        cls = getattr(L, classes[name[:-len("_default")]])
+        o = cls()
+        getattr(lib, name)(C.byref(o))
+        assert o.struct_size == C.sizeof(cls), name
+    for helper, cls in ((L.default_options, L.Options), (L.default_tsne_options, L.TsneOptions), (L.default_kmeans_options, L.KmeansOptions),
+                        (L.default_umap_options, L.UmapOptions), (L.default_louvain_options, L.LouvainOptions),
+                        (L.default_hvg_options, L.HvgOptions), (L.default_spectral_options, L.SpectralOptions)):
+        o = helper()
+        assert type(o) is cls and o.struct_size == C.sizeof(cls)
+
+
+def test_every_header_constant_is_in_the_binding():
+    """every enumerator and integer #define of the header is an attribute of sapca._lib under its name without SAPCA_,
+    with the header's value (the test's own regexes, not the generators')"""
+    hdr = _header_text()
+    want = {name: int(value) for name, value in re.findall(r"^#define[ \t]+SAPCA_(\w+)[ \t]+(\d+)u?[ \t]*$", hdr, flags=re.M)}
+    assert want["ABI_VERSION"] == 4 and want["KNN_MAX_NEIGHBORS"] == 128 and want["CSR_NONFINITE"] == 16
+    n_defines = len(want)
+    for body in re.findall(r"typedef\s+enum\s+\w+\s*\{(.*?)\}", hdr, flags=re.S):
+        nxt = 0
+        for item in filter(None, (x.strip() for x in body.split(","))):
+            m = re.match(r"SAPCA_(\w+)(?:\s*=\s*(\d+))?$", item)
+            nxt = int(m.group(2)) if m.group(2) else nxt
+            want[m.group(1)] = nxt
+            nxt += 1
+    assert n_defines >= 17 and len(want) - n_defines >= 28
+    for name, value in want.items():
+        assert getattr(L, name) == value, name
+    assert (L.OK, L.ERR_NOMEM, L.KNN_PEARSON, L.SCALE_WEIGHTS) == (0, 7, 2, 2)
 
 
 def test_rust_sys_crate_declares_the_whole_header():
@@ -113,11 +194,13 @@ def test_rust_sys_crate_declares_the_whole_header():
     for name, n in want.items():
         assert have[name] == n, f"{name}: header has {n} arguments, sapca-sys {have[name]}"
     assert len(want) >= 91
-    # struct layouts: field counts and order of the two POD structs
-    hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "sapca.h")).read(), flags=re.S)
-    for struct, cls in (("sapca_options", L.Options), ("sapca_timings", L.Timings)):
+    # struct layouts: field counts and order of the POD structs
+    hdr = _header_text()
+    assert len(STRUCT_CLASSES) == len(re.findall(r"typedef\s+struct\s+\w+\s*\{", hdr))
+    for struct, cls in ((s, getattr(L, c)) for s, c in STRUCT_CLASSES):
         body = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}" % struct, hdr, flags=re.S).group(1)
-        c_fields = [re.match(r".*?(\w+)\s*(?:\[\d+\])?$", " ".join(d.split())).group(1) for d in body.split(";") if d.strip()]
+        c_fields = [re.match(r".*?(\w+)\s*(?:\[\d+\])?$", part.strip()).group(1)   # (`uint64_t a, b, c;` declares three)
+                    for d in body.split(";") if d.strip() for part in " ".join(d.split()).split(",")]
         r_body = re.search(r"pub struct %s \{(.*?)\}" % struct, rs, flags=re.S).group(1)
         r_fields = re.findall(r"pub (\w+):", r_body)
         assert c_fields == r_fields == [f[0] for f in cls._fields_], struct
