@@ -42,6 +42,16 @@
  *      against all previous ones (two passes of classical Gram-Schmidt on the device: one GEMV pair instead of las2's
  *      bookkeeping of which Ritz vectors have converged).  Converged triplets agree to kappa; the number of Lanczos steps
  *      taken, and triplets that have NOT converged at the cap, can differ.
+ *      Repeated values: the Krylov space of one start vector holds one vector per DISTINCT singular value, so a
+ *      single-vector Lanczos may return fewer copies of a repeated (or, within kappa, nearly repeated) singular value than its
+ *      multiplicity and fill up with the next smaller ones, as las2 may; every returned triplet is a true one.
+ *      Rank: a Ritz value of the Gram matrix at or below 1e-12 of the largest (sigma_i <= 1e-6 sigma_1) is a zero with its
+ *      rounding, whatever its sign, and is never accepted as a triplet.  When the Krylov space is exhausted (beta_j <= 1e-13 of
+ *      the largest Ritz value) with at least n_components values above that floor the fit ends there with exact triplets; with
+ *      fewer -- a matrix of rank below n_components, a matrix of zeros -- it is SAPCA_ERR_SVD, "SVD computation failed: the
+ *      operator has r singular values above 1e-6 of the largest, k singular triplets were asked for" (deviation 1), on the
+ *      tall and the wide side alike and on every call.  The cap reached without k accepted triplets: "SVD computation failed:
+ *      Lanczos did not converge k singular triplets within j steps".
  */
 #ifndef SAPCA_H
 #define SAPCA_H
@@ -85,7 +95,10 @@ extern "C" {
                                  additive, ABI 4: sapca_graph_components_device, sapca_spectral_options_default,
                                                   sapca_spectral_scale_device_*, sapca_spectral_apply_device_*,
                                                   sapca_spectral_device_*, sapca_spectral_*,
-                                                  sapca_umap_spectral_init_device_*                                    */
+                                                  sapca_umap_spectral_init_device_*
+                                 additive, ABI 4: sapca_spectral_options.reserved became single_round (same size and offsets;
+                                                  0, what a zeroed or defaulted struct holds, is the default; a value above 1,
+                                                  ignored before, is now SAPCA_ERR_ARG)                                 */
 
 typedef struct sapca_handle_s* sapca_handle;
 
@@ -1156,14 +1169,33 @@ sapca_status sapca_louvain_f64(sapca_handle h, uint64_t m, uint64_t nnz, const i
  *   5. Otherwise a single-vector Lanczos iteration on S in the orthogonal complement of the c locked vectors: start vector
  *      gaussian_panel (m x 1) under random_seed; every new vector (the start included) goes through classical Gram-Schmidt
  *      twice against the locked vectors and the whole Lanczos basis, with the fixed-order kernels of the Lanczos SVD; alpha_j
- *      and beta_j are those of the Lanczos part.  From step n_eigen - c on the host reads alpha and beta back (every step up
- *      to 64, then every 2nd, 4th, 8th as the Lanczos SVD does) and runs implicit QL with the bottom row: the run stops when
- *      the n_eigen - c largest (algebraic) Ritz values all have |beta_j s_ji| <= tol, or when the Krylov space is exhausted
- *      (beta_j <= 1e-13 times the largest |Ritz value|, or j = m - c).  max_steps without that: SAPCA_ERR_SVD, "spectral:
- *      Lanczos did not converge k of n pairs in j steps".  A Krylov space exhausted in fewer than n_eigen - c steps (beta_j <=
- *      1e-13 (max_i |alpha_i| + 2 |beta_i|), looked at every step until then: a graph without weights, or components so small
- *      that the start vector spans less) holds fewer pairs than were asked for: SAPCA_ERR_SVD, "spectral: the Krylov space is
- *      exhausted after j steps, k pairs were to be iterated", no padded pairs.
+ *      and beta_j are those of the Lanczos part.  A run that wants p pairs: from step p on the host reads alpha and beta back
+ *      (every step up to 64, then every 2nd, 4th, 8th as the Lanczos SVD does) and runs implicit QL with the bottom row: the
+ *      run stops when the p largest (algebraic) Ritz values all have |beta_j s_ji| <= tol, or when the Krylov space is
+ *      exhausted (beta_j <= 1e-13 times the largest |Ritz value|, or j = the dimension of the complement; before step p:
+ *      beta_j <= 1e-13 (max_i |alpha_i| + 2 |beta_i|), looked at every step; with a locked pair |S| >= 1 and either scale is at
+ *      least 1: in the null space of S the run's own values are rounding noise).  Every Ritz pair of an exhausted run is an
+ *      eigenpair; it gives min(p, j) of them and no padded ones.  The one exception is a graph without weights (no vertex with
+ *      s_i > 0, c = 0, S the zero matrix, of which every vector is an eigenvector): its single run is all there is, no round
+ *      follows it, and exhausted in fewer than n_eigen steps it is SAPCA_ERR_SVD, "spectral: the Krylov space is exhausted
+ *      after j steps, k pairs were to be iterated".
+ *      Rounds.  The Krylov space of ONE start vector holds one vector per DISTINCT eigenvalue, and full re-orthogonalisation
+ *      keeps the further copies of a repeated value (a ring, a grid, a lattice, a complete graph, a star, any graph with a
+ *      symmetry) at rounding level: a single run returns each value once and fills up with smaller ones.  So the solve
+ *      runs in rounds.  A round locks the Ritz vectors it accepted behind the analytic ones and the next round starts from
+ *      gaussian_panel under random_seed + 0x9E3779B9 round (mod 2^32; round 0 is random_seed itself) in the complement of
+ *      all of them.  While fewer than n_eigen - c pairs are held a round wants the missing ones (an exhausted run ends its
+ *      round, it is no error).  Then a round wants 1 pair, the largest of the complement: if it exceeds the current
+ *      (n_eigen - c)-th largest held value by more than tol it is a missed copy and is merged (held values are re-sorted,
+ *      ties in the order found) and another round follows, at most n_eigen - c of them; if not, or if the complement is empty,
+ *      the solve ends with the n_eigen - c largest held pairs.  On a graph whose leading values are simple the first round's
+ *      pairs are the result, bit for bit what a single run gives, and the one closing round is the price of knowing it.
+ *      single_round = 1 ends after the round that completes n_eigen - c pairs: the single run, for a caller who knows the
+ *      leading values to be simple.  Values closer than tol are one value to the rule: their pairs come in either order.
+ *      n_steps is the sum over the rounds.  A round that reaches max_steps: SAPCA_ERR_SVD, "spectral: Lanczos did not
+ *      converge k of n pairs in j steps" while pairs are missing (k the missing ones, j the steps of all rounds so far),
+ *      "spectral: the round that looks for a missed copy of a repeated eigenvalue did not converge in j steps (t in all)"
+ *      afterwards.
  *   6. Output: eigenvalues descending (the locked 1.0s, then the Ritz values); eigenvectors m x n_eigen row-major.  Ritz
  *      vectors are combined on the device in f64, their sign fixed so that the entry of largest magnitude (lowest index on a
  *      tie) is positive, and rounded once to T; the locked vectors are positive already.  n_components counts every
@@ -1179,7 +1211,8 @@ sapca_status sapca_louvain_f64(sapca_handle h, uint64_t m, uint64_t nnz, const i
  * All work is in buffers of the handle's own: the UMAP graph, Louvain's buffers, the upload, a fitted model and a cached
  * preparation stay valid and untouched; on a handle that belongs to a communicator the calls are local and issue no
  * collective.  A column outside [0, m) is skipped where it is read.  Negative or non-finite weights or an asymmetric graph
- * give unspecified numbers; the call still terminates at max_steps.  The Lanczos basis takes (c + max_steps + 1) m doubles;
+ * give unspecified numbers; every round still terminates at max_steps.  The Lanczos basis takes (2 n_eigen - c + max_steps + 1) m
+ * doubles (the locked vectors, up to 2 (n_eigen - c) held Ritz vectors, a round's basis);
  * one that cannot be allocated is SAPCA_ERR_NOMEM.
  * SAPCA_ERR_ARG, checked on the host before anything is enqueued (the handle stays usable), each with a message that names the
  * offending number: a wrong struct_size; an unknown kind; n_eigen outside 1 .. 64 or above m; max_steps above 4096; tol
@@ -1192,7 +1225,7 @@ typedef struct sapca_spectral_options {
   uint32_t kind;          /* sapca_spectral_kind, default NORMALIZED          */
   uint32_t n_eigen;       /* default 16; 1 .. 64 and <= m                     */
   uint32_t max_steps;     /* default 0: min(m, 1000); at most 4096            */
-  uint32_t reserved;
+  uint32_t single_round;  /* default 0: rounds until no copy is missed; 1: one */
   double tol;             /* default 1e-8                                     */
 } sapca_spectral_options;
 void sapca_spectral_options_default(sapca_spectral_options* opts);

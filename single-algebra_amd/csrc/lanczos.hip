@@ -731,7 +731,7 @@ void lanczos_fit(sapca_handle_s& h, bool centred) {
   // the bottom row of the eigenvector matrix (the error bounds need nothing else), so while T is small every step is
   // checked and no step is run past convergence; as T grows the checks thin out.  SAPCA_LANCZOS_CHECK=<n> fixes the
   // interval (experiments).
-  static const int check_env = dbg_env("SAPCA_LANCZOS_CHECK") ? atoi(dbg_env("SAPCA_LANCZOS_CHECK")) : 0;
+  const int check_env = dbg_env("SAPCA_LANCZOS_CHECK") ? atoi(dbg_env("SAPCA_LANCZOS_CHECK")) : 0;   // (per fit, like the other switches)
   auto check_due = [&](int64_t j) {
     const int every = check_env > 0 ? check_env : j <= 64 ? 1 : j <= 128 ? 2 : j <= 256 ? 4 : 8;
     return j % every == 0;
@@ -765,13 +765,27 @@ void lanczos_fit(sapca_handle_s& h, bool centred) {
                   "SVD computation failed: tridiagonal QL did not converge");
       theta = d;  // ascending
       const double bj = b_host[steps - 1];
+      // A Ritz value at or below rank_floor (sigma <= 1e-6 sigma_1) is a zero of the Gram matrix with its rounding, whatever its
+      // sign: it is never accepted as a triplet (include/sapca.h, deviation 5).
+      const double rank_floor = 1e-12 * std::fabs(theta[steps - 1]);
       bool ok = std::isfinite(bj);
       for (int i = 0; i < k && ok; ++i) {
         const int c = (int)steps - 1 - i;
         const double bound = std::fabs(bj * S[c]);
-        ok = theta[c] > 0 && bound <= kappa * std::fabs(theta[c]);
+        ok = theta[c] > rank_floor && bound <= kappa * std::fabs(theta[c]);
       }
-      if (ok || bj <= 1e-300 * std::fabs(theta[steps - 1])) {  // converged, or the Krylov space is exhausted
+      if (ok) {
+        converged = true;
+        break;
+      }
+      if (bj <= 1e-13 * std::fabs(theta[steps - 1])) {
+        // The Krylov space is exhausted: every Ritz pair is exact, further steps would only normalise rounding noise into
+        // basis vectors, and the values above the floor are all the operator has along the start vector.
+        int rank = 0;
+        while (rank < steps && theta[steps - 1 - rank] > rank_floor) ++rank;
+        SAPCA_CHECK(rank >= k, SAPCA_ERR_SVD,
+                    "SVD computation failed: the operator has " + std::to_string(rank) + " singular values above 1e-6 of the largest, " +
+                        std::to_string(k) + " singular triplets were asked for");
         converged = true;
         break;
       }

@@ -3,6 +3,7 @@
 // small_svd.cpp's): argument checks, buffer layouts, launches, the convergence test.  Everything that can be refused is refused
 // before anything is enqueued or a buffer is touched.  All work space lives in h.spectral: a fitted model, a cached preparation,
 // the upload, the UMAP graph and the Louvain buffers are not touched.
+#include <algorithm>
 #include <cmath>
 
 #include "lanczos_step.h"
@@ -37,6 +38,7 @@ void check_options(const sapca_spectral_options* o, uint64_t m, const std::strin
   check_kind(o->kind, w);
   SAPCA_CHECK(o->n_eigen >= 1 && o->n_eigen <= 64, SAPCA_ERR_ARG, w + ": n_eigen = " + num(o->n_eigen) + " is outside 1 .. 64");
   SAPCA_CHECK(o->max_steps <= 4096, SAPCA_ERR_ARG, w + ": max_steps = " + num(o->max_steps) + " exceeds 4096");
+  SAPCA_CHECK(o->single_round <= 1, SAPCA_ERR_ARG, w + ": single_round = " + num(o->single_round) + " is neither 0 nor 1");
   check_constant(o->tol, "tol", w);
   check_rows(m, w);
   SAPCA_CHECK(m == 0 || o->n_eigen <= m, SAPCA_ERR_ARG, w + ": n_eigen = " + num(o->n_eigen) + " exceeds m = " + num(m));
@@ -153,14 +155,20 @@ int locked_pairs(H& h, int64_t m, uint64_t ncomp, const int32_t* d_labels, const
   return nlock;
 }
 
-// The iteration of stage 5 on S in the complement of the c locked vectors that open the basis V.  Returns the steps taken; on
-// return theta (ascending) and Z (steps x steps, columns) are the eigenpairs of the final tridiagonal.
+// One round of stage 5 on S in the complement of the c locked vectors that open the basis V (the analytic ones and the Ritz
+// vectors of earlier rounds), for the k largest pairs of that complement.  Returns the steps taken; on return theta (ascending)
+// and Z (steps x steps, columns) are the eigenpairs of the final tridiagonal.  exhausted: the Krylov space of the start vector
+// ended (possibly in fewer than k steps); every Ritz pair of the run is then an eigenpair, and there are `steps` of them.
+// floor: a lower bound of |S| (1 when a pair of eigenvalue 1 is locked).  A beta_j is zero against the larger of it and the
+// run's own Ritz values: in the null space of S those are rounding noise themselves, and a run that went on there would
+// normalise noise into basis vectors.
 struct LanczosRun {
   int64_t steps = 0;
-  bool converged = false;
+  bool converged = false, exhausted = false;
   std::vector<double> theta, Z;
 };
-LanczosRun run_lanczos(H& h, const CsrView<double>& S, int g, int c, int k, int64_t jmax, double tol, uint32_t seed, double* V) {
+LanczosRun run_lanczos(H& h, const CsrView<double>& S, int g, int c, int k, int64_t jmax, double tol, uint32_t seed, double floor,
+                       double* V) {
   H::Spectral& wk = h.spectral;
   hipStream_t s = h.stream;
   const int64_t m = S.rows;
@@ -206,25 +214,30 @@ LanczosRun run_lanczos(H& h, const CsrView<double>& S, int g, int c, int k, int6
     const double* b_host = ab_host + L;
     if (steps < k) {
       // Fewer steps than wanted pairs: only an exhausted Krylov space matters here.  Behind it the basis would be padded with
-      // zero vectors and T with zero rows, whose Ritz pairs are not eigenpairs: refuse instead of returning them.
-      double reach = 0.0;   // (Gershgorin: no eigenvalue of T lies further out)
+      // zero vectors and T with zero rows, whose Ritz pairs are not eigenpairs: the round ends with the `steps` pairs it has.
+      double reach = floor;   // (Gershgorin: no eigenvalue of T lies further out)
       for (int64_t i = 0; i < steps; ++i) reach = std::max(reach, std::fabs(ab_host[i]) + 2.0 * std::fabs(b_host[i]));
-      SAPCA_CHECK(!(b_host[steps - 1] <= 1e-13 * reach), SAPCA_ERR_SVD,
+      if (!(b_host[steps - 1] <= 1e-13 * reach)) continue;
+      // Nothing locked (floor == 0): no vertex has a positive scale, S is the zero matrix -- a graph without weights -- and
+      // every vector is an "eigenvector" of it: refused as ever, not answered with arbitrary vectors.
+      SAPCA_CHECK(floor > 0.0, SAPCA_ERR_SVD,
                   "spectral: the Krylov space is exhausted after " + num((uint64_t)steps) + " steps, " + num((uint64_t)k) +
                       " pairs were to be iterated");
-      continue;
+      run.converged = run.exhausted = true;
+      break;
     }
     std::vector<double> d(ab_host, ab_host + steps), e((size_t)steps, 0.0), bottom;
     for (int64_t i = 1; i < steps; ++i) e[(size_t)i] = b_host[i - 1];
     SAPCA_CHECK(tridiag_eigh(d, e, (int)steps, bottom, true), SAPCA_ERR_SVD, "spectral: tridiagonal QL did not converge");
     const double bj = b_host[steps - 1];
-    double radius = 0.0;
+    double radius = floor;
     for (double t : d) radius = std::max(radius, std::fabs(t));
     bool ok = std::isfinite(bj);
     for (int i = 0; i < k && ok; ++i) ok = std::fabs(bj * bottom[(size_t)(steps - 1 - i)]) <= tol;
     const bool exhausted = steps == m - c || bj <= 1e-13 * radius;
     if (ok || (exhausted && std::isfinite(bj))) {
       run.converged = true;
+      run.exhausted = exhausted;
       break;
     }
   }
@@ -307,7 +320,8 @@ void spectral_device(H& h, const CsrView<T>& G, const sapca_spectral_options* op
   const int k = n_eigen - c;   // pairs the iteration owes
   const int64_t max_steps = opts->max_steps ? (int64_t)opts->max_steps : std::min<int64_t>(m, 1000);
   const int64_t jmax = k > 0 ? std::min<int64_t>(max_steps, m - c) : 0;
-  double* V = w.basis.as<double>((size_t)(c + jmax + 1) * (size_t)m);   // (SAPCA_ERR_NOMEM from here)
+  // (SAPCA_ERR_NOMEM from here; the rounds lock at most 2 k Ritz vectors: k to fill, and a k-th merged copy ends the merging)
+  double* V = w.basis.as<double>((size_t)(c + 2 * std::max(k, 0) + jmax + 1) * (size_t)m);
   KK::spectral_locked(labels, lock_of, inv_norm, t, m, c, V, s);
   int* signs = w.signs.as<int>(64);
   KK::spectral_store<T>(V, m, 1, m, c, false, signs, d_evecs, n_eigen, 0, s);
@@ -319,25 +333,61 @@ void spectral_device(H& h, const CsrView<T>& G, const sapca_spectral_options* op
                 who + ": Lanczos did not converge " + num((uint64_t)k) + " of " + num((uint64_t)n_eigen) + " pairs in " + num((uint64_t)jmax) +
                     " steps");
     const CsrView<double> S = enqueue_scaled_copy<T>(h, G, sc, true);
-    const LanczosRun run = run_lanczos(h, S, g, c, k, jmax, opts->tol, opts->random_seed, V);
-    steps = run.steps;
-    SAPCA_CHECK(run.converged, SAPCA_ERR_SVD,
-                who + ": Lanczos did not converge " + num((uint64_t)k) + " of " + num((uint64_t)n_eigen) + " pairs in " + num((uint64_t)steps) +
-                    " steps");
-    // the Ritz vectors of the k largest values: combined in f64, sign-fixed, rounded once
-    std::vector<double> Zk((size_t)steps * k);
-    for (int i = 0; i < k; ++i) {
-      const int64_t col = steps - 1 - i;
-      evals[c + i] = run.theta[(size_t)col];
-      for (int64_t j = 0; j < steps; ++j) Zk[(size_t)j * k + i] = run.Z[(size_t)j * steps + col];
-    }
-    double* Zdev = w.ritz_s.as<double>(Zk.size());
-    SAPCA_HIP(hipMemcpyAsync(Zdev, Zk.data(), Zk.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    const bool verify = opts->single_round == 0 && c > 0;   // (c == 0: S is the zero matrix, one run says all there is to say)
+    // Rounds (include/sapca.h, stage 5).  vals[i] belongs to the Ritz vector V[c + i]: the rounds lock what they accept, so the
+    // next one iterates in the complement of all of it and finds the copies of a repeated value that one start vector cannot.
+    std::vector<double> vals;
+    std::vector<int> order;   // of vals, descending (ties in the order found)
+    auto sort_vals = [&] {
+      order.resize(vals.size());
+      for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
+      std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return vals[(size_t)a] > vals[(size_t)b]; });
+    };
     double* R = w.ritz_v.as<double>((size_t)m * k);
-    KK::lanczos_combine<double>(V + (size_t)c * m, m, (int)steps, Zdev, k, k, R, s);
-    KK::spectral_store<T>(R, 1, k, m, k, true, signs, d_evecs, n_eigen, c, s);
+    for (uint32_t round = 0;; ++round) {
+      const int have = (int)vals.size();
+      const int lock = c + have;
+      const bool checking = have >= k;   // all pairs are there: is a larger one left in the complement?
+      // (merged values come in non-increasing order and each exceeds the k-th held one: the k-th merge is the last, and the
+      // basis has room for 2 k held vectors)
+      if (lock == m || (checking && (!verify || have >= 2 * k))) break;
+      const int want = checking ? 1 : k - have;
+      const int64_t jr = std::min<int64_t>(max_steps, m - lock);
+      const LanczosRun run = run_lanczos(h, S, g, lock, want, jr, opts->tol, opts->random_seed + 0x9E3779B9u * round, c > 0 ? 1.0 : 0.0, V);
+      steps += run.steps;
+      SAPCA_CHECK(run.converged, SAPCA_ERR_SVD,
+                  checking ? who + ": the round that looks for a missed copy of a repeated eigenvalue did not converge in " +
+                                 num((uint64_t)run.steps) + " steps (" + num((uint64_t)steps) + " in all)"
+                           : who + ": Lanczos did not converge " + num((uint64_t)want) + " of " + num((uint64_t)n_eigen) + " pairs in " +
+                                 num((uint64_t)steps) + " steps");
+      const int got = run.exhausted ? (int)std::min<int64_t>(want, run.steps) : want;
+      if (checking && !(run.theta[(size_t)(run.steps - 1)] > vals[(size_t)order[(size_t)(k - 1)]] + opts->tol)) break;
+      // the Ritz vectors of the `got` largest values, combined in f64 one by one, then moved in behind the locked ones
+      std::vector<double> Zk((size_t)run.steps * got);
+      for (int i = 0; i < got; ++i) {
+        const int64_t col = run.steps - 1 - i;
+        vals.push_back(run.theta[(size_t)col]);
+        for (int64_t j = 0; j < run.steps; ++j) Zk[(size_t)i * run.steps + j] = run.Z[(size_t)j * run.steps + col];
+      }
+      double* Zdev = w.ritz_s.as<double>(Zk.size());
+      SAPCA_HIP(hipMemcpyAsync(Zdev, Zk.data(), Zk.size() * sizeof(double), hipMemcpyHostToDevice, s));
+      double* basis = V + (size_t)lock * m;
+      for (int i = 0; i < got; ++i)
+        KK::lanczos_combine<double>(basis, m, (int)run.steps, Zdev + (size_t)i * run.steps, 1, 1, R + (size_t)i * m, s);
+      SAPCA_HIP(hipMemcpyAsync(basis, R, (size_t)got * m * sizeof(double), hipMemcpyDeviceToDevice, s));
+      SAPCA_HIP(hipStreamSynchronize(s));   // (Zk leaves scope)
+      sort_vals();
+    }
+    SAPCA_CHECK((int)vals.size() >= k, SAPCA_ERR_SVD,
+                who + ": the complement of the locked vectors is empty with " + num((uint64_t)vals.size()) + " of " + num((uint64_t)k) +
+                    " pairs");
+    // the k largest, sign-fixed and rounded once
+    for (int i = 0; i < k; ++i) {
+      evals[c + i] = vals[(size_t)order[(size_t)i]];
+      KK::spectral_store<T>(V + (size_t)(c + order[(size_t)i]) * m, m, 1, m, 1, true, signs, d_evecs, n_eigen, c + i, s);
+    }
   }
-  SAPCA_HIP(hipStreamSynchronize(s));   // complete when the call returns (Zk leaves scope behind it)
+  SAPCA_HIP(hipStreamSynchronize(s));   // complete when the call returns
   if (n_components) *n_components = ncomp;
   if (n_steps) *n_steps = (uint32_t)steps;
 }

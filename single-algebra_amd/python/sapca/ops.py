@@ -727,8 +727,9 @@ class Session:
             raise ValueError(f"unknown kind {kind!r}: one of {sorted(L.SPECTRAL_KINDS)}")
         return L.SPECTRAL_KINDS[kind.lower()]
 
-    def _spectral_options(self, n_eigen, kind, tol, max_steps, seed):
+    def _spectral_options(self, n_eigen, kind, tol, max_steps, seed, single_round=False):
         o = L.default_spectral_options()
+        o.single_round = 1 if single_round else 0
         o.kind = self._spectral_kind(kind)
         if not 1 <= int(n_eigen) <= 64:
             raise ValueError(f"n_eigen = {n_eigen} is outside 1 .. 64")
@@ -781,13 +782,15 @@ class Session:
             C.c_uint32(code), C.c_void_p(x.data_ptr() if m else None), C.c_void_p(y.data_ptr() if m else None)))
         return y
 
-    def spectral(self, G, n_eigen=16, kind="normalized", tol=1e-8, max_steps=None, seed=None):
+    def spectral(self, G, n_eigen=16, kind="normalized", tol=1e-8, max_steps=None, seed=None, single_round=False):
         """sapca_spectral_device_*: (evals, evecs, n_components, n_steps) -- the n_eigen leading eigenpairs of S = diag(s) G diag(s)
         for the symmetric graph G (a ResidentCsr).  evals: n_eigen f64 (numpy, descending); evecs: m x n_eigen on the device in
         G's dtype, one exact pair (eigenvalue 1.0) per connected component first, the sign of every other vector fixed by its
-        entry of largest magnitude.  max_steps None: min(m, 1000).  The same bytes from call to call."""
+        entry of largest magnitude.  max_steps None: min(m, 1000).  The same bytes from call to call.  The solve runs Lanczos
+        rounds until no copy of a repeated eigenvalue is missed (n_steps: their sum); single_round=True stops after the first,
+        which is right only where the leading eigenvalues are simple."""
         import torch
-        o = self._spectral_options(n_eigen, kind, tol, max_steps, seed)
+        o = self._spectral_options(n_eigen, kind, tol, max_steps, seed, single_round)
         m, suf = self._louvain_graph(G)
         if m and o.n_eigen > m:
             raise ValueError(f"n_eigen = {n_eigen} exceeds m = {m}")
@@ -801,9 +804,10 @@ class Session:
             _p(evals, C.c_double), C.c_void_p(evecs.data_ptr() if m else None), C.byref(ncomp), C.byref(steps)))
         return evals, evecs, ncomp.value, steps.value
 
-    def spectral_host(self, indptr, indices, data, n_eigen=16, kind="normalized", tol=1e-8, max_steps=None, seed=None):
+    def spectral_host(self, indptr, indices, data, n_eigen=16, kind="normalized", tol=1e-8, max_steps=None, seed=None,
+                      single_round=False):
         """sapca_spectral_*: the same with a host CSR in (scipy's three arrays) and host eigenvectors out."""
-        o = self._spectral_options(n_eigen, kind, tol, max_steps, seed)
+        o = self._spectral_options(n_eigen, kind, tol, max_steps, seed, single_round)
         data = np.ascontiguousarray(data)
         if data.dtype not in _SUF:
             raise ValueError(f"data must be float32 / float64, got {data.dtype}")

@@ -1,7 +1,8 @@
 """A numpy restatement of the spectral section of include/sapca.h: the components of a graph's structure, the two scales,
 the dense S = diag(s) W diag(s), the locked pairs, the eigenpairs of the deflated matrix by numpy's eigh, the sign rule and
-UMAP's spectral start.  Dense and slow on purpose: test_spectral_cpu.py holds it to scipy and scikit-learn, the GPU tests hold
-the library to it."""
+UMAP's spectral start; and the Lanczos run and rounds of stage 5 (lanczos_run, lanczos_rounds), held to eigh on graphs with
+repeated eigenvalues.  Dense and slow on purpose: test_spectral_cpu.py holds it to scipy and scikit-learn, the GPU tests hold
+the library to it (to eigenpairs(), never to the restated iteration)."""
 import numpy as np
 
 NORMALIZED, DIFFMAP = "normalized", "diffmap"
@@ -163,6 +164,97 @@ def refined_pairs(r):
         at = int(np.argmax(np.abs(v)))
         evecs[:, i] = -v if v[at] < 0 else v
     return dict(evals=evals, evecs=evecs)
+
+
+# ---- stage 5 restated: the Lanczos run and the rounds of csrc/spectral.cpp, in f64 with numpy's own start vectors (so the
+# pairs, not the bytes, are the library's).  test_spectral_cpu.py holds it to eigh on graphs with repeated eigenvalues.
+def check_due(j):
+    """spectral.cpp / lanczos.hip check_due: the steps at which the host looks at T"""
+    every = 1 if j <= 64 else 2 if j <= 128 else 4 if j <= 256 else 8
+    return j % every == 0
+
+
+def lanczos_run(S, X, want, jmax, tol, start, every_step=False, floor=0.0):
+    """run_lanczos: one run on S in the complement of X's orthonormal columns for the `want` largest pairs.  dict: steps,
+    converged, exhausted, theta (ascending), Y (m x steps: the Ritz vectors of theta).  floor: a lower bound of |S| (1 when a
+    pair of eigenvalue 1 is locked), the least scale a beta_j is called zero against"""
+    m = S.shape[0]
+    B = np.zeros((m, X.shape[1] + jmax + 1))
+    c = X.shape[1]
+    B[:, :c] = X
+
+    def cgs2(w, n):
+        h1 = B[:, :n].T @ w
+        w = w - B[:, :n] @ h1
+        h2 = B[:, :n].T @ w
+        return w - B[:, :n] @ h2, h1 + h2
+    w, _ = cgs2(np.asarray(start, dtype=np.float64), c)
+    B[:, c] = w / np.linalg.norm(w)
+    alpha, beta = np.zeros(jmax), np.zeros(jmax)
+    out = dict(steps=0, converged=False, exhausted=False)
+    for j in range(jmax):
+        w, h = cgs2(S @ B[:, c + j], c + j + 1)
+        alpha[j] = h[c + j]
+        beta[j] = np.linalg.norm(w)
+        B[:, c + j + 1] = w / beta[j] if beta[j] > 0 else 0.0
+        steps = out["steps"] = j + 1
+        if steps >= want and not (every_step or check_due(steps) or steps == jmax):
+            continue
+        if steps < want:
+            reach = max(floor, np.max(np.abs(alpha[:steps]) + 2.0 * np.abs(beta[:steps])))
+            if not beta[j] <= 1e-13 * reach:
+                continue
+            if floor == 0.0:          # nothing locked: S is the zero matrix, refused
+                raise RuntimeError(f"the Krylov space is exhausted after {steps} steps, {want} pairs were to be iterated")
+            out["converged"] = out["exhausted"] = True
+            break
+        T = np.diag(alpha[:steps]) + np.diag(beta[:steps - 1], 1) + np.diag(beta[:steps - 1], -1)
+        theta, Z = np.linalg.eigh(T)
+        ok = np.isfinite(beta[j]) and np.all(np.abs(beta[j] * Z[-1, steps - want:]) <= tol)
+        exhausted = steps == m - c or beta[j] <= 1e-13 * max(floor, np.max(np.abs(theta)))
+        if ok or (exhausted and np.isfinite(beta[j])):
+            out["converged"], out["exhausted"] = True, bool(exhausted)
+            break
+    steps = out["steps"]
+    T = np.diag(alpha[:steps]) + np.diag(beta[:steps - 1], 1) + np.diag(beta[:steps - 1], -1)
+    out["theta"], Z = np.linalg.eigh(T)
+    out["Y"] = B[:, c:c + steps] @ Z
+    return out
+
+
+def lanczos_rounds(S, U, k, tol=1e-8, max_steps=None, seed=42, single_round=False):
+    """spectral_device's rounds for the k largest pairs of S in the complement of U's columns (the locked vectors).  dict: evals
+    (k, descending), evecs (m x k, sign rule applied), steps (the sum), rounds (the runs made), first (the values the first
+    run alone would return: what a single run gives)"""
+    m = S.shape[0]
+    c = U.shape[1]
+    max_steps = min(m, 1000) if max_steps is None else max_steps
+    vals, vecs, steps, rounds, first = [], [], 0, 0, None
+    while True:
+        have = len(vals)
+        lock = c + have
+        checking = have >= k
+        if lock == m or (checking and (single_round or c == 0 or have >= 2 * k)):    # (the k-th merge is the last one)
+            break
+        want = 1 if checking else k - have
+        X = np.concatenate([U] + [v[:, None] for v in vecs], axis=1) if vecs else U
+        run = lanczos_run(S, X, want, min(max_steps, m - lock), tol, np.random.default_rng([seed, rounds]).normal(size=m),
+                          floor=1.0 if c else 0.0)
+        rounds += 1
+        steps += run["steps"]
+        if not run["converged"]:
+            raise RuntimeError(f"no convergence in round {rounds - 1} after {steps} steps")
+        got = min(want, run["steps"]) if run["exhausted"] else want
+        if first is None:
+            first = run["theta"][::-1][:got].copy()
+        if checking and not run["theta"][-1] > np.sort(vals)[::-1][k - 1] + tol:
+            break
+        for i in range(got):
+            vals.append(run["theta"][-1 - i])
+            vecs.append(run["Y"][:, -1 - i])
+    order = np.argsort(-np.array(vals), kind="stable")[:k]
+    return dict(evals=np.array(vals)[order], evecs=fix_sign(np.stack([vecs[i] for i in order], axis=1)), steps=steps, rounds=rounds,
+                first=first)
 
 
 def _mix64(z):

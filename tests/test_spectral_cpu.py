@@ -173,6 +173,44 @@ def test_locked_vectors_are_orthonormal_eigenvectors(restated):
         np.testing.assert_allclose(V.T @ V, np.eye(16), atol=1e-10)
 
 
+def test_rounds_restatement_equals_eigh_with_multiplicity():
+    """SR.lanczos_rounds (stage 5 of include/sapca.h restated: runs, locking, the closing round) on graphs whose leading
+    eigenvalues are repeated, nearly repeated or few: values equal eigh's counted with multiplicity, every vector lies in the
+    eigenspace of its value's cluster, the columns are orthonormal; on a graph with simple leading values the first run's
+    pairs are the result and one closing round is made; single_round is the single run"""
+    import lanczos_spectra_cases as LC
+    for name in LC.GRAPHS:
+        for kind in KINDS:
+            g = LC.graph_spectrum(name, kind)
+            c = g["U"].shape[1]
+            for n_eigen in (3, 9):
+                k = n_eigen - c
+                r = SR.lanczos_rounds(g["S"], g["U"], k)
+                np.testing.assert_allclose(r["evals"], g["w"][:k], rtol=0, atol=1e-10, err_msg=f"{name} {kind} {n_eigen}")
+                V = r["evecs"]
+                np.testing.assert_allclose(V.T @ V, np.eye(k), atol=1e-12)
+                np.testing.assert_allclose(g["U"].T @ V, 0, atol=1e-12)
+                groups = LC.clusters(g["w"], 10 * LC.TOL)
+                for i in range(k):
+                    a, b = next(x for x in groups if x[0] <= i < x[1])
+                    gap = min(g["w"][a - 1] - g["w"][a] if a else np.inf, g["w"][b - 1] - g["w"][b] if b < len(g["w"]) else np.inf)
+                    Qc = g["Q"][:, a:b]
+                    assert np.linalg.norm(V[:, i] - Qc @ (Qc.T @ V[:, i])) <= 4 * np.sqrt(1 + 2 * k) * LC.TOL / gap + 1e-10, (name, kind, i)
+                    assert V[np.argmax(np.abs(V[:, i])), i] > 0
+    # simple leading values: the golden connected graph
+    z = np.load(os.path.join(ROOT, "tests", "golden", "g14_spectral.npz"))
+    ptr, idx, dat, _ = _csr(z, "conn")
+    ref = SR.eigenpairs(ptr, idx, dat, SR.NORMALIZED, 6)
+    W = SR.dense(ptr, idx, dat)
+    S, s = SR.operator(W, SR.NORMALIZED)
+    U = SR.locked_vectors(SR.analytic(W, SR.NORMALIZED, s), ref["labels"], ref["n_components"])
+    r = SR.lanczos_rounds(S, U, 5)
+    one = SR.lanczos_rounds(S, U, 5, single_round=True)
+    assert r["rounds"] == 2 and one["rounds"] == 1 and one["steps"] < r["steps"]
+    assert np.array_equal(r["evals"], one["evals"]) and np.array_equal(r["evecs"], one["evecs"]) and np.array_equal(r["first"], r["evals"])
+    np.testing.assert_allclose(r["evals"], ref["evals"][1:], rtol=0, atol=1e-10)
+
+
 def test_sign_rule_and_start_formula():
     V = np.array([[0.5, -0.2], [-0.5, 0.1], [0.1, -0.2]])
     F = SR.fix_sign(V)

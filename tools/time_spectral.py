@@ -16,7 +16,8 @@ Device time from events on the stream around whole calls (launches, gaps and rea
                  with 1) / 100, so the scale and the copy of the stage call cancel; with the short-row kernel at its own packing
                  and at every forced one, and with the wave-per-row k::spmv (SAPCA_SPECTRAL_SPMV_ROW) on the same matrix.  These
                  switches exist in the debug variant of the library only; this script loads it.
-  solve          Session.spectral for 16 pairs of each kind, at least 3 timed calls: steps, the whole call, a step's mean
+  solve          Session.spectral for 16 pairs of each kind, at least 3 timed calls: steps (the sum over the rounds), the whole
+                 call, the same with single_round = 1 (the first round alone: what the closing round costs), a step's mean
                  (whole / steps), and its split BY SUBTRACTION, not by a measurement inside the step: the operator is the figure
                  of the line above for the route the step takes (k::spmv), the rest is the re-orthogonalisation (four passes over
                  the basis) and the host's checks.  The same solve with the short-row kernel in the step
@@ -130,6 +131,8 @@ def main():
                 print(lines[-1], flush=True)
                 continue
             whole = timed(lambda: sess.spectral(G, n_eigen=args.n_eigen, kind=kind), max(3, args.reps))
+            one_steps = sess.spectral(G, n_eigen=args.n_eigen, kind=kind, single_round=True)[3]
+            one = timed(lambda: sess.spectral(G, n_eigen=args.n_eigen, kind=kind, single_round=True), max(3, args.reps))
             env(SAPCA_SPECTRAL_STEP_SHORT=1)
             whole_short = timed(lambda: sess.spectral(G, n_eigen=args.n_eigen, kind=kind), max(3, args.reps))
             env(SAPCA_SPECTRAL_STEP_SHORT=None)
@@ -148,6 +151,7 @@ def main():
                 line += (f"; a step {step:.4f} on average, by subtraction: operator (k::spmv) {row[1]:.4f} ({100 * row[1] / step:.1f} %), "
                          f"re-orthogonalisation and checks {step - row[1]:.4f}; with the short-row kernel in the step "
                          f"{whole_short[0]:9.2f} / {whole_short[1]:9.2f}")
+                line += f"; single_round = 1 (no closing round): {one_steps} steps, {one[0]:9.2f} / {one[1]:9.2f}"
             line += f"; largest residual {worst:.3e}, bound {1e-8 + 64 * st64 * eps:.3e} ({st64} steps, f64)"
             lines.append(line)
             lines.append(f"      eigenvalues {np.array2string(evals, precision=6, max_line_width=200)}")
