@@ -234,7 +234,9 @@ PrepPlan plan_preparation(H& h, const CsrView<T>& A) {
     const int64_t l = std::min<int64_t>((int64_t)(h.opt.n_components + h.opt.n_oversamples), std::min<int64_t>(m, n_used));
     p.tiled_ldp = staged_sweep_ldp<T>(m, n_used, (double)nnz * ((double)n_used / (double)n), l, h.opt.spmm_variant);
   }
-  const bool at_tile_major = p.tiled_ldp != 0 && dbg_env("SAPCA_AT_NATURAL") == nullptr;
+  // (SAPCA_TRANSPOSE_GATHER: transpose_csr's permutation + gather route for f64 only knows the natural row order)
+  const bool at_tile_major = p.tiled_ldp != 0 && dbg_env("SAPCA_AT_NATURAL") == nullptr &&
+                             !(sizeof(T) == 8 && dbg_env("SAPCA_TRANSPOSE_GATHER") != nullptr);
   p.at_nct = at_tile_major ? k::tiled_tile_count(m, p.tiled_ldp * (int)sizeof(T) / 4) : 0;   // (a panel row in 4-byte words)
 
   bool from_upload = h.up_stats.valid && A.ptr == h.in_ptr.p && A.idx == h.in_idx.p && A.val == h.in_val.p &&
