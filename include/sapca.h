@@ -98,7 +98,9 @@ extern "C" {
                                                   sapca_umap_spectral_init_device_*
                                  additive, ABI 4: sapca_spectral_options.reserved became single_round (same size and offsets;
                                                   0, what a zeroed or defaulted struct holds, is the default; a value above 1,
-                                                  ignored before, is now SAPCA_ERR_ARG)                                 */
+                                                  ignored before, is now SAPCA_ERR_ARG)
+                                 additive, ABI 4: sapca_harmony_assign_device_*, sapca_harmony_centroids_device_*,
+                                                  sapca_harmony_correct_device_*, sapca_harmony_device_*, sapca_harmony_* */
 
 typedef struct sapca_handle_s* sapca_handle;
 
@@ -1444,6 +1446,114 @@ sapca_status sapca_hvg_csr_device_f64(sapca_handle h, uint64_t m, uint64_t n, ui
                                       const sapca_hvg_options* opts, double* means, double* variances, double* variances_norm,
                                       double* dispersions, double* dispersions_norm, double* rank, uint32_t* n_batches_hv,
                                       uint8_t* highly_variable);
+
+/* ---- Harmony: batch integration of device-resident score rows (sapca_harmony_*): an opt-in superset ----
+ * The ninth consumer of the score rows, the step between the fit and the neighbour search on data of several samples:
+ * Harmony (Korsunsky et al. 2019; scanpy.external.pp.harmony_integrate).  harmonypy is not available to this project: the
+ * algorithm is stated here in full and pinned by a numpy restatement (tests/harmony_ref.py: dense one-hot designs and
+ * numpy.linalg.solve) that is itself held to scikit-learn's Ridge and scipy's softmax (tests/test_harmony_cpu.py).
+ * Inputs: Z, a row-major DEVICE panel, m x d, row stride ldz >= d (nothing beyond column d of a row is read); batch, m int32
+ * DEVICE labels in [0, B); K = n_clusters; theta, sigma, lambda.  N_b = the rows of batch b, Pr_b = N_b / m.  Zc = the rows of
+ * the current corrected panel scaled to unit L2 norm (the norm in f64; a row of norm 0 stays 0).
+ *   1. Initialisation.  init = SAPCA_HARMONY_KMEANS: Y = the centroids of sapca_kmeans_device_* on Zc (n_clusters = K, the given
+ *      seed, max_iter = 25, tol = 1e-4, init = PLUSPLUS); SAPCA_HARMONY_GIVEN: the caller's K x d centroids.  Then the rows of
+ *      Y are scaled to unit norm, dist_ik = 2 (1 - <Zc_i, Y_k>), R_ik = exp(-(dist_ik - min_k dist_ik) / sigma) with every row
+ *      of R divided by its sum, rs_k = sum_i R_ik, O_bk = sum_{i in b} R_ik, E_bk = Pr_b rs_k.  (harmonypy evaluates the
+ *      objective here once; no test of item 4 can reach that value -- see there -- and it is not an output, so it is not formed.)
+ *   2. One clustering pass.  Y = normalise_rows(R^T Zc); dist as in 1; S_ik = exp(-(dist_ik - min_k dist_ik) / sigma).  The
+ *      update order of pass number c (counted over the whole call, from 0) is the rows sorted by
+ *      (hash_u01(random_seed, 61, c m + i), i) -- the counter generator behind sapca_generate_omega_*, sapca.synth.hash_u01,
+ *      on a stream of its own -- cut into n_blocks consecutive blocks as numpy.array_split cuts it (the first m mod n_blocks
+ *      blocks get one more row; an empty block is a no-op).  For each block in turn: its rows are removed from rs and O (and
+ *      hence from E = Pr rs^T); R_ik = S_ik ((E_bk + 1) / (O_bk + 1))^theta with b = batch_i, the row divided by its sum; the
+ *      block is added back.  rs, O, E, the sums behind Y and every reduction are f64 whatever T is, in an order fixed by
+ *      (m, K, B, n_blocks, seed); no floating-point atomic is used.  Zc, R and Y are stored in T; the inner products run on
+ *      the f32 / f64 matrix cores, everything behind them (dist, the exponential, the penalty, the row sum) in f64, and R is
+ *      rounded once.
+ *   3. The objective after a pass, in f64, three terms: sum_ik R_ik dist_ik;  sigma sum_ik R_ik log R_ik (0 log 0 = 0);
+ *      sigma theta sum_ik R_ik log((O_bk + 1) / (E_bk + 1)).  (dist is held in T between the pass and this sum.)
+ *   4. cluster(): passes i = 0 .. max_iter_cluster - 1; after pass i > 3, with obj_j the objective after pass j of this call
+ *      to cluster(): new = obj_{i-2} + obj_{i-1} + obj_i, old = obj_{i-3} + obj_{i-2} + obj_{i-1} (harmonypy's window-3 sums,
+ *      which at i > 3 hold objectives of this call alone); stop when (old - new) / |old| < epsilon_cluster.  The host reads
+ *      the three terms back once per pass.
+ *   5. Correction (mixture-of-experts ridge), always from the ORIGINAL Z.  For every cluster k, with Phi~ the (B + 1) x m
+ *      design (an intercept row over the one-hot batch rows): A_k = Phi~ diag(R_.k) Phi~^T + diag(0, lambda, .., lambda),
+ *      W_k = A_k^-1 Phi~ diag(R_.k) Z, the intercept row of W_k set to 0, Zcorr -= diag(R_.k) Phi~^T W_k; Zc is recomputed from
+ *      Zcorr.  A_k is an arrow matrix and the solve has a closed form, which is what runs: o_b = sum_{i in b} R_ik,
+ *      t_b = sum_{i in b} R_ik z_i, c_b = o_b / (o_b + lambda), a = sum_b (1 - c_b) t_b / sum_b (1 - c_b) o_b,
+ *      beta_b = (t_b - o_b a) / (o_b + lambda), Zcorr_i = z_i - sum_k R_ik beta_{k, batch_i}.  A cluster with rs_k = 0
+ *      contributes nothing.  All in f64, rounded once to T.  The rows are sorted by (batch, row) with a stable radix sort once per
+ *      call and every (cluster, batch) sum runs over fixed slices of the batch's list that are added in order.
+ *   6. Outer loop: for it = 1 .. max_iter_harmony: cluster(); record its last objective and its passes; correct(); from the
+ *      second iteration on stop (converged = 1) when (obj[it-2] - obj[it-1]) / |obj[it-2]| < epsilon_harmony.
+ * DEVIATIONS from harmonypy: one batch variable, not several covariates; scalar theta / sigma / lambda; no tau discount; no
+ * automatic lambda; the update order comes from this library's counter generator, not numpy's (results equal harmonypy's in
+ * distribution, not bit for bit); the initial k-means is this library's, with one start.
+ * Deterministic: the same bytes from call to call.  Outputs are complete when the call returns.  Every call runs on the
+ * handle's stream in buffers of its own: a fitted model, a cached preparation, the selection and every other consumer's
+ * buffers are untouched (init = KMEANS runs in the k-means buffers); on a handle that belongs to a communicator the call is
+ * local to the rank and issues no collective.
+ * SAPCA_ERR_ARG, checked before the algorithm starts (the handle stays usable), each with a message that names the offending
+ * number: n_clusters == 0; n_clusters > m when m > 0 (the whole run); n_clusters > SAPCA_KMEANS_MAX_CLUSTERS; n_batches == 0
+ * or > SAPCA_HARMONY_MAX_BATCHES; n_blocks == 0; max_iter_harmony == 0; max_iter_cluster == 0; sigma <= 0; lambda <= 0; theta < 0; any scalar not finite; an unknown init;
+ * the d and stride limits of sapca_knn_device_* (d in 1 .. 1024, strides >= d and < 2^28); m >= 2^31; a null pointer with a
+ * non-empty shape; a batch label outside [0, n_batches) -- found by the counting pass that produces N_b (an integer atomic
+ * keeps the first offending row, one read-back), the message names that row.  m == 0 is valid and writes nothing (*n_iter =
+ * 0, *converged = 0, objective terms 0).  A batch with no rows is valid.                                                  */
+typedef enum sapca_harmony_init { SAPCA_HARMONY_KMEANS = 0, SAPCA_HARMONY_GIVEN = 1 } sapca_harmony_init;
+#define SAPCA_HARMONY_MAX_BATCHES 1024
+/* Item 2 alone, a stage-level operator: d_zc (m x d, DEVICE, unit rows, stride ldz), d_batch (m int32, DEVICE), d_y (K x d,
+ * DEVICE, packed: written when recompute_centroids != 0, used as given -- scaled to unit norm by the caller -- otherwise),
+ * d_r (m x K, DEVICE, packed, in/out).  pass_index is c of the update order.  On the HOST, any of which may be NULL: o
+ * (n_batches x K f64), rs (K f64) after the pass and objective (the three terms of item 3).                                 */
+sapca_status sapca_harmony_assign_device_f32(sapca_handle h, uint64_t m, const float* d_zc, uint64_t ldz, uint64_t d,
+                                             const int32_t* d_batch, uint32_t n_batches, uint32_t n_clusters, float* d_y,
+                                             int32_t recompute_centroids, float* d_r, double theta, double sigma, uint32_t n_blocks,
+                                             uint32_t random_seed, uint64_t pass_index, double* o, double* rs, double* objective);
+sapca_status sapca_harmony_assign_device_f64(sapca_handle h, uint64_t m, const double* d_zc, uint64_t ldz, uint64_t d,
+                                             const int32_t* d_batch, uint32_t n_batches, uint32_t n_clusters, double* d_y,
+                                             int32_t recompute_centroids, double* d_r, double theta, double sigma, uint32_t n_blocks,
+                                             uint32_t random_seed, uint64_t pass_index, double* o, double* rs, double* objective);
+/* d_y (K x d, DEVICE, packed) = normalise_rows(R^T Zc) alone; a cluster whose sum has norm 0 gets zeros.                    */
+sapca_status sapca_harmony_centroids_device_f32(sapca_handle h, uint64_t m, const float* d_zc, uint64_t ldz, uint64_t d,
+                                                uint32_t n_clusters, const float* d_r, float* d_y);
+sapca_status sapca_harmony_centroids_device_f64(sapca_handle h, uint64_t m, const double* d_zc, uint64_t ldz, uint64_t d,
+                                                uint32_t n_clusters, const double* d_r, double* d_y);
+/* Item 5 alone: d_zcorr (m x d, DEVICE, stride ldc; may not overlap d_z) from d_z, d_r (m x K, packed) and d_batch; beta
+ * (HOST, K x n_batches x d f64, may be NULL) receives the coefficients.                                                    */
+sapca_status sapca_harmony_correct_device_f32(sapca_handle h, uint64_t m, const float* d_z, uint64_t ldz, uint64_t d,
+                                              const int32_t* d_batch, uint32_t n_batches, uint32_t n_clusters, const float* d_r,
+                                              double lambda, float* d_zcorr, uint64_t ldc, double* beta);
+sapca_status sapca_harmony_correct_device_f64(sapca_handle h, uint64_t m, const double* d_z, uint64_t ldz, uint64_t d,
+                                              const int32_t* d_batch, uint32_t n_batches, uint32_t n_clusters, const double* d_r,
+                                              double lambda, double* d_zcorr, uint64_t ldc, double* beta);
+/* Items 1-6 on resident panels.  d_y (K x d, DEVICE, packed) is read when init == SAPCA_HARMONY_GIVEN and receives the final
+ * centroids; d_r (m x K, DEVICE, packed) may be NULL.  On the HOST, may be NULL: objectives and passes (max_iter_harmony
+ * entries each: the last objective and the number of passes of every outer iteration; entries from *n_iter on are not
+ * written), n_iter, converged.                                                                                             */
+sapca_status sapca_harmony_device_f32(sapca_handle h, uint64_t m, const float* d_z, uint64_t ldz, uint64_t d, const int32_t* d_batch,
+                                      uint32_t n_batches, uint32_t n_clusters, uint32_t init, double theta, double sigma,
+                                      double lambda, uint32_t n_blocks, uint32_t max_iter_harmony, uint32_t max_iter_cluster,
+                                      double epsilon_cluster, double epsilon_harmony, uint32_t random_seed, float* d_zcorr,
+                                      uint64_t ldc, float* d_r, float* d_y, double* objectives, uint32_t* passes, uint32_t* n_iter,
+                                      int32_t* converged);
+sapca_status sapca_harmony_device_f64(sapca_handle h, uint64_t m, const double* d_z, uint64_t ldz, uint64_t d, const int32_t* d_batch,
+                                      uint32_t n_batches, uint32_t n_clusters, uint32_t init, double theta, double sigma,
+                                      double lambda, uint32_t n_blocks, uint32_t max_iter_harmony, uint32_t max_iter_cluster,
+                                      double epsilon_cluster, double epsilon_harmony, uint32_t random_seed, double* d_zcorr,
+                                      uint64_t ldc, double* d_r, double* d_y, double* objectives, uint32_t* passes, uint32_t* n_iter,
+                                      int32_t* converged);
+/* The same with HOST arrays in and out (z, zcorr: m x d packed; batch: m; r: m x K, may be NULL; y: K x d).                  */
+sapca_status sapca_harmony_f32(sapca_handle h, uint64_t m, uint64_t d, const float* z, const int32_t* batch, uint32_t n_batches,
+                               uint32_t n_clusters, uint32_t init, double theta, double sigma, double lambda, uint32_t n_blocks,
+                               uint32_t max_iter_harmony, uint32_t max_iter_cluster, double epsilon_cluster, double epsilon_harmony,
+                               uint32_t random_seed, float* zcorr, float* r, float* y, double* objectives, uint32_t* passes,
+                               uint32_t* n_iter, int32_t* converged);
+sapca_status sapca_harmony_f64(sapca_handle h, uint64_t m, uint64_t d, const double* z, const int32_t* batch, uint32_t n_batches,
+                               uint32_t n_clusters, uint32_t init, double theta, double sigma, double lambda, uint32_t n_blocks,
+                               uint32_t max_iter_harmony, uint32_t max_iter_cluster, double epsilon_cluster, double epsilon_harmony,
+                               uint32_t random_seed, double* zcorr, double* r, double* y, double* objectives, uint32_t* passes,
+                               uint32_t* n_iter, int32_t* converged);
 
 /* Measurement support: the rate (GB/s, read + write counted) of a 16-byte-per-lane streaming copy of `bytes`
  * bytes on the handle's device, best of `reps` -- the HBM rate a kernel of this library can attain, reported by

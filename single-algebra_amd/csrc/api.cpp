@@ -1107,6 +1107,51 @@ sapca_status sapca_get_column_scale(sapca_handle h, int32_t* mode, double* out, 
                                   T* centroids, int32_t* labels, double* inertia, uint64_t* n_iter) {                      \
     return guarded(h, [&] { resident::kmeans_host<T>(*h, m, d, x, opts, centroids, labels, inertia, n_iter); });         \
   }                                                                                                                      \
+  sapca_status sapca_harmony_assign_device_##SUF(sapca_handle h, uint64_t m, const T* d_zc, uint64_t ldz, uint64_t d,       \
+                                                 const int32_t* d_batch, uint32_t n_batches, uint32_t n_clusters, T* d_y,   \
+                                                 int32_t recompute_centroids, T* d_r, double theta, double sigma,           \
+                                                 uint32_t n_blocks, uint32_t random_seed, uint64_t pass_index, double* o,   \
+                                                 double* rs, double* objective) {                                           \
+    return guarded(h, [&] {                                                                                              \
+      resident::harmony_assign<T>(*h, m, d_zc, ldz, d, d_batch, n_batches, n_clusters, d_y, recompute_centroids, d_r, theta, sigma, \
+                                  n_blocks, random_seed, pass_index, o, rs, objective);                                  \
+    });                                                                                                                  \
+  }                                                                                                                      \
+  sapca_status sapca_harmony_centroids_device_##SUF(sapca_handle h, uint64_t m, const T* d_zc, uint64_t ldz, uint64_t d,    \
+                                                    uint32_t n_clusters, const T* d_r, T* d_y) {                            \
+    return guarded(h, [&] { resident::harmony_centroids<T>(*h, m, d_zc, ldz, d, n_clusters, d_r, d_y); });               \
+  }                                                                                                                      \
+  sapca_status sapca_harmony_correct_device_##SUF(sapca_handle h, uint64_t m, const T* d_z, uint64_t ldz, uint64_t d,       \
+                                                  const int32_t* d_batch, uint32_t n_batches, uint32_t n_clusters,          \
+                                                  const T* d_r, double lambda, T* d_zcorr, uint64_t ldc, double* beta) {    \
+    return guarded(h, [&] {                                                                                              \
+      resident::harmony_correct<T>(*h, m, d_z, ldz, d, d_batch, n_batches, n_clusters, d_r, lambda, d_zcorr, ldc, beta); \
+    });                                                                                                                  \
+  }                                                                                                                      \
+  sapca_status sapca_harmony_device_##SUF(sapca_handle h, uint64_t m, const T* d_z, uint64_t ldz, uint64_t d,               \
+                                          const int32_t* d_batch, uint32_t n_batches, uint32_t n_clusters, uint32_t init,   \
+                                          double theta, double sigma, double lambda, uint32_t n_blocks,                     \
+                                          uint32_t max_iter_harmony, uint32_t max_iter_cluster, double epsilon_cluster,     \
+                                          double epsilon_harmony, uint32_t random_seed, T* d_zcorr, uint64_t ldc, T* d_r,   \
+                                          T* d_y, double* objectives, uint32_t* passes, uint32_t* n_iter,                   \
+                                          int32_t* converged) {                                                             \
+    return guarded(h, [&] {                                                                                              \
+      const resident::HarmonyParams p{n_batches, n_clusters, init, n_blocks, max_iter_harmony, max_iter_cluster, random_seed, \
+                                      theta, sigma, lambda, epsilon_cluster, epsilon_harmony};                           \
+      resident::harmony_device<T>(*h, m, d_z, ldz, d, d_batch, p, d_zcorr, ldc, d_r, d_y, objectives, passes, n_iter, converged); \
+    });                                                                                                                  \
+  }                                                                                                                      \
+  sapca_status sapca_harmony_##SUF(sapca_handle h, uint64_t m, uint64_t d, const T* z, const int32_t* batch,                \
+                                   uint32_t n_batches, uint32_t n_clusters, uint32_t init, double theta, double sigma,      \
+                                   double lambda, uint32_t n_blocks, uint32_t max_iter_harmony, uint32_t max_iter_cluster,  \
+                                   double epsilon_cluster, double epsilon_harmony, uint32_t random_seed, T* zcorr, T* r,    \
+                                   T* y, double* objectives, uint32_t* passes, uint32_t* n_iter, int32_t* converged) {      \
+    return guarded(h, [&] {                                                                                              \
+      const resident::HarmonyParams p{n_batches, n_clusters, init, n_blocks, max_iter_harmony, max_iter_cluster, random_seed, \
+                                      theta, sigma, lambda, epsilon_cluster, epsilon_harmony};                           \
+      resident::harmony_host<T>(*h, m, d, z, batch, p, zcorr, r, y, objectives, passes, n_iter, converged);              \
+    });                                                                                                                  \
+  }                                                                                                                      \
   sapca_status sapca_sum_row_n_top_csr_device_##SUF(sapca_handle h, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* p, \
                                                     const int32_t* i, const T* v, const uint64_t* ns, uint32_t n_ns,        \
                                                     double* out) {                                                          \

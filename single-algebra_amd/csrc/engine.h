@@ -185,6 +185,13 @@ struct sapca_handle_s {
     sapca::DevBuf bias, xb, amb, lab0, lab1, cnt, tab, scan, order, partial, shiftpart, ctl, scal, rowd, sum_part, colpart, cols;
     sapca::DevBuf rows, seed_dist, seed_bsum, x, cen, labels;
   } kmeans;
+  // sapca_harmony_*: the unit rows, R, Y, dist and the penalty table, O / rs / Pr, the batch counts, offsets and sorted rows, the
+  // update order's keys, permutations and the sort's work space, the slices' sums, beta, the objective's rows, sums and scalars,
+  // and the panels of the host route.  Nothing else lives in these (init = KMEANS runs sapca_kmeans_device_* in its own).
+  struct Harmony {
+    sapca::DevBuf zc, r, y, dist, pen, o, rs, pr, cnt, seg, by_batch, key32, key32_out, val32, hkey, hkey_out, iota, perm, key2, keys,
+        list, sort_tmp, partial, colsum, beta, rowd, sum_part, scal, labels, x, zcorr, batch, rhost;
+  } harmony;
   // sapca_umap_*: the fuzzy union and what built it (a graph of its own: a t-SNE call never disturbs it), the row sums and their
   // total, the layout's schedule, its second embedding buffer, and the arrays of the host and one-call routes.  Nothing else
   // lives in these.

@@ -556,6 +556,60 @@ void kmeans_fold_columns(const double* partial, int slices, int d, int64_t m, do
 // a strict run's labels are those of its last iteration: out = (ctl[kKmIter] - 1) & 1 ? lab1 : lab0 when ctl[kKmStrict]
 void kmeans_take_labels(const unsigned long long* ctl, const int32_t* lab0, const int32_t* lab1, int32_t* out, int64_t m, hipStream_t s);
 
+// ---- harmony.hip: Harmony on dense row panels (sapca_harmony_*); include/sapca.h states the algorithm -----------------------
+// unit (rows x d, row stride ldu) = the rows of x scaled to unit L2 norm (the norm in f64; a row of norm 0 stays 0)
+template <typename T>
+void harmony_unit_rows(const T* x, int64_t ldx, int64_t rows, int d, T* unit, int64_t ldu, hipStream_t s);
+// cnt[b] (B + 1 words, zeroed here) = the rows of batch b, cnt[B] = the first row whose label lies outside [0, B) (m: none)
+void harmony_count(const int32_t* batch, int64_t m, int B, unsigned long long* cnt, hipStream_t s);
+// by_batch (m words) = the rows sorted by (batch, row), a stable radix sort of the labels; key / key_out / val: m words of work
+// space each
+void harmony_sort_batches(const int32_t* batch, int64_t m, int B, uint32_t* key, uint32_t* key_out, uint32_t* val, uint32_t* by_batch,
+                          DevBuf& sort_tmp, hipStream_t s);
+// The update order of pass c: list (m words) = the rows sorted by (block, batch, order), where order is the rank under
+// (hash_u01(seed, 61, c m + i), i) and block the numpy.array_split piece of that rank among nb pieces; keys (m words) = block *
+// B + batch of every list entry, ascending.  hkey / hkey_out / key2 (u64) and perm / iota (u32): m words of work space each.
+void harmony_order(const int32_t* batch, int64_t m, int B, int64_t nb, uint64_t seed, uint64_t pass, uint64_t* hkey, uint64_t* hkey_out,
+                   uint32_t* iota, uint32_t* perm, uint64_t* key2, uint64_t* keys, uint32_t* list, DevBuf& sort_tmp, hipStream_t s);
+int harmony_slices(int64_t rows);   // pieces of a list in harmony_sums, by the list's length alone
+// partial[((b * K + k) * slices + sl) * D + t] = the f64 sum over slice sl of batch b's list (order[seg[b] .. seg[b + 1]); order
+// and seg null: B == 1, the rows 0 .. m - 1) of R[row][k] x[row][t]; D = d + 1 with `ones` (column d of x counts as 1), else d
+template <typename T>
+void harmony_sums(const T* x, int64_t ldx, int64_t m, int d, bool ones, const T* R, int K, const uint32_t* order, const int64_t* seg, int B,
+                  int slices, double* partial, hipStream_t s);
+// Y[k] (K x d, packed) = the slices' sums of cluster k (B == 1, no ones column) added in order, scaled to unit norm in f64
+template <typename T>
+void harmony_centroids(const double* partial, int K, int d, int slices, T* Y, hipStream_t s);
+// beta[(k * B + b) * d + t] from the slices' sums with the ones column (item 5's closed form; a cluster without weight: zeros)
+void harmony_beta(const double* partial, int K, int B, int d, int slices, double lambda, double* beta, hipStream_t s);
+// out[i] = T(z_i - sum_k R_ik beta[k][batch_i]) in f64
+template <typename T>
+void harmony_apply(const T* z, int64_t ldz, int64_t m, int d, const T* R, int K, const int32_t* batch, int B, const double* beta, T* out,
+                   int64_t ldc, hipStream_t s);
+// O (B x K) and rs (K) = the sums of R over every batch's list, formed from zero: the f64 column sums of R over fixed slices of
+// each list, folded in order.  colsum: B * slices * K doubles of work space.
+template <typename T>
+void harmony_totals(const T* R, int64_t m, int K, const uint32_t* by_batch, const int64_t* seg, int B, int slices, double* colsum, double* O,
+                    double* rs, hipStream_t s);
+// The fold around block `remove` of a pass (nb blocks, -1: none): the rows of block `add` (-1: none) are added to O / rs from R
+// as it stands, the rows of block `remove` taken out, and pen[b * K + k] = ((Pr_b rs_k + 1) / (O_bk + 1))^theta set for it.
+// Every (batch, k) sum runs over the block's list segment of that batch in 256 interleaved lanes added pairwise in a fixed tree.
+template <typename T>
+void harmony_fold(const T* R, int64_t m, int K, int B, int64_t nb, int64_t add, int64_t remove, const uint64_t* keys, const uint32_t* list,
+                  const double* Pr, double theta, double* O, double* rs, double* pen, hipStream_t s);
+// The fused block update on the matrix cores: for the rows list[p0 .. p0 + n) (list null: the rows p0 .. p0 + n - 1),
+// R[row][k] = T(e_k pen[batch_row][k] / their sum) with e_k = exp(-(dist_k - min dist) / sigma), dist_k = 2 (1 - <zc_row, Y_k>)
+// (pen null: 1); dist (nullable, m x K) receives T(dist_k).  Three sweeps over Y recompute the same FMA chains: the row's
+// scores never leave the chip.
+template <typename T>
+void harmony_block(const T* zc, int64_t ldz, int64_t m, int d, const T* Y, int K, const int32_t* batch, int B, const uint32_t* list, int64_t p0,
+                   int64_t n, const double* pen, double sigma, T* R, T* dist, hipStream_t s);
+int64_t harmony_block_begin(int64_t j, int64_t m, int64_t nb);   // the first list position of block j of a pass (j == nb: m)
+// rowd[c * m + i] (c < 3) = row i's share of the three terms of the objective
+template <typename T>
+void harmony_objective(const T* R, const T* dist, const int32_t* batch, int64_t m, int K, int B, const double* O, const double* rs,
+                       const double* Pr, double sigma, double theta, double* rowd, hipStream_t s);
+
 // ---- louvain.hip: Louvain clustering of a symmetric CSR graph (sapca_louvain_*); include/sapca.h states the algorithm ------
 // The control block of a level (device).  A kernel that takes a LouvainState returns at once when ctl->done is set (and, where
 // it works on the candidate assignment, when ctl->moved is 0); ctl null: never.  `cur` says which of the two label / total

@@ -162,6 +162,28 @@ template <typename T>
 void kmeans_host(H& h, uint64_t m, uint64_t d, const T* x, const sapca_kmeans_options* opts, T* centroids, int32_t* labels, double* inertia,
                  uint64_t* n_iter);
 
+// sapca_harmony_* (harmony.cpp): one clustering pass, the centroids, the correction, and the whole run on device panels or on
+// host arrays
+template <typename T>
+void harmony_assign(H& h, uint64_t m, const T* d_zc, uint64_t ldz, uint64_t d, const int32_t* d_batch, uint32_t B, uint32_t K, T* d_y,
+                    int32_t recompute, T* d_r, double theta, double sigma, uint32_t n_blocks, uint32_t seed, uint64_t pass, double* o,
+                    double* rs, double* objective);
+template <typename T>
+void harmony_centroids(H& h, uint64_t m, const T* d_zc, uint64_t ldz, uint64_t d, uint32_t K, const T* d_r, T* d_y);
+template <typename T>
+void harmony_correct(H& h, uint64_t m, const T* d_z, uint64_t ldz, uint64_t d, const int32_t* d_batch, uint32_t B, uint32_t K, const T* d_r,
+                     double lambda, T* d_zcorr, uint64_t ldc, double* beta);
+struct HarmonyParams {
+  uint32_t B, K, init, n_blocks, max_iter_harmony, max_iter_cluster, seed;
+  double theta, sigma, lambda, epsilon_cluster, epsilon_harmony;
+};
+template <typename T>
+void harmony_device(H& h, uint64_t m, const T* d_z, uint64_t ldz, uint64_t d, const int32_t* d_batch, const HarmonyParams& p, T* d_zcorr,
+                    uint64_t ldc, T* d_r, T* d_y, double* objectives, uint32_t* passes, uint32_t* n_iter, int32_t* converged);
+template <typename T>
+void harmony_host(H& h, uint64_t m, uint64_t d, const T* z, const int32_t* batch, const HarmonyParams& p, T* zcorr, T* r, T* y,
+                  double* objectives, uint32_t* passes, uint32_t* n_iter, int32_t* converged);
+
 // sapca_umap_* (umap.cpp): the curve fit (host only), the fuzzy union of neighbour lists, the layout, and the whole chain on a
 // device panel or on host arrays
 void umap_find_ab(double spread, double min_dist, double* a, double* b);

@@ -30,6 +30,18 @@ def _knn_panel(name, t):
     return rows, d, ld, t.dtype
 
 
+class HarmonyResult:
+    """What Session.harmony returns beside the corrected panel: R (m x K soft assignment) and centroids (K x d, unit rows) where
+    the rows live, and on the host the last objective and the number of clustering passes of every outer iteration, n_iter and
+    converged."""
+
+    def __init__(self, R, centroids, objectives, passes, n_iter, converged):
+        self.R, self.centroids, self.objectives, self.passes, self.n_iter, self.converged = R, centroids, objectives, passes, n_iter, converged
+
+    def __repr__(self):
+        return f"HarmonyResult(n_iter={self.n_iter}, converged={self.converged}, passes={list(self.passes)})"
+
+
 class Session:
     """A bare handle (default options) to run stage-level operators on."""
 
@@ -601,6 +613,169 @@ class Session:
             self._h, C.c_uint64(m), C.c_void_p(X.data_ptr() if m else None), C.c_uint64(ld), C.c_uint64(d), C.byref(o),
             C.c_void_p(cen.data_ptr()), C.c_void_p(labels.data_ptr() if m else None), C.byref(inertia), C.byref(n_iter)))
         return labels, cen, inertia.value, n_iter.value
+
+    # ---- Harmony (sapca_harmony_*): one clustering pass, the centroids, the correction, the whole run ----
+    @staticmethod
+    def _harmony_batch(batch, m, device):
+        """The batch labels as they are where they are a contiguous int32 device tensor beside the rows (what k-means or the
+        user left on the device); anything else is converted and uploaded."""
+        import torch
+        if not isinstance(batch, torch.Tensor):
+            batch = torch.as_tensor(np.ascontiguousarray(np.asarray(batch), dtype=np.int32))
+        if batch.dim() != 1 or int(batch.shape[0]) != m:
+            raise ValueError(f"batch must hold one label per row ({m}), got shape {tuple(batch.shape)}")
+        if batch.dtype != torch.int32 or batch.device != device or not batch.is_contiguous():
+            batch = batch.to(device=device, dtype=torch.int32).contiguous()
+        return batch
+
+    @staticmethod
+    def _harmony_panel(name, t, rows, cols, dt, device):
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == (rows, cols) and t.device == device):
+            raise ValueError(f"{name} must be a device tensor of shape {(rows, cols)} and dtype {dt} beside the rows")
+        return t.contiguous()
+
+    @staticmethod
+    def _harmony_rows(name, X):
+        import torch
+        m, d, ld, dt = _knn_panel(name, X)
+        if not X.is_cuda:
+            raise ValueError(f"{name} must live on the device (a CUDA tensor), got a tensor on {X.device}")
+        return m, d, ld, dt, "f32" if dt == torch.float32 else "f64"
+
+    def harmony_centroids(self, Zc, R):
+        """sapca_harmony_centroids_device_*: normalise_rows(R^T Zc) as a K x d device tensor; Zc: m x d device rows (unit
+        norm), R: m x K device tensor of the same dtype.  The sums are f64 in a fixed order."""
+        import torch
+        m, d, ld, dt, suf = self._harmony_rows("Zc", Zc)
+        if not isinstance(R, torch.Tensor) or R.dim() != 2:
+            raise ValueError("R must be a two-dimensional device tensor")
+        K = int(R.shape[1])
+        R = self._harmony_panel("R", R, m, K, dt, Zc.device)
+        Y = torch.zeros((K, d), dtype=dt, device=Zc.device)
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_harmony_centroids_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_void_p(Zc.data_ptr() if m else None), C.c_uint64(ld), C.c_uint64(d), C.c_uint32(K),
+            C.c_void_p(R.data_ptr() if m else None), C.c_void_p(Y.data_ptr())))
+        return Y
+
+    def harmony_assign(self, Zc, batch, n_batches, R, Y=None, theta=2.0, sigma=0.1, n_blocks=20, seed=None, pass_index=0):
+        """sapca_harmony_assign_device_*: one clustering pass (item 2 of include/sapca.h) -> (R, Y, O, rs, objective).  Zc: m x d
+        device rows of unit norm; batch: m labels in [0, n_batches); R: the m x K assignment going in (not modified: a copy is
+        updated); Y: K x d unit centroids used as given, or None to recompute them from R.  O (n_batches x K), rs (K) and the
+        three terms of the objective come back as numpy f64 arrays."""
+        import torch
+        m, d, ld, dt, suf = self._harmony_rows("Zc", Zc)
+        if not isinstance(R, torch.Tensor) or R.dim() != 2:
+            raise ValueError("R must be a two-dimensional device tensor")
+        K, B = int(R.shape[1]), int(n_batches)
+        R = self._harmony_panel("R", R, m, K, dt, Zc.device).clone()
+        recompute = Y is None
+        Y = torch.zeros((K, d), dtype=dt, device=Zc.device) if recompute else self._harmony_panel("Y", Y, K, d, dt, Zc.device).clone()
+        batch = self._harmony_batch(batch, m, Zc.device)
+        O = np.zeros((max(B, 0), K), dtype=np.float64)
+        rs = np.zeros((K,), dtype=np.float64)
+        obj = np.zeros((3,), dtype=np.float64)
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_harmony_assign_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_void_p(Zc.data_ptr() if m else None), C.c_uint64(ld), C.c_uint64(d),
+            C.c_void_p(batch.data_ptr() if m else None), C.c_uint32(B), C.c_uint32(K), C.c_void_p(Y.data_ptr()),
+            C.c_int32(1 if recompute else 0), C.c_void_p(R.data_ptr() if m else None), C.c_double(float(theta)), C.c_double(float(sigma)),
+            C.c_uint32(int(n_blocks)), C.c_uint32(int(self._seed if seed is None else seed)), C.c_uint64(int(pass_index)),
+            O.ctypes.data_as(C.c_void_p), rs.ctypes.data_as(C.c_void_p), obj.ctypes.data_as(C.c_void_p)))
+        return R, Y, O, rs, obj
+
+    def harmony_correct(self, Z, batch, n_batches, R, lam=1.0):
+        """sapca_harmony_correct_device_*: the mixture-of-experts ridge correction (item 5) -> (Zcorr, beta).  Z: m x d device
+        rows (a column slice of the scores is read in place), R: m x K; Zcorr is a new m x d device tensor, beta the K x
+        n_batches x d coefficients as a numpy f64 array."""
+        import torch
+        m, d, ld, dt, suf = self._harmony_rows("Z", Z)
+        if not isinstance(R, torch.Tensor) or R.dim() != 2:
+            raise ValueError("R must be a two-dimensional device tensor")
+        K, B = int(R.shape[1]), int(n_batches)
+        R = self._harmony_panel("R", R, m, K, dt, Z.device)
+        batch = self._harmony_batch(batch, m, Z.device)
+        out = torch.empty((m, d), dtype=dt, device=Z.device)
+        beta = np.zeros((K, max(B, 0), d), dtype=np.float64)
+        torch.cuda.current_stream().synchronize()
+        L.check(self._h, getattr(L.load(), f"sapca_harmony_correct_device_{suf}")(
+            self._h, C.c_uint64(m), C.c_void_p(Z.data_ptr() if m else None), C.c_uint64(ld), C.c_uint64(d),
+            C.c_void_p(batch.data_ptr() if m else None), C.c_uint32(B), C.c_uint32(K), C.c_void_p(R.data_ptr() if m else None),
+            C.c_double(float(lam)), C.c_void_p(out.data_ptr() if m else None), C.c_uint64(d), beta.ctypes.data_as(C.c_void_p)))
+        return out, beta
+
+    def harmony(self, X, batch, n_clusters=None, n_batches=None, init="kmeans", theta=2.0, sigma=0.1, lam=1.0, n_blocks=20,
+                max_iter_harmony=10, max_iter_cluster=20, epsilon_cluster=1e-5, epsilon_harmony=1e-4, seed=None):
+        """sapca_harmony_device_* / sapca_harmony_*: (Zcorr, result) -- Harmony batch integration of the score rows X
+        (include/sapca.h states the algorithm and its deviations from harmonypy; what scanpy.external.pp.harmony_integrate
+        does between the PCA and `neighbors`).  X: an m x d torch device tensor of float32 / float64 with contiguous rows (a
+        column slice of the scores is read in place; the corrected panel is a new device tensor), or a numpy array (the host
+        route; a numpy array back).  batch: one integer label per row in [0, n_batches) -- an int32 device tensor is taken as
+        it is; n_batches defaults to the largest label + 1.  n_clusters defaults to min(round(m / 30), 100), at least 1.  init:
+        "kmeans" (this library's k-means++ / Lloyd under `seed`) or an n_clusters x d array of centroids.  result: a
+        HarmonyResult with R (m x K), centroids (K x d), objectives, passes, n_iter, converged.  The same bytes from call to call."""
+        given = not isinstance(init, str)
+        if not given and init != "kmeans":
+            raise ValueError(f"unknown init {init!r}: 'kmeans' or an array of centroids")
+        host = isinstance(X, np.ndarray)
+        if host:
+            if X.ndim != 2 or X.dtype not in _SUF:
+                raise ValueError(f"X must be a two-dimensional float32 / float64 array, got {X.dtype} {X.shape}")
+            X = np.ascontiguousarray(X)
+            m, d = X.shape
+        else:
+            import torch
+            m, d, ld, dt, suf = self._harmony_rows("X", X)
+        K = max(1, min(int(round(m / 30.0)), 100)) if n_clusters is None else int(n_clusters)
+        if K < 0 or int(max_iter_harmony) < 0 or int(max_iter_cluster) < 0 or int(n_blocks) < 0:
+            raise ValueError("n_clusters, n_blocks and the iteration limits must not be negative")
+        if host:
+            batch = np.ascontiguousarray(np.asarray(batch), dtype=np.int32)
+            if batch.shape != (m,):
+                raise ValueError(f"batch must hold one label per row ({m}), got shape {batch.shape}")
+            B = (int(batch.max()) + 1 if m else 1) if n_batches is None else int(n_batches)
+        else:
+            batch = self._harmony_batch(batch, m, X.device)
+            B = (int(batch.max().item()) + 1 if m else 1) if n_batches is None else int(n_batches)
+        B = max(B, 0)
+        objectives = np.zeros((max(int(max_iter_harmony), 1),), dtype=np.float64)
+        passes = np.zeros((max(int(max_iter_harmony), 1),), dtype=np.uint32)
+        n_iter, converged = C.c_uint32(), C.c_int32()
+        scalars = (C.c_uint32(B), C.c_uint32(K), C.c_uint32(L.HARMONY_GIVEN if given else L.HARMONY_KMEANS), C.c_double(float(theta)),
+                   C.c_double(float(sigma)), C.c_double(float(lam)), C.c_uint32(int(n_blocks)), C.c_uint32(int(max_iter_harmony)),
+                   C.c_uint32(int(max_iter_cluster)), C.c_double(float(epsilon_cluster)), C.c_double(float(epsilon_harmony)),
+                   C.c_uint32(int(self._seed if seed is None else seed)))
+        tail = (objectives.ctypes.data_as(C.c_void_p), passes.ctypes.data_as(C.c_void_p), C.byref(n_iter), C.byref(converged))
+        if host:
+            suf = _SUF[X.dtype][0]
+            Y = np.zeros((K, d), dtype=X.dtype)
+            if given:
+                init = np.asarray(init)
+                if init.shape != (K, d):
+                    raise ValueError(f"init must have shape {(K, d)}, got {init.shape}")
+                Y[...] = init
+            out = np.zeros((m, d), dtype=X.dtype)
+            R = np.zeros((m, K), dtype=X.dtype)
+            L.check(self._h, getattr(L.load(), f"sapca_harmony_{suf}")(
+                self._h, C.c_uint64(m), C.c_uint64(d), X.ctypes.data_as(C.c_void_p), batch.ctypes.data_as(C.c_void_p), *scalars,
+                out.ctypes.data_as(C.c_void_p), R.ctypes.data_as(C.c_void_p), Y.ctypes.data_as(C.c_void_p), *tail))
+        else:
+            if given and not isinstance(init, torch.Tensor):   # a host array of centroids beside device rows: uploaded
+                init = np.asarray(init)
+                if init.shape != (K, d):
+                    raise ValueError(f"init must have shape {(K, d)}, got {init.shape}")
+                init = torch.as_tensor(init, device=X.device).to(dt)
+            Y = self._harmony_panel("init", init, K, d, dt, X.device).clone() if given else torch.zeros((K, d), dtype=dt, device=X.device)
+            out = torch.empty((m, d), dtype=dt, device=X.device)
+            R = torch.zeros((m, K), dtype=dt, device=X.device)
+            torch.cuda.current_stream().synchronize()
+            L.check(self._h, getattr(L.load(), f"sapca_harmony_device_{suf}")(
+                self._h, C.c_uint64(m), C.c_void_p(X.data_ptr() if m else None), C.c_uint64(ld), C.c_uint64(d),
+                C.c_void_p(batch.data_ptr() if m else None), *scalars, C.c_void_p(out.data_ptr() if m else None), C.c_uint64(d),
+                C.c_void_p(R.data_ptr() if m else None), C.c_void_p(Y.data_ptr()), *tail))
+        n = int(n_iter.value)
+        return out, HarmonyResult(R, Y, objectives[:n].copy(), passes[:n].astype(np.int64), n, bool(converged.value))
 
     # ---- Louvain (sapca_louvain_*): the modularity of labels, one sweep, one aggregation, the whole run ----
     @staticmethod

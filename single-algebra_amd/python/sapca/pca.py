@@ -646,6 +646,44 @@ class KMeans:
         return labels.cpu().numpy() if host else labels
 
 
+class Harmony:
+    """Harmony batch integration of dense score rows on the GPU (sapca_harmony_*): what scanpy.external.pp.harmony_integrate does
+    between the PCA and `neighbors`, restated deterministically (include/sapca.h lists the deviations from harmonypy).
+
+        hm = sapca.Harmony(theta=2.0).fit(scores, batch)   # a torch device tensor (read in place), or a numpy array
+        hm.Z_corr_, hm.R_, hm.cluster_centers_, hm.objectives_, hm.passes_, hm.n_iter_, hm.converged_
+        corrected = sapca.Harmony().fit_transform(scores, batch)
+
+    `batch` holds one integer label per row; an int32 device tensor -- what KMeans or the user left on the device -- is taken as
+    it is.  n_clusters defaults to min(round(m / 30), 100)."""
+
+    def __init__(self, n_clusters=None, theta=2.0, sigma=0.1, lam=1.0, n_blocks=20, max_iter_harmony=10, max_iter_cluster=20,
+                 epsilon_cluster=1e-5, epsilon_harmony=1e-4, init="kmeans", seed=42):
+        self.n_clusters, self.theta, self.sigma, self.lam, self.n_blocks = n_clusters, float(theta), float(sigma), float(lam), int(n_blocks)
+        self.max_iter_harmony, self.max_iter_cluster = int(max_iter_harmony), int(max_iter_cluster)
+        self.epsilon_cluster, self.epsilon_harmony, self.init, self.seed = float(epsilon_cluster), float(epsilon_harmony), init, int(seed)
+        self.Z_corr_ = self.R_ = self.cluster_centers_ = self.objectives_ = self.passes_ = self.n_iter_ = self.converged_ = None
+        self._session = None
+
+    def _ops(self):
+        from .ops import Session
+        if self._session is None:
+            self._session = Session(seed=self.seed)
+        return self._session
+
+    def fit(self, X, batch, n_batches=None):
+        self.Z_corr_, res = self._ops().harmony(
+            X, batch, n_clusters=self.n_clusters, n_batches=n_batches, init=self.init, theta=self.theta, sigma=self.sigma, lam=self.lam,
+            n_blocks=self.n_blocks, max_iter_harmony=self.max_iter_harmony, max_iter_cluster=self.max_iter_cluster,
+            epsilon_cluster=self.epsilon_cluster, epsilon_harmony=self.epsilon_harmony, seed=self.seed)
+        self.R_, self.cluster_centers_, self.objectives_, self.passes_ = res.R, res.centroids, res.objectives, res.passes
+        self.n_iter_, self.converged_ = res.n_iter, res.converged
+        return self
+
+    def fit_transform(self, X, batch, n_batches=None):
+        return self.fit(X, batch, n_batches).Z_corr_
+
+
 class Louvain:
     """Louvain communities of the neighbour graph on the GPU (sapca_louvain_*): what scanpy runs after `neighbors`, restated as
     deterministic synchronous sweeps (include/sapca.h).
