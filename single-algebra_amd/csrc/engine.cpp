@@ -456,8 +456,11 @@ void column_statistics(H& h, const CsrView<T>& A, const PrepPlan& p, PrepOutcome
       std::fill(tail, tail + ntail, 0.0);
       tail[0] = (double)m;
       if (ride && h.tiled_at.valid) {
+        // (the vote is for the panel the fit will sweep: above 64 columns it is wider than the format and the sweep stays whole.
+        //  m_global is not known yet; where it cuts l to 64 or less every rank has still voted 0 alike)
+        const int64_t l_vote = std::min<int64_t>((int64_t)h.opt.n_components + (int64_t)h.opt.n_oversamples, p.n_used);
         tail[1] = 1.0;
-        tail[2 + h.comm.rank] = (double)Engine<T>::piece_vote(h, h.tiled_at.ldp);
+        tail[2 + h.comm.rank] = l_vote <= 64 ? (double)Engine<T>::piece_vote(h, h.tiled_at.ldp) : 0.0;
       }
       SAPCA_HIP(hipMemcpyAsync(d_stats + 3 * n, tail, ntail * sizeof(double), hipMemcpyHostToDevice, s));
       { Scope cs(h, C_COMM); h.comm.allreduce(d_stats, (uint64_t)3 * n + ntail, 1, s); }
